@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the compute_paths hot path on N MI355X GPUs (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment, bench.py launches its own N rank
 processes (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1,
@@ -32,6 +32,9 @@ measured right after and reported as first-class numbers:
     value_with_gather     every rank's packed records -> rank 0 over RCCL (xGMI), serialised into the step
     value_with_d2h        every rank copies its own packed records to its host over its own PCIe link
                           (--collect d2h / both; no root)
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (see dump_outputs) as
+DIR/<name>.npy; the workloads are fixed, so the same arguments give the same inputs in every run.
 
 Prints ONE JSON line on rank 0.  metric = resolved propagation paths per second (scatter records
 written, blocked ones included, + LoS entries), whole job; ray-triangle tests/s of the brute-force
@@ -123,6 +126,54 @@ def cpu_baseline(c, budget_s=20.0):
     return port
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # all files, .npy headers included
+
+
+def dump_outputs(tr, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write what a caller of the timed path receives from its last step, as float32 / float64 .npy:
+
+        path_rx, path_tx, path_bounce, path_index   float64 [n]   dense slot of each record (global path index)
+        a_te_re, a_te_im, a_tm_re, a_tm_im, tau     float32 [n]   the non-zero scatter records (Tracer.paths())
+        direction_rx                                float32 [n, 3]
+        freq_shift                                  float32 [n]
+        los                                         float32 [nrx, ntx, 8]   the LoS block
+        hit_counts                                  float64 [nb]  rays that hit at each bounce
+
+    Records are put in dense-slot order (rx, tx, bounce, path), so two builds compare row for row whatever
+    order their kernels wrote them in.  If all of it would exceed `budget` bytes, the record arrays keep a
+    fixed, seeded sample of rows (sorted indices into that order; `path_sample_rows` holds them)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    p = tr.paths()
+    slot = ((p["rx"] * tr.ntx + p["tx"]) * tr.nb + p["bounce"]) * tr.num_paths + p["path"]
+    order = torch.sort(slot, stable=True).indices
+    cols = dict(path_rx=(p["rx"], np.float64), path_tx=(p["tx"], np.float64),
+                path_bounce=(p["bounce"], np.float64), path_index=(p["path"], np.float64),
+                a_te_re=(p["a_te"].real, np.float32), a_te_im=(p["a_te"].imag, np.float32),
+                a_tm_re=(p["a_tm"].real, np.float32), a_tm_im=(p["a_tm"].imag, np.float32),
+                tau=(p["tau"], np.float32), direction_rx=(p["direction_rx"], np.float32),
+                freq_shift=(p["freq_shift"], np.float32))
+    n = int(order.numel())
+    counts = tr.counts()
+    fixed = dict(los=np.ascontiguousarray(tr.los(), dtype=np.float32),
+                 hit_counts=np.asarray(counts[1:tr.nb + 1], dtype=np.float64))
+    row_bytes = sum(np.dtype(dt).itemsize * (3 if k == "direction_rx" else 1) for k, (_, dt) in cols.items())
+    room = max(0, budget - sum(a.nbytes for a in fixed.values()) - 16 * 256)   # (16 .npy headers of <= 256 B)
+    sampled = n * row_bytes > room
+    if sampled:
+        k = room // (row_bytes + 8)   # (+ the row indices themselves)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        fixed["path_sample_rows"] = rows.astype(np.float64)
+        order = order[torch.from_numpy(rows).to(order.device)]
+    files = dict(fixed)
+    for name, (t, dt) in cols.items():
+        files[name] = t[order].cpu().numpy().astype(dt)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return dict(dir=out_dir, records=n, rows_written=int(order.numel()), sampled=bool(sampled), seed=seed,
+                bytes=int(sum(a.nbytes for a in files.values())))
+
+
 def self_launch(args):
     """--gpus N > 1 without a torch.distributed environment: start the N ranks ourselves.  This
     process has not touched the GPU (no HIP call, no torch.cuda query), so starting children is safe;
@@ -182,7 +233,14 @@ def main():
                          "128 MiB read + 128 MiB written, 4 B/lane) to calibrate PMC byte counters")
     ap.add_argument("--dropin", action="store_true",
                     help="only time the host-array drop-in C ABI (hrt_compute_paths_ex), cold and warm")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(DIR/rank<r>/ for N > 1; at most 64 MB per rank, a seeded sample of the records beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dropin and args.dump_outputs:
+        ap.error("--dump-outputs dumps the timed path; --dropin does not run it")
     if args.no_gather:
         args.collect = "none"
 
@@ -300,6 +358,9 @@ def main():
         if not void:
             break
         void_retimed += 1
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(tr, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank))
     # per-kernel HIP events (one hrt_timer = the events of one step, recorded on the launch stream,
     # read afterwards): a SEPARATE untimed pass right after the timed region, every step of it
     # instrumented -- the timed steps carry no events (they cost ~4 % of a 1.6 ms step)
@@ -454,6 +515,8 @@ def main():
         # the GPU was shared) and how often the timed region was timed again because a step in it was void
         out["fallback_state"] = int(_libm.load().hrt_fallback_state())
         out["void_regions_retimed"] = void_retimed
+        if dumped:
+            out["dump_outputs"] = dumped
         if kstats:
             out["kernel_stats_all_steps"] = dict(columns=["wave_traces", "usable_packets", "candidates", "stage2", "stage3", "exact", "c6", "c7"], primary0=kstats[0], primary=kstats[1], shadow=kstats[2])
 

@@ -8,6 +8,8 @@ glibc).  'Relative' for a complex amplitude is taken on the complex value: |a - 
 1e-5 * |a_ref| (+ a tiny absolute floor for exact zeros), the standard for phasors; the
 real/imaginary parts alone can be arbitrarily close to zero.
 """
+import hashlib
+
 import numpy as np
 
 AMP_RTOL = 1e-5
@@ -86,3 +88,34 @@ def compare_dense(got, ref, amp_rtol=AMP_RTOL, check_rays=True, exact_freq_shift
         for k in ("los_rays", "los_active", "scat_rays", "scat_active"):
             assert_bit_equal(got[k], ref[k], k)
     return stats
+
+
+def array_digest(a):
+    """shape and SHA-256 of an array's bit patterns: what a recorded reference output is stored as."""
+    x = bits(np.ascontiguousarray(a))
+    return "%s:%s" % ("x".join(str(n) for n in x.shape), hashlib.sha256(x.tobytes()).hexdigest())
+
+
+def result_digests(res, normals):
+    """array_digest of every output of a dense result (abi.run_compute_paths / oracle.compute_paths:
+    both channel blocks, RaysInfo snapshots, active masks) and of the normals left in the scene."""
+    out = {"%s.%s" % (blk, k): array_digest(v) for blk in ("los", "scat") for k, v in res[blk].items()}
+    for k in ("los_rays", "los_active", "scat_rays", "scat_active"):
+        out[k] = array_digest(res[k])
+    out["normals"] = array_digest(normals)
+    return out
+
+
+def recorded(group, name):
+    """The reference's recorded result_digests of one case (tests/golden/make_reference_digests.py)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")) as f:
+        return json.load(f)[group][name]
+
+
+def assert_matches_recorded(got, want, name):
+    """got/want: result_digests dicts; every recorded array must have the same bits."""
+    assert set(got) == set(want), "%s: arrays %s vs recorded %s" % (name, sorted(got), sorted(want))
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, "%s: %s differ from the reference's recorded outputs" % (name, bad)

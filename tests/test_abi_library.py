@@ -2,6 +2,7 @@
 struct layouts match the reference's, host-only entry points work, and compute entry points
 fail loudly (no CPU fallback) when there is no HIP device."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -122,12 +123,9 @@ def test_product_never_touches_the_oracle():
     assert "oracle" not in deps
 
 
-REF_INC = "/root/reference/inc"
-
 CALLER_SRC = r'''
-/* a caller written against the REFERENCE's headers only (INTEGRATION.md section 1) */
-#include "compute_paths.h"
-#include "scene.h"
+/* a caller written against the reference's declarations only (INTEGRATION.md section 1) */
+#include "hermespy_rt.h"
 #include <stdio.h>
 #include <string.h>
 int main(int argc, char **argv)
@@ -159,17 +157,22 @@ int main(int argc, char **argv)
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INC), reason="needs the reference headers (build container only)")
-def test_caller_built_against_reference_headers_links_unchanged(tmp_path):
-    """INTEGRATION.md section 1, literally: a C caller compiled with -I/root/reference/inc (not our
-    headers) links against libhermespy_rt_amd.so and runs: scene_load returns the reference's Scene
-    by value, scene_save writes the same bytes, compute_paths resolves (and, with a GPU, is called
-    and returns the SURVEY 8c LoS anchor)."""
+def test_caller_built_against_reference_layout_links_unchanged(tmp_path):
+    """the public structs of include/hermespy_rt.h have the size and every
+    field offset of the reference's headers (recorded by tests/golden/make_reference_digests.py), and a
+    C caller written against the reference's declarations -- compute_paths taken as a pointer of the
+    reference's prototype, -Werror -- links against libhermespy_rt_amd.so and runs: scene_load returns
+    the reference's Scene by value, scene_save writes the same bytes, compute_paths resolves (and, with
+    a GPU, is called and returns the SURVEY 8c LoS anchor)."""
+    from .golden.make_reference_digests import header_layout
+    with open(os.path.join(REPO, "tests", "golden", "reference_digests.json")) as f:
+        want = json.load(f)["header_layout"]
+    assert header_layout(INC, ["hermespy_rt.h"], str(tmp_path)) == want
     src = tmp_path / "caller.c"
     src.write_text(CALLER_SRC)
     exe = tmp_path / "caller"
     libdir = os.path.dirname(lib.LIB_PATH)
-    subprocess.check_call(["gcc", "-O1", "-Wall", "-I", REF_INC, str(src), "-o", str(exe), "-L", libdir,
+    subprocess.check_call(["gcc", "-O1", "-Wall", "-Werror", "-I", INC, str(src), "-o", str(exe), "-L", libdir,
                            "-lhermespy_rt_amd", "-Wl,-rpath," + libdir, "-lm"])
     box = os.path.join(REPO, "scenes", "box.hrt")
     out = tmp_path / "again.hrt"

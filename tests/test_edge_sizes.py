@@ -3,7 +3,7 @@ byte of the active mask, less and one more than a wavefront, one more than a wor
 of ONE triangle, a mesh with ZERO triangles next to a real one, a scene no ray can hit (every
 list empty after launch 0), 32 bounces and 40 bounces (the reference's loop has no cap, src/compute_paths.c:591;
 the library's per-launch tables are sized by the bounce count, only hrt_stats.live keeps its 34 slots).
-CPU part: oracle against the LIVE reference.  GPU part: product against the oracle."""
+CPU part: oracle against the reference's recorded outputs (tests/golden/make_reference_digests.py).  GPU part: product against the oracle."""
 import os
 
 import numpy as np
@@ -14,7 +14,7 @@ from oracle import oracle
 
 from . import configs as K
 from . import scenes_gen as G
-from .parity import compare_dense
+from .parity import assert_matches_recorded, compare_dense, recorded, result_digests
 
 
 def _scenes(tmp):
@@ -54,12 +54,9 @@ NAMES = ["box_1_rays", "box_7_rays", "box_9_rays", "box_64_rays", "box_65_rays",
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_oracle_equals_reference_edge_sizes(ref_lib, name, tmp_path):
-    c = _cases(tmp_path)[name]
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    got = oracle.compute_paths(*K.args(c))
-    st = compare_dense(got, ref)
-    assert all(v == 0 for v in st.values()), st
+def test_oracle_equals_reference_edge_sizes(name, tmp_path):
+    got = oracle.compute_paths(*K.args(_cases(tmp_path)[name]))
+    assert_matches_recorded(result_digests(got, got["extras"]["normals"]), recorded("edge_sizes", name), name)
 
 
 @pytest.mark.gpu

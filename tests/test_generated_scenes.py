@@ -1,6 +1,6 @@
 """Parity on generated scenes (tests/scenes_gen.py): code paths the bundled scenes do not reach.
-CPU part: the oracle against the LIVE reference on every generated scene (skipped where
-oracle/_ref is absent).  GPU part: the product against the oracle, all intersection variants."""
+CPU part: the oracle against the reference's recorded outputs on every generated scene
+(tests/golden/make_reference_digests.py).  GPU part: the product against the oracle, all intersection variants."""
 import os
 import subprocess
 import sys
@@ -10,12 +10,11 @@ import pytest
 
 from tests.tune import tuned
 
-from hermespy_rt_amd import abi
 from oracle import oracle
 
 from . import configs as K
 from . import scenes_gen as G
-from .parity import assert_bit_equal, compare_dense
+from .parity import assert_matches_recorded, recorded, result_digests
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,15 +39,9 @@ NAMES = ["t300", "t300_tilted", "t1104", "t2004_global_table", "t6012_six_blocks
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_oracle_equals_reference_on_generated_scene(ref_lib, name, tmp_path):
-    c = make(tmp_path, name)
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    got = oracle.compute_paths(*K.args(c))
-    for blk in ("los", "scat"):
-        for k in ref[blk]:
-            assert_bit_equal(got[blk][k], ref[blk][k], "%s.%s" % (blk, k))
-    for k in ("los_rays", "los_active", "scat_rays", "scat_active"):
-        assert_bit_equal(got[k], ref[k], k)
+def test_oracle_equals_reference_on_generated_scene(name, tmp_path):
+    got = oracle.compute_paths(*K.args(make(tmp_path, name)))
+    assert_matches_recorded(result_digests(got, got["extras"]["normals"]), recorded("generated_scenes", name), name)
     hits = got["extras"]["live"]
     assert hits[1] > 0
 

@@ -2,8 +2,8 @@
   * eta table (precompute_materials, src/compute_paths.c:171-206; csrc/host/materials.c) for all
     17 ITU-R P.2040 materials at 3.0 / 3.5 / 70 GHz, bit for bit;
   * triangle normals (precompute_normals, :208-224): what hrt_problem_normals reports and what
-    compute_paths() leaves in the caller's Scene (mesh->ns), against the oracle's and -- where
-    oracle/_ref is built -- the real reference's;
+    compute_paths() leaves in the caller's Scene (mesh->ns), against the oracle's and the real
+    reference's (recorded by tests/golden/make_reference_digests.py);
   * the table order map (hrt_problem_tri_order) is a permutation consistent with hrt_problem_tri_ids.
 """
 import ctypes as C
@@ -17,7 +17,7 @@ from oracle import oracle
 
 from . import configs as K
 from . import scenes_gen as G
-from .parity import assert_bit_equal
+from .parity import array_digest, assert_bit_equal, recorded
 
 pytestmark = pytest.mark.gpu
 
@@ -78,11 +78,13 @@ def test_normals_product_vs_oracle(product_lib, tmp_path, name):
     tr.close()
 
 
-def test_normals_product_vs_live_reference(product_lib, ref_lib):
-    c = K.small(K.C3, 128)
-    got = abi.run_compute_paths(product_lib, *K.args(c))
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    assert_bit_equal(np.concatenate(got["normals"]), np.concatenate(ref["normals"]), "mesh->ns vs reference")
+REF_CASES = {"c3_128": K.small(K.C3, 128)}   # recorded by tests/golden/make_reference_digests.py
+
+
+def test_normals_product_vs_reference(product_lib):
+    got = abi.run_compute_paths(product_lib, *K.args(REF_CASES["c3_128"]))
+    assert array_digest(np.concatenate(got["normals"])) == recorded("problem_tables", "c3_128")["normals"], \
+        "mesh->ns differs from the reference's recorded normals"
 
 
 def test_two_tx_sign_of_zero_freq_shift(product_lib):

@@ -1,6 +1,6 @@
 """Endpoints exactly in the planes of scene triangles (tests/configs.py IN_PLANE): the reference's
 hit decisions there are rounding noise, and parity means reproducing that noise.
-CPU part: the oracle against the LIVE reference (skipped where oracle/_ref is absent).
+CPU part: the oracle against the reference's recorded outputs (tests/golden/make_reference_digests.py).
 GPU part: the product against the oracle, all three intersection variants."""
 import os
 import subprocess
@@ -10,22 +10,18 @@ import pytest
 
 from tests.tune import tuned
 
-from hermespy_rt_amd import abi
 from oracle import oracle
 
 from . import configs as K
-from .parity import compare_dense
+from .parity import assert_matches_recorded, recorded, result_digests
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", list(K.IN_PLANE))
-def test_oracle_equals_reference_in_plane(ref_lib, name):
-    c = K.IN_PLANE[name]
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    got = oracle.compute_paths(*K.args(c))
-    st = compare_dense(got, ref)
-    assert all(v == 0 for v in st.values()), st
+def test_oracle_equals_reference_in_plane(name):
+    got = oracle.compute_paths(*K.args(K.IN_PLANE[name]))
+    assert_matches_recorded(result_digests(got, got["extras"]["normals"]), recorded("in_plane", name), name)
 
 
 CODE = r"""

@@ -1,6 +1,5 @@
-"""The oracle against the real reference run LIVE (oracle/_ref/libhrt_ref.so, built in place
-from /root/reference; skipped where that build is absent), on inputs beyond the committed
-fixtures: odd ray counts, several TX with velocities (the reference's multi-TX layout quirks
+"""The oracle against the real reference's outputs (recorded by tests/golden/make_reference_digests.py),
+on inputs beyond the full golden arrays: odd ray counts, several TX with velocities (the reference's multi-TX layout quirks
 Q9/Q11/Q12), coincident TX/RX, sub-sampled runs."""
 import numpy as np
 import pytest
@@ -9,7 +8,7 @@ from hermespy_rt_amd import abi
 from oracle import oracle
 
 from . import configs as K
-from .parity import assert_bit_equal
+from .parity import assert_bit_equal, assert_matches_recorded, recorded, result_digests
 
 CASES = {
     "c3_777": K.small(K.C3, 777),
@@ -25,18 +24,10 @@ CASES = {
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_oracle_equals_reference(ref_lib, name):
-    c = CASES[name]
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    got = oracle.compute_paths(*K.args(c))
-    for blk in ("los", "scat"):
-        for k in ref[blk]:
-            assert_bit_equal(got[blk][k], ref[blk][k], "%s.%s" % (blk, k))
-    for k in ("los_rays", "los_active", "scat_rays", "scat_active"):
-        assert_bit_equal(got[k], ref[k], k)
-    # normals the reference left in the scene
-    n_ref = np.concatenate(ref["normals"])
-    assert_bit_equal(got["extras"]["normals"], n_ref, "normals")
+def test_oracle_equals_reference(name):
+    # every output array and the normals the reference left in the scene, bit for bit
+    got = oracle.compute_paths(*K.args(CASES[name]))
+    assert_matches_recorded(result_digests(got, got["extras"]["normals"]), recorded("oracle_vs_ref", name), name)
 
 
 def test_oracle_threads_do_not_change_bits():

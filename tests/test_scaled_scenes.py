@@ -2,7 +2,7 @@
 is centimetres) and rescaled (a millimetre box a kilometre away, kilometre cars): the reference's
 arithmetic loses precision there, and parity means losing it the same way; the culling proof's
 tolerances scale with the distances involved, not with a scene size it assumes.
-CPU part: oracle against the LIVE reference.  GPU part: product against the oracle."""
+CPU part: oracle against the reference's recorded outputs (tests/golden/make_reference_digests.py).  GPU part: product against the oracle."""
 import os
 
 import numpy as np
@@ -13,7 +13,7 @@ from oracle import oracle
 
 from . import configs as K
 from . import scenes_gen as G
-from .parity import compare_dense
+from .parity import assert_matches_recorded, compare_dense, recorded, result_digests
 
 CASES = {
     "canyon_utm": ("simple_street_canyon_with_cars.hrt", "C3", [5e5, 4e6, 300.0], 1.0),
@@ -38,12 +38,9 @@ def _case(tmp, name):
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_oracle_equals_reference_scaled(ref_lib, name, tmp_path):
-    c = _case(tmp_path, name)
-    ref = abi.run_compute_paths(ref_lib, *K.args(c))
-    got = oracle.compute_paths(*K.args(c))
-    st = compare_dense(got, ref)
-    assert all(v == 0 for v in st.values()), st
+def test_oracle_equals_reference_scaled(name, tmp_path):
+    got = oracle.compute_paths(*K.args(_case(tmp_path, name)))
+    assert_matches_recorded(result_digests(got, got["extras"]["normals"]), recorded("scaled_scenes", name), name)
 
 
 @pytest.mark.gpu
