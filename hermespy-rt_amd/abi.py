@@ -293,3 +293,44 @@ def run_compute_paths_list(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_gh
         lib.hrt_path_list_free(C.byref(pl))
         free_scene(scene)
     return out
+
+
+CHANNEL_LOS, CHANNEL_SCATTER = 1, 2   # hrt_channel_spec.parts
+
+
+class ChannelSpec(C.Structure):
+    """include/hermespy_rt.h hrt_channel_spec"""
+    _fields_ = [("f0_hz", C.c_double), ("df_hz", C.c_double), ("num_freqs", C.c_uint32),
+                ("t0_s", C.c_double), ("dt_s", C.c_double), ("num_times", C.c_uint32),
+                ("parts", C.c_uint32)]
+
+
+def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, parts=None):
+    if parts is None:
+        parts = (CHANNEL_LOS if los else 0) | (CHANNEL_SCATTER if scatter else 0)
+    return ChannelSpec(float(f0), float(df), int(num_freqs), float(t0), float(dt), int(num_times), int(parts))
+
+
+def run_compute_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                        stats=None):
+    """hrt_compute_channel through ctypes -> complex64 [nrx, ntx, 2, num_times, num_freqs].  Raises
+    RuntimeError("hrt_compute_channel failed (<rc>): ...") on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    out = np.zeros((nrx, ntx, 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1)), np.complex64)
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_channel(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
+                                     C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+                                     C.byref(spec), out.ctypes.data_as(c_float_p),
+                                     C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return out

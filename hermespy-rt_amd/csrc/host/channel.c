@@ -1,0 +1,260 @@
+/* channel.c -- channel frequency responses from traced paths, on the device (include/hrt_device.h:
+ * hrt_channel; include/hermespy_rt.h: hrt_compute_channel).
+ *
+ *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
+ *
+ * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
+ * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
+ * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip;
+ * the drop-in entry is built like hrt_compute_paths_list (path_list.c): the same workspace budget, pool and
+ * batch rule, device launch tables, the same void-step retry; one device output accumulated over the batches
+ * and one small download at the end.
+ */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "hrt_internal.h"
+#include "../hrt_channel.h"
+
+#define HRT_CH_MAX_POINTS (1u << 20)         /* num_freqs * num_times */
+#define HRT_CH_TARGET_GROUPS 8192u           /* waves of the partial kernel worth launching (32 per CU) */
+#define HRT_CH_MIN_CHUNK 512u                /* records of one TX segment per chunk, at least */
+#define HRT_CH_PARTIAL_MAX (512ull << 20)    /* partial sums beyond one chunk per tile: at most this */
+
+static uint64_t ch_round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+static int spec_check(const hrt_channel_spec *spec)
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_channel: NULL spec");
+    if (spec->num_freqs == 0 || spec->num_times == 0)
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: num_freqs and num_times must be > 0");
+    if ((uint64_t)spec->num_freqs * spec->num_times > HRT_CH_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: num_freqs * num_times = %llu > 2^20",
+                        (unsigned long long)spec->num_freqs * spec->num_times);
+    if (spec->parts == 0 || (spec->parts & ~(uint32_t)(HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)))
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: parts 0x%x (HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)", spec->parts);
+    if (!isfinite(spec->f0_hz) || !isfinite(spec->df_hz) || !isfinite(spec->t0_s) || !isfinite(spec->dt_s))
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: f0, df, t0 and dt must be finite");
+    return HRT_OK;
+}
+
+/* the tiling of one call: a pure function of the problem, the shard and the spec (so the sums, and their
+ * order, do not depend on anything else) */
+static int ch_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, hrt_layout *L,
+                   hrt_kchannel *K, uint64_t *bytes)
+{
+    int rc = spec_check(spec);
+    if (rc) return rc;
+    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_channel: NULL argument");
+    if ((rc = hrt_layout_query(p, s, L))) return rc;
+    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
+    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_channel: num_rx * num_tx = %llu > 65535",
+                                        (unsigned long long)links);
+    memset(K, 0, sizeof *K);
+    K->cap = L->cap; K->off_counts = L->off_counts; K->off_los = L->off_los; K->off_hits = L->off_hits;
+    K->hit_block_bytes = L->hit_block_bytes; K->off_recs = L->off_recs; K->rec_block_bytes = L->rec_block_bytes;
+    K->off_masks = L->off_masks;
+    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
+    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    K->K = spec->num_freqs; K->T = spec->num_times;
+    K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
+    K->rows = K->K1 * K->T;
+    K->tiles = (K->rows + HRT_CH_ROWS - 1) / HRT_CH_ROWS;
+    K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
+    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
+    const uint64_t tile_bytes = (uint64_t)HRT_CH_TILE_FLOATS * 4u, per_chunk = links * K->tiles * tile_bytes;
+    uint64_t nch = 0;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
+        /* enough waves to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, and partial sums
+         * of at most HRT_CH_PARTIAL_MAX (but one chunk always) */
+        const uint64_t groups = links * K->tiles;
+        nch = (HRT_CH_TARGET_GROUPS + groups - 1) / groups;
+        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
+        if (nch > by_recs) nch = by_recs;
+        if (nch > HRT_CH_PARTIAL_MAX / per_chunk) nch = HRT_CH_PARTIAL_MAX / per_chunk;
+        if (nch < 1) nch = 1;
+    }
+    K->nchunks = (uint32_t)nch;
+    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
+    *bytes = seg_bytes + nch * per_chunk;
+    return HRT_OK;
+}
+
+int hrt_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, uint64_t *out)
+{
+    hrt_layout L;
+    hrt_kchannel K;
+    uint64_t bytes = 0;
+    int rc = ch_plan(p, s, spec, &L, &K, &bytes);
+    if (rc) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_channel_scratch_bytes: NULL out");
+    *out = bytes;
+    return HRT_OK;
+}
+
+int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_channel_spec *spec,
+                void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream)
+{
+    hrt_layout L;
+    hrt_kchannel K;
+    uint64_t need = 0;
+    int rc = ch_plan(p, s, spec, &L, &K, &need);
+    if (rc) return rc;
+    if (!d_workspace || !d_out || !d_scratch)
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: NULL workspace, scratch or output");
+    if (scratch_bytes < need)
+        return hrt_fail(HRT_E_INVALID, "hrt_channel: scratch of %llu bytes, %llu needed (hrt_channel_scratch_bytes)",
+                        (unsigned long long)scratch_bytes, (unsigned long long)need);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "hrt_channel: accumulate must be 0 or 1");
+    K.ws = (const uint8_t *)d_workspace;
+    K.accumulate = (uint32_t)accumulate;
+    K.seg = (uint32_t *)d_scratch;
+    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_channel(&K, stream), "channel kernels");
+    return HRT_OK;
+}
+
+static uint64_t ch_env_u64(const char *name, uint64_t dflt)
+{
+    const char *v = getenv(name);
+    return (v && *v) ? (uint64_t)strtoull(v, NULL, 10) : dflt;
+}
+
+int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                        const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                        const hrt_channel_spec *spec, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = spec_check(spec);
+    if (rc) return rc;
+    if (!scene || !out || !rx_pos || !tx_pos || !rx_vel || !tx_vel)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel: NULL argument");
+    if (nrx == 0 || ntx == 0 || np == 0 || nb == 0)
+        return hrt_fail(HRT_E_INVALID, "num_rx, num_tx, num_rays and num_bounces must be > 0");
+    if (nb > 65535) return hrt_fail(HRT_E_INVALID, "num_bounces > 65535 is not supported");
+
+    const int device = (int)ch_env_u64("HRT_DEVICE", 0);
+    hrt_stats st;
+    memset(&st, 0, sizeof st);
+    st.device = device;
+    st.num_devices = 1;
+    hrt_problem *prob = NULL;
+    rc = hrt_problem_create_for(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, device, (uint64_t)ntx * np,
+                                &prob);
+    if (rc) return rc;
+    st.t_setup_s = hrt_now_s() - t_begin;
+
+    dev_ctx wc;   /* the drop-in's worker buffers: workspace + staging, pooled between calls */
+    memset(&wc, 0, sizeof wc);
+    int pool_taken = 0;
+    void *d_out = NULL, *d_scratch = NULL;
+    uint64_t scratch_bytes = 0;
+    const uint64_t out_bytes = (uint64_t)nrx * ntx * 2u * spec->num_times * spec->num_freqs * 8u;
+    double t_dev = 0.0, t_dirs = 0.0;
+
+    /* batches of round-robin shards so that one workspace fits the budget (as path_list.c) */
+    uint64_t free_b = 0, total_b = 0;
+    if ((rc = hrt_device_mem_info(device, &free_b, &total_b))) goto done;
+    uint64_t budget = ch_env_u64("HRT_WORKSPACE_BYTES", 0);
+    if (!budget) {
+        budget = free_b / 2;
+        if (budget > (16ull << 30)) budget = 16ull << 30;
+    }
+    uint32_t G = 1, G_budget = 0;
+    hrt_layout L;
+    for (;;) {
+        hrt_shard s = {np, 0, G, 0, (uint32_t)nb};
+        rc = hrt_layout_query(prob, &s, &L);
+        const int fits = rc == HRT_OK && L.total_bytes + hrt_shard_num_local(&s) * 16 <= budget;
+        if (fits && !G_budget) G_budget = G;
+        if (fits && (G_budget > 2u || hrt_batch_fits_pool(L.total_bytes, hrt_shard_num_local(&s) + 64, L.cap))) break;
+        if (rc != HRT_OK && rc != HRT_E_CAPACITY) goto done;
+        if ((uint64_t)G * 4096 >= np) {
+            if (rc == HRT_OK) break;
+            goto done;
+        }
+        G *= 2;
+    }
+    wc.prob = prob; wc.nrx = nrx; wc.ntx = ntx; wc.np = np; wc.nb = nb; wc.G = G; wc.index = 0; wc.count = 1;
+    wc.device = device;
+    pool_taken = hrt_pool_begin();
+    wc.use_pool = pool_taken;
+    if ((rc = hrt_worker_alloc(&wc))) { wc.rc = rc; goto done; }
+    /* scratch: the largest any batch needs (batch 0 has the most local rays) */
+    for (uint32_t g = 0; g < G; ++g) {
+        hrt_shard s = {np, g, G, 0, (uint32_t)nb};
+        if (hrt_shard_num_local(&s) == 0) continue;
+        uint64_t b = 0;
+        if ((rc = hrt_channel_scratch_bytes(prob, &s, spec, &b))) goto done;
+        if (b > scratch_bytes) scratch_bytes = b;
+    }
+    if ((rc = hrt_device_malloc(device, &d_out, out_bytes))) goto done;
+    if ((rc = hrt_device_malloc(device, &d_scratch, scratch_bytes))) goto done;
+
+    for (uint32_t g = 0, first = 1; g < G; ++g) {
+        hrt_shard s = {np, g, G, 0, (uint32_t)nb};
+        if (hrt_shard_num_local(&s) == 0) continue;
+        if ((rc = hrt_layout_query(prob, &s, &L))) goto done;
+        double t0 = hrt_now_s();
+        if ((rc = hrt_launch_dirs_device(&s, (float *)wc.w.d_dirs, device, NULL, NULL))) goto done;
+        if ((rc = hrt_launch_order_device(&s, (uint32_t *)wc.w.d_order, device, NULL))) goto done;
+        t_dirs += hrt_now_s() - t0;
+        t0 = hrt_now_s();
+        for (int attempt = 0;; ++attempt) {
+            if ((rc = hrt_trace(prob, &s, (const float *)wc.w.d_dirs, (const uint32_t *)wc.w.d_order, wc.w.d_ws,
+                                L.total_bytes, NULL, NULL))) goto done;
+            if ((rc = hrt_device_sync(device, NULL))) goto done;
+            if ((rc = hrt_device_download(device, wc.w.h_counts, (const uint8_t *)wc.w.d_ws + L.off_counts,
+                                          (nb + 2) * 4))) goto done;
+            /* (a fused launch timed out on a shared GPU: the step is void, once more unfused -- compute_paths.c) */
+            if (!(wc.w.h_counts[nb + 1] & HRT_ERR_VOID) || attempt >= 2 || !hrt_void_step_retry(wc.w.h_counts[nb + 1]))
+                break;
+        }
+        if (wc.w.h_counts[nb + 1] != 0) {
+            rc = hrt_fail(HRT_E_HIP, "device reported internal error flags %u", wc.w.h_counts[nb + 1]);
+            goto done;
+        }
+        {
+            hrt_stats bs;
+            hrt_work_from_counts(prob, &s, wc.w.h_counts, &bs);
+            for (size_t b = 0; b <= nb && b < 34; ++b) st.live[b] += bs.live[b];
+            st.records += bs.records;
+            st.tests += bs.tests - (g ? (uint64_t)nrx * ntx * prob->num_tri : 0);
+        }
+        /* batch 0 is rank 0 of the launch set: it adds the LoS term; the others add their records */
+        if ((rc = hrt_channel(prob, &s, wc.w.d_ws, spec, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1,
+                              NULL))) goto done;
+        first = 0;
+        if ((rc = hrt_device_sync(device, NULL))) goto done;
+        t_dev += hrt_now_s() - t0;
+    }
+    {
+        const double t0 = hrt_now_s();
+        if ((rc = hrt_device_download(device, out, d_out, out_bytes))) goto done;
+        st.t_readback_s = hrt_now_s() - t0;
+    }
+    st.num_batches = G;
+    st.dev_id[0] = device;
+    st.dev_batches[0] = G;
+    st.t_launch_dirs_s = t_dirs;
+    st.t_device_s = t_dev;
+    st.dev_t_device_s[0] = t_dev;
+    st.dev_t_readback_s[0] = st.t_readback_s;
+    st.t_total_s = hrt_now_s() - t_begin;
+    if (stats) *stats = st;
+    rc = HRT_OK;
+
+done:
+    if (d_scratch) hrt_device_free(device, d_scratch);
+    if (d_out) hrt_device_free(device, d_out);
+    if (wc.w.d_ws || wc.w.ray) {
+        wc.rc = rc;
+        hrt_worker_release(&wc);
+    }
+    hrt_pool_end(pool_taken);
+    hrt_problem_destroy(prob);
+    return rc;
+}

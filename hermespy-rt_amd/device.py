@@ -377,6 +377,44 @@ class Tracer:
                 out[k] = torch.empty(shape, dtype=dt, device=self.device)
         return out
 
+    # ------------------------------------------------------------------ channel
+    def channel(self, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
+                accumulate=False):
+        """Channel frequency response of the last trace, formed on the device (hrt_channel):
+
+            H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)),  f_k = f0 + k df, t_m = t0 + m dt
+
+        over the LoS entry (los=True; added by shard rank 0 only, so the shards of one launch set sum to the whole
+        channel) and every scatter record (scatter=True).  f_k is an absolute frequency (the amplitudes carry no
+        carrier phase).  Returns a complex64 tensor [nrx, ntx, 2, num_times, num_freqs] (pol 0 = TE, 1 = TM) on
+        the device, enqueued on the current stream; `out` (such a tensor) is written in place, or added to with
+        accumulate=True.  The error word is read first (counts()): a void step is traced again."""
+        torch = self.torch
+        self.counts()
+        spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
+        need = C.c_uint64(0)
+        _lib.check(self.L.hrt_channel_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need)),
+                   "hrt_channel_scratch_bytes")
+        shape = (self.nrx, self.ntx, 2, int(num_times), int(num_freqs))
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            scratch = getattr(self, "_ch_scratch", None)
+            if scratch is None or scratch.numel() < int(need.value):
+                scratch = self._ch_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
+                                                         device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.L.hrt_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
+                                      C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
+                                      C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream)),
+                   "hrt_channel")
+        return out
+
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):
         """Assemble the reference's dense [rx][tx][b][p] scatter arrays on the host from the

@@ -176,6 +176,33 @@ int hrt_compute_paths_list(Scene *scene, const Vec3 *rx_positions, const Vec3 *t
                            hrt_stats *stats);
 void hrt_path_list_free(hrt_path_list *list);
 
+/* Channel frequency responses of the traced paths, formed on the device (include/hrt_device.h: hrt_channel).
+ * For every (rx, tx), polarisation pol (0 = TE, 1 = TM), time sample m < num_times and frequency k < num_freqs:
+ *     H[rx][tx][pol][m][k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)),  f_k = f0 + k df (Hz),  t_m = t0 + m dt (s)
+ * over the paths of that link the caller selects in `parts`:
+ *   HRT_CHANNEL_LOS      the LoS entry as the dense LoS output defines it: coincident a = 1, tau = nu = 0; blocked
+ *                        a = 0; clear a = HRT_LOS_A (TE = TM, real), tau = HRT_LOS_TAU, nu = HRT_LOS_FS;
+ *   HRT_CHANNEL_SCATTER  every scatter record of every bounce: a = the record's a_te / a_tm, tau = its tau,
+ *                        nu = freq_shift as hrt_compute_paths_list reports it; blocked records add nothing.
+ * The inputs of the sum are bit for bit the floats compute_paths returns.  The amplitudes carry no carrier phase
+ * (the reference accumulates gains and delays separately), so f_k is an ABSOLUTE frequency: the baseband response
+ * of an OFDM grid is f0 = carrier + offset of the first subcarrier.
+ * out: complex [num_rx][num_tx][2][num_times][num_freqs], re/im interleaved (numpy complex64).
+ * hrt_compute_channel traces like hrt_compute_paths_list (same batches, same device launch tables) and copies
+ * only `out` back.  HRT_E_INVALID: num_freqs or num_times 0, num_freqs * num_times > 2^20, parts 0 or with unknown
+ * bits, f0 / df / t0 / dt not finite. */
+#define HRT_CHANNEL_LOS 1u
+#define HRT_CHANNEL_SCATTER 2u
+typedef struct {
+    double f0_hz, df_hz;  uint32_t num_freqs;   /* f_k = f0 + k*df */
+    double t0_s, dt_s;    uint32_t num_times;   /* t_m = t0 + m*dt */
+    uint32_t parts;                             /* HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER */
+} hrt_channel_spec;
+int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                        const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                        size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                        float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

@@ -287,6 +287,22 @@ int hrt_rccl_comm_create(const hrt_rccl_id *id, int world, int rank, int device,
 int hrt_rccl_comm_destroy(void *comm);
 int hrt_gather_rccl(hrt_gather *g, void *comm, const void *d_workspace, void *stream, int self_loop);
 
+/* ---- channel frequency responses from the traced paths (csrc/host/channel.c, csrc/hrt_channel.hip) ----
+ * H[rx][tx][pol][m][k] as hermespy_rt.h defines it (hrt_channel_spec, hrt_compute_channel), formed from the
+ * workspace of a finished hrt_trace (its counts too, on the device: no host synchronisation), asynchronous on
+ * `stream`.  accumulate = 0 overwrites d_out, 1 adds to it.  Only shard rank 0 adds the LoS term, so the
+ * outputs of the shards of one launch set sum to the whole channel.  If the trace's error word
+ * (counts[num_bounces + 1]) is nonzero the output is undefined: check it first, as before reading records.
+ * Deterministic: partial sums go to the caller's scratch (hrt_channel_scratch_bytes) and are reduced in a fixed
+ * order, no floating-point atomics; two calls with the same inputs give the same bits.
+ * HRT_E_INVALID, before the device is touched: num_freqs or num_times 0, num_freqs * num_times > 2^20, parts 0
+ * or with unknown bits, f0 / df / t0 / dt not finite, scratch too small. */
+int hrt_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec,
+                              uint64_t *out);
+int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                const hrt_channel_spec *spec, void *d_scratch, uint64_t scratch_bytes,
+                float *d_out, int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
