@@ -334,3 +334,53 @@ def run_compute_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, 
     if rc != 0:
         raise RuntimeError("hrt_compute_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
     return out
+
+
+class ArraySpec(C.Structure):
+    """include/hrt_device.h hrt_array_spec (the element pointers are device pointers)"""
+    _fields_ = [("num_rx_elements", C.c_uint32), ("num_tx_elements", C.c_uint32),
+                ("rx_elements", C.c_void_p), ("tx_elements", C.c_void_p), ("array_frequency_hz", C.c_double)]
+
+
+def elements(e, name):
+    """element offsets as a contiguous float32 [n, 3] numpy array (n >= 0; the library checks the limits)"""
+    a = np.ascontiguousarray(np.asarray(e, np.float32))
+    if a.ndim == 1 and a.size == 3:
+        a = a.reshape(1, 3)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s must have shape (n, 3), got %s" % (name, a.shape))
+    return a
+
+
+def run_compute_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                              rx_elements, tx_elements, array_frequency=None, stats=None):
+    """hrt_compute_array_channel through ctypes -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_freqs]
+    (array_frequency defaults to the carrier).  Raises RuntimeError("hrt_compute_array_channel failed (<rc>): ...")
+    on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
+    nr, nt = re.shape[0], te.shape[0]
+    V3 = C.POINTER(Vec3)
+    fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
+    shape = (nrx, ntx, max(nr, 1), max(nt, 1), 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    pts = nr * nt * int(spec.num_times) * int(spec.num_freqs)
+    out = np.zeros(shape if 0 < pts <= (1 << 24) else (1,), np.complex64)
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_array_channel(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
+                                           C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+                                           C.byref(spec), re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3),
+                                           C.c_size_t(nt), C.c_double(fa), out.ctypes.data_as(c_float_p),
+                                           C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_array_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return out

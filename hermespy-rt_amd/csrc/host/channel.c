@@ -1,5 +1,5 @@
 /* channel.c -- channel frequency responses from traced paths, on the device (include/hrt_device.h:
- * hrt_channel; include/hermespy_rt.h: hrt_compute_channel).
+ * hrt_channel, hrt_array_channel; include/hermespy_rt.h: hrt_compute_channel, hrt_compute_array_channel).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "hrt_internal.h"
+#include "../hrt_array_channel.h"
 #include "../hrt_channel.h"
 
 #define HRT_CH_MAX_POINTS (1u << 20)         /* num_freqs * num_times */
@@ -123,19 +124,28 @@ static uint64_t ch_env_u64(const char *name, uint64_t dflt)
     return (v && *v) ? (uint64_t)strtoull(v, NULL, 10) : dflt;
 }
 
-int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
-                        const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
-                        const hrt_channel_spec *spec, float *out, hrt_stats *stats)
-{
-    const double t_begin = hrt_now_s();
-    int rc = spec_check(spec);
-    if (rc) return rc;
-    if (!scene || !out || !rx_pos || !tx_pos || !rx_vel || !tx_vel)
-        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel: NULL argument");
-    if (nrx == 0 || ntx == 0 || np == 0 || nb == 0)
-        return hrt_fail(HRT_E_INVALID, "num_rx, num_tx, num_rays and num_bounces must be > 0");
-    if (nb > 65535) return hrt_fail(HRT_E_INVALID, "num_bounces > 65535 is not supported");
+/* One drop-in call: what hrt_compute_channel and hrt_compute_array_channel share.  `scratch_bytes` and `run` are
+ * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
+ * batch, and `run` finds it at d_const. */
+typedef struct ch_job ch_job;
+struct ch_job {
+    const hrt_channel_spec *spec;
+    uint64_t out_bytes;
+    const void *h_const;
+    uint64_t const_bytes;
+    void *d_const;
+    int (*scratch_bytes)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out);
+    int (*run)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+               uint64_t scratch_bytes, float *d_out, int accumulate);
+    uint32_t nr, nt;   /* the array call's element counts (hrt_compute_array_channel) */
+    double fa;
+};
 
+static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
+                      float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, float *out,
+                      hrt_stats *stats, double t_begin)
+{
+    int rc;
     const int device = (int)ch_env_u64("HRT_DEVICE", 0);
     hrt_stats st;
     memset(&st, 0, sizeof st);
@@ -152,8 +162,9 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
     int pool_taken = 0;
     void *d_out = NULL, *d_scratch = NULL;
     uint64_t scratch_bytes = 0;
-    const uint64_t out_bytes = (uint64_t)nrx * ntx * 2u * spec->num_times * spec->num_freqs * 8u;
+    const uint64_t out_bytes = job->out_bytes;
     double t_dev = 0.0, t_dirs = 0.0;
+    job->d_const = NULL;
 
     /* batches of round-robin shards so that one workspace fits the budget (as path_list.c) */
     uint64_t free_b = 0, total_b = 0;
@@ -183,12 +194,16 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
     pool_taken = hrt_pool_begin();
     wc.use_pool = pool_taken;
     if ((rc = hrt_worker_alloc(&wc))) { wc.rc = rc; goto done; }
+    if (job->const_bytes) {
+        if ((rc = hrt_device_malloc(device, &job->d_const, job->const_bytes))) goto done;
+        if ((rc = hrt_device_upload(device, job->d_const, job->h_const, job->const_bytes))) goto done;
+    }
     /* scratch: the largest any batch needs (batch 0 has the most local rays) */
     for (uint32_t g = 0; g < G; ++g) {
         hrt_shard s = {np, g, G, 0, (uint32_t)nb};
         if (hrt_shard_num_local(&s) == 0) continue;
         uint64_t b = 0;
-        if ((rc = hrt_channel_scratch_bytes(prob, &s, spec, &b))) goto done;
+        if ((rc = job->scratch_bytes(job, prob, &s, &b))) goto done;
         if (b > scratch_bytes) scratch_bytes = b;
     }
     if ((rc = hrt_device_malloc(device, &d_out, out_bytes))) goto done;
@@ -225,8 +240,8 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
             st.tests += bs.tests - (g ? (uint64_t)nrx * ntx * prob->num_tri : 0);
         }
         /* batch 0 is rank 0 of the launch set: it adds the LoS term; the others add their records */
-        if ((rc = hrt_channel(prob, &s, wc.w.d_ws, spec, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1,
-                              NULL))) goto done;
+        if ((rc = job->run(job, prob, &s, wc.w.d_ws, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1)))
+            goto done;
         first = 0;
         if ((rc = hrt_device_sync(device, NULL))) goto done;
         t_dev += hrt_now_s() - t0;
@@ -250,11 +265,239 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
 done:
     if (d_scratch) hrt_device_free(device, d_scratch);
     if (d_out) hrt_device_free(device, d_out);
+    if (job->d_const) hrt_device_free(device, job->d_const);
+    job->d_const = NULL;
     if (wc.w.d_ws || wc.w.ray) {
         wc.rc = rc;
         hrt_worker_release(&wc);
     }
     hrt_pool_end(pool_taken);
     hrt_problem_destroy(prob);
+    return rc;
+}
+
+static int ch_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    return hrt_channel_scratch_bytes(p, s, j->spec, out);
+}
+
+static int ch_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, float *d_out, int accumulate)
+{
+    return hrt_channel(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+static int ch_drop_in_check(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                            const Vec3 *tx_vel, size_t nrx, size_t ntx, size_t np, size_t nb, const void *out,
+                            const char *who)
+{
+    if (!scene || !out || !rx_pos || !tx_pos || !rx_vel || !tx_vel) return hrt_fail(HRT_E_INVALID, "%s: NULL argument", who);
+    if (nrx == 0 || ntx == 0 || np == 0 || nb == 0)
+        return hrt_fail(HRT_E_INVALID, "num_rx, num_tx, num_rays and num_bounces must be > 0");
+    if (nb > 65535) return hrt_fail(HRT_E_INVALID, "num_bounces > 65535 is not supported");
+    return HRT_OK;
+}
+
+int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                        const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                        const hrt_channel_spec *spec, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = spec_check(spec);
+    if (rc) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, "hrt_compute_channel")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ch_job_scratch;
+    job.run = ch_job_run;
+    return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ antenna arrays (hrt_array_channel) */
+
+#define HRT_AC_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_AC_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
+#define HRT_SPEED_OF_LIGHT 299792458.0
+
+/* the checks of an array call that need no problem (device pointers are not read) */
+static int array_check(const hrt_channel_spec *spec, const hrt_array_spec *a)
+{
+    int rc = spec_check(spec);
+    if (rc) return rc;
+    if (!a) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL arrays");
+    if (a->num_rx_elements < 1 || a->num_rx_elements > HRT_AC_MAX_ELEMENTS || a->num_tx_elements < 1 ||
+        a->num_tx_elements > HRT_AC_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: %u RX and %u TX elements (1 .. %u each)",
+                        a->num_rx_elements, a->num_tx_elements, HRT_AC_MAX_ELEMENTS);
+    const uint64_t pts = (uint64_t)a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_freqs;
+    if (pts > HRT_AC_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: Nr * Nt * num_times * num_freqs = %llu > 2^24",
+                        (unsigned long long)pts);
+    if (!isfinite(a->array_frequency_hz) || !(a->array_frequency_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: the array frequency must be finite and > 0");
+    if (!a->rx_elements || !a->tx_elements) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL element offsets");
+    return HRT_OK;
+}
+
+/* the tiling of one array call: a pure function of the problem, the shard, the spec and the array sizes */
+static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, const hrt_array_spec *a,
+                   hrt_karray *K, uint64_t *bytes)
+{
+    int rc = array_check(spec, a);
+    if (rc) return rc;
+    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL argument");
+    hrt_layout L;
+    if ((rc = hrt_layout_query(p, s, &L))) return rc;
+    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
+    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: num_rx * num_tx = %llu > 65535",
+                                        (unsigned long long)links);
+    if (links * 2u * a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_freqs >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: more than 2^39 outputs");
+    memset(K, 0, sizeof *K);
+    K->cap = L.cap; K->off_counts = L.off_counts; K->off_los = L.off_los; K->off_hits = L.off_hits;
+    K->hit_block_bytes = L.hit_block_bytes; K->off_recs = L.off_recs; K->rec_block_bytes = L.rec_block_bytes;
+    K->off_masks = L.off_masks;
+    K->num_paths = s->num_paths;
+    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
+    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
+    K->nr = a->num_rx_elements; K->nt = a->num_tx_elements; K->npairs = K->nr * K->nt;
+    K->K = spec->num_freqs; K->T = spec->num_times;
+    K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
+    K->rows = K->K1 * K->T;
+    K->pblocks = (K->npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
+    K->cblocks = (K->rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
+    K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
+    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
+    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
+    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->K * 8u;
+    uint64_t nch = 0;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
+        /* enough workgroups to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at
+         * most HRT_AC_PARTIAL_MAX (but one chunk always), and a grid y of at most 65535 */
+        const uint64_t groups = links * K->pblocks * K->cblocks;
+        nch = (HRT_AC_TARGET_GROUPS + groups - 1) / groups;
+        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
+        if (nch > by_recs) nch = by_recs;
+        if (nch > HRT_AC_PARTIAL_MAX / per_chunk) nch = HRT_AC_PARTIAL_MAX / per_chunk;
+        if (nch > 65535u) nch = 65535u;
+        if (nch < 1) nch = 1;
+    }
+    K->nchunks = (uint32_t)nch;
+    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
+    *bytes = seg_bytes + nch * per_chunk;
+    return HRT_OK;
+}
+
+int hrt_array_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec,
+                                    const hrt_array_spec *arrays, uint64_t *out)
+{
+    hrt_karray K;
+    uint64_t bytes = 0;
+    int rc = ac_plan(p, s, spec, arrays, &K, &bytes);
+    if (rc) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_array_channel_scratch_bytes: NULL out");
+    *out = bytes;
+    return HRT_OK;
+}
+
+int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                      const hrt_channel_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
+                      uint64_t scratch_bytes, float *d_out, int accumulate, void *stream)
+{
+    hrt_karray K;
+    uint64_t need = 0;
+    int rc = ac_plan(p, s, spec, arrays, &K, &need);
+    if (rc) return rc;
+    if (!d_workspace || !d_out || !d_scratch)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL workspace, scratch or output");
+    if (scratch_bytes < need)
+        return hrt_fail(HRT_E_INVALID,
+                        "hrt_array_channel: scratch of %llu bytes, %llu needed (hrt_array_channel_scratch_bytes)",
+                        (unsigned long long)scratch_bytes, (unsigned long long)need);
+    if (accumulate != 0 && accumulate != 1)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: accumulate must be 0 or 1");
+    K.ws = (const uint8_t *)d_workspace;
+    K.accumulate = (uint32_t)accumulate;
+    K.rx_el = arrays->rx_elements;
+    K.tx_el = arrays->tx_elements;
+    K.seg = (const uint32_t *)d_scratch;
+    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_array_channel(&K, stream), "array channel kernels");
+    return HRT_OK;
+}
+
+/* the array spec of a drop-in call: the offsets uploaded by ch_compute (rx then tx) */
+static hrt_array_spec ac_job_arrays(const ch_job *j)
+{
+    hrt_array_spec a;
+    a.num_rx_elements = j->nr;
+    a.num_tx_elements = j->nt;
+    a.rx_elements = (const float *)j->d_const;
+    a.tx_elements = (const float *)j->d_const + 3u * j->nr;
+    a.array_frequency_hz = j->fa;
+    return a;
+}
+
+static int ac_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_channel_scratch_bytes(p, s, j->spec, &a, out);
+}
+
+static int ac_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, float *d_out, int accumulate)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_channel(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                              const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                              const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                              size_t nt, double f_a, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    if (nr > HRT_AC_MAX_ELEMENTS || nt > HRT_AC_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: %zu RX and %zu TX elements (1 .. %u each)", nr, nt,
+                        HRT_AC_MAX_ELEMENTS);
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    int rc = array_check(spec, &a);
+    if (rc) return rc;
+    for (size_t i = 0; i < nr; ++i)
+        if (!isfinite(rx_el[i].x) || !isfinite(rx_el[i].y) || !isfinite(rx_el[i].z))
+            return hrt_fail(HRT_E_INVALID, "hrt_array_channel: RX element %zu is not finite", i);
+    for (size_t j = 0; j < nt; ++j)
+        if (!isfinite(tx_el[j].x) || !isfinite(tx_el[j].y) || !isfinite(tx_el[j].z))
+            return hrt_fail(HRT_E_INVALID, "hrt_array_channel: TX element %zu is not finite", j);
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_array_channel")))
+        return rc;
+    float *el = (float *)malloc((nr + nt) * 3u * sizeof(float));
+    if (!el) return hrt_fail(HRT_E_NOMEM, "out of host memory");
+    for (size_t i = 0; i < nr; ++i) { el[3 * i] = rx_el[i].x; el[3 * i + 1] = rx_el[i].y; el[3 * i + 2] = rx_el[i].z; }
+    for (size_t j = 0; j < nt; ++j) {
+        float *q = el + 3u * (nr + j);
+        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
+    }
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.h_const = el;
+    job.const_bytes = (nr + nt) * 3u * sizeof(float);
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.nr = (uint32_t)nr;
+    job.nt = (uint32_t)nt;
+    job.fa = f_a;
+    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+    free(el);
     return rc;
 }

@@ -37,6 +37,8 @@ typedef struct {
 } hrt_kchannel;
 
 int hrt_hip_launch_channel(const hrt_kchannel *P, void *stream);
+/* hrt_channel_segments_kernel alone: P->seg[b][t] for every bounce b and t <= ntx */
+int hrt_hip_launch_channel_segments(const hrt_kchannel *P, void *stream);
 
 #ifdef __cplusplus
 }

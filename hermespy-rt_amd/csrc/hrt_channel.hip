@@ -221,3 +221,11 @@ extern "C" int hrt_hip_launch_channel(const hrt_kchannel *P, void *stream)
     hipLaunchKernelGGL(hrt_channel_reduce_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
     return (int)hipGetLastError();
 }
+
+// the segments kernel alone (the array channel, csrc/hrt_array_channel.hip, reads the same TX segments; only the
+// fields it reads -- ws, cap, off_counts, off_hits, hit_block_bytes, nb, ntx, num_local, seg -- need be set)
+extern "C" int hrt_hip_launch_channel_segments(const hrt_kchannel *P, void *stream)
+{
+    hipLaunchKernelGGL(hrt_channel_segments_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *P);
+    return (int)hipGetLastError();
+}

@@ -53,6 +53,7 @@
 #include <stdlib.h>
 
 #include "hrt_kparams.h"
+#include "hrt_launch_dir.h"
 #include "hrt_libm.h"
 
 #pragma clang fp contract(off)
@@ -3410,7 +3411,8 @@ __global__ __launch_bounds__(HRT_BLOCK) void hrt_los_big_kernel(const hrt_kparam
 // Launch directions on the device.  The reference evaluates
 //   k = p + .5f; phi = (float)acos(1.f - 2.f*k/N); theta = pi_f*(1.f + sqrtf(5.f))*k   (float)
 //   d = ((float)(cos(theta)*sin(phi)), (float)(sin(theta)*sin(phi)), (float)cos(phi))   (double libm)
-// (src/compute_paths.c:444-451).  The float steps are exact IEEE operations and identical here.
+// (src/compute_paths.c:444-451; evaluated by hrt_launch_dir, csrc/hrt_launch_dir.h, which the array channel
+// shares).  The float steps are exact IEEE operations and identical here.
 // The double-precision acos/cos/sin are the DEVICE library's, which may differ from glibc's in
 // the last bits -- harmless unless the value is about to be rounded to float right next to a
 // rounding boundary.  So every double -> float rounding is checked: if the double lies within
@@ -3434,21 +3436,13 @@ __global__ void hrt_launch_dirs_kernel(uint64_t num_paths, uint32_t rank, uint32
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= num_local) return;
-    const uint64_t p = ((i / chunk) * count + rank) * chunk + i % chunk;
-    const float k = (float)p + .5f;
-    const float arg = 1.f - 2.f * k / (float)num_paths;
-    const double ph_d = acos((double)arg);
-    const float phi = (float)ph_d;
-    const float theta = kPi * (1.f + sqrtf(5.f)) * k;
-    const double sp = sin((double)phi);
-    const double x = cos((double)theta) * sp, y = sin((double)theta) * sp, z = cos((double)phi);
-    const float fx = (float)x, fy = (float)y, fz = (float)z;
-    dirs[3 * i] = fx;
-    dirs[3 * i + 1] = fy;
-    dirs[3 * i + 2] = fz;
+    const hrt_launch_dir_t d = hrt_launch_dir(hrt_shard_path(i, chunk, count, rank), num_paths);
+    dirs[3 * i] = d.fx;
+    dirs[3 * i + 1] = d.fy;
+    dirs[3 * i + 2] = d.fz;
     // the products inherit ~2 ulp from each factor: still far inside the guard
-    if (near_float_boundary(ph_d, phi) || near_float_boundary(x, fx) ||
-        near_float_boundary(y, fy) || near_float_boundary(z, fz)) {
+    if (near_float_boundary(d.ph_d, d.phi) || near_float_boundary(d.x, d.fx) ||
+        near_float_boundary(d.y, d.fy) || near_float_boundary(d.z, d.fz)) {
         const uint32_t slot = atomicAdd(fix_count, 1u);
         if (slot < fix_cap) fix_list[slot] = (uint32_t)i;
     }

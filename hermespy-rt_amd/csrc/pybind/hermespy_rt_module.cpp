@@ -290,6 +290,57 @@ py::array_t<std::complex<float>> compute_channel_py(
     return out;
 }
 
+// compute_array_channel: the antenna-array channel of the traced paths, formed on the device (extension; see
+// hrt_compute_array_channel in hermespy_rt.h): complex64 (num_rx, num_tx, Nr, Nt, 2, num_times, num_freqs).  Element
+// offsets are (Nr, 3) / (Nt, 3) metres from the traced RX / TX positions; array_frequency (Hz) defaults to the carrier.
+py::array_t<std::complex<float>> compute_array_channel_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency)
+{
+    if (!num_rx || !num_tx || !num_paths || !num_bounces)
+        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_freqs and num_times must fit 32 bits");
+    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
+    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
+    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
+    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
+    if (rx_elements.size() % 3 || tx_elements.size() % 3)
+        throw std::invalid_argument("rx_elements and tx_elements must have shape (n, 3)");
+    const size_t nr = (size_t)rx_elements.size() / 3, nt = (size_t)tx_elements.size() / 3;
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
+    // beyond the 2^24 points of the limit would be refused, so only one within it is allocated.)
+    const unsigned long long pts = (unsigned long long)nr * nt * num_times * num_freqs;
+    const bool fits = pts > 0 && pts <= (1ull << 24) && nr <= 1024 && nt <= 1024;
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, nr, nt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_freqs}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    int rc;
+    std::string err;
+    {
+        py::gil_scoped_release nogil;
+        Scene scene = scene_load(mesh_filepath.c_str());
+        rc = hrt_compute_array_channel(&scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                       num_bounces, &spec, reinterpret_cast<const Vec3 *>(rx_elements.data()), nr,
+                                       reinterpret_cast<const Vec3 *>(tx_elements.data()), nt, fa, dst, nullptr);
+        if (rc != HRT_OK) err = hrt_last_error();
+        free_scene(&scene);
+    }
+    if (rc == HRT_E_INVALID) throw py::value_error("hermespy_rt.compute_array_channel: " + err);
+    if (rc != HRT_OK)
+        throw std::runtime_error("hermespy_rt.compute_array_channel failed (" + std::to_string(rc) + "): " + err);
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(hermespy_rt, m)
@@ -321,6 +372,15 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
+    m.def("compute_array_channel", &compute_array_channel_py,
+          "Antenna-array channel of the traced paths, formed on the device: complex64 "
+          "(num_rx, num_tx, Nr, Nt, 2, num_times, num_freqs)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none());
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

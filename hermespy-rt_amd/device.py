@@ -415,6 +415,59 @@ class Tracer:
                    "hrt_channel")
         return out
 
+    def array_channel(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                      scatter=True, array_frequency=None, out=None, accumulate=False):
+        """Antenna-array (MIMO) channel of the last trace, formed on the device (hrt_array_channel):
+
+            H[rx, tx, i, j, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
+                                               * exp(j 2 pi f_a (r_i . u_p^rx + q_j . u_p^tx) / c)
+
+        rx_elements (Nr, 3) / tx_elements (Nt, 3): element offsets in metres from the traced RX / TX positions (one
+        geometry for all RX, one for all TX; numpy or torch), f_a = array_frequency (Hz, default the carrier).  The
+        paths and parts are those of channel(); u^rx is the arrival direction (directions_rx), u^tx the departure
+        direction (directions_tx for LoS, the launch direction of the ray for a scatter record).  Returns a complex64
+        tensor [nrx, ntx, Nr, Nt, 2, num_times, num_freqs] on the device, enqueued on the current stream; `out` is
+        written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
+        te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
+        if not (np.isfinite(re).all() and np.isfinite(te).all()):
+            raise ValueError("element offsets must be finite")
+        nr, nt = re.shape[0], te.shape[0]
+        fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
+        spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
+        self.counts()
+        with torch.cuda.device(self.device):
+            d_el = torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
+        arr = abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa)
+        need = C.c_uint64(0)
+        rc = self.L.hrt_array_channel_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(arr),
+                                                    C.byref(need))
+        if rc == -1:
+            raise ValueError("hrt_array_channel: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_array_channel_scratch_bytes")
+        shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_freqs))
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            scratch = getattr(self, "_ac_scratch", None)
+            if scratch is None or scratch.numel() < int(need.value):
+                scratch = self._ac_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
+                                                         device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.hrt_array_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
+                                            C.byref(spec), C.byref(arr), C.c_void_p(scratch.data_ptr()),
+                                            C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
+                                            1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
+                   "hrt_array_channel")
+        d_el.record_stream(stream)   # (the kernels read the offsets after this call returns)
+        return out
+
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):
         """Assemble the reference's dense [rx][tx][b][p] scatter arrays on the host from the

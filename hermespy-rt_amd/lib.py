@@ -28,6 +28,7 @@ EXPORTED = (
     "hrt_gather_pack", "hrt_gather_recv_buffer", "hrt_gather_export", "hrt_gather_received", "hrt_rccl_unique_id",
     "hrt_rccl_comm_create", "hrt_rccl_comm_destroy", "hrt_gather_rccl", "hrt_stats_size", "hrt_layout_size",
     "hrt_channel_scratch_bytes", "hrt_channel", "hrt_compute_channel",
+    "hrt_array_channel_scratch_bytes", "hrt_array_channel", "hrt_compute_array_channel",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -208,6 +209,16 @@ def load():
     L.hrt_compute_channel.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
                                       C.c_size_t, C.c_size_t, spp, f32p, C.POINTER(Stats)]
     L.hrt_compute_channel.restype = C.c_int
+    # antenna-array channel responses (hrt_array_spec: abi.ArraySpec)
+    app = C.POINTER(abi.ArraySpec)
+    L.hrt_array_channel_scratch_bytes.argtypes = [vp, C.POINTER(Shard), spp, app, C.POINTER(u64)]
+    L.hrt_array_channel_scratch_bytes.restype = C.c_int
+    L.hrt_array_channel.argtypes = [vp, C.POINTER(Shard), vp, spp, app, vp, u64, vp, C.c_int, vp]
+    L.hrt_array_channel.restype = C.c_int
+    L.hrt_compute_array_channel.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                            C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                            f32p, C.POINTER(Stats)]
+    L.hrt_compute_array_channel.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

@@ -203,6 +203,31 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
                         size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
                         float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Antenna-array (MIMO) channel responses of the traced paths, formed on the device (include/hrt_device.h:
+ * hrt_array_channel).  One array geometry is shared by all RX and one by all TX: element i < Nr of an RX sits at
+ * offset r_i (metres, scene coordinates) from the traced RX position, element j < Nt of a TX at q_j from the
+ * traced TX position.  Elements are isotropic.  For every link, polarisation (0 = TE, 1 = TM) and grid point:
+ *     H[rx][tx][i][j][pol][m][k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
+ *                                        * exp(j 2 pi f_a (r_i . u_p^rx + q_j . u_p^tx) / c)
+ * over the paths hrt_channel sums (the same parts, LoS and scatter terms; blocked records add nothing), c =
+ * 299 792 458 m/s.  u^rx is the arrival direction as the dense output defines directions_rx: a unit vector from
+ * the RX back along the incoming path.  u^tx is the departure direction: for the LoS entry directions_tx (the
+ * coincident case too: u^rx = (1, 0, 0), u^tx = (-1, 0, 0)); for a scatter record the launch direction of its ray
+ * (RaysInfo bounce 0).  The reference never writes directions_tx of scatter paths; this is the direction it
+ * would hold.  The steering phase is narrowband: it is evaluated at the array frequency f_a, not at each f_k, so
+ * it is off by at most 2 pi |f_k - f_a| max(|r_i| + |q_j|) / c.  With Nr = Nt = 1 and zero offsets the result is
+ * hrt_compute_channel's, and the layout reduces to its layout.
+ * out: complex [num_rx][num_tx][Nr][Nt][2][num_times][num_freqs], re/im interleaved (numpy complex64).
+ * rx_elements / tx_elements: HOST arrays of Nr / Nt offsets.  Traced and batched like hrt_compute_channel; only
+ * `out` is copied back.  HRT_E_INVALID, before the device is touched: every hrt_channel_spec check; Nr or Nt
+ * outside 1..1024; Nr * Nt * num_times * num_freqs > 2^24; an offset or f_a not finite; f_a <= 0. */
+int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                              const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                              size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                              const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                              size_t num_tx_elements, double array_frequency_hz,
+                              float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

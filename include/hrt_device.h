@@ -303,6 +303,27 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
                 const hrt_channel_spec *spec, void *d_scratch, uint64_t scratch_bytes,
                 float *d_out, int accumulate, void *stream);
 
+/* ---- antenna-array channel responses from the traced paths (csrc/host/channel.c, csrc/hrt_array_channel.hip) ----
+ * H[rx][tx][i][j][pol][m][k] as hermespy_rt.h defines it (hrt_compute_array_channel), formed from the workspace of
+ * a finished hrt_trace, asynchronous on `stream`, with the guarantees of hrt_channel: accumulate = 0 overwrites
+ * d_out, 1 adds to it; only shard rank 0 adds the LoS term; partial sums go to the caller's scratch
+ * (hrt_array_channel_scratch_bytes) and are reduced in a fixed order, no floating-point atomics, so two calls with
+ * the same inputs give the same bits.  The element offsets are DEVICE pointers here ([Nr][3] and [Nt][3] floats,
+ * e.g. torch tensors) and are not read on the host: their finiteness is the caller's to ensure (the host entries
+ * check it).  HRT_E_INVALID, before the device is touched: every hrt_channel check; NULL arrays or element
+ * pointers; Nr or Nt outside 1..1024; Nr * Nt * num_times * num_freqs > 2^24; f_a not finite or <= 0. */
+typedef struct {
+    uint32_t num_rx_elements, num_tx_elements;   /* Nr, Nt: 1 .. 1024 */
+    const float *rx_elements;                    /* device [Nr][3]: r_i (m) */
+    const float *tx_elements;                    /* device [Nt][3]: q_j (m) */
+    double array_frequency_hz;                   /* f_a: the frequency of the steering phases */
+} hrt_array_spec;
+int hrt_array_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec,
+                                    const hrt_array_spec *arrays, uint64_t *out);
+int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                      const hrt_channel_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
+                      uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
