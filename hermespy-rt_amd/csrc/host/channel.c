@@ -6,9 +6,8 @@
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip;
- * the drop-in entry is built like hrt_compute_paths_list (path_list.c): the same workspace budget, pool and
- * batch rule, device launch tables, the same void-step retry; one device output accumulated over the batches
- * and one small download at the end.
+ * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
+ * small download at the end.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -118,12 +117,6 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-static uint64_t ch_env_u64(const char *name, uint64_t dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? (uint64_t)strtoull(v, NULL, 10) : dflt;
-}
-
 /* One drop-in call: what hrt_compute_channel and hrt_compute_array_channel share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
@@ -145,55 +138,22 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
                       float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, float *out,
                       hrt_stats *stats, double t_begin)
 {
-    int rc;
-    const int device = (int)ch_env_u64("HRT_DEVICE", 0);
     hrt_stats st;
     memset(&st, 0, sizeof st);
-    st.device = device;
     st.num_devices = 1;
-    hrt_problem *prob = NULL;
-    rc = hrt_problem_create_for(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, device, (uint64_t)ntx * np,
-                                &prob);
-    if (rc) return rc;
-    st.t_setup_s = hrt_now_s() - t_begin;
-
-    dev_ctx wc;   /* the drop-in's worker buffers: workspace + staging, pooled between calls */
-    memset(&wc, 0, sizeof wc);
-    int pool_taken = 0;
     void *d_out = NULL, *d_scratch = NULL;
     uint64_t scratch_bytes = 0;
     const uint64_t out_bytes = job->out_bytes;
     double t_dev = 0.0, t_dirs = 0.0;
     job->d_const = NULL;
-
-    /* batches of round-robin shards so that one workspace fits the budget (as path_list.c) */
-    uint64_t free_b = 0, total_b = 0;
-    if ((rc = hrt_device_mem_info(device, &free_b, &total_b))) goto done;
-    uint64_t budget = ch_env_u64("HRT_WORKSPACE_BYTES", 0);
-    if (!budget) {
-        budget = free_b / 2;
-        if (budget > (16ull << 30)) budget = 16ull << 30;
-    }
-    uint32_t G = 1, G_budget = 0;
+    hrt_solo so;   /* device, problem, batch count and the drop-in's worker buffers, pooled between calls (batch.c) */
+    int rc = hrt_solo_begin(&so, scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &st, t_begin);
+    if (rc) goto done;
+    hrt_problem *prob = so.prob;
+    work_t *w = &so.wc.w;
+    const int device = so.wc.device;
+    const uint32_t G = so.wc.G;
     hrt_layout L;
-    for (;;) {
-        hrt_shard s = {np, 0, G, 0, (uint32_t)nb};
-        rc = hrt_layout_query(prob, &s, &L);
-        const int fits = rc == HRT_OK && L.total_bytes + hrt_shard_num_local(&s) * 16 <= budget;
-        if (fits && !G_budget) G_budget = G;
-        if (fits && (G_budget > 2u || hrt_batch_fits_pool(L.total_bytes, hrt_shard_num_local(&s) + 64, L.cap))) break;
-        if (rc != HRT_OK && rc != HRT_E_CAPACITY) goto done;
-        if ((uint64_t)G * 4096 >= np) {
-            if (rc == HRT_OK) break;
-            goto done;
-        }
-        G *= 2;
-    }
-    wc.prob = prob; wc.nrx = nrx; wc.ntx = ntx; wc.np = np; wc.nb = nb; wc.G = G; wc.index = 0; wc.count = 1;
-    wc.device = device;
-    pool_taken = hrt_pool_begin();
-    wc.use_pool = pool_taken;
-    if ((rc = hrt_worker_alloc(&wc))) { wc.rc = rc; goto done; }
     if (job->const_bytes) {
         if ((rc = hrt_device_malloc(device, &job->d_const, job->const_bytes))) goto done;
         if ((rc = hrt_device_upload(device, job->d_const, job->h_const, job->const_bytes))) goto done;
@@ -214,33 +174,13 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
         if (hrt_shard_num_local(&s) == 0) continue;
         if ((rc = hrt_layout_query(prob, &s, &L))) goto done;
         double t0 = hrt_now_s();
-        if ((rc = hrt_launch_dirs_device(&s, (float *)wc.w.d_dirs, device, NULL, NULL))) goto done;
-        if ((rc = hrt_launch_order_device(&s, (uint32_t *)wc.w.d_order, device, NULL))) goto done;
+        if ((rc = hrt_launch_dirs_device(&s, (float *)w->d_dirs, device, NULL, NULL))) goto done;
+        if ((rc = hrt_launch_order_device(&s, (uint32_t *)w->d_order, device, NULL))) goto done;
         t_dirs += hrt_now_s() - t0;
         t0 = hrt_now_s();
-        for (int attempt = 0;; ++attempt) {
-            if ((rc = hrt_trace(prob, &s, (const float *)wc.w.d_dirs, (const uint32_t *)wc.w.d_order, wc.w.d_ws,
-                                L.total_bytes, NULL, NULL))) goto done;
-            if ((rc = hrt_device_sync(device, NULL))) goto done;
-            if ((rc = hrt_device_download(device, wc.w.h_counts, (const uint8_t *)wc.w.d_ws + L.off_counts,
-                                          (nb + 2) * 4))) goto done;
-            /* (a fused launch timed out on a shared GPU: the step is void, once more unfused -- compute_paths.c) */
-            if (!(wc.w.h_counts[nb + 1] & HRT_ERR_VOID) || attempt >= 2 || !hrt_void_step_retry(wc.w.h_counts[nb + 1]))
-                break;
-        }
-        if (wc.w.h_counts[nb + 1] != 0) {
-            rc = hrt_fail(HRT_E_HIP, "device reported internal error flags %u", wc.w.h_counts[nb + 1]);
-            goto done;
-        }
-        {
-            hrt_stats bs;
-            hrt_work_from_counts(prob, &s, wc.w.h_counts, &bs);
-            for (size_t b = 0; b <= nb && b < 34; ++b) st.live[b] += bs.live[b];
-            st.records += bs.records;
-            st.tests += bs.tests - (g ? (uint64_t)nrx * ntx * prob->num_tri : 0);
-        }
+        if ((rc = hrt_trace_batch(prob, &s, &L, w, &st))) goto done;   /* (batch.c) */
         /* batch 0 is rank 0 of the launch set: it adds the LoS term; the others add their records */
-        if ((rc = job->run(job, prob, &s, wc.w.d_ws, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1)))
+        if ((rc = job->run(job, prob, &s, w->d_ws, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1)))
             goto done;
         first = 0;
         if ((rc = hrt_device_sync(device, NULL))) goto done;
@@ -263,16 +203,11 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
     rc = HRT_OK;
 
 done:
-    if (d_scratch) hrt_device_free(device, d_scratch);
-    if (d_out) hrt_device_free(device, d_out);
-    if (job->d_const) hrt_device_free(device, job->d_const);
+    if (d_scratch) hrt_device_free(st.device, d_scratch);
+    if (d_out) hrt_device_free(st.device, d_out);
+    if (job->d_const) hrt_device_free(st.device, job->d_const);
     job->d_const = NULL;
-    if (wc.w.d_ws || wc.w.ray) {
-        wc.rc = rc;
-        hrt_worker_release(&wc);
-    }
-    hrt_pool_end(pool_taken);
-    hrt_problem_destroy(prob);
+    hrt_solo_end(&so, rc);
     return rc;
 }
 

@@ -31,19 +31,6 @@
 
 /* (the parallel-for of the host writers, hrt_parallel_ranges, and hrt_host_threads: parallel.c) */
 
-static int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
-static uint64_t env_u64(const char *name, uint64_t dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? strtoull(v, NULL, 10) : dflt;
-}
-
-
 /* ---- launch-table cache -------------------------------------------------------------------
  * The launch directions depend on num_rays only, and the coherent launch order of an unbatched
  * call on them only: callers that sample a channel again and again (moving endpoints, same ray
@@ -53,20 +40,18 @@ static uint64_t env_u64(const char *name, uint64_t dflt)
 static pthread_mutex_t g_cache_lock = PTHREAD_MUTEX_INITIALIZER;
 static struct { uint64_t np; float *dirs; uint32_t *order; } g_cache;
 
-static void pool_release_all(void);
-
 void hrt_cache_clear(void)
 {
     pthread_mutex_lock(&g_cache_lock);
     free(g_cache.dirs); free(g_cache.order);
     g_cache.np = 0; g_cache.dirs = NULL; g_cache.order = NULL;
     pthread_mutex_unlock(&g_cache_lock);
-    pool_release_all();
+    hrt_pool_release_all();   /* (batch.c) */
     hrt_list_cache_clear();   /* (path_list.c) */
     hrt_parallel_release();   /* ... and the calling thread's parked helper threads */
 }
 
-int hrt_launch_cache_enabled(uint64_t np) { return !env_int("HRT_NO_CACHE", 0) && np * 16 <= (1ull << 30); }
+int hrt_launch_cache_enabled(uint64_t np) { return !hrt_env_int("HRT_NO_CACHE", 0) && np * 16 <= (1ull << 30); }
 
 /* copies of the cached tables for `np` into dirs / order (either may be NULL); 1 if served */
 int hrt_launch_cache_get(uint64_t np, float *dirs, uint32_t *order)
@@ -94,34 +79,6 @@ void hrt_launch_cache_put(uint64_t np, const float *dirs, const uint32_t *order)
     if (order && !g_cache.order && (g_cache.order = (uint32_t *)malloc(np * 4))) memcpy(g_cache.order, order, np * 4);
     if (!g_cache.dirs) { free(g_cache.order); g_cache.order = NULL; g_cache.np = 0; }
     pthread_mutex_unlock(&g_cache_lock);
-}
-
-static void work_free(work_t *w)
-{
-    if (w->copy_stream) {   /* no copy may be in flight into the staging buffers freed below */
-        hrt_hip_stream_sync(w->copy_stream);
-        hrt_hip_stream_destroy(w->copy_stream);
-    }
-    if (w->copy_stream2) {
-        hrt_hip_stream_sync(w->copy_stream2);
-        hrt_hip_stream_destroy(w->copy_stream2);
-    }
-    if (w->d_dirs) hrt_device_free(w->device, w->d_dirs);
-    if (w->d_order) hrt_device_free(w->device, w->d_order);
-    free(w->h_order);
-    if (w->d_ws) hrt_device_free(w->device, w->d_ws);
-    free(w->h_dirs); free(w->h_counts); free(w->h_los);
-    /* D2H staging is page-locked (hipHostMalloc): 2-4x the pageable copy rate */
-    hrt_hip_host_free(w->ray); hrt_hip_host_free(w->tri); hrt_hip_host_free(w->fs0);
-    hrt_hip_host_free(w->ray2); hrt_hip_host_free(w->tri2); hrt_hip_host_free(w->fs02);
-    for (int k = 0; k < 6; ++k) hrt_hip_host_free(w->st[k]);
-    for (int k = 0; k < 4; ++k) { hrt_hip_host_free(w->hs[k]); hrt_hip_host_free(w->hs2[k]); }
-    for (int k = 0; k < HRT_REC_FIELDS; ++k) hrt_hip_host_free(w->rec[k]);
-    hrt_hip_host_free(w->mask);
-    for (int k = 0; k < HRT_REC_FIELDS; ++k) hrt_hip_host_free(w->rec2[k]);
-    hrt_hip_host_free(w->mask2);
-    free(w->run_start); free(w->run_tx);
-    free(w->dirs_batch); free(w->cur_rays); free(w->active); free(w->next_active);
 }
 
 #ifndef HRT_SCATTER_AHEAD
@@ -343,7 +300,6 @@ static void q10_range(void *vctx, uint64_t i0, uint64_t i1, int tid)
  * own problem copy, workspace, streams and page-locked staging; every device copies its records
  * over its own PCIe link straight into the caller's dense arrays (the slots of different batches are
  * disjoint: no exchange step, no RCCL). */
-#define HRT_MAX_DEVICES 16
 static int parse_devices(int *dev)
 {
     const char *v = getenv("HRT_DEVICES");
@@ -359,36 +315,9 @@ static int parse_devices(int *dev)
             while (*q == ',' || *q == ' ') ++q;
         }
     }
-    if (n == 0) { dev[0] = env_int("HRT_DEVICE", 0); n = 1; }
+    if (n == 0) { dev[0] = hrt_env_int("HRT_DEVICE", 0); n = 1; }
     return n;
 }
-
-/* ---- buffers kept between calls -------------------------------------------------------------
- * Device workspace and page-locked staging of the last call, one slot per worker, reused when the
- * next call fits (same device, capacity >= needed): a warm call saves ~25 ms of hipMalloc /
- * hipHostMalloc / hipFree on C3.  Released by hrt_cache_clear(); HRT_NO_CACHE=1 disables;
- * slots holding more than HRT_POOL_MAX_BYTES (default 5 GiB device + pinned: a warm C3 call holds 4.0 GB; a
- * reference-API caller never calls hrt_cache_clear(), so the default stays near what the headline configuration
- * needs.  C4 holds 14 GB -- its warm call is 0.04 s with them kept, 0.24 s without: such a caller raises it) are
- * not kept. */
-typedef struct {
-    int valid, device, with_rays, slim;
-    uint64_t cap, ws_bytes, dirs_rows;
-    work_t w;
-} pool_slot;
-static pthread_mutex_t g_pool_lock = PTHREAD_MUTEX_INITIALIZER;
-static pool_slot g_pool[HRT_MAX_DEVICES];
-static int g_pool_busy;
-
-static void pool_release_all(void)
-{
-    pthread_mutex_lock(&g_pool_lock);
-    if (!g_pool_busy)
-        for (int k = 0; k < HRT_MAX_DEVICES; ++k)
-            if (g_pool[k].valid) { work_free(&g_pool[k].w); memset(&g_pool[k], 0, sizeof g_pool[k]); }
-    pthread_mutex_unlock(&g_pool_lock);
-}
-
 
 #define DL(dst, off, bytes)                                                              \
     do {                                                                                 \
@@ -396,134 +325,13 @@ static void pool_release_all(void)
         if (rc) goto done;                                                               \
     } while (0)
 
-/* device + page-locked bytes a worker holds for batches of `cap` entries (workspace, launch tables, staging) */
-uint64_t hrt_worker_held_bytes(uint64_t ws_bytes, uint64_t dirs_rows, uint64_t cap)
-{
-    return ws_bytes + dirs_rows * 16 + cap * 4 * (5 + 2 * HRT_REC_FIELDS + 6 + 8);
-}
-/* may a batch of this size be chosen by default?  (the pool is on and the caller did not set the budget: then what
- * a worker holds must fit the pool, or every call allocates it again) */
-int hrt_batch_fits_pool(uint64_t ws_bytes, uint64_t dirs_rows, uint64_t cap)
-{
-    if (env_u64("HRT_WORKSPACE_BYTES", 0) || env_int("HRT_NO_CACHE", 0)) return 1;
-    return hrt_worker_held_bytes(ws_bytes, dirs_rows, cap) <= env_u64("HRT_POOL_MAX_BYTES", HRT_POOL_MAX_DEFAULT);
-}
-
-/* one call at a time owns the pool (compute_paths is not re-entrant; a concurrent call just
- * allocates its own buffers) */
-int hrt_pool_begin(void)
-{
-    int taken = 0;
-    if (env_int("HRT_NO_CACHE", 0)) return 0;
-    pthread_mutex_lock(&g_pool_lock);
-    if (!g_pool_busy) { g_pool_busy = 1; taken = 1; }
-    pthread_mutex_unlock(&g_pool_lock);
-    return taken;
-}
-void hrt_pool_end(int taken)
-{
-    if (!taken) return;
-    pthread_mutex_lock(&g_pool_lock);
-    g_pool_busy = 0;
-    pthread_mutex_unlock(&g_pool_lock);
-}
-
-/* buffers of one worker, sized for its largest batch (from the pool when they fit) */
-int hrt_worker_alloc(dev_ctx *c)
-{
-    work_t *w = &c->w;
-    const size_t nb = c->nb, nrx = c->nrx, ntx = c->ntx, np = c->np;
-    hrt_layout L;
-    hrt_shard s0 = {np, (uint32_t)c->index, c->G, 0, (uint32_t)nb};
-    int rc = hrt_layout_query(c->prob, &s0, &L);   /* a worker's first batch is never smaller than its others */
-    if (rc) return rc;
-    const uint64_t n_loc_max = hrt_shard_num_local(&(hrt_shard){np, 0, c->G, 0, (uint32_t)nb});
-    const uint64_t cap = L.cap;
-    const int with_rays = c->scat_rays != NULL;
-    const int slim = !env_int("HRT_FULL_RECORDS", 0);   /* (the per-hit staging arrays hs / hs2 exist only then) */
-    if (c->use_pool) {
-        pool_slot *ps = &g_pool[c->index];
-        if (ps->valid && ps->device == c->device && ps->cap >= cap && ps->ws_bytes >= L.total_bytes &&
-            ps->dirs_rows >= n_loc_max + 64 && ps->with_rays >= with_rays && ps->slim >= slim) {
-            *w = ps->w;
-            c->cap_alloc = ps->cap; c->ws_alloc = ps->ws_bytes; c->dirs_rows_alloc = ps->dirs_rows;
-            memset(ps, 0, sizeof *ps);
-            w->device = c->device;
-            /* per-call host arrays are not pooled; the small ones sized by nrx / ntx are re-made */
-            w->h_dirs = NULL; w->cur_rays = NULL; w->active = w->next_active = NULL; w->dirs_batch = NULL;
-            free(w->h_los); free(w->run_start); free(w->run_tx); free(w->h_counts);
-            w->h_counts = (uint32_t *)calloc(nb + 4, 4);
-            w->h_los = (float *)malloc(nrx * ntx * HRT_LOS_FLOATS * sizeof(float));
-            w->run_start = (uint64_t *)malloc((ntx + 2) * sizeof(uint64_t));
-            w->run_tx = (uint32_t *)malloc((ntx + 1) * sizeof(uint32_t));
-            if (!w->h_los || !w->run_start || !w->run_tx || !w->h_counts) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-            return HRT_OK;
-        }
-        if (ps->valid) { work_free(&ps->w); memset(ps, 0, sizeof *ps); }
-    }
-    memset(w, 0, sizeof *w);
-    w->device = c->device;
-    if ((rc = hrt_device_malloc(w->device, &w->d_ws, L.total_bytes))) return rc;
-    if ((rc = hrt_device_malloc(w->device, &w->d_dirs, (n_loc_max + 64) * 12))) return rc;   /* + rounding of a prefill piece */
-    if ((rc = hrt_device_malloc(w->device, &w->d_order, (n_loc_max + 64) * 4))) return rc;
-    w->h_order = (uint32_t *)malloc((n_loc_max + 64) * 4);
-    w->h_counts = (uint32_t *)calloc(c->nb + 4, 4);
-    w->h_los = (float *)malloc(nrx * ntx * HRT_LOS_FLOATS * sizeof(float));
-    w->run_start = (uint64_t *)malloc((ntx + 2) * sizeof(uint64_t));
-    w->run_tx = (uint32_t *)malloc((ntx + 1) * sizeof(uint32_t));
-    int ok = w->h_order && w->h_counts && w->h_los && w->run_start && w->run_tx;
-    ok &= hrt_hip_host_malloc((void **)&w->ray, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->tri, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->ray2, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->tri2, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->fs02, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->fs0, cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->mask, cap / 64 * 8 + 8) == 0;
-    for (int k = 0; k < 6 && with_rays; ++k) ok &= hrt_hip_host_malloc((void **)&w->st[k], cap * 4) == 0;
-    for (int k = 0; k < 4 && slim; ++k) {
-        ok &= hrt_hip_host_malloc((void **)&w->hs[k], cap * 4) == 0;
-        ok &= hrt_hip_host_malloc((void **)&w->hs2[k], cap * 4) == 0;
-    }
-    for (int k = 0; k < HRT_REC_FIELDS; ++k) ok &= hrt_hip_host_malloc((void **)&w->rec[k], cap * 4) == 0;
-    for (int k = 0; k < HRT_REC_FIELDS; ++k) ok &= hrt_hip_host_malloc((void **)&w->rec2[k], cap * 4) == 0;
-    ok &= hrt_hip_host_malloc((void **)&w->mask2, cap / 64 * 8 + 8) == 0;
-    ok &= hrt_hip_stream_create(&w->copy_stream) == 0;
-    ok &= hrt_hip_stream_create(&w->copy_stream2) == 0;
-    if (!ok) return hrt_fail(HRT_E_NOMEM, "out of host memory (page-locked staging)");
-    c->cap_alloc = cap; c->ws_alloc = L.total_bytes; c->dirs_rows_alloc = n_loc_max + 64;
-    return HRT_OK;
-}
-
-/* give the buffers back (pool) or free them */
-void hrt_worker_release(dev_ctx *c)
-{
-    work_t *w = &c->w;
-    free(w->h_dirs); w->h_dirs = NULL;
-    free(w->cur_rays); w->cur_rays = NULL;
-    free(w->active); free(w->next_active); w->active = w->next_active = NULL;
-    free(w->dirs_batch); w->dirs_batch = NULL;
-    const uint64_t held = hrt_worker_held_bytes(c->ws_alloc, c->dirs_rows_alloc, c->cap_alloc);
-    if (c->use_pool && c->rc == HRT_OK && w->d_ws && held <= env_u64("HRT_POOL_MAX_BYTES", HRT_POOL_MAX_DEFAULT)) {
-        if (w->copy_stream) hrt_hip_stream_sync(w->copy_stream);
-        if (w->copy_stream2) hrt_hip_stream_sync(w->copy_stream2);
-        pool_slot *ps = &g_pool[c->index];
-        ps->valid = 1; ps->device = c->device; ps->with_rays = w->st[0] != NULL; ps->slim = w->hs[0] != NULL;
-        ps->cap = c->cap_alloc; ps->ws_bytes = c->ws_alloc; ps->dirs_rows = c->dirs_rows_alloc;
-        ps->w = *w;
-        memset(w, 0, sizeof *w);
-        return;
-    }
-    work_free(w);
-    memset(w, 0, sizeof *w);
-}
-
 /* one batch (shard g of G) on this worker's device: tables, trace, readback into the dense arrays */
 static int run_batch(dev_ctx *c, uint32_t g)
 {
     work_t *w = &c->w;
     hrt_problem *prob = c->prob;
     const size_t nb = c->nb, nrx = c->nrx, ntx = c->ntx, np = c->np, nq = c->nq;
-    const uint32_t G = c->G, T = prob->num_tri;
+    const uint32_t G = c->G;
     ChannelInfo *los = c->los, *scat = c->scat;
     RaysInfo *los_rays = c->los_rays, *scat_rays = c->scat_rays;
     const Vec3 *rx_pos = c->rx_pos, *tx_pos = c->tx_pos;
@@ -563,29 +371,10 @@ static int run_batch(dev_ctx *c, uint32_t g)
         c->t_launch += hrt_now_s() - t0;
         t0 = hrt_now_s();
     }
-    for (int attempt = 0;; ++attempt) {
-        if ((rc = hrt_trace(prob, &s, (const float *)w->d_dirs, (const uint32_t *)w->d_order, w->d_ws, L.total_bytes, NULL, NULL))) goto done;
-        if ((rc = hrt_device_sync(w->device, NULL))) goto done;
-        DL(w->h_counts, L.off_counts, (nb + 2) * 4);
-        /* a fused launch / the chain kernel gave up waiting (the GPU is shared with other such kernels:
-         * hrt_kernels.hip, lb_exclusive, hrt_chain_kernel): the step is void -- once more with that switched off
-         * (chain -> a kernel per launch -> two kernels per launch), and so from now on */
-        if (!(w->h_counts[nb + 1] & HRT_ERR_VOID) || attempt >= 2 || !hrt_void_step_retry(w->h_counts[nb + 1])) break;
-    }
+    if ((rc = hrt_trace_batch(prob, &s, &L, w, st))) goto done;   /* (batch.c) */
     c->t_dev += hrt_now_s() - t0;
 
     t0 = hrt_now_s();
-    if (w->h_counts[nb + 1] != 0) {
-        rc = hrt_fail(HRT_E_HIP, "device reported internal error flags %u", w->h_counts[nb + 1]);
-        goto done;
-    }
-    {
-        hrt_stats bs;
-        hrt_work_from_counts(prob, &s, w->h_counts, &bs);
-        for (size_t b = 0; b <= nb && b < 34; ++b) st->live[b] += bs.live[b];
-        st->records += bs.records;
-        st->tests += bs.tests - (g ? (uint64_t)nrx * ntx * T : 0);   /* LoS counted once */
-    }
 
     /* ---- LoS block (identical in every batch; written once, by the owner of batch 0) :515-577 ---- */
     if (g == 0) {
@@ -655,7 +444,7 @@ static int run_batch(dev_ctx *c, uint32_t g)
     }
     const int can_pre = !prob->tune.no_bounce_prefetch;
     /* slim records (default; HRT_FULL_RECORDS=1 copies all nine fields): see scatter_ctx */
-    const int slim = !env_int("HRT_FULL_RECORDS", 0);
+    const int slim = !hrt_env_int("HRT_FULL_RECORDS", 0);
     static const int hs_field[4] = {HRT_HIT_OX, HRT_HIT_OY, HRT_HIT_OZ, HRT_HIT_TAU};
     int pre = 0, pre_block_next = 0, flip = 0;   /* staging set of a block: (slot + flip) & 1 */
     for (size_t b = 0; b < nb; ++b) {
@@ -901,7 +690,7 @@ static int compute_paths_impl(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
         c->los = los; c->scat = scat; c->los_rays = los_rays; c->scat_rays = scat_rays;
         c->amp_stride = amp_stride;
         c->index = d; c->count = D; c->device = devs[d];
-        c->host_launch = env_int("HRT_HOST_LAUNCH", 0);
+        c->host_launch = hrt_env_int("HRT_HOST_LAUNCH", 0);
         int thr = hrt_host_threads() / D;
         c->scatter_threads = thr > 0 ? thr : 1;
     }
@@ -928,46 +717,13 @@ static int compute_paths_impl(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
     }
     st.t_setup_s = hrt_now_s() - t_begin;
 
-    /* ---- batches: how many round-robin shards so one workspace fits the budget, at least one per
-     * device, a multiple of the device count ---- */
+    /* ---- batches: how many round-robin shards so one workspace fits the budget (batch.c), a multiple of the
+     * device count, at most one per granule ---- */
     uint32_t G = 1;
     {
-        uint64_t free_b = 0, total_b = 0;
-        rc = hrt_device_mem_info(ctx[0].device, &free_b, &total_b);
-        if (rc) goto done;
-        uint64_t budget = env_u64("HRT_WORKSPACE_BYTES", 0);
-        if (!budget) {
-            budget = free_b / 2;
-            if (budget > (16ull << 30)) budget = 16ull << 30;
-            /* logical devices on one GPU share its memory */
-            int same = 0;
-            for (int d = 0; d < D; ++d) same += ctx[d].device == ctx[0].device;
-            budget /= (uint64_t)(same > 0 ? same : 1);
-        }
-        /* ... and, unless the caller set the budget, so that what a worker holds fits the buffer pool (hrt_worker_release):
-         * buffers above HRT_POOL_MAX_BYTES are freed after the call and allocated again by the next one -- C4's 14 GB in
-         * one batch: a warm call of 0.31 s, 0.17 of them hipMalloc / hipHostMalloc / hipFree; in four batches 0.04 s
-         * (the batches' copies and host scatter overlap the next batch's kernels anyway) */
-        hrt_layout L;
-        uint32_t G_budget = 0;   /* the first G that fits the memory budget */
-        for (;;) {
-            hrt_shard s = {np, 0, G, 0, (uint32_t)nb};
-            rc = hrt_layout_query(prob, &s, &L);
-            const uint64_t n_loc = hrt_shard_num_local(&s);
-            const int fits = rc == HRT_OK && G >= (uint32_t)D && L.total_bytes + n_loc * 12 <= budget;
-            if (fits && !G_budget) G_budget = G;
-            /* (the pool rule only where it pays: a call of one or two budget-sized batches per device.  A call of
-             * many batches amortises its allocations -- C5: 0.2 of 3.7 s -- and smaller batches cost it more than
-             * that: 64 instead of 16 took 7.7 s) */
-            if (fits && (G_budget > 2u * (uint32_t)D || hrt_batch_fits_pool(L.total_bytes, n_loc + 64, L.cap))) break;
-            if (rc != HRT_OK && rc != HRT_E_CAPACITY) goto done;
-            if ((uint64_t)G * 4096 >= np) {   /* one granule per batch and still too big */
-                if (rc == HRT_OK) break;      /* try anyway; hipMalloc decides */
-                goto done;
-            }
-            G *= 2;
-        }
-        rc = HRT_OK;
+        int same = 0;   /* logical devices on one GPU share its memory */
+        for (int d = 0; d < D; ++d) same += ctx[d].device == ctx[0].device;
+        if ((rc = hrt_plan_batches(prob, np, nb, D, same, 12, &G))) goto done;
         if (G > 1 && G % (uint32_t)D) G = (G / (uint32_t)D + 1) * (uint32_t)D;
         if ((uint64_t)G * 4096 > np + 4095) {   /* fewer granules than batches: fewer workers */
             G = (uint32_t)((np + 4095) / 4096);
@@ -998,7 +754,7 @@ static int compute_paths_impl(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
             w->h_dirs = (float *)malloc(np * 3 * sizeof(float));
             if (!w->h_dirs) { rc = hrt_fail(HRT_E_NOMEM, "out of host memory"); goto done; }
             if (!(hrt_launch_cache_enabled(np) && hrt_launch_cache_get(np, w->h_dirs, NULL))) {
-                rc = hrt_launch_dirs_host(&whole, w->h_dirs, env_int("HRT_HOST_THREADS", 0));
+                rc = hrt_launch_dirs_host(&whole, w->h_dirs, hrt_env_int("HRT_HOST_THREADS", 0));
                 if (rc) goto done;
                 hrt_launch_cache_put(np, w->h_dirs, NULL);
             }

@@ -125,12 +125,18 @@ int hrt_fuse_disabled(void);
 void hrt_chain_disable(void);
 int hrt_chain_disabled(void);
 int hrt_void_step_retry(uint32_t err_word);
+void hrt_list_cache_clear(void);   /* path_list.c: the blocks kept from the last freed path list */
+
+/* ---- the batch loop of the drop-in entries (batch.c) ---- */
+int hrt_env_int(const char *name, int dflt);            /* atoi of a set, non-empty variable, else dflt */
+uint64_t hrt_env_u64(const char *name, uint64_t dflt);  /* strtoull(v, NULL, 10) of the same */
+#define HRT_MAX_DEVICES 16
 #define HRT_POOL_MAX_DEFAULT (5ull << 30)   /* HRT_POOL_MAX_BYTES: what a worker may keep between calls */
 uint64_t hrt_worker_held_bytes(uint64_t ws_bytes, uint64_t dirs_rows, uint64_t cap);
 int hrt_batch_fits_pool(uint64_t ws_bytes, uint64_t dirs_rows, uint64_t cap);
-void hrt_list_cache_clear(void);   /* path_list.c: the blocks kept from the last freed path list */
+void hrt_pool_release_all(void);   /* (hrt_cache_clear) */
 
-/* ---- buffers of one device worker of the drop-in calls (compute_paths.c), pooled between calls ---- */
+/* buffers of one device worker of the drop-in calls, pooled between calls */
 typedef struct {
     void *d_dirs, *d_ws, *d_order;
     uint32_t *h_order;      /* coherent launch order of one batch */
@@ -149,7 +155,6 @@ typedef struct {
     uint64_t *mask2;              /* overlaps the dense scatter of the current one */
     void *copy_stream, *copy_stream2;   /* two streams: two DMA engines (one engine moves ~28 GB/s) */
     Ray *cur_rays;          /* RaysInfo emulation: state of every ray of the current batch, [ntx][n_loc] */
-    uint8_t *active, *next_active;   /* (unused since the snapshots are per batch; kept for the pool's layout) */
     float *dirs_batch;      /* gathered launch directions of one batch */
     uint64_t *run_start;    /* per bounce: runs of equal TX in the hit list */
     uint32_t *run_tx;
@@ -186,6 +191,21 @@ int hrt_pool_begin(void);             /* 1 if this call owns the pool of kept bu
 void hrt_pool_end(int taken);
 int hrt_worker_alloc(dev_ctx *c);     /* needs c->prob, nrx, ntx, np, nb, G, index, device, use_pool, scat_rays */
 void hrt_worker_release(dev_ctx *c);  /* back to the pool (when c->rc == HRT_OK) or freed */
+/* the batch count G: at least `devices`, one batch's workspace + np / G * bytes_per_local_ray within the budget */
+int hrt_plan_batches(const hrt_problem *prob, size_t np, size_t nb, int devices, int sharers,
+                     uint64_t bytes_per_local_ray, uint32_t *G_out);
+/* trace shard s (the void-step retry), counts into w->h_counts, the batch's work added to *st */
+int hrt_trace_batch(const hrt_problem *prob, const hrt_shard *s, const hrt_layout *L, work_t *w, hrt_stats *st);
+/* the single-device entries: HRT_DEVICE, its problem, wc.G batches and one worker's buffers */
+typedef struct {
+    hrt_problem *prob;
+    dev_ctx wc;
+    int pool_taken;
+} hrt_solo;
+int hrt_solo_begin(hrt_solo *so, Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                   const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, hrt_stats *st,
+                   double t_begin);
+void hrt_solo_end(hrt_solo *so, int rc);   /* also after a failed hrt_solo_begin */
 
 /* host helpers shared by the dense writer and the path-list writer (compute_paths.c) */
 #define HRT_MAX_SCATTER_THREADS 32

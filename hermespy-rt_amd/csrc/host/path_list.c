@@ -5,8 +5,8 @@
  * reference's src/compute_paths.c:419-757), same values bit for bit; what differs is the output
  * side: the dense form is > 95 % unwritten slots (C3: 2.3 GB of caller arrays for 23 M non-zero
  * records, most of a warm call's time goes into page-faulting them in), the list holds exactly the
- * records, each with the indices of the dense slot it would occupy.  Built on the public
- * device-resident API (include/hrt_device.h) only.
+ * records, each with the indices of the dense slot it would occupy.  Built on the device-resident
+ * API (include/hrt_device.h) and the batch loop the drop-in entries share (batch.c).
  */
 #define _GNU_SOURCE
 #include <malloc.h>
@@ -27,12 +27,6 @@
 #if defined(__FAST_MATH__)
 #error "path_list.c must not be built with -ffast-math"
 #endif
-
-static uint64_t pl_env_u64(const char *name, uint64_t dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? (uint64_t)strtoull(v, NULL, 10) : dflt;
-}
 
 /* The blocks of the last freed list are kept for the next one (one set, at most HRT_LIST_KEEP_MAX bytes;
  * hrt_cache_clear() releases them, HRT_NO_CACHE=1 disables): a list is written once, front to back, and on fresh
@@ -224,85 +218,38 @@ int hrt_compute_paths_list(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
     if (nb > 65535) return hrt_fail(HRT_E_INVALID, "num_bounces > 65535 is not supported");
     memset(out, 0, sizeof *out);
 
-    const int device = (int)pl_env_u64("HRT_DEVICE", 0);
     hrt_stats st;
     memset(&st, 0, sizeof st);
-    st.device = device;
-    hrt_problem *prob = NULL;
-    int rc = hrt_problem_create_for(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, device,
-                                    (uint64_t)ntx * np, &prob);
-    if (rc) return rc;
-    st.t_setup_s = hrt_now_s() - t_begin;
-
-    dev_ctx wc;                      /* the drop-in's worker buffers: workspace + staging, pooled between calls */
-    memset(&wc, 0, sizeof wc);
-    int pool_taken = 0, have_buffers = 0;
-    void *d_ws = NULL, *d_dirs = NULL, *d_order = NULL;
-    float *h_dirs = NULL, **h_field = NULL, **h_field2 = NULL, *h_fs0 = NULL, *h_fs02 = NULL;
-    uint64_t *h_mask = NULL, *h_mask2 = NULL;
-    void *copy_stream = NULL, *copy_stream2 = NULL;
-    const int host_launch = (int)pl_env_u64("HRT_HOST_LAUNCH", 0);
-    uint32_t *h_order = NULL, *h_ray = NULL, *h_tri = NULL, *h_ray2 = NULL, *h_tri2 = NULL, *h_counts = NULL;
-    float *h_hs[4] = {NULL, NULL, NULL, NULL}, *h_hs2[4] = {NULL, NULL, NULL, NULL};
-    int slim = 0;
+    float *h_dirs = NULL;
+    hrt_solo so;   /* device, problem, batch count and the drop-in's worker buffers, pooled between calls (batch.c) */
+    int rc = hrt_solo_begin(&so, scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &st, t_begin);
+    if (rc) goto done;
+    hrt_problem *prob = so.prob;
+    work_t *w = &so.wc.w;
+    const int device = so.wc.device;
+    const uint32_t G = so.wc.G;
+    void *const d_ws = w->d_ws, *const d_dirs = w->d_dirs, *const d_order = w->d_order;
+    float **h_field = w->rec, **h_field2 = w->rec2, *h_fs0 = w->fs0, *h_fs02 = w->fs02;
+    uint64_t *h_mask = w->mask, *h_mask2 = w->mask2;
+    void *const copy_stream = w->copy_stream, *const copy_stream2 = w->copy_stream2;
+    uint32_t *const h_order = w->h_order, *const h_counts = w->h_counts;
+    uint32_t *h_ray = w->ray, *h_tri = w->tri, *h_ray2 = w->ray2, *h_tri2 = w->tri2;
+    float *h_hs[4], *h_hs2[4];
+    for (int k = 0; k < 4; ++k) { h_hs[k] = w->hs[k]; h_hs2[k] = w->hs2[k]; }
+    const int slim = w->hs[0] != NULL && w->hs2[0] != NULL;   /* (allocated unless HRT_FULL_RECORDS=1) */
+    const int host_launch = hrt_env_int("HRT_HOST_LAUNCH", 0);
     uint64_t cap_out = 0;
     const int threads = hrt_host_threads();
     double t_dev = 0.0, t_rb = 0.0, t_dirs = 0.0;
-
-    /* batches of round-robin shards so that one workspace fits the budget (as the drop-in does) */
-    uint64_t free_b = 0, total_b = 0;
-    if ((rc = hrt_device_mem_info(device, &free_b, &total_b))) goto done;
-    uint64_t budget = pl_env_u64("HRT_WORKSPACE_BYTES", 0);
-    if (!budget) {
-        budget = free_b / 2;
-        if (budget > (16ull << 30)) budget = 16ull << 30;
-    }
-    uint32_t G = 1, G_budget = 0;
     hrt_layout L;
-    for (;;) {
-        hrt_shard s = {np, 0, G, 0, (uint32_t)nb};
-        rc = hrt_layout_query(prob, &s, &L);
-        const int fits = rc == HRT_OK && L.total_bytes + hrt_shard_num_local(&s) * 16 <= budget;
-        if (fits && !G_budget) G_budget = G;
-        /* (the pool rule for calls of one or two budget-sized batches: compute_paths.c) */
-        if (fits && (G_budget > 2u || hrt_batch_fits_pool(L.total_bytes, hrt_shard_num_local(&s) + 64, L.cap))) break;
-        if (rc != HRT_OK && rc != HRT_E_CAPACITY) goto done;
-        if ((uint64_t)G * 4096 >= np) {
-            if (rc == HRT_OK) break;
-            goto done;
-        }
-        G *= 2;
+    if (host_launch) {
+        h_dirs = (float *)malloc(hrt_shard_num_local(&(hrt_shard){np, 0, G, 0, (uint32_t)nb}) * 12);
+        if (!h_dirs) { rc = hrt_fail(HRT_E_NOMEM, "out of host memory"); goto done; }
     }
-    {
-        wc.prob = prob; wc.nrx = nrx; wc.ntx = ntx; wc.np = np; wc.nb = nb; wc.G = G; wc.index = 0; wc.count = 1;
-        wc.device = device;
-        pool_taken = hrt_pool_begin();
-        wc.use_pool = pool_taken;
-        if ((rc = hrt_worker_alloc(&wc))) { wc.rc = rc; goto done; }
-        have_buffers = 1;
-        d_ws = wc.w.d_ws; d_dirs = wc.w.d_dirs; d_order = wc.w.d_order;
-        h_order = wc.w.h_order; h_counts = wc.w.h_counts;
-        h_ray = wc.w.ray; h_tri = wc.w.tri; h_fs0 = wc.w.fs0;
-        h_ray2 = wc.w.ray2; h_tri2 = wc.w.tri2; h_fs02 = wc.w.fs02;
-        h_field = wc.w.rec; h_field2 = wc.w.rec2; h_mask = wc.w.mask; h_mask2 = wc.w.mask2;
-        slim = wc.w.hs[0] != NULL && wc.w.hs2[0] != NULL;   /* (allocated unless HRT_FULL_RECORDS=1) */
-        for (int k = 0; k < 4; ++k) { h_hs[k] = wc.w.hs[k]; h_hs2[k] = wc.w.hs2[k]; }
-        copy_stream = wc.w.copy_stream;
-        copy_stream2 = wc.w.copy_stream2;
-        if (host_launch) {
-            h_dirs = (float *)malloc(hrt_shard_num_local(&(hrt_shard){np, 0, G, 0, (uint32_t)nb}) * 12);
-            if (!h_dirs) { rc = hrt_fail(HRT_E_NOMEM, "out of host memory"); goto done; }
-        }
-        out->los = (float *)malloc(nrx * ntx * HRT_LOS_FLOATS * sizeof(float));
-        if (!out->los) { rc = hrt_fail(HRT_E_NOMEM, "out of host memory"); goto done; }
-    }
+    out->los = (float *)malloc(nrx * ntx * HRT_LOS_FLOATS * sizeof(float));
+    if (!out->los) { rc = hrt_fail(HRT_E_NOMEM, "out of host memory"); goto done; }
     out->num_rx = (uint32_t)nrx;
     out->num_tx = (uint32_t)ntx;
-
-#define DLP(dst, off, bytes)                                                                    \
-    do {                                                                                        \
-        if ((rc = hrt_device_download(device, (dst), (const uint8_t *)d_ws + (off), (bytes)))) goto done; \
-    } while (0)
 
     for (uint32_t g = 0; g < G; ++g) {
         hrt_shard s = {np, g, G, 0, (uint32_t)nb};
@@ -326,29 +273,12 @@ int hrt_compute_paths_list(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
             t_dirs += hrt_now_s() - t0;
             t0 = hrt_now_s();
         }
-        for (int attempt = 0;; ++attempt) {
-            if ((rc = hrt_trace(prob, &s, (const float *)d_dirs, (const uint32_t *)d_order, d_ws,
-                                L.total_bytes, NULL, NULL))) goto done;
-            if ((rc = hrt_device_sync(device, NULL))) goto done;
-            DLP(h_counts, L.off_counts, (nb + 2) * 4);
-            /* (a fused launch timed out on a shared GPU: the step is void, once more unfused -- compute_paths.c) */
-            if (!(h_counts[nb + 1] & HRT_ERR_VOID) || attempt >= 2 || !hrt_void_step_retry(h_counts[nb + 1])) break;
-        }
+        if ((rc = hrt_trace_batch(prob, &s, &L, w, &st))) goto done;   /* (batch.c) */
         t_dev += hrt_now_s() - t0;
 
         t0 = hrt_now_s();
-        if (h_counts[nb + 1] != 0) {
-            rc = hrt_fail(HRT_E_HIP, "device reported internal error flags %u", h_counts[nb + 1]);
-            goto done;
-        }
-        {
-            hrt_stats bs;
-            hrt_work_from_counts(prob, &s, h_counts, &bs);
-            for (size_t b = 0; b <= nb && b < 34; ++b) st.live[b] += bs.live[b];
-            st.records += bs.records;
-            st.tests += bs.tests - (g ? (uint64_t)nrx * ntx * prob->num_tri : 0);
-        }
-        if (g == 0) DLP(out->los, L.off_los, nrx * ntx * HRT_LOS_FLOATS * sizeof(float));
+        if (g == 0 && (rc = hrt_device_download(device, out->los, (const uint8_t *)d_ws + L.off_los,
+                                                nrx * ntx * HRT_LOS_FLOATS * sizeof(float)))) goto done;
         {   /* room for every record of this batch (exact with include_blocked, <= 1.2x otherwise).  With several
              * batches the first one sizes the whole list: the batches are round-robin shards of one launch set, so
              * each holds 1 / G of the records within a fraction of a percent -- growing the list batch by batch
@@ -457,7 +387,6 @@ int hrt_compute_paths_list(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
     }
 #undef FETCH_PL
 #undef FETCH_HITS
-#undef DLP
     st.num_batches = G;
     st.t_launch_dirs_s = t_dirs;
     st.t_device_s = t_dev;
@@ -467,15 +396,8 @@ int hrt_compute_paths_list(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
     rc = HRT_OK;
 
 done:
-    if (have_buffers || wc.w.d_ws || wc.w.ray) {
-        wc.rc = rc;
-        if (copy_stream) hrt_hip_stream_sync(copy_stream);
-        if (copy_stream2) hrt_hip_stream_sync(copy_stream2);
-        hrt_worker_release(&wc);
-    }
-    hrt_pool_end(pool_taken);
+    hrt_solo_end(&so, rc);
     free(h_dirs);
-    hrt_problem_destroy(prob);
     if (rc != HRT_OK) hrt_path_list_free(out);
     return rc;
 }
