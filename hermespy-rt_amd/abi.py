@@ -384,3 +384,42 @@ def run_compute_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f
     if rc != 0:
         raise RuntimeError("hrt_compute_array_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
     return out
+
+
+class TapsSpec(C.Structure):
+    """include/hermespy_rt.h hrt_taps_spec"""
+    _fields_ = [("fs_hz", C.c_double), ("fc_hz", C.c_double), ("t0_s", C.c_double), ("dt_s", C.c_double),
+                ("l_min", C.c_int32), ("num_taps", C.c_uint32), ("num_times", C.c_uint32), ("parts", C.c_uint32)]
+
+
+def taps_spec(fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, parts=None):
+    if parts is None:
+        parts = (CHANNEL_LOS if los else 0) | (CHANNEL_SCATTER if scatter else 0)
+    return TapsSpec(float(fs), float(fc), float(t0), float(dt), int(l_min), int(num_taps), int(num_times), int(parts))
+
+
+def run_compute_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                     stats=None):
+    """hrt_compute_taps through ctypes -> complex64 [nrx, ntx, 2, num_times, num_taps].  Raises
+    RuntimeError("hrt_compute_taps failed (<rc>): ...") on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    nt, nl = int(spec.num_times), int(spec.num_taps)
+    out = np.zeros((nrx, ntx, 2, nt, nl) if 0 < nt * nl <= (1 << 20) else (1,), np.complex64)
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_taps(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
+                                  C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+                                  C.byref(spec), out.ctypes.data_as(c_float_p),
+                                  C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return out

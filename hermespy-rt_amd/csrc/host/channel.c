@@ -1,11 +1,13 @@
-/* channel.c -- channel frequency responses from traced paths, on the device (include/hrt_device.h:
- * hrt_channel, hrt_array_channel; include/hermespy_rt.h: hrt_compute_channel, hrt_compute_array_channel).
+/* channel.c -- channel frequency responses and impulse responses from traced paths, on the device
+ * (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps; include/hermespy_rt.h: hrt_compute_channel,
+ * hrt_compute_array_channel, hrt_compute_taps).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
- * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip;
+ * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
+ * csrc/hrt_array_channel.hip and csrc/hrt_taps.hip;
  * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
  * small download at the end.
  */
@@ -16,6 +18,7 @@
 #include "hrt_internal.h"
 #include "../hrt_array_channel.h"
 #include "../hrt_channel.h"
+#include "../hrt_taps.h"
 
 #define HRT_CH_MAX_POINTS (1u << 20)         /* num_freqs * num_times */
 #define HRT_CH_TARGET_GROUPS 8192u           /* waves of the partial kernel worth launching (32 per CU) */
@@ -122,7 +125,7 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
 struct ch_job {
-    const hrt_channel_spec *spec;
+    const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel) or hrt_taps_spec */
     uint64_t out_bytes;
     const void *h_const;
     uint64_t const_bytes;
@@ -435,4 +438,141 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
     rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
     free(el);
     return rc;
+}
+
+/* ------------------------------------------------------------------ impulse responses (hrt_taps) */
+
+#define HRT_TP_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_TP_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
+
+static int taps_check(const hrt_taps_spec *spec)
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL spec");
+    if (spec->num_taps == 0 || spec->num_times == 0)
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: num_taps and num_times must be > 0");
+    if ((uint64_t)spec->num_taps * spec->num_times > HRT_TP_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: num_taps * num_times = %llu > 2^20",
+                        (unsigned long long)spec->num_taps * spec->num_times);
+    if (!isfinite(spec->fs_hz) || !(spec->fs_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: the sampling rate must be finite and > 0");
+    if (!isfinite(spec->fc_hz) || !isfinite(spec->t0_s) || !isfinite(spec->dt_s))
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: fc, t0 and dt must be finite");
+    const int64_t lo = spec->l_min, hi = (int64_t)spec->l_min + spec->num_taps;
+    if (lo < -HRT_TP_MAX_TAP || lo > HRT_TP_MAX_TAP || hi > HRT_TP_MAX_TAP)
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: tap indices l_min = %lld .. %lld outside +-2^24", (long long)lo,
+                        (long long)hi);
+    if (spec->parts == 0 || (spec->parts & ~(uint32_t)(HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)))
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: parts 0x%x (HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)", spec->parts);
+    return HRT_OK;
+}
+
+/* the tiling of one taps call: a pure function of the problem, the shard and the spec */
+static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, hrt_ktaps *K,
+                     uint64_t *bytes)
+{
+    int rc = taps_check(spec);
+    if (rc) return rc;
+    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL argument");
+    hrt_layout L;
+    if ((rc = hrt_layout_query(p, s, &L))) return rc;
+    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
+    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_taps: num_rx * num_tx = %llu > 65535",
+                                        (unsigned long long)links);
+    memset(K, 0, sizeof *K);
+    K->cap = L.cap; K->off_counts = L.off_counts; K->off_los = L.off_los; K->off_hits = L.off_hits;
+    K->hit_block_bytes = L.hit_block_bytes; K->off_recs = L.off_recs; K->rec_block_bytes = L.rec_block_bytes;
+    K->off_masks = L.off_masks;
+    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
+    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
+    K->rtiles = (4u * K->T + 15u) / 16u;
+    K->ctiles = (K->L + 15u) / 16u;
+    /* four row tiles per wave (U read once per MFMA, V formed once per four) where the grid has them; one row tile
+     * and four column tiles otherwise (T < 4: the rows past 4 T of the tile are padding) */
+    K->rt = K->rtiles >= 4u ? 4u : 1u;
+    const uint32_t ct = HRT_TP_WTILES / K->rt;
+    K->rblocks = (K->rtiles + K->rt - 1u) / K->rt;
+    K->cblocks = (K->ctiles + 4u * ct - 1u) / (4u * ct);
+    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
+    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
+    const uint64_t per_chunk = links * 2u * K->T * K->L * 8u;
+    uint64_t nch = 0;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
+        /* enough workgroups to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at
+         * most HRT_TP_PARTIAL_MAX (but one chunk always), and a grid y of at most 65535 */
+        const uint64_t groups = links * K->rblocks * K->cblocks;
+        nch = (HRT_TP_TARGET_GROUPS + groups - 1) / groups;
+        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
+        if (nch > by_recs) nch = by_recs;
+        if (nch > HRT_TP_PARTIAL_MAX / per_chunk) nch = HRT_TP_PARTIAL_MAX / per_chunk;
+        if (nch > 65535u) nch = 65535u;
+        if (nch < 1) nch = 1;
+    }
+    K->nchunks = (uint32_t)nch;
+    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
+    *bytes = seg_bytes + nch * per_chunk;
+    return HRT_OK;
+}
+
+int hrt_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, uint64_t *out)
+{
+    hrt_ktaps K;
+    uint64_t bytes = 0;
+    int rc = taps_plan(p, s, spec, &K, &bytes);
+    if (rc) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_taps_scratch_bytes: NULL out");
+    *out = bytes;
+    return HRT_OK;
+}
+
+int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+             void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream)
+{
+    hrt_ktaps K;
+    uint64_t need = 0;
+    int rc = taps_plan(p, s, spec, &K, &need);
+    if (rc) return rc;
+    if (!d_workspace || !d_out || !d_scratch)
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL workspace, scratch or output");
+    if (scratch_bytes < need)
+        return hrt_fail(HRT_E_INVALID, "hrt_taps: scratch of %llu bytes, %llu needed (hrt_taps_scratch_bytes)",
+                        (unsigned long long)scratch_bytes, (unsigned long long)need);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "hrt_taps: accumulate must be 0 or 1");
+    K.ws = (const uint8_t *)d_workspace;
+    K.accumulate = (uint32_t)accumulate;
+    K.seg = (const uint32_t *)d_scratch;
+    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_taps(&K, stream), "taps kernels");
+    return HRT_OK;
+}
+
+static int tp_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    return hrt_taps_scratch_bytes(p, s, j->spec, out);
+}
+
+static int tp_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, float *d_out, int accumulate)
+{
+    return hrt_taps(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
+                     float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, const hrt_taps_spec *spec, float *out,
+                     hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = taps_check(spec);
+    if (rc) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, "hrt_compute_taps")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * 2u * spec->num_times * spec->num_taps * 8u;
+    job.scratch_bytes = tp_job_scratch;
+    job.run = tp_job_run;
+    return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
 }

@@ -1,0 +1,284 @@
+// hrt_taps.hip -- sampled channel impulse responses (taps) from the workspace of a finished hrt_trace, for gfx950.
+//
+//     h[rx, tx, pol, m, i] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) sinc(l_i - f_s tau_p)
+//     t_m = t0 + m dt,  l_i = l_min + i
+//
+// over the LoS entry (hrt_taps_reduce_kernel) and every unblocked scatter record (hrt_taps_partial_kernel) of the
+// link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip).
+//   hrt_taps_partial_kernel  one workgroup (4 waves) per (row block x column block, record chunk, link): the real
+//                            GEMM of csrc/hrt_taps.h on v_mfma_f32_16x16x4_f32, partial sums to the scratch.  The
+//                            unblocked records of the chunk are compacted by mask ballots and staged HRT_TP_BATCH at a
+//                            time: their sinc parameters, then U over the block's rows in LDS; every lane forms its
+//                            own B operand V (one record, one tap) in registers.
+//   hrt_taps_reduce_kernel   per output: the chunks in a fixed order, plus the LoS term, into out.
+// No floating-point atomics anywhere: two calls with the same inputs give the same bits.
+//
+// Precision: every phase is reduced in FP64 to a fraction of a revolution -- nu t_m, f_c tau
+// and x = f_s tau.  With n = rint(x), f = x - n, sinc(l - x) = -(-1)^(l - n) sin(pi f) / (pi (l - n - f)): one f32
+// sinpi per record and, per tap, an exact integer difference, one v_rcp_f32 and a sign.  Where |l - x| < 1e-4 the
+// weight is 1 (the f32 rounding of sinc there; exactly 1 where l - x is exactly 0).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "hrt_channel.h"
+#include "hrt_device.h"
+#include "hrt_taps.h"
+
+typedef float hrt_f32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+// the fraction of a phase in revolutions, as the argument of sincospi (half revolutions, in [-1, 1])
+__device__ __forceinline__ float half_revs(double ph)
+{
+    return (float)(2.0 * (ph - rint(ph)));
+}
+
+__device__ __forceinline__ const float *rec_field(const hrt_ktaps &P, uint32_t b, uint32_t rx, uint32_t f)
+{
+    return reinterpret_cast<const float *>(P.ws + P.off_recs + (uint64_t)b * P.rec_block_bytes +
+                                           ((uint64_t)rx * HRT_REC_FIELDS + f) * P.cap * 4u);
+}
+
+__device__ __forceinline__ const uint32_t *hit_field(const hrt_ktaps &P, uint32_t b, uint32_t f)
+{
+    return reinterpret_cast<const uint32_t *>(P.ws + P.off_hits + (uint64_t)b * P.hit_block_bytes +
+                                              (uint64_t)f * P.cap * 4u);
+}
+
+// the records [start, end) of chunk c of the TX segment of hit block b
+__device__ __forceinline__ void chunk_range(const hrt_ktaps &P, uint32_t b, uint32_t tx, uint32_t c, uint32_t &start,
+                                            uint32_t &end)
+{
+    const uint32_t s0 = P.seg[b * (P.ntx + 1u) + tx], s1 = P.seg[b * (P.ntx + 1u) + tx + 1u];
+    const uint64_t n = s1 - s0;
+    start = s0 + (uint32_t)(n * c / P.nchunks);
+    end = s0 + (uint32_t)(n * (c + 1u) / P.nchunks);
+}
+
+// The sinc of one delay, x = f_s tau: sinc(l - x) = (-1)^l c / ((l - k) - r) with k = rint(x) clamped to
+// +-2^26 (so l - k is an exact int32 for |l| <= 2^24), r = x - k and c = -(-1)^n sin(pi (x - n)) / pi, n = rint(x).
+// Unclamped, |r| <= 1/2; clamped, r has the sign of k and l - k the other one, so (l - k) - r never vanishes.
+struct sinc_rec {
+    int32_t k;
+    float r, c;
+};
+
+__device__ __forceinline__ sinc_rec sinc_prep(double fs, float tau)
+{
+    const double x = fs * (double)tau;
+    const double n = rint(x);
+    const double k = fmin(fmax(n, -67108864.0), 67108864.0);
+    const double h = 0.5 * n;   // n odd <=> n / 2 has a fraction (exact below 2^53; beyond it x is even, f = 0)
+    const float s = sinpif((float)(x - n)) * 0.318309886183790672f;   // sin(pi f) / pi
+    sinc_rec q;
+    q.k = (int32_t)k;
+    q.r = (float)(x - k);
+    q.c = h != floor(h) ? s : -s;
+    return q;
+}
+
+__device__ __forceinline__ float sinc_tap(int32_t l, const sinc_rec &q)
+{
+    const float d = (float)(l - q.k) - q.r;
+    const float c = (l & 1) ? -q.c : q.c;
+    return fabsf(d) < 1e-4f ? 1.f : c * __builtin_amdgcn_rcpf(d);
+}
+
+}  // namespace
+
+// RT row tiles x (HRT_TP_WTILES / RT) column tiles per wave (csrc/hrt_taps.h)
+template <uint32_t RT>
+__global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const hrt_ktaps P)
+{
+    constexpr uint32_t CT = HRT_TP_WTILES / RT;
+    constexpr uint32_t BT = RT * 4u;   // time samples of the block
+    const uint32_t blk = blockIdx.x, c = blockIdx.y, link = blockIdx.z;
+    const uint32_t rb = blk % P.rblocks, cb = blk / P.rblocks;
+    const uint32_t rx = link / P.ntx, tx = link % P.ntx;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    const uint32_t kq = lane >> 4, col = lane & 15u;   // A / B operand: record 4 g + kq; row / tap `col` of a tile
+
+    __shared__ float sU[HRT_TP_BATCH][BT * 4u];   // U of the block's rows g = 4 mm + q
+    __shared__ float sRec[HRT_TP_BATCH][6];        // te re, te im, tm re, tm im, tau, nu
+    __shared__ sinc_rec sS[HRT_TP_BATCH];
+    __shared__ uint32_t sB[HRT_TP_BATCH], sI[HRT_TP_BATCH];   // (bounce, hit) of the staged records
+
+    const uint32_t r0 = rb * RT, c0 = (cb * 4u + w) * CT;   // this wave's first row tile and column tile
+    bool live[HRT_TP_WTILES];
+    int32_t tap[CT];
+#pragma unroll
+    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) live[t] = r0 + t / CT < P.rtiles && c0 + t % CT < P.ctiles;
+#pragma unroll
+    for (uint32_t t = 0; t < CT; ++t) tap[t] = P.l_min + (int32_t)((c0 + t) * 16u + col);
+    hrt_f32x4 acc[HRT_TP_WTILES];
+#pragma unroll
+    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) acc[t] = hrt_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const uint64_t words = P.cap / 64u;
+    uint32_t b = 0, cur = 0, end = 0;
+    chunk_range(P, 0, tx, c, cur, end);
+    for (;;) {
+        // fill a batch with the next unblocked records of the chunk (every wave takes the same decisions; wave 0
+        // writes the list)
+        uint32_t n = 0;
+        while (n < HRT_TP_BATCH && b < P.nb) {
+            if (cur >= end) {
+                if (++b < P.nb) chunk_range(P, b, tx, c, cur, end);
+                continue;
+            }
+            const uint32_t i = cur + lane;
+            const uint64_t *mask = reinterpret_cast<const uint64_t *>(P.ws + P.off_masks) + ((uint64_t)b * P.nrx + rx) * words;
+            const bool ok = i < end && ((mask[i >> 6] >> (i & 63u)) & 1u);
+            const uint64_t bal = __ballot(ok);
+            const uint32_t cnt = __popcll(bal), take = min(cnt, HRT_TP_BATCH - n);
+            const uint32_t rank = __popcll(bal & ((1ull << lane) - 1ull));
+            if (w == 0 && ok && rank < take) {
+                sB[n + rank] = b;
+                sI[n + rank] = i;
+            }
+            if (take < cnt) {   // resume at the first live record not taken
+                uint64_t rest = bal;
+                for (uint32_t t = 0; t < take; ++t) rest &= rest - 1ull;
+                cur += (uint32_t)__builtin_ctzll(rest);
+            } else {
+                cur += 64u;
+            }
+            n += take;
+        }
+        if (n == 0) break;
+        __syncthreads();
+        if (tid < HRT_TP_BATCH) {   // the record's fields and sinc parameters (zeros past n: U = 0 there)
+            float *R = sRec[tid];
+            sinc_rec q = {0, 0.f, 0.f};
+            if (tid < n) {
+                const uint32_t rb2 = sB[tid], i = sI[tid];
+                R[0] = rec_field(P, rb2, rx, HRT_REC_A_TE_RE)[i];
+                R[1] = rec_field(P, rb2, rx, HRT_REC_A_TE_IM)[i];
+                R[2] = rec_field(P, rb2, rx, HRT_REC_A_TM_RE)[i];
+                R[3] = rec_field(P, rb2, rx, HRT_REC_A_TM_IM)[i];
+                R[4] = rec_field(P, rb2, rx, HRT_REC_TAU)[i];
+                R[5] = __uint_as_float(hit_field(P, rb2, HRT_HIT_FS0)[i]) - rec_field(P, rb2, rx, HRT_REC_DFS)[i];
+                q = sinc_prep(P.fs, R[4]);
+            } else {
+                for (int f = 0; f < 6; ++f) R[f] = 0.f;
+            }
+            sS[tid] = q;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t e = tid; e < HRT_TP_BATCH * BT; e += HRT_TP_THREADS) {   // U
+            const uint32_t j = e / BT, mm = e % BT, m = rb * BT + mm;
+            const float *R = sRec[j];
+            float u0 = 0.f, u1 = 0.f, u2 = 0.f, u3 = 0.f;
+            if (j < n && m < P.T) {
+                const double t = P.t0 + (double)m * P.dt;
+                float sn, cs;
+                sincospif(half_revs((double)R[5] * t - P.fc * (double)R[4]), &sn, &cs);
+                u0 = R[0] * cs - R[1] * sn;
+                u1 = R[0] * sn + R[1] * cs;
+                u2 = R[2] * cs - R[3] * sn;
+                u3 = R[2] * sn + R[3] * cs;
+            }
+            float *U = &sU[j][4u * mm];
+            U[0] = u0; U[1] = u1; U[2] = u2; U[3] = u3;
+        }
+        __syncthreads();
+        for (uint32_t g = 0; 4u * g < n; ++g) {
+            const uint32_t j = 4u * g + kq;
+            const sinc_rec q = sS[j];
+            float v[CT];
+#pragma unroll
+            for (uint32_t t = 0; t < CT; ++t) v[t] = sinc_tap(tap[t], q);
+#pragma unroll
+            for (uint32_t rt = 0; rt < RT; ++rt) {
+                const float a = sU[j][rt * 16u + col];
+#pragma unroll
+                for (uint32_t t = 0; t < CT; ++t)
+                    if (live[rt * CT + t])
+                        acc[rt * CT + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, v[t], acc[rt * CT + t], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    // D: lane = (row group kq, column col), register q: row 4 kq + q of the tile = (time 4 R + kq, part q)
+    const uint64_t tl = (uint64_t)P.T * P.L;
+    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * P.nchunks + c) * 2u * tl;
+#pragma unroll
+    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) {
+        const uint32_t m = (r0 + t / CT) * 4u + kq, i = (c0 + t % CT) * 16u + col;
+        if (live[t] && m < P.T && i < P.L) {
+            float2 *d = dst + (uint64_t)m * P.L + i;
+            d[0] = make_float2(acc[t][0], acc[t][1]);
+            d[tl] = make_float2(acc[t][2], acc[t][3]);
+        }
+    }
+}
+
+// one thread per output (link, pol, m, i): the chunks in order, + LoS, -> out
+__global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
+{
+    const uint64_t tl = (uint64_t)P.T * P.L;
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t per_link = 2u * tl;
+    if (gid >= per_link * P.nrx * P.ntx) return;
+    const uint32_t link = (uint32_t)(gid / per_link);
+    const uint64_t e = gid - (uint64_t)link * per_link;   // = pol * tl + m * L + i
+
+    float2 s = make_float2(0.f, 0.f);
+    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * P.nchunks * per_link + e;
+    for (uint32_t c = 0; c < P.nchunks; ++c) {
+        const float2 v = src[(uint64_t)c * per_link];
+        s.x += v.x;
+        s.y += v.y;
+    }
+    if (P.los) {
+        const float *L = reinterpret_cast<const float *>(P.ws + P.off_los) + (uint64_t)link * HRT_LOS_FLOATS;
+        const uint32_t status = __float_as_uint(L[HRT_LOS_STATUS]);
+        if (status == 0u || status == 2u) {   // coincident: a = 1, tau = nu = 0; clear: a = HRT_LOS_A (TE = TM)
+            float a = 1.f, tau = 0.f, nu = 0.f;
+            if (status == 2u) {
+                a = L[HRT_LOS_A]; tau = L[HRT_LOS_TAU]; nu = L[HRT_LOS_FS];
+            }
+            const uint64_t mi = e % tl;
+            const uint32_t m = (uint32_t)(mi / P.L), i = (uint32_t)(mi % P.L);
+            const double t = P.t0 + (double)m * P.dt;
+            float sn, cs;
+            sincospif(half_revs((double)nu * t - P.fc * (double)tau), &sn, &cs);
+            const float v = a * sinc_tap(P.l_min + (int32_t)i, sinc_prep(P.fs, tau));
+            s.x += v * cs;
+            s.y += v * sn;
+        }
+    }
+    float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
+    if (P.accumulate) {
+        const float2 v = o[0];
+        s.x += v.x;
+        s.y += v.y;
+    }
+    o[0] = s;
+}
+
+extern "C" int hrt_hip_launch_taps(const hrt_ktaps *P, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t links = P->nrx * P->ntx;
+    if (P->nchunks) {
+        hrt_kchannel S = {};
+        S.ws = P->ws; S.cap = P->cap; S.off_counts = P->off_counts; S.off_hits = P->off_hits;
+        S.hit_block_bytes = P->hit_block_bytes; S.nb = P->nb; S.ntx = P->ntx; S.num_local = P->num_local;
+        S.seg = const_cast<uint32_t *>(P->seg);
+        const int e = hrt_hip_launch_channel_segments(&S, stream);
+        if (e) return e;
+        const dim3 grid(P->rblocks * P->cblocks, P->nchunks, links);
+        if (P->rt == 4u)
+            hipLaunchKernelGGL(hrt_taps_partial_kernel<4u>, grid, dim3(HRT_TP_THREADS), 0, st, *P);
+        else
+            hipLaunchKernelGGL(hrt_taps_partial_kernel<1u>, grid, dim3(HRT_TP_THREADS), 0, st, *P);
+    }
+    const uint64_t n = (uint64_t)links * 2u * P->T * P->L;
+    hipLaunchKernelGGL(hrt_taps_reduce_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
+    return (int)hipGetLastError();
+}

@@ -341,6 +341,55 @@ py::array_t<std::complex<float>> compute_array_channel_py(
     return out;
 }
 
+// compute_taps: the sampled channel impulse response of the traced paths, formed on the device (extension; see
+// hrt_compute_taps in hermespy_rt.h): complex64 (num_rx, num_tx, 2, num_times, num_taps),
+// h = sum_p a_p exp(j 2 pi (nu_p t_m - f_c tau_p)) sinc(l_i - f_s tau_p), l_i = l_min + i; center_frequency f_c (Hz)
+// defaults to the carrier.
+py::array_t<std::complex<float>> compute_taps_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double sampling_rate, unsigned long num_taps, long l_min, py::object center_frequency,
+    double t0, double dt, unsigned long num_times, bool los, bool scatter)
+{
+    if (!num_rx || !num_tx || !num_paths || !num_bounces)
+        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_taps and num_times must fit 32 bits");
+    if (l_min < -(1L << 30) || l_min > (1L << 30))
+        throw py::value_error("hermespy_rt.compute_taps: tap indices l_min outside +-2^24");
+    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
+    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
+    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
+    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
+    const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_taps_spec spec{};
+    spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
+    spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)num_times;
+    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    // (the library validates the spec before it traces anything: a refused one raises ValueError; an output too
+    // large for its limits is not allocated)
+    const bool fits = num_taps && num_times && (uint64_t)num_taps * num_times <= (1ull << 20);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, (size_t)2,
+                                                                     (size_t)num_times, (size_t)num_taps}
+                                              : std::vector<size_t>{(size_t)1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    int rc;
+    std::string err;
+    {
+        py::gil_scoped_release nogil;
+        Scene scene = scene_load(mesh_filepath.c_str());
+        rc = hrt_compute_taps(&scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
+                              &spec, dst, nullptr);
+        if (rc != HRT_OK) err = hrt_last_error();
+        free_scene(&scene);
+    }
+    if (rc == HRT_E_INVALID) throw py::value_error("hermespy_rt.compute_taps: " + err);
+    if (rc != HRT_OK)
+        throw std::runtime_error("hermespy_rt.compute_taps failed (" + std::to_string(rc) + "): " + err);
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(hermespy_rt, m)
@@ -381,6 +430,15 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
           py::arg("scatter") = true, py::arg("array_frequency") = py::none());
+    m.def("compute_taps", &compute_taps_py,
+          "Sampled channel impulse response of the traced paths, formed on the device: complex64 "
+          "(num_rx, num_tx, 2, num_times, num_taps)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("sampling_rate"), py::arg("num_taps"), py::arg("l_min") = 0,
+          py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

@@ -468,6 +468,46 @@ class Tracer:
         d_el.record_stream(stream)   # (the kernels read the offsets after this call returns)
         return out
 
+    def taps(self, fs, num_taps, l_min=0, fc=None, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
+             accumulate=False):
+        """Sampled channel impulse response of the last trace, formed on the device (hrt_taps):
+
+            h[rx, tx, pol, m, i] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) sinc(l_i - f_s tau_p)
+            t_m = t0 + m dt,  l_i = l_min + i
+
+        over the paths and parts of channel().  fs is the sampling rate (Hz), fc the frequency the baseband is taken
+        around (Hz; None: the carrier, 0 the raw sum).  Its DTFT at |f| < fs / 2 is channel() at fc + f.  Returns a
+        complex64 tensor [nrx, ntx, 2, num_times, num_taps] on the device, enqueued on the current stream; `out` is
+        written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        fc = self.f_ghz * 1e9 if fc is None else float(fc)
+        spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
+        self.counts()
+        need = C.c_uint64(0)
+        rc = self.L.hrt_taps_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need))
+        if rc == -1:
+            raise ValueError("hrt_taps: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_taps_scratch_bytes")
+        shape = (self.nrx, self.ntx, 2, int(num_times), int(num_taps))
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            scratch = getattr(self, "_tp_scratch", None)
+            if scratch is None or scratch.numel() < int(need.value):
+                scratch = self._tp_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
+                                                         device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.L.hrt_taps(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
+                                   C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
+                                   C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream)),
+                   "hrt_taps")
+        return out
+
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):
         """Assemble the reference's dense [rx][tx][b][p] scatter arrays on the host from the

@@ -29,6 +29,7 @@ EXPORTED = (
     "hrt_rccl_comm_create", "hrt_rccl_comm_destroy", "hrt_gather_rccl", "hrt_stats_size", "hrt_layout_size",
     "hrt_channel_scratch_bytes", "hrt_channel", "hrt_compute_channel",
     "hrt_array_channel_scratch_bytes", "hrt_array_channel", "hrt_compute_array_channel",
+    "hrt_taps_scratch_bytes", "hrt_taps", "hrt_compute_taps",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -219,6 +220,15 @@ def load():
                                             C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                             f32p, C.POINTER(Stats)]
     L.hrt_compute_array_channel.restype = C.c_int
+    # sampled channel impulse responses (hrt_taps_spec: abi.TapsSpec)
+    tpp = C.POINTER(abi.TapsSpec)
+    L.hrt_taps_scratch_bytes.argtypes = [vp, C.POINTER(Shard), tpp, C.POINTER(u64)]
+    L.hrt_taps_scratch_bytes.restype = C.c_int
+    L.hrt_taps.argtypes = [vp, C.POINTER(Shard), vp, tpp, vp, u64, vp, C.c_int, vp]
+    L.hrt_taps.restype = C.c_int
+    L.hrt_compute_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                   C.c_size_t, C.c_size_t, tpp, f32p, C.POINTER(Stats)]
+    L.hrt_compute_taps.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

@@ -228,6 +228,30 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
                               size_t num_tx_elements, double array_frequency_hz,
                               float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Sampled channel impulse responses (taps) of the traced paths, formed on the device (include/hrt_device.h:
+ * hrt_taps).  For every (rx, tx), polarisation pol (0 = TE, 1 = TM), time sample m < num_times and tap i < num_taps:
+ *     h[rx][tx][pol][m][i] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) sinc(l_i - f_s tau_p)
+ *     t_m = t0 + m dt (s),  l_i = l_min + i,  sinc(x) = sin(pi x) / (pi x),  sinc(0) = 1
+ * over the paths hrt_channel sums (the same parts, LoS and scatter terms; blocked records add nothing).  f_s is the
+ * sampling rate; f_c the frequency the baseband is taken around (the amplitudes carry no carrier phase, so f_c = 0
+ * gives the raw sum).  This is the band-limited discrete-time channel: for |f| < f_s / 2 its DTFT
+ * sum_i h[i] exp(-j 2 pi f l_i / f_s) is hrt_compute_channel's H at f_k = f_c + f.
+ * out: complex [num_rx][num_tx][2][num_times][num_taps], re/im interleaved (numpy complex64).
+ * hrt_compute_taps traces and batches like hrt_compute_channel (one device, one download at the end).
+ * HRT_E_INVALID, before the device is touched: num_taps or num_times 0; num_taps * num_times > 2^20; f_s not finite
+ * or <= 0; f_c, t0 or dt not finite; |l_min| or |l_min + num_taps| > 2^24; parts 0 or with unknown bits. */
+typedef struct {
+    double fs_hz, fc_hz;                        /* sampling rate, baseband centre frequency */
+    double t0_s, dt_s;                          /* t_m = t0 + m*dt */
+    int32_t l_min;  uint32_t num_taps;          /* l_i = l_min + i */
+    uint32_t num_times;
+    uint32_t parts;                             /* HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER */
+} hrt_taps_spec;
+int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                     const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                     size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
+                     float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

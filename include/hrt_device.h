@@ -324,6 +324,19 @@ int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_wo
                       const hrt_channel_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
                       uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
 
+/* ---- sampled channel impulse responses from the traced paths (csrc/host/channel.c, csrc/hrt_taps.hip) ----
+ * h[rx][tx][pol][m][i] as hermespy_rt.h defines it (hrt_taps_spec, hrt_compute_taps), formed from the workspace of
+ * a finished hrt_trace (its counts read on the device: no host synchronisation), asynchronous on `stream`, with the
+ * guarantees of hrt_channel: accumulate = 0 overwrites d_out, 1 adds to it; only shard rank 0 adds the LoS term, so
+ * the outputs of the shards of one launch set sum to the whole result; partial sums go to the caller's scratch
+ * (hrt_taps_scratch_bytes) and are reduced in a fixed order, no floating-point atomics, so two calls with the same
+ * inputs give the same bits; the output is undefined if the trace's error word is set.
+ * HRT_E_INVALID, before the device is touched: every hrt_compute_taps spec check, num_rx * num_tx > 65535,
+ * scratch too small. */
+int hrt_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, uint64_t *out);
+int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+             void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
