@@ -311,10 +311,11 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
     return ChannelSpec(float(f0), float(df), int(num_freqs), float(t0), float(dt), int(num_times), int(parts))
 
 
-def run_compute_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
-                        stats=None):
-    """hrt_compute_channel through ctypes -> complex64 [nrx, ntx, 2, num_times, num_freqs].  Raises
-    RuntimeError("hrt_compute_channel failed (<rc>): ...") on an error code."""
+def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                 out_shape, extra, stats):
+    """One of hrt_compute_channel / _array_channel / _taps (`name`) through ctypes, into a complex64 numpy array of
+    shape (nrx, ntx) + out_shape (out_shape None: a placeholder the library refuses to write); `extra` are the
+    arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
     tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
     nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
@@ -322,19 +323,26 @@ def run_compute_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, 
     _, txp = _vec3_arg(tx_pos, ntx)
     rxv_a, rxv = _vec3_arg(rx_vel, nrx)
     txv_a, txv = _vec3_arg(tx_vel, ntx)
-    out = np.zeros((nrx, ntx, 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1)), np.complex64)
+    out = np.zeros((nrx, ntx) + tuple(out_shape) if out_shape is not None else (1,), np.complex64)
     scene = lib.scene_load(str(scene_path).encode())
     try:
-        rc = lib.hrt_compute_channel(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
-                                     C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
-                                     C.byref(spec), out.ctypes.data_as(c_float_p),
-                                     C.byref(stats) if stats is not None else None)
+        rc = getattr(lib, name)(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx), C.c_size_t(ntx),
+                                C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)), C.byref(spec), *extra,
+                                out.ctypes.data_as(c_float_p), C.byref(stats) if stats is not None else None)
     finally:
         free_scene(scene)
     if rc != 0:
-        raise RuntimeError("hrt_compute_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+        raise RuntimeError("%s failed (%d): %s" % (name, rc, lib.hrt_last_error().decode()))
     return out
 
+
+def run_compute_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                        stats=None):
+    """hrt_compute_channel through ctypes -> complex64 [nrx, ntx, 2, num_times, num_freqs].  Raises
+    RuntimeError("hrt_compute_channel failed (<rc>): ...") on an error code."""
+    shape = (2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
+    return _run_pathsum(lib, "hrt_compute_channel", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, shape, (), stats)
 
 class ArraySpec(C.Structure):
     """include/hrt_device.h hrt_array_spec (the element pointers are device pointers)"""
@@ -357,34 +365,16 @@ def run_compute_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f
     """hrt_compute_array_channel through ctypes -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_freqs]
     (array_frequency defaults to the carrier).  Raises RuntimeError("hrt_compute_array_channel failed (<rc>): ...")
     on an error code."""
-    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
-    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
-    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
-    _, rxp = _vec3_arg(rx_pos, nrx)
-    _, txp = _vec3_arg(tx_pos, ntx)
-    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
-    txv_a, txv = _vec3_arg(tx_vel, ntx)
     re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
     nr, nt = re.shape[0], te.shape[0]
     V3 = C.POINTER(Vec3)
     fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
-    shape = (nrx, ntx, max(nr, 1), max(nt, 1), 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
     # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
     pts = nr * nt * int(spec.num_times) * int(spec.num_freqs)
-    out = np.zeros(shape if 0 < pts <= (1 << 24) else (1,), np.complex64)
-    scene = lib.scene_load(str(scene_path).encode())
-    try:
-        rc = lib.hrt_compute_array_channel(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
-                                           C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
-                                           C.byref(spec), re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3),
-                                           C.c_size_t(nt), C.c_double(fa), out.ctypes.data_as(c_float_p),
-                                           C.byref(stats) if stats is not None else None)
-    finally:
-        free_scene(scene)
-    if rc != 0:
-        raise RuntimeError("hrt_compute_array_channel failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
-    return out
-
+    shape = (max(nr, 1), max(nt, 1), 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
+    extra = (re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3), C.c_size_t(nt), C.c_double(fa))
+    return _run_pathsum(lib, "hrt_compute_array_channel", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, shape if 0 < pts <= (1 << 24) else None, extra, stats)
 
 class TapsSpec(C.Structure):
     """include/hermespy_rt.h hrt_taps_spec"""
@@ -402,24 +392,7 @@ def run_compute_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num
                      stats=None):
     """hrt_compute_taps through ctypes -> complex64 [nrx, ntx, 2, num_times, num_taps].  Raises
     RuntimeError("hrt_compute_taps failed (<rc>): ...") on an error code."""
-    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
-    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
-    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
-    _, rxp = _vec3_arg(rx_pos, nrx)
-    _, txp = _vec3_arg(tx_pos, ntx)
-    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
-    txv_a, txv = _vec3_arg(tx_vel, ntx)
     # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
     nt, nl = int(spec.num_times), int(spec.num_taps)
-    out = np.zeros((nrx, ntx, 2, nt, nl) if 0 < nt * nl <= (1 << 20) else (1,), np.complex64)
-    scene = lib.scene_load(str(scene_path).encode())
-    try:
-        rc = lib.hrt_compute_taps(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
-                                  C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
-                                  C.byref(spec), out.ctypes.data_as(c_float_p),
-                                  C.byref(stats) if stats is not None else None)
-    finally:
-        free_scene(scene)
-    if rc != 0:
-        raise RuntimeError("hrt_compute_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
-    return out
+    return _run_pathsum(lib, "hrt_compute_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, (2, nt, nl) if 0 < nt * nl <= (1 << 20) else None, (), stats)

@@ -7,7 +7,7 @@
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
- * csrc/hrt_array_channel.hip and csrc/hrt_taps.hip;
+ * csrc/hrt_array_channel.hip and csrc/hrt_taps.hip, over the workspace view of csrc/hrt_pathsum.h;
  * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
  * small download at the end.
  */
@@ -18,14 +18,92 @@
 #include "hrt_internal.h"
 #include "../hrt_array_channel.h"
 #include "../hrt_channel.h"
+#include "../hrt_pathsum.h"
 #include "../hrt_taps.h"
+
+/* ------------------------------------------------------------------ what the three path sums share (hrt_pathsum.h) */
+
+#define HRT_CH_MIN_CHUNK 512u                /* records of one TX segment per chunk, at least */
+
+static int parts_check(uint32_t parts, const char *who)
+{
+    if (parts == 0 || (parts & ~(uint32_t)(HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)))
+        return hrt_fail(HRT_E_INVALID, "%s: parts 0x%x (HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)", who, parts);
+    return HRT_OK;
+}
+
+/* the workspace view of one call: the layout of the shard, the counts and the LoS rule (shard rank 0 adds the LoS
+ * term, so the shards of one launch set sum to the whole response); nchunks 0 */
+static int ps_view(const hrt_problem *p, const hrt_shard *s, uint32_t parts, const char *who, hrt_kview *v)
+{
+    if (!p || !s) return hrt_fail(HRT_E_INVALID, "%s: NULL argument", who);
+    hrt_layout L;
+    int rc = hrt_layout_query(p, s, &L);
+    if (rc) return rc;
+    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
+    if (links > 65535u)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx * num_tx = %llu > 65535", who, (unsigned long long)links);
+    memset(v, 0, sizeof *v);
+    v->cap = L.cap; v->off_counts = L.off_counts; v->off_los = L.off_los; v->off_hits = L.off_hits;
+    v->hit_block_bytes = L.hit_block_bytes; v->off_recs = L.off_recs; v->rec_block_bytes = L.rec_block_bytes;
+    v->off_masks = L.off_masks;
+    v->nb = s->num_bounces; v->nrx = p->num_rx; v->ntx = p->num_tx;
+    v->num_local = (uint32_t)hrt_shard_num_local(s);
+    v->los = (parts & HRT_CHANNEL_LOS) && s->rank == 0;
+    return HRT_OK;
+}
+
+/* record chunks per (link, block) of the scatter part: enough of the `groups` blocks per chunk to reach
+ * target_groups, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at most partial_max bytes (but one
+ * chunk always), and at most y_max (the chunks' grid dimension) */
+static uint32_t ps_nchunks(uint64_t groups, uint64_t target_groups, uint32_t num_local, uint64_t per_chunk,
+                           uint64_t partial_max, uint64_t y_max)
+{
+    uint64_t nch = (target_groups + groups - 1) / groups;
+    const uint64_t by_recs = num_local / HRT_CH_MIN_CHUNK;
+    if (nch > by_recs) nch = by_recs;
+    if (nch > partial_max / per_chunk) nch = partial_max / per_chunk;
+    if (nch > y_max) nch = y_max;
+    if (nch < 1) nch = 1;
+    return (uint32_t)nch;
+}
+
+/* the scratch of one call: seg, then nchunks * per_chunk bytes of partial sums */
+static uint64_t ps_seg_bytes(const hrt_kview *v)
+{
+    return ((uint64_t)v->nb * (v->ntx + 1u) * 4u + 255u) / 256u * 256u;
+}
+
+static int ps_scratch_out(int rc, uint64_t bytes, uint64_t *out, const char *query)
+{
+    if (rc) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "%s: NULL out", query);
+    *out = bytes;
+    return HRT_OK;
+}
+
+/* the device buffers of one call, once its plan needs `need` bytes of scratch (`query` names the size query) */
+static int ps_bind(hrt_kview *v, uint64_t need, const void *d_workspace, void *d_scratch, uint64_t scratch_bytes,
+                   const float *d_out, int accumulate, const char *who, const char *query, float **partial)
+{
+    if (!d_workspace || !d_out || !d_scratch)
+        return hrt_fail(HRT_E_INVALID, "%s: NULL workspace, scratch or output", who);
+    if (scratch_bytes < need)
+        return hrt_fail(HRT_E_INVALID, "%s: scratch of %llu bytes, %llu needed (%s)", who,
+                        (unsigned long long)scratch_bytes, (unsigned long long)need, query);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "%s: accumulate must be 0 or 1", who);
+    v->ws = (const uint8_t *)d_workspace;
+    v->accumulate = (uint32_t)accumulate;
+    v->seg = (uint32_t *)d_scratch;
+    *partial = (float *)((uint8_t *)d_scratch + ps_seg_bytes(v));
+    return HRT_OK;
+}
+
+/* ------------------------------------------------------------------ frequency responses (hrt_channel) */
 
 #define HRT_CH_MAX_POINTS (1u << 20)         /* num_freqs * num_times */
 #define HRT_CH_TARGET_GROUPS 8192u           /* waves of the partial kernel worth launching (32 per CU) */
-#define HRT_CH_MIN_CHUNK 512u                /* records of one TX segment per chunk, at least */
 #define HRT_CH_PARTIAL_MAX (512ull << 20)    /* partial sums beyond one chunk per tile: at most this */
-
-static uint64_t ch_round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 static int spec_check(const hrt_channel_spec *spec)
 {
@@ -35,8 +113,8 @@ static int spec_check(const hrt_channel_spec *spec)
     if ((uint64_t)spec->num_freqs * spec->num_times > HRT_CH_MAX_POINTS)
         return hrt_fail(HRT_E_INVALID, "hrt_channel: num_freqs * num_times = %llu > 2^20",
                         (unsigned long long)spec->num_freqs * spec->num_times);
-    if (spec->parts == 0 || (spec->parts & ~(uint32_t)(HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)))
-        return hrt_fail(HRT_E_INVALID, "hrt_channel: parts 0x%x (HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)", spec->parts);
+    int rc = parts_check(spec->parts, "hrt_channel");
+    if (rc) return rc;
     if (!isfinite(spec->f0_hz) || !isfinite(spec->df_hz) || !isfinite(spec->t0_s) || !isfinite(spec->dt_s))
         return hrt_fail(HRT_E_INVALID, "hrt_channel: f0, df, t0 and dt must be finite");
     return HRT_OK;
@@ -44,76 +122,46 @@ static int spec_check(const hrt_channel_spec *spec)
 
 /* the tiling of one call: a pure function of the problem, the shard and the spec (so the sums, and their
  * order, do not depend on anything else) */
-static int ch_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, hrt_layout *L,
-                   hrt_kchannel *K, uint64_t *bytes)
+static int ch_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, hrt_kchannel *K,
+                   uint64_t *bytes)
 {
     int rc = spec_check(spec);
     if (rc) return rc;
-    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_channel: NULL argument");
-    if ((rc = hrt_layout_query(p, s, L))) return rc;
-    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
-    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_channel: num_rx * num_tx = %llu > 65535",
-                                        (unsigned long long)links);
     memset(K, 0, sizeof *K);
-    K->cap = L->cap; K->off_counts = L->off_counts; K->off_los = L->off_los; K->off_hits = L->off_hits;
-    K->hit_block_bytes = L->hit_block_bytes; K->off_recs = L->off_recs; K->rec_block_bytes = L->rec_block_bytes;
-    K->off_masks = L->off_masks;
-    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
-    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_channel", &K->v))) return rc;
     K->K = spec->num_freqs; K->T = spec->num_times;
     K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
     K->rows = K->K1 * K->T;
     K->tiles = (K->rows + HRT_CH_ROWS - 1) / HRT_CH_ROWS;
     K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
-    const uint64_t tile_bytes = (uint64_t)HRT_CH_TILE_FLOATS * 4u, per_chunk = links * K->tiles * tile_bytes;
-    uint64_t nch = 0;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
-        /* enough waves to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, and partial sums
-         * of at most HRT_CH_PARTIAL_MAX (but one chunk always) */
-        const uint64_t groups = links * K->tiles;
-        nch = (HRT_CH_TARGET_GROUPS + groups - 1) / groups;
-        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
-        if (nch > by_recs) nch = by_recs;
-        if (nch > HRT_CH_PARTIAL_MAX / per_chunk) nch = HRT_CH_PARTIAL_MAX / per_chunk;
-        if (nch < 1) nch = 1;
-    }
-    K->nchunks = (uint32_t)nch;
-    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
-    *bytes = seg_bytes + nch * per_chunk;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
+    const uint64_t per_chunk = links * K->tiles * HRT_CH_TILE_FLOATS * 4u;
+    /* (the chunks are grid x: no cap; HRT_CH_MIN_CHUNK keeps them below 2^23) */
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
+        K->v.nchunks = ps_nchunks(links * K->tiles, HRT_CH_TARGET_GROUPS, K->v.num_local, per_chunk,
+                                  HRT_CH_PARTIAL_MAX, UINT32_MAX);
+    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
     return HRT_OK;
 }
 
 int hrt_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, uint64_t *out)
 {
-    hrt_layout L;
     hrt_kchannel K;
     uint64_t bytes = 0;
-    int rc = ch_plan(p, s, spec, &L, &K, &bytes);
-    if (rc) return rc;
-    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_channel_scratch_bytes: NULL out");
-    *out = bytes;
-    return HRT_OK;
+    const int rc = ch_plan(p, s, spec, &K, &bytes);
+    return ps_scratch_out(rc, bytes, out, "hrt_channel_scratch_bytes");
 }
 
 int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_channel_spec *spec,
                 void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream)
 {
-    hrt_layout L;
     hrt_kchannel K;
     uint64_t need = 0;
-    int rc = ch_plan(p, s, spec, &L, &K, &need);
+    int rc = ch_plan(p, s, spec, &K, &need);
     if (rc) return rc;
-    if (!d_workspace || !d_out || !d_scratch)
-        return hrt_fail(HRT_E_INVALID, "hrt_channel: NULL workspace, scratch or output");
-    if (scratch_bytes < need)
-        return hrt_fail(HRT_E_INVALID, "hrt_channel: scratch of %llu bytes, %llu needed (hrt_channel_scratch_bytes)",
-                        (unsigned long long)scratch_bytes, (unsigned long long)need);
-    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "hrt_channel: accumulate must be 0 or 1");
-    K.ws = (const uint8_t *)d_workspace;
-    K.accumulate = (uint32_t)accumulate;
-    K.seg = (uint32_t *)d_scratch;
-    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_channel",
+                      "hrt_channel_scratch_bytes", &K.partial)))
+        return rc;
     K.out = d_out;
     HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
     HRT_HIP(hrt_hip_launch_channel(&K, stream), "channel kernels");
@@ -286,21 +334,12 @@ static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_s
 {
     int rc = array_check(spec, a);
     if (rc) return rc;
-    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL argument");
-    hrt_layout L;
-    if ((rc = hrt_layout_query(p, s, &L))) return rc;
-    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
-    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: num_rx * num_tx = %llu > 65535",
-                                        (unsigned long long)links);
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_array_channel", &K->v))) return rc;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     if (links * 2u * a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_freqs >= (1ull << 39))
         return hrt_fail(HRT_E_INVALID, "hrt_array_channel: more than 2^39 outputs");
-    memset(K, 0, sizeof *K);
-    K->cap = L.cap; K->off_counts = L.off_counts; K->off_los = L.off_los; K->off_hits = L.off_hits;
-    K->hit_block_bytes = L.hit_block_bytes; K->off_recs = L.off_recs; K->rec_block_bytes = L.rec_block_bytes;
-    K->off_masks = L.off_masks;
     K->num_paths = s->num_paths;
-    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
-    K->num_local = (uint32_t)hrt_shard_num_local(s);
     K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
     K->nr = a->num_rx_elements; K->nt = a->num_tx_elements; K->npairs = K->nr * K->nt;
     K->K = spec->num_freqs; K->T = spec->num_times;
@@ -310,23 +349,11 @@ static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_s
     K->cblocks = (K->rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
     K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
     K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
-    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
     const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->K * 8u;
-    uint64_t nch = 0;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
-        /* enough workgroups to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at
-         * most HRT_AC_PARTIAL_MAX (but one chunk always), and a grid y of at most 65535 */
-        const uint64_t groups = links * K->pblocks * K->cblocks;
-        nch = (HRT_AC_TARGET_GROUPS + groups - 1) / groups;
-        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
-        if (nch > by_recs) nch = by_recs;
-        if (nch > HRT_AC_PARTIAL_MAX / per_chunk) nch = HRT_AC_PARTIAL_MAX / per_chunk;
-        if (nch > 65535u) nch = 65535u;
-        if (nch < 1) nch = 1;
-    }
-    K->nchunks = (uint32_t)nch;
-    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
-    *bytes = seg_bytes + nch * per_chunk;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
+        K->v.nchunks = ps_nchunks(links * K->pblocks * K->cblocks, HRT_AC_TARGET_GROUPS, K->v.num_local, per_chunk,
+                                  HRT_AC_PARTIAL_MAX, 65535u);
+    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
     return HRT_OK;
 }
 
@@ -335,11 +362,8 @@ int hrt_array_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, co
 {
     hrt_karray K;
     uint64_t bytes = 0;
-    int rc = ac_plan(p, s, spec, arrays, &K, &bytes);
-    if (rc) return rc;
-    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_array_channel_scratch_bytes: NULL out");
-    *out = bytes;
-    return HRT_OK;
+    const int rc = ac_plan(p, s, spec, arrays, &K, &bytes);
+    return ps_scratch_out(rc, bytes, out, "hrt_array_channel_scratch_bytes");
 }
 
 int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
@@ -350,20 +374,11 @@ int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_wo
     uint64_t need = 0;
     int rc = ac_plan(p, s, spec, arrays, &K, &need);
     if (rc) return rc;
-    if (!d_workspace || !d_out || !d_scratch)
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL workspace, scratch or output");
-    if (scratch_bytes < need)
-        return hrt_fail(HRT_E_INVALID,
-                        "hrt_array_channel: scratch of %llu bytes, %llu needed (hrt_array_channel_scratch_bytes)",
-                        (unsigned long long)scratch_bytes, (unsigned long long)need);
-    if (accumulate != 0 && accumulate != 1)
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: accumulate must be 0 or 1");
-    K.ws = (const uint8_t *)d_workspace;
-    K.accumulate = (uint32_t)accumulate;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_array_channel",
+                      "hrt_array_channel_scratch_bytes", &K.partial)))
+        return rc;
     K.rx_el = arrays->rx_elements;
     K.tx_el = arrays->tx_elements;
-    K.seg = (const uint32_t *)d_scratch;
-    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
     K.out = d_out;
     HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
     HRT_HIP(hrt_hip_launch_array_channel(&K, stream), "array channel kernels");
@@ -461,9 +476,7 @@ static int taps_check(const hrt_taps_spec *spec)
     if (lo < -HRT_TP_MAX_TAP || lo > HRT_TP_MAX_TAP || hi > HRT_TP_MAX_TAP)
         return hrt_fail(HRT_E_INVALID, "hrt_taps: tap indices l_min = %lld .. %lld outside +-2^24", (long long)lo,
                         (long long)hi);
-    if (spec->parts == 0 || (spec->parts & ~(uint32_t)(HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)))
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: parts 0x%x (HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER)", spec->parts);
-    return HRT_OK;
+    return parts_check(spec->parts, "hrt_taps");
 }
 
 /* the tiling of one taps call: a pure function of the problem, the shard and the spec */
@@ -472,18 +485,8 @@ static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_sp
 {
     int rc = taps_check(spec);
     if (rc) return rc;
-    if (!p || !s) return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL argument");
-    hrt_layout L;
-    if ((rc = hrt_layout_query(p, s, &L))) return rc;
-    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
-    if (links > 65535u) return hrt_fail(HRT_E_INVALID, "hrt_taps: num_rx * num_tx = %llu > 65535",
-                                        (unsigned long long)links);
     memset(K, 0, sizeof *K);
-    K->cap = L.cap; K->off_counts = L.off_counts; K->off_los = L.off_los; K->off_hits = L.off_hits;
-    K->hit_block_bytes = L.hit_block_bytes; K->off_recs = L.off_recs; K->rec_block_bytes = L.rec_block_bytes;
-    K->off_masks = L.off_masks;
-    K->nb = s->num_bounces; K->nrx = p->num_rx; K->ntx = p->num_tx;
-    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_taps", &K->v))) return rc;
     K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
     K->rtiles = (4u * K->T + 15u) / 16u;
     K->ctiles = (K->L + 15u) / 16u;
@@ -494,23 +497,12 @@ static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_sp
     K->rblocks = (K->rtiles + K->rt - 1u) / K->rt;
     K->cblocks = (K->ctiles + 4u * ct - 1u) / (4u * ct);
     K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    K->los = (spec->parts & HRT_CHANNEL_LOS) && s->rank == 0;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     const uint64_t per_chunk = links * 2u * K->T * K->L * 8u;
-    uint64_t nch = 0;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0) {
-        /* enough workgroups to fill the device, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at
-         * most HRT_TP_PARTIAL_MAX (but one chunk always), and a grid y of at most 65535 */
-        const uint64_t groups = links * K->rblocks * K->cblocks;
-        nch = (HRT_TP_TARGET_GROUPS + groups - 1) / groups;
-        const uint64_t by_recs = K->num_local / HRT_CH_MIN_CHUNK;
-        if (nch > by_recs) nch = by_recs;
-        if (nch > HRT_TP_PARTIAL_MAX / per_chunk) nch = HRT_TP_PARTIAL_MAX / per_chunk;
-        if (nch > 65535u) nch = 65535u;
-        if (nch < 1) nch = 1;
-    }
-    K->nchunks = (uint32_t)nch;
-    const uint64_t seg_bytes = ch_round_up((uint64_t)K->nb * (K->ntx + 1u) * 4u, 256);
-    *bytes = seg_bytes + nch * per_chunk;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
+        K->v.nchunks = ps_nchunks(links * K->rblocks * K->cblocks, HRT_TP_TARGET_GROUPS, K->v.num_local, per_chunk,
+                                  HRT_TP_PARTIAL_MAX, 65535u);
+    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
     return HRT_OK;
 }
 
@@ -518,11 +510,8 @@ int hrt_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_t
 {
     hrt_ktaps K;
     uint64_t bytes = 0;
-    int rc = taps_plan(p, s, spec, &K, &bytes);
-    if (rc) return rc;
-    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_taps_scratch_bytes: NULL out");
-    *out = bytes;
-    return HRT_OK;
+    const int rc = taps_plan(p, s, spec, &K, &bytes);
+    return ps_scratch_out(rc, bytes, out, "hrt_taps_scratch_bytes");
 }
 
 int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
@@ -532,16 +521,9 @@ int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, 
     uint64_t need = 0;
     int rc = taps_plan(p, s, spec, &K, &need);
     if (rc) return rc;
-    if (!d_workspace || !d_out || !d_scratch)
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL workspace, scratch or output");
-    if (scratch_bytes < need)
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: scratch of %llu bytes, %llu needed (hrt_taps_scratch_bytes)",
-                        (unsigned long long)scratch_bytes, (unsigned long long)need);
-    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "hrt_taps: accumulate must be 0 or 1");
-    K.ws = (const uint8_t *)d_workspace;
-    K.accumulate = (uint32_t)accumulate;
-    K.seg = (const uint32_t *)d_scratch;
-    K.partial = (float *)((uint8_t *)d_scratch + ch_round_up((uint64_t)K.nb * (K.ntx + 1u) * 4u, 256));
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_taps",
+                      "hrt_taps_scratch_bytes", &K.partial)))
+        return rc;
     K.out = d_out;
     HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
     HRT_HIP(hrt_hip_launch_taps(&K, stream), "taps kernels");

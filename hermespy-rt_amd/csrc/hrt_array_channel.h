@@ -10,11 +10,13 @@
  * B row 0 = Re W, row 1 = Im W, over 32 padded columns.
  * A workgroup (4 waves) forms HRT_AC_PAIRS pairs x HRT_AC_COLS padded columns of one link from one chunk of the
  * link's records and writes them to the partial sums of the scratch; the reduce kernel adds the chunks in a fixed
- * order (no atomics: bit-reproducible). */
+ * order (csrc/hrt_pathsum.h). */
 #ifndef HRT_ARRAY_CHANNEL_H
 #define HRT_ARRAY_CHANNEL_H
 
 #include <stdint.h>
+
+#include "hrt_pathsum.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -28,19 +30,15 @@ extern "C" {
 #define HRT_AC_MAX_POINTS (1u << 24)   /* Nr * Nt * T * K */
 
 typedef struct {
-    const uint8_t *ws;              /* workspace of a finished hrt_trace */
-    uint64_t cap, off_counts, off_los, off_hits, hit_block_bytes, off_recs, rec_block_bytes, off_masks;
+    hrt_kview v;
     uint64_t num_paths;             /* the shard's N: departure directions from the global path */
-    uint32_t nb, nrx, ntx, num_local, rank, count, chunk;
+    uint32_t rank, count, chunk;
     uint32_t nr, nt, npairs;        /* elements; npairs = nr * nt */
     uint32_t K, T, K1, rows;        /* rows = T * K1 */
     uint32_t pblocks, cblocks;      /* ceil(npairs / HRT_AC_PAIRS), ceil(rows / HRT_AC_GROWS) */
-    uint32_t nchunks;               /* record chunks per (link, block); 0: no scatter part */
-    uint32_t los, accumulate;       /* add the LoS term (shard rank 0 only) / add into out */
     double f0, df, t0, dt;
     double fa_c;                    /* f_a / c: revolutions per metre of path difference */
     const float *rx_el, *tx_el;     /* device [nr][3], [nt][3] element offsets (m) */
-    const uint32_t *seg;            /* scratch: [nb][ntx + 1] first hit of every TX segment */
     float *partial;                 /* scratch: complex [link][chunk][pol][pair][T * K] */
     float *out;                     /* complex [nrx][ntx][nr][nt][2][T][K] */
 } hrt_karray;

@@ -4,7 +4,8 @@
 //     H[rx, tx, i, j, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) exp(j 2 pi f_a (r_i . u_rx + q_j . u_tx) / c)
 //
 // over the LoS entry (hrt_array_reduce_kernel) and every unblocked scatter record (hrt_array_partial_kernel) of
-// the link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip).
+// the link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip); the
+// workspace view and its readers are csrc/hrt_pathsum.h.
 //   hrt_array_partial_kernel  one workgroup (4 waves) per (pair block x column block, record chunk, link): the
 //                             complex GEMM of csrc/hrt_array_channel.h on v_mfma_f32_32x32x2_f32, partial sums to
 //                             the scratch.  The unblocked records of the chunk are compacted by mask ballots and
@@ -25,51 +26,20 @@
 
 #include "hrt_array_channel.h"
 #include "hrt_channel.h"
-#include "hrt_device.h"
 #include "hrt_launch_dir.h"
+#include "hrt_pathsum.h"
 
 typedef float hrt_f32x16 __attribute__((ext_vector_type(16)));
-
-namespace {
-
-// the fraction of a phase in revolutions, as the argument of sincospi (half revolutions, in [-1, 1])
-__device__ __forceinline__ float half_revs(double ph)
-{
-    return (float)(2.0 * (ph - rint(ph)));
-}
-
-__device__ __forceinline__ const float *rec_field(const hrt_karray &P, uint32_t b, uint32_t rx, uint32_t f)
-{
-    return reinterpret_cast<const float *>(P.ws + P.off_recs + (uint64_t)b * P.rec_block_bytes +
-                                           ((uint64_t)rx * HRT_REC_FIELDS + f) * P.cap * 4u);
-}
-
-__device__ __forceinline__ const uint32_t *hit_field(const hrt_karray &P, uint32_t b, uint32_t f)
-{
-    return reinterpret_cast<const uint32_t *>(P.ws + P.off_hits + (uint64_t)b * P.hit_block_bytes +
-                                              (uint64_t)f * P.cap * 4u);
-}
-
-// the records [start, end) of chunk c of the TX segment of hit block b
-__device__ __forceinline__ void chunk_range(const hrt_karray &P, uint32_t b, uint32_t tx, uint32_t c, uint32_t &start,
-                                            uint32_t &end)
-{
-    const uint32_t s0 = P.seg[b * (P.ntx + 1u) + tx], s1 = P.seg[b * (P.ntx + 1u) + tx + 1u];
-    const uint64_t n = s1 - s0;
-    start = s0 + (uint32_t)(n * c / P.nchunks);
-    end = s0 + (uint32_t)(n * (c + 1u) / P.nchunks);
-}
-
-}  // namespace
 
 // record fields staged per record: te re, te im, tm re, tm im, tau, nu, u_rx (3), u_tx (3)
 #define HRT_AC_REC_FLOATS 12u
 
 __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const hrt_karray P)
 {
+    const hrt_kview &V = P.v;
     const uint32_t blk = blockIdx.x, c = blockIdx.y, link = blockIdx.z;
     const uint32_t pb = blk % P.pblocks, cb = blk / P.pblocks;
-    const uint32_t rx = link / P.ntx, tx = link % P.ntx;
+    const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t h = lane >> 5, k2 = lane & 15u, rsub = (lane >> 4) & 1u;
 
@@ -107,20 +77,19 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[a][t][q][r] = 0.f;
 
-    const uint64_t words = P.cap / 64u;
     uint32_t b = 0, cur = 0, end = 0;
-    chunk_range(P, 0, tx, c, cur, end);
+    chunk_range(V, 0, tx, c, cur, end);
     for (;;) {
-        // fill a batch with the next unblocked records of the chunk (every wave takes the same decisions; wave 0
-        // writes the list)
+        // the batch fill of fill_batch (csrc/hrt_pathsum.h), written out: through the helper the compiler schedules
+        // this kernel's staging differently (376 VGPRs instead of 384) and the kernel ran about 1 % slower on C3
         uint32_t n = 0;
-        while (n < HRT_AC_BATCH && b < P.nb) {
+        while (n < HRT_AC_BATCH && b < V.nb) {
             if (cur >= end) {
-                if (++b < P.nb) chunk_range(P, b, tx, c, cur, end);
+                if (++b < V.nb) chunk_range(V, b, tx, c, cur, end);
                 continue;
             }
             const uint32_t i = cur + lane;
-            const uint64_t *mask = reinterpret_cast<const uint64_t *>(P.ws + P.off_masks) + ((uint64_t)b * P.nrx + rx) * words;
+            const uint64_t *mask = mask_row(V, b, rx);
             const bool live = i < end && ((mask[i >> 6] >> (i & 63u)) & 1u);
             const uint64_t bal = __ballot(live);
             const uint32_t cnt = __popcll(bal), take = min(cnt, HRT_AC_BATCH - n);
@@ -143,16 +112,16 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
         if (tid < n) {   // the record's fields and its departure direction
             const uint32_t rb = sB[tid], i = sI[tid];
             float *R = sRec[tid];
-            R[0] = rec_field(P, rb, rx, HRT_REC_A_TE_RE)[i];
-            R[1] = rec_field(P, rb, rx, HRT_REC_A_TE_IM)[i];
-            R[2] = rec_field(P, rb, rx, HRT_REC_A_TM_RE)[i];
-            R[3] = rec_field(P, rb, rx, HRT_REC_A_TM_IM)[i];
-            R[4] = rec_field(P, rb, rx, HRT_REC_TAU)[i];
-            R[5] = __uint_as_float(hit_field(P, rb, HRT_HIT_FS0)[i]) - rec_field(P, rb, rx, HRT_REC_DFS)[i];
-            R[6] = rec_field(P, rb, rx, HRT_REC_DIRX)[i];
-            R[7] = rec_field(P, rb, rx, HRT_REC_DIRY)[i];
-            R[8] = rec_field(P, rb, rx, HRT_REC_DIRZ)[i];
-            const uint32_t local = hit_field(P, rb, HRT_HIT_RAY)[i] - tx * P.num_local;
+            R[0] = rec_field(V, rb, rx, HRT_REC_A_TE_RE)[i];
+            R[1] = rec_field(V, rb, rx, HRT_REC_A_TE_IM)[i];
+            R[2] = rec_field(V, rb, rx, HRT_REC_A_TM_RE)[i];
+            R[3] = rec_field(V, rb, rx, HRT_REC_A_TM_IM)[i];
+            R[4] = rec_field(V, rb, rx, HRT_REC_TAU)[i];
+            R[5] = __uint_as_float(hit_field(V, rb, HRT_HIT_FS0)[i]) - rec_field(V, rb, rx, HRT_REC_DFS)[i];
+            R[6] = rec_field(V, rb, rx, HRT_REC_DIRX)[i];
+            R[7] = rec_field(V, rb, rx, HRT_REC_DIRY)[i];
+            R[8] = rec_field(V, rb, rx, HRT_REC_DIRZ)[i];
+            const uint32_t local = hit_field(V, rb, HRT_HIT_RAY)[i] - tx * V.num_local;
             const hrt_launch_dir_t d = hrt_launch_dir(hrt_shard_path(local, P.chunk, P.count, P.rank), P.num_paths);
             R[9] = d.fx;
             R[10] = d.fy;
@@ -229,7 +198,7 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
 
     // D: lane = column, register r = row (r & 3) + 8 (r >> 2) + 4 h; rows 0..15 Re H, 16..31 Im H of 16 pairs
     const uint64_t tk = (uint64_t)P.T * P.K;
-    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * P.nchunks + c) * 2u * P.npairs * tk;
+    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * V.nchunks + c) * 2u * P.npairs * tk;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const uint32_t g = cb * HRT_AC_GROWS + 4u * w + 2u * t + rsub;
@@ -252,48 +221,39 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
 // one thread per output (link, pair, pol, m, k): the chunks in order, + LoS, -> out
 __global__ void hrt_array_reduce_kernel(const hrt_karray P)
 {
+    const hrt_kview &V = P.v;
     const uint64_t tk = (uint64_t)P.T * P.K;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t per_link = (uint64_t)P.npairs * 2u * tk;
-    if (gid >= per_link * P.nrx * P.ntx) return;
+    if (gid >= per_link * V.nrx * V.ntx) return;
     const uint32_t link = (uint32_t)(gid / per_link);
     const uint64_t e = gid - (uint64_t)link * per_link;   // = (pair * 2 + pol) * tk + col
     const uint32_t pair = (uint32_t)(e / (2u * tk)), pol = (uint32_t)(e / tk) & 1u;
     const uint64_t col = e % tk;
 
     float2 s = make_float2(0.f, 0.f);
-    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * P.nchunks * per_link +
+    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link +
                         ((uint64_t)pol * P.npairs + pair) * tk + col;
-    for (uint32_t c = 0; c < P.nchunks; ++c) {
+    for (uint32_t c = 0; c < V.nchunks; ++c) {
         const float2 v = src[(uint64_t)c * per_link];
         s.x += v.x;
         s.y += v.y;
     }
-    if (P.los) {
-        const float *L = reinterpret_cast<const float *>(P.ws + P.off_los) + (uint64_t)link * HRT_LOS_FLOATS;
-        const uint32_t status = __float_as_uint(L[HRT_LOS_STATUS]);
-        if (status == 0u || status == 2u) {
-            // HRT_LOS_DIR is directions_tx; directions_rx = -directions_tx.  Coincident: a = 1, tau = nu = 0,
-            // directions_rx = (1, 0, 0), directions_tx = (-1, 0, 0) (src/compute_paths.c:533-534)
-            float a = 1.f, tau = 0.f, nu = 0.f, ux = -1.f, uy = 0.f, uz = 0.f;
-            if (status == 2u) {
-                a = L[HRT_LOS_A]; tau = L[HRT_LOS_TAU]; nu = L[HRT_LOS_FS];
-                ux = L[HRT_LOS_DIRX]; uy = L[HRT_LOS_DIRY]; uz = L[HRT_LOS_DIRZ];
-            }
-            const uint32_t i = pair / P.nt, j = pair - i * P.nt;
-            const float *r = P.rx_el + 3u * i, *q = P.tx_el + 3u * j;
-            const double pr = (double)r[0] * -ux + (double)r[1] * -uy + (double)r[2] * -uz;   // r_i . u_rx
-            const double pt = (double)q[0] * ux + (double)q[1] * uy + (double)q[2] * uz;      // q_j . u_tx
-            const uint32_t m = (uint32_t)(col / P.K), k = (uint32_t)(col % P.K);
-            const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
-            float sn, cs;
-            sincospif(half_revs((double)nu * t - f * (double)tau + P.fa_c * (pr + pt)), &sn, &cs);
-            s.x += a * cs;
-            s.y += a * sn;
-        }
+    hrt_los_entry L;
+    if (V.los && los_entry(V, link, L)) {
+        const uint32_t i = pair / P.nt, j = pair - i * P.nt;
+        const float *r = P.rx_el + 3u * i, *q = P.tx_el + 3u * j;
+        const double pr = (double)r[0] * -L.ux + (double)r[1] * -L.uy + (double)r[2] * -L.uz;   // r_i . u_rx
+        const double pt = (double)q[0] * L.ux + (double)q[1] * L.uy + (double)q[2] * L.uz;      // q_j . u_tx
+        const uint32_t m = (uint32_t)(col / P.K), k = (uint32_t)(col % P.K);
+        const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
+        float sn, cs;
+        sincospif(half_revs((double)L.nu * t - f * (double)L.tau + P.fa_c * (pr + pt)), &sn, &cs);
+        s.x += L.a * cs;
+        s.y += L.a * sn;
     }
     float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
-    if (P.accumulate) {
+    if (V.accumulate) {
         const float2 v = o[0];
         s.x += v.x;
         s.y += v.y;
@@ -304,15 +264,11 @@ __global__ void hrt_array_reduce_kernel(const hrt_karray P)
 extern "C" int hrt_hip_launch_array_channel(const hrt_karray *P, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t links = P->nrx * P->ntx;
-    if (P->nchunks) {
-        hrt_kchannel S = {};
-        S.ws = P->ws; S.cap = P->cap; S.off_counts = P->off_counts; S.off_hits = P->off_hits;
-        S.hit_block_bytes = P->hit_block_bytes; S.nb = P->nb; S.ntx = P->ntx; S.num_local = P->num_local;
-        S.seg = const_cast<uint32_t *>(P->seg);
-        const int e = hrt_hip_launch_channel_segments(&S, stream);
+    const uint32_t links = P->v.nrx * P->v.ntx;
+    if (P->v.nchunks) {
+        const int e = hrt_hip_launch_segments(&P->v, stream);
         if (e) return e;
-        hipLaunchKernelGGL(hrt_array_partial_kernel, dim3(P->pblocks * P->cblocks, P->nchunks, links),
+        hipLaunchKernelGGL(hrt_array_partial_kernel, dim3(P->pblocks * P->cblocks, P->v.nchunks, links),
                            dim3(HRT_AC_THREADS), 0, st, *P);
     }
     const uint64_t n = (uint64_t)links * P->npairs * 2u * P->T * P->K;

@@ -7,11 +7,13 @@
  *     U = a_p exp(j 2 pi (nu_p t_m - (f0 + k1 K2 df) tau_p)),   V = exp(-j 2 pi k2 df tau_p).
  * Rows (m, k1) are cut into tiles of HRT_CH_ROWS; one workgroup (one wave) forms one tile of one
  * link from a chunk of that link's records and writes it to the partial sums of the scratch; the
- * reduce kernel adds the chunks in a fixed order (no atomics: bit-reproducible). */
+ * reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h). */
 #ifndef HRT_CHANNEL_H
 #define HRT_CHANNEL_H
 
 #include <stdint.h>
+
+#include "hrt_pathsum.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -24,21 +26,14 @@ extern "C" {
 #define HRT_CH_TILE_FLOATS (HRT_CH_ROWS * HRT_CH_K2 * 4u)   /* te re, te im, tm re, tm im */
 
 typedef struct {
-    const uint8_t *ws;              /* workspace of a finished hrt_trace */
-    uint64_t cap, off_counts, off_los, off_hits, hit_block_bytes, off_recs, rec_block_bytes, off_masks;
-    uint32_t nb, nrx, ntx, num_local;
+    hrt_kview v;                    /* nchunks: record chunks per (link, tile) */
     uint32_t K, T, K1, rows, tiles; /* rows = T * K1, tiles = ceil(rows / HRT_CH_ROWS) */
-    uint32_t nchunks;               /* record chunks per (link, tile); 0: no scatter part */
-    uint32_t los, accumulate;       /* add the LoS term (shard rank 0 only) / add into out */
     double f0, df, t0, dt;
-    uint32_t *seg;                  /* scratch: [nb][ntx + 1] first hit of every TX segment */
     float *partial;                 /* scratch: [link][chunk][tile][HRT_CH_TILE_FLOATS] */
     float *out;                     /* complex [nrx][ntx][2][T][K] */
 } hrt_kchannel;
 
 int hrt_hip_launch_channel(const hrt_kchannel *P, void *stream);
-/* hrt_channel_segments_kernel alone: P->seg[b][t] for every bounce b and t <= ntx */
-int hrt_hip_launch_channel_segments(const hrt_kchannel *P, void *stream);
 
 #ifdef __cplusplus
 }

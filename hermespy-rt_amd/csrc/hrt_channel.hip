@@ -12,7 +12,9 @@
 //                                csrc/hrt_channel.h as an FP32 complex GEMM on the VALU (explicit fmaf; the
 //                                library builds with -ffp-contract=off), partial sums to the scratch;
 //   hrt_channel_reduce_kernel    per output: the chunks in a fixed order, plus the LoS term, into out.
-// No floating-point atomics anywhere: two calls with the same inputs give the same bits.
+// No floating-point atomics anywhere: two calls with the same inputs give the same bits.  The workspace view and the
+// helpers that read it are csrc/hrt_pathsum.h, shared with the array channel and the taps, which reuse the segments
+// kernel.
 //
 // Phases are reduced in FP64 (fract of f * tau in revolutions; f tau reaches 10^4 revolutions at 70 GHz,
 // more than an f32 product keeps) and then evaluated with an f32 sincospi.
@@ -21,54 +23,33 @@
 #include <stdint.h>
 
 #include "hrt_channel.h"
-#include "hrt_device.h"
-
-namespace {
-
-// the fraction of a phase in revolutions, as the argument of sincospi (half revolutions, in [-1, 1])
-__device__ __forceinline__ float half_revs(double ph)
-{
-    return (float)(2.0 * (ph - rint(ph)));
-}
-
-__device__ __forceinline__ const float *rec_field(const hrt_kchannel &P, uint32_t b, uint32_t rx, uint32_t f)
-{
-    return reinterpret_cast<const float *>(P.ws + P.off_recs + (uint64_t)b * P.rec_block_bytes +
-                                           ((uint64_t)rx * HRT_REC_FIELDS + f) * P.cap * 4u);
-}
-
-__device__ __forceinline__ const uint32_t *hit_field(const hrt_kchannel &P, uint32_t b, uint32_t f)
-{
-    return reinterpret_cast<const uint32_t *>(P.ws + P.off_hits + (uint64_t)b * P.hit_block_bytes +
-                                              (uint64_t)f * P.cap * 4u);
-}
-
-}  // namespace
+#include "hrt_pathsum.h"
 
 // one thread per (bounce, t <= ntx): seg[b][t] = first entry of hit block b whose ray belongs to TX >= t
-__global__ void hrt_channel_segments_kernel(const hrt_kchannel P)
+__global__ void hrt_channel_segments_kernel(const hrt_kview V)
 {
-    const uint32_t *counts = reinterpret_cast<const uint32_t *>(P.ws + P.off_counts);
-    const uint32_t per = P.ntx + 1u;
-    for (uint32_t i = threadIdx.x; i < P.nb * per; i += blockDim.x) {
+    const uint32_t *counts = reinterpret_cast<const uint32_t *>(V.ws + V.off_counts);
+    const uint32_t per = V.ntx + 1u;
+    for (uint32_t i = threadIdx.x; i < V.nb * per; i += blockDim.x) {
         const uint32_t b = i / per, t = i % per;
-        const uint32_t *ray = hit_field(P, b, HRT_HIT_RAY);
+        const uint32_t *ray = hit_field(V, b, HRT_HIT_RAY);
         uint32_t lo = 0, hi = counts[b + 1];
-        if (hi > P.cap) hi = (uint32_t)P.cap;   // (a corrupt count must not walk out of the block)
-        const uint64_t key = (uint64_t)t * P.num_local;
+        if (hi > V.cap) hi = (uint32_t)V.cap;   // (a corrupt count must not walk out of the block)
+        const uint64_t key = (uint64_t)t * V.num_local;
         while (lo < hi) {
             const uint32_t mid = lo + (hi - lo) / 2u;
             if ((uint64_t)ray[mid] < key) lo = mid + 1u;
             else hi = mid;
         }
-        P.seg[i] = lo;
+        V.seg[i] = lo;
     }
 }
 
 __global__ void __launch_bounds__(HRT_CH_THREADS) hrt_channel_partial_kernel(const hrt_kchannel P)
 {
+    const hrt_kview &V = P.v;
     const uint32_t c = blockIdx.x, tile = blockIdx.y, link = blockIdx.z;
-    const uint32_t rx = link / P.ntx, tx = link % P.ntx;
+    const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint32_t l = threadIdx.x;
     const uint32_t tc = l & 3u, tr = l >> 2;        // this thread's outputs: rows 4 tr .. +3, cols 4 tc .. +3
     const uint32_t sj = l & (HRT_CH_BATCH - 1u);    // staging: record sj of the batch,
@@ -85,17 +66,15 @@ __global__ void __launch_bounds__(HRT_CH_THREADS) hrt_channel_partial_kernel(con
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.f;
 
-    const uint64_t words = P.cap / 64u;
-    for (uint32_t b = 0; b < P.nb; ++b) {
-        const uint32_t s0 = P.seg[b * (P.ntx + 1u) + tx], s1 = P.seg[b * (P.ntx + 1u) + tx + 1u];
-        const uint64_t n = s1 - s0;
-        const uint32_t start = s0 + (uint32_t)(n * c / P.nchunks), end = s0 + (uint32_t)(n * (c + 1u) / P.nchunks);
+    for (uint32_t b = 0; b < V.nb; ++b) {
+        uint32_t start, end;
+        chunk_range(V, b, tx, c, start, end);
         if (start >= end) continue;
-        const float *are = rec_field(P, b, rx, HRT_REC_A_TE_RE), *aim = rec_field(P, b, rx, HRT_REC_A_TE_IM);
-        const float *bre = rec_field(P, b, rx, HRT_REC_A_TM_RE), *bim = rec_field(P, b, rx, HRT_REC_A_TM_IM);
-        const float *tau_f = rec_field(P, b, rx, HRT_REC_TAU), *dfs_f = rec_field(P, b, rx, HRT_REC_DFS);
-        const float *fs0_f = reinterpret_cast<const float *>(hit_field(P, b, HRT_HIT_FS0));
-        const uint64_t *mask = reinterpret_cast<const uint64_t *>(P.ws + P.off_masks) + ((uint64_t)b * P.nrx + rx) * words;
+        const float *are = rec_field(V, b, rx, HRT_REC_A_TE_RE), *aim = rec_field(V, b, rx, HRT_REC_A_TE_IM);
+        const float *bre = rec_field(V, b, rx, HRT_REC_A_TM_RE), *bim = rec_field(V, b, rx, HRT_REC_A_TM_IM);
+        const float *tau_f = rec_field(V, b, rx, HRT_REC_TAU), *dfs_f = rec_field(V, b, rx, HRT_REC_DFS);
+        const float *fs0_f = reinterpret_cast<const float *>(hit_field(V, b, HRT_HIT_FS0));
+        const uint64_t *mask = mask_row(V, b, rx);
         for (uint32_t p0 = start; p0 < end; p0 += HRT_CH_BATCH) {
             {   // stage U and V of records p0 .. p0 + 15 (zeros past the chunk and for blocked records: their
                 // amplitudes are exact zeros and their Doppler term is not written)
@@ -154,7 +133,7 @@ __global__ void __launch_bounds__(HRT_CH_THREADS) hrt_channel_partial_kernel(con
         }
     }
     float4 *dst = reinterpret_cast<float4 *>(P.partial) +
-                  (((uint64_t)link * P.nchunks + c) * P.tiles + tile) * (HRT_CH_ROWS * HRT_CH_K2);
+                  (((uint64_t)link * V.nchunks + c) * P.tiles + tile) * (HRT_CH_ROWS * HRT_CH_K2);
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -165,9 +144,10 @@ __global__ void __launch_bounds__(HRT_CH_THREADS) hrt_channel_partial_kernel(con
 // one thread per (link, row, column) of the padded grid: sum of the chunks in order, + LoS, -> out
 __global__ void hrt_channel_reduce_kernel(const hrt_kchannel P)
 {
+    const hrt_kview &V = P.v;
     const uint64_t per_link = (uint64_t)P.tiles * HRT_CH_ROWS * HRT_CH_K2;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= per_link * P.nrx * P.ntx) return;
+    if (gid >= per_link * V.nrx * V.ntx) return;
     const uint32_t link = (uint32_t)(gid / per_link);
     const uint64_t e = gid - (uint64_t)link * per_link;   // = tile * ROWS * K2 + row_in_tile * K2 + col
     const uint32_t g = (uint32_t)(e / HRT_CH_K2), k2 = (uint32_t)(e % HRT_CH_K2);
@@ -176,31 +156,24 @@ __global__ void hrt_channel_reduce_kernel(const hrt_kchannel P)
     if (k >= P.K) return;
 
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 *src = reinterpret_cast<const float4 *>(P.partial) + (uint64_t)link * P.nchunks * per_link + e;
-    for (uint32_t c = 0; c < P.nchunks; ++c) {
+    const float4 *src = reinterpret_cast<const float4 *>(P.partial) + (uint64_t)link * V.nchunks * per_link + e;
+    for (uint32_t c = 0; c < V.nchunks; ++c) {
         const float4 v = src[(uint64_t)c * per_link];
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    if (P.los) {
-        const float *L = reinterpret_cast<const float *>(P.ws + P.off_los) + (uint64_t)link * HRT_LOS_FLOATS;
-        const uint32_t status = __float_as_uint(L[HRT_LOS_STATUS]);
-        float re = 0.f, im = 0.f;
-        if (status == 0u) {   // coincident: a = 1, tau = 0, nu = 0
-            re = 1.f;
-        } else if (status == 2u) {   // clear: a = HRT_LOS_A (real, TE = TM)
-            const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
-            float sn, cs;
-            sincospif(half_revs((double)L[HRT_LOS_FS] * t - f * (double)L[HRT_LOS_TAU]), &sn, &cs);
-            re = L[HRT_LOS_A] * cs;
-            im = L[HRT_LOS_A] * sn;
-        }
+    hrt_los_entry L;
+    if (V.los && los_entry(V, link, L)) {   // a real: TE = TM
+        const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
+        float sn, cs;
+        sincospif(half_revs((double)L.nu * t - f * (double)L.tau), &sn, &cs);
+        const float re = L.a * cs, im = L.a * sn;
         s.x += re; s.y += im; s.z += re; s.w += im;
     }
-    const uint32_t rx = link / P.ntx, tx = link % P.ntx;
+    const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint64_t tk = (uint64_t)P.T * P.K;
-    float2 *o = reinterpret_cast<float2 *>(P.out) + ((uint64_t)rx * P.ntx + tx) * 2u * tk + (uint64_t)m * P.K + k;
+    float2 *o = reinterpret_cast<float2 *>(P.out) + ((uint64_t)rx * V.ntx + tx) * 2u * tk + (uint64_t)m * P.K + k;
     float2 te = make_float2(s.x, s.y), tm = make_float2(s.z, s.w);
-    if (P.accumulate) {
+    if (V.accumulate) {
         const float2 a = o[0], bb = o[tk];
         te.x += a.x; te.y += a.y; tm.x += bb.x; tm.y += bb.y;
     }
@@ -211,21 +184,20 @@ __global__ void hrt_channel_reduce_kernel(const hrt_kchannel P)
 extern "C" int hrt_hip_launch_channel(const hrt_kchannel *P, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t links = P->nrx * P->ntx;
-    if (P->nchunks) {
-        hipLaunchKernelGGL(hrt_channel_segments_kernel, dim3(1), dim3(256), 0, st, *P);
-        hipLaunchKernelGGL(hrt_channel_partial_kernel, dim3(P->nchunks, P->tiles, links), dim3(HRT_CH_THREADS), 0, st,
-                           *P);
+    const uint32_t links = P->v.nrx * P->v.ntx;
+    if (P->v.nchunks) {
+        const int e = hrt_hip_launch_segments(&P->v, stream);
+        if (e) return e;
+        hipLaunchKernelGGL(hrt_channel_partial_kernel, dim3(P->v.nchunks, P->tiles, links), dim3(HRT_CH_THREADS), 0,
+                           st, *P);
     }
     const uint64_t n = (uint64_t)links * P->tiles * HRT_CH_ROWS * HRT_CH_K2;
     hipLaunchKernelGGL(hrt_channel_reduce_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
     return (int)hipGetLastError();
 }
 
-// the segments kernel alone (the array channel, csrc/hrt_array_channel.hip, reads the same TX segments; only the
-// fields it reads -- ws, cap, off_counts, off_hits, hit_block_bytes, nb, ntx, num_local, seg -- need be set)
-extern "C" int hrt_hip_launch_channel_segments(const hrt_kchannel *P, void *stream)
+extern "C" int hrt_hip_launch_segments(const hrt_kview *V, void *stream)
 {
-    hipLaunchKernelGGL(hrt_channel_segments_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *P);
+    hipLaunchKernelGGL(hrt_channel_segments_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *V);
     return (int)hipGetLastError();
 }

@@ -1,0 +1,134 @@
+/* hrt_pathsum.h -- what the three path-sum families (hrt_channel, hrt_array_channel, hrt_taps) share: the view of the
+ * workspace of a finished hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray and
+ * hrt_ktaps; filled by csrc/host/channel.c) and, for the .hip files, the device helpers that read it.
+ *
+ * Every family sums, per link (rx, tx), the LoS entry (shard rank 0 only) and the scatter records of the link's TX
+ * segment in every hit block.  The records of a segment are cut into nchunks chunks; a partial kernel writes one
+ * chunk's sums to the scratch and a reduce kernel adds the chunks in a fixed order (no atomics: bit-reproducible).
+ * The scratch starts with seg, the TX segments found by hrt_channel_segments_kernel (csrc/hrt_channel.hip). */
+#ifndef HRT_PATHSUM_H
+#define HRT_PATHSUM_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct {
+    const uint8_t *ws;              /* workspace of a finished hrt_trace */
+    uint64_t cap, off_counts, off_los, off_hits, hit_block_bytes, off_recs, rec_block_bytes, off_masks;
+    uint32_t nb, nrx, ntx, num_local;
+    uint32_t nchunks;               /* record chunks per (link, block); 0: no scatter part */
+    uint32_t los, accumulate;       /* add the LoS term (shard rank 0 only) / add into out */
+    uint32_t *seg;                  /* scratch: [nb][ntx + 1] first hit of every TX segment */
+} hrt_kview;
+
+/* hrt_channel_segments_kernel: V->seg[b][t] for every bounce b and t <= ntx */
+int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+#include "hrt_device.h"
+
+namespace {
+
+// the fraction of a phase in revolutions, as the argument of sincospi (half revolutions, in [-1, 1])
+__device__ __forceinline__ float half_revs(double ph)
+{
+    return (float)(2.0 * (ph - rint(ph)));
+}
+
+__device__ __forceinline__ const float *rec_field(const hrt_kview &V, uint32_t b, uint32_t rx, uint32_t f)
+{
+    return reinterpret_cast<const float *>(V.ws + V.off_recs + (uint64_t)b * V.rec_block_bytes +
+                                           ((uint64_t)rx * HRT_REC_FIELDS + f) * V.cap * 4u);
+}
+
+__device__ __forceinline__ const uint32_t *hit_field(const hrt_kview &V, uint32_t b, uint32_t f)
+{
+    return reinterpret_cast<const uint32_t *>(V.ws + V.off_hits + (uint64_t)b * V.hit_block_bytes +
+                                              (uint64_t)f * V.cap * 4u);
+}
+
+// the unblocked bits of the records of hit block b at receiver rx: hit i is bit i & 63 of word i >> 6
+__device__ __forceinline__ const uint64_t *mask_row(const hrt_kview &V, uint32_t b, uint32_t rx)
+{
+    return reinterpret_cast<const uint64_t *>(V.ws + V.off_masks) + ((uint64_t)b * V.nrx + rx) * (V.cap / 64u);
+}
+
+// the records [start, end) of chunk c of the TX segment of hit block b
+__device__ __forceinline__ void chunk_range(const hrt_kview &V, uint32_t b, uint32_t tx, uint32_t c, uint32_t &start,
+                                            uint32_t &end)
+{
+    const uint32_t s0 = V.seg[b * (V.ntx + 1u) + tx], s1 = V.seg[b * (V.ntx + 1u) + tx + 1u];
+    const uint64_t n = s1 - s0;
+    start = s0 + (uint32_t)(n * c / V.nchunks);
+    end = s0 + (uint32_t)(n * (c + 1u) / V.nchunks);
+}
+
+// The LoS entry of a link: a (real, TE = TM), tau, nu (the path list's freq_shift) and u = directions_tx
+// (directions_rx = -u).  False where the LoS is blocked.  Coincident: a = 1, tau = nu = 0, directions_rx = (1, 0, 0),
+// directions_tx = (-1, 0, 0) (src/compute_paths.c:533-534).
+struct hrt_los_entry {
+    float a, tau, nu, ux, uy, uz;
+};
+
+__device__ __forceinline__ bool los_entry(const hrt_kview &V, uint32_t link, hrt_los_entry &e)
+{
+    const float *L = reinterpret_cast<const float *>(V.ws + V.off_los) + (uint64_t)link * HRT_LOS_FLOATS;
+    const uint32_t status = __float_as_uint(L[HRT_LOS_STATUS]);
+    e = hrt_los_entry{1.f, 0.f, 0.f, -1.f, 0.f, 0.f};
+    if (status == 2u) {   // clear
+        e.a = L[HRT_LOS_A]; e.tau = L[HRT_LOS_TAU]; e.nu = L[HRT_LOS_FS];
+        e.ux = L[HRT_LOS_DIRX]; e.uy = L[HRT_LOS_DIRY]; e.uz = L[HRT_LOS_DIRZ];
+    }
+    return status == 0u || status == 2u;
+}
+
+// Fill sB / sI (bounce, hit) with the next at most BATCH unblocked records of chunk c of link (rx, tx), compacted by
+// mask ballots; (b, cur, end) is where the walk stands (start it with b = 0 and chunk_range of block 0).  Every wave
+// takes the same decisions; wave 0 writes the list.  Returns the number of records staged: 0 once the chunk is done.
+// (hrt_array_partial_kernel writes the same loop out: see there.)
+template <uint32_t BATCH>
+__device__ __forceinline__ uint32_t fill_batch(const hrt_kview &V, uint32_t rx, uint32_t tx, uint32_t c, uint32_t lane,
+                                               uint32_t w, uint32_t &b, uint32_t &cur, uint32_t &end, uint32_t *sB,
+                                               uint32_t *sI)
+{
+    uint32_t n = 0;
+    while (n < BATCH && b < V.nb) {
+        if (cur >= end) {
+            if (++b < V.nb) chunk_range(V, b, tx, c, cur, end);
+            continue;
+        }
+        const uint32_t i = cur + lane;
+        const uint64_t *mask = mask_row(V, b, rx);
+        const bool live = i < end && ((mask[i >> 6] >> (i & 63u)) & 1u);
+        const uint64_t bal = __ballot(live);
+        const uint32_t cnt = __popcll(bal), take = min(cnt, BATCH - n);
+        const uint32_t rank = __popcll(bal & ((1ull << lane) - 1ull));
+        if (w == 0 && live && rank < take) {
+            sB[n + rank] = b;
+            sI[n + rank] = i;
+        }
+        if (take < cnt) {   // resume at the first live record not taken
+            uint64_t rest = bal;
+            for (uint32_t t = 0; t < take; ++t) rest &= rest - 1ull;
+            cur += (uint32_t)__builtin_ctzll(rest);
+        } else {
+            cur += 64u;
+        }
+        n += take;
+    }
+    return n;
+}
+
+}  // namespace
+#endif /* __HIPCC__ */
+
+#endif /* HRT_PATHSUM_H */

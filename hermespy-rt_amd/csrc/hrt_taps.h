@@ -8,12 +8,13 @@
  * records.  A workgroup (4 waves) forms HRT_TP_WTILES accumulator tiles per wave: RT row tiles x CT column tiles with
  * RT * CT = 4 (RT = 4 when the grid has at least 4 row tiles, else RT = 1); wave w takes column tiles
  * (cb * 4 + w) * CT .. + CT - 1 and row tiles rb * RT .. + RT - 1.  It writes one chunk of the link's records to
- * the partial sums of the scratch; the reduce kernel adds the chunks in a fixed order (no atomics:
- * bit-reproducible). */
+ * the partial sums of the scratch; the reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h). */
 #ifndef HRT_TAPS_H
 #define HRT_TAPS_H
 
 #include <stdint.h>
+
+#include "hrt_pathsum.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -26,18 +27,13 @@ extern "C" {
 #define HRT_TP_MAX_TAP (1 << 24)        /* |l_min|, |l_min + num_taps|: tap indices exact in f32 */
 
 typedef struct {
-    const uint8_t *ws;              /* workspace of a finished hrt_trace */
-    uint64_t cap, off_counts, off_los, off_hits, hit_block_bytes, off_recs, rec_block_bytes, off_masks;
-    uint32_t nb, nrx, ntx, num_local;
+    hrt_kview v;
     uint32_t L, T;                  /* taps, time samples */
     int32_t l_min;
     uint32_t rtiles, ctiles;        /* ceil(4 T / 16), ceil(L / 16) */
     uint32_t rt;                    /* row tiles per wave: 4 or 1 (column tiles per wave: 4 / rt) */
     uint32_t rblocks, cblocks;      /* ceil(rtiles / rt), ceil(ctiles / (4 * (4 / rt))) */
-    uint32_t nchunks;               /* record chunks per (link, block); 0: no scatter part */
-    uint32_t los, accumulate;       /* add the LoS term (shard rank 0 only) / add into out */
     double fs, fc, t0, dt;
-    const uint32_t *seg;            /* scratch: [nb][ntx + 1] first hit of every TX segment */
     float *partial;                 /* scratch: complex [link][chunk][pol][T][L] */
     float *out;                     /* complex [nrx][ntx][2][T][L] */
 } hrt_ktaps;

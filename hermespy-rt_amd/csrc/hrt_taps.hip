@@ -4,7 +4,8 @@
 //     t_m = t0 + m dt,  l_i = l_min + i
 //
 // over the LoS entry (hrt_taps_reduce_kernel) and every unblocked scatter record (hrt_taps_partial_kernel) of the
-// link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip).
+// link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip); the workspace
+// view, its readers and the batch fill are csrc/hrt_pathsum.h.
 //   hrt_taps_partial_kernel  one workgroup (4 waves) per (row block x column block, record chunk, link): the real
 //                            GEMM of csrc/hrt_taps.h on v_mfma_f32_16x16x4_f32, partial sums to the scratch.  The
 //                            unblocked records of the chunk are compacted by mask ballots and staged HRT_TP_BATCH at a
@@ -21,41 +22,12 @@
 
 #include <stdint.h>
 
-#include "hrt_channel.h"
-#include "hrt_device.h"
+#include "hrt_pathsum.h"
 #include "hrt_taps.h"
 
 typedef float hrt_f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-// the fraction of a phase in revolutions, as the argument of sincospi (half revolutions, in [-1, 1])
-__device__ __forceinline__ float half_revs(double ph)
-{
-    return (float)(2.0 * (ph - rint(ph)));
-}
-
-__device__ __forceinline__ const float *rec_field(const hrt_ktaps &P, uint32_t b, uint32_t rx, uint32_t f)
-{
-    return reinterpret_cast<const float *>(P.ws + P.off_recs + (uint64_t)b * P.rec_block_bytes +
-                                           ((uint64_t)rx * HRT_REC_FIELDS + f) * P.cap * 4u);
-}
-
-__device__ __forceinline__ const uint32_t *hit_field(const hrt_ktaps &P, uint32_t b, uint32_t f)
-{
-    return reinterpret_cast<const uint32_t *>(P.ws + P.off_hits + (uint64_t)b * P.hit_block_bytes +
-                                              (uint64_t)f * P.cap * 4u);
-}
-
-// the records [start, end) of chunk c of the TX segment of hit block b
-__device__ __forceinline__ void chunk_range(const hrt_ktaps &P, uint32_t b, uint32_t tx, uint32_t c, uint32_t &start,
-                                            uint32_t &end)
-{
-    const uint32_t s0 = P.seg[b * (P.ntx + 1u) + tx], s1 = P.seg[b * (P.ntx + 1u) + tx + 1u];
-    const uint64_t n = s1 - s0;
-    start = s0 + (uint32_t)(n * c / P.nchunks);
-    end = s0 + (uint32_t)(n * (c + 1u) / P.nchunks);
-}
 
 // The sinc of one delay, x = f_s tau: sinc(l - x) = (-1)^l c / ((l - k) - r) with k = rint(x) clamped to
 // +-2^26 (so l - k is an exact int32 for |l| <= 2^24), r = x - k and c = -(-1)^n sin(pi (x - n)) / pi, n = rint(x).
@@ -94,9 +66,10 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
 {
     constexpr uint32_t CT = HRT_TP_WTILES / RT;
     constexpr uint32_t BT = RT * 4u;   // time samples of the block
+    const hrt_kview &V = P.v;
     const uint32_t blk = blockIdx.x, c = blockIdx.y, link = blockIdx.z;
     const uint32_t rb = blk % P.rblocks, cb = blk / P.rblocks;
-    const uint32_t rx = link / P.ntx, tx = link % P.ntx;
+    const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t kq = lane >> 4, col = lane & 15u;   // A / B operand: record 4 g + kq; row / tap `col` of a tile
 
@@ -116,37 +89,10 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
 #pragma unroll
     for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) acc[t] = hrt_f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const uint64_t words = P.cap / 64u;
     uint32_t b = 0, cur = 0, end = 0;
-    chunk_range(P, 0, tx, c, cur, end);
+    chunk_range(V, 0, tx, c, cur, end);
     for (;;) {
-        // fill a batch with the next unblocked records of the chunk (every wave takes the same decisions; wave 0
-        // writes the list)
-        uint32_t n = 0;
-        while (n < HRT_TP_BATCH && b < P.nb) {
-            if (cur >= end) {
-                if (++b < P.nb) chunk_range(P, b, tx, c, cur, end);
-                continue;
-            }
-            const uint32_t i = cur + lane;
-            const uint64_t *mask = reinterpret_cast<const uint64_t *>(P.ws + P.off_masks) + ((uint64_t)b * P.nrx + rx) * words;
-            const bool ok = i < end && ((mask[i >> 6] >> (i & 63u)) & 1u);
-            const uint64_t bal = __ballot(ok);
-            const uint32_t cnt = __popcll(bal), take = min(cnt, HRT_TP_BATCH - n);
-            const uint32_t rank = __popcll(bal & ((1ull << lane) - 1ull));
-            if (w == 0 && ok && rank < take) {
-                sB[n + rank] = b;
-                sI[n + rank] = i;
-            }
-            if (take < cnt) {   // resume at the first live record not taken
-                uint64_t rest = bal;
-                for (uint32_t t = 0; t < take; ++t) rest &= rest - 1ull;
-                cur += (uint32_t)__builtin_ctzll(rest);
-            } else {
-                cur += 64u;
-            }
-            n += take;
-        }
+        const uint32_t n = fill_batch<HRT_TP_BATCH>(V, rx, tx, c, lane, w, b, cur, end, sB, sI);
         if (n == 0) break;
         __syncthreads();
         if (tid < HRT_TP_BATCH) {   // the record's fields and sinc parameters (zeros past n: U = 0 there)
@@ -154,12 +100,12 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
             sinc_rec q = {0, 0.f, 0.f};
             if (tid < n) {
                 const uint32_t rb2 = sB[tid], i = sI[tid];
-                R[0] = rec_field(P, rb2, rx, HRT_REC_A_TE_RE)[i];
-                R[1] = rec_field(P, rb2, rx, HRT_REC_A_TE_IM)[i];
-                R[2] = rec_field(P, rb2, rx, HRT_REC_A_TM_RE)[i];
-                R[3] = rec_field(P, rb2, rx, HRT_REC_A_TM_IM)[i];
-                R[4] = rec_field(P, rb2, rx, HRT_REC_TAU)[i];
-                R[5] = __uint_as_float(hit_field(P, rb2, HRT_HIT_FS0)[i]) - rec_field(P, rb2, rx, HRT_REC_DFS)[i];
+                R[0] = rec_field(V, rb2, rx, HRT_REC_A_TE_RE)[i];
+                R[1] = rec_field(V, rb2, rx, HRT_REC_A_TE_IM)[i];
+                R[2] = rec_field(V, rb2, rx, HRT_REC_A_TM_RE)[i];
+                R[3] = rec_field(V, rb2, rx, HRT_REC_A_TM_IM)[i];
+                R[4] = rec_field(V, rb2, rx, HRT_REC_TAU)[i];
+                R[5] = __uint_as_float(hit_field(V, rb2, HRT_HIT_FS0)[i]) - rec_field(V, rb2, rx, HRT_REC_DFS)[i];
                 q = sinc_prep(P.fs, R[4]);
             } else {
                 for (int f = 0; f < 6; ++f) R[f] = 0.f;
@@ -205,7 +151,7 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
 
     // D: lane = (row group kq, column col), register q: row 4 kq + q of the tile = (time 4 R + kq, part q)
     const uint64_t tl = (uint64_t)P.T * P.L;
-    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * P.nchunks + c) * 2u * tl;
+    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * V.nchunks + c) * 2u * tl;
 #pragma unroll
     for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) {
         const uint32_t m = (r0 + t / CT) * 4u + kq, i = (c0 + t % CT) * 16u + col;
@@ -220,40 +166,34 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
 // one thread per output (link, pol, m, i): the chunks in order, + LoS, -> out
 __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
 {
+    const hrt_kview &V = P.v;
     const uint64_t tl = (uint64_t)P.T * P.L;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t per_link = 2u * tl;
-    if (gid >= per_link * P.nrx * P.ntx) return;
+    if (gid >= per_link * V.nrx * V.ntx) return;
     const uint32_t link = (uint32_t)(gid / per_link);
     const uint64_t e = gid - (uint64_t)link * per_link;   // = pol * tl + m * L + i
 
     float2 s = make_float2(0.f, 0.f);
-    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * P.nchunks * per_link + e;
-    for (uint32_t c = 0; c < P.nchunks; ++c) {
+    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link + e;
+    for (uint32_t c = 0; c < V.nchunks; ++c) {
         const float2 v = src[(uint64_t)c * per_link];
         s.x += v.x;
         s.y += v.y;
     }
-    if (P.los) {
-        const float *L = reinterpret_cast<const float *>(P.ws + P.off_los) + (uint64_t)link * HRT_LOS_FLOATS;
-        const uint32_t status = __float_as_uint(L[HRT_LOS_STATUS]);
-        if (status == 0u || status == 2u) {   // coincident: a = 1, tau = nu = 0; clear: a = HRT_LOS_A (TE = TM)
-            float a = 1.f, tau = 0.f, nu = 0.f;
-            if (status == 2u) {
-                a = L[HRT_LOS_A]; tau = L[HRT_LOS_TAU]; nu = L[HRT_LOS_FS];
-            }
-            const uint64_t mi = e % tl;
-            const uint32_t m = (uint32_t)(mi / P.L), i = (uint32_t)(mi % P.L);
-            const double t = P.t0 + (double)m * P.dt;
-            float sn, cs;
-            sincospif(half_revs((double)nu * t - P.fc * (double)tau), &sn, &cs);
-            const float v = a * sinc_tap(P.l_min + (int32_t)i, sinc_prep(P.fs, tau));
-            s.x += v * cs;
-            s.y += v * sn;
-        }
+    hrt_los_entry L;
+    if (V.los && los_entry(V, link, L)) {   // a real: TE = TM
+        const uint64_t mi = e % tl;
+        const uint32_t m = (uint32_t)(mi / P.L), i = (uint32_t)(mi % P.L);
+        const double t = P.t0 + (double)m * P.dt;
+        float sn, cs;
+        sincospif(half_revs((double)L.nu * t - P.fc * (double)L.tau), &sn, &cs);
+        const float v = L.a * sinc_tap(P.l_min + (int32_t)i, sinc_prep(P.fs, L.tau));
+        s.x += v * cs;
+        s.y += v * sn;
     }
     float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
-    if (P.accumulate) {
+    if (V.accumulate) {
         const float2 v = o[0];
         s.x += v.x;
         s.y += v.y;
@@ -264,15 +204,11 @@ __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
 extern "C" int hrt_hip_launch_taps(const hrt_ktaps *P, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t links = P->nrx * P->ntx;
-    if (P->nchunks) {
-        hrt_kchannel S = {};
-        S.ws = P->ws; S.cap = P->cap; S.off_counts = P->off_counts; S.off_hits = P->off_hits;
-        S.hit_block_bytes = P->hit_block_bytes; S.nb = P->nb; S.ntx = P->ntx; S.num_local = P->num_local;
-        S.seg = const_cast<uint32_t *>(P->seg);
-        const int e = hrt_hip_launch_channel_segments(&S, stream);
+    const uint32_t links = P->v.nrx * P->v.ntx;
+    if (P->v.nchunks) {
+        const int e = hrt_hip_launch_segments(&P->v, stream);
         if (e) return e;
-        const dim3 grid(P->rblocks * P->cblocks, P->nchunks, links);
+        const dim3 grid(P->rblocks * P->cblocks, P->v.nchunks, links);
         if (P->rt == 4u)
             hipLaunchKernelGGL(hrt_taps_partial_kernel<4u>, grid, dim3(HRT_TP_THREADS), 0, st, *P);
         else

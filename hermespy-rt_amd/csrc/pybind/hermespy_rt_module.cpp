@@ -248,6 +248,25 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
+// the call of a compute_channel / compute_array_channel / compute_taps entry (`name`): the scene loaded and freed
+// around `call` without the GIL; a refused argument raises ValueError, any other error RuntimeError
+template <typename F>
+void run_pathsum(const char *name, const std::string &mesh_filepath, F call)
+{
+    int rc;
+    std::string err;
+    {
+        py::gil_scoped_release nogil;
+        Scene scene = scene_load(mesh_filepath.c_str());
+        rc = call(&scene);
+        if (rc != HRT_OK) err = hrt_last_error();
+        free_scene(&scene);
+    }
+    if (rc == HRT_E_INVALID) throw py::value_error(std::string("hermespy_rt.") + name + ": " + err);
+    if (rc != HRT_OK)
+        throw std::runtime_error(std::string("hermespy_rt.") + name + " failed (" + std::to_string(rc) + "): " + err);
+}
+
 // compute_channel: the channel frequency response of the traced paths, formed on the device (extension; see
 // hrt_compute_channel in hermespy_rt.h): complex64 (num_rx, num_tx, 2, num_times, num_freqs), pol 0 = TE, 1 = TM,
 // H = sum_p a_p exp(j 2 pi (nu_p t_m - f_k tau_p)) with f_k = f0 + k df ABSOLUTE (Hz), t_m = t0 + m dt (s).
@@ -274,19 +293,10 @@ py::array_t<std::complex<float>> compute_channel_py(
     py::array_t<std::complex<float>> out({(size_t)num_rx, (size_t)num_tx, (size_t)2, (size_t)num_times,
                                           (size_t)num_freqs});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
-    int rc;
-    std::string err;
-    {
-        py::gil_scoped_release nogil;
-        Scene scene = scene_load(mesh_filepath.c_str());
-        rc = hrt_compute_channel(&scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
-                                 num_bounces, &spec, dst, nullptr);
-        if (rc != HRT_OK) err = hrt_last_error();
-        free_scene(&scene);
-    }
-    if (rc == HRT_E_INVALID) throw py::value_error("hermespy_rt.compute_channel: " + err);
-    if (rc != HRT_OK)
-        throw std::runtime_error("hermespy_rt.compute_channel failed (" + std::to_string(rc) + "): " + err);
+    run_pathsum("compute_channel", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_channel(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                   num_bounces, &spec, dst, nullptr);
+    });
     return out;
 }
 
@@ -324,20 +334,12 @@ py::array_t<std::complex<float>> compute_array_channel_py(
                                                                     (size_t)num_times, (size_t)num_freqs}
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
-    int rc;
-    std::string err;
-    {
-        py::gil_scoped_release nogil;
-        Scene scene = scene_load(mesh_filepath.c_str());
-        rc = hrt_compute_array_channel(&scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
-                                       num_bounces, &spec, reinterpret_cast<const Vec3 *>(rx_elements.data()), nr,
-                                       reinterpret_cast<const Vec3 *>(tx_elements.data()), nt, fa, dst, nullptr);
-        if (rc != HRT_OK) err = hrt_last_error();
-        free_scene(&scene);
-    }
-    if (rc == HRT_E_INVALID) throw py::value_error("hermespy_rt.compute_array_channel: " + err);
-    if (rc != HRT_OK)
-        throw std::runtime_error("hermespy_rt.compute_array_channel failed (" + std::to_string(rc) + "): " + err);
+    const Vec3 *rxe = reinterpret_cast<const Vec3 *>(rx_elements.data());
+    const Vec3 *txe = reinterpret_cast<const Vec3 *>(tx_elements.data());
+    run_pathsum("compute_array_channel", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_array_channel(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                         num_bounces, &spec, rxe, nr, txe, nt, fa, dst, nullptr);
+    });
     return out;
 }
 
@@ -374,19 +376,10 @@ py::array_t<std::complex<float>> compute_taps_py(
                                                                      (size_t)num_times, (size_t)num_taps}
                                               : std::vector<size_t>{(size_t)1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
-    int rc;
-    std::string err;
-    {
-        py::gil_scoped_release nogil;
-        Scene scene = scene_load(mesh_filepath.c_str());
-        rc = hrt_compute_taps(&scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
-                              &spec, dst, nullptr);
-        if (rc != HRT_OK) err = hrt_last_error();
-        free_scene(&scene);
-    }
-    if (rc == HRT_E_INVALID) throw py::value_error("hermespy_rt.compute_taps: " + err);
-    if (rc != HRT_OK)
-        throw std::runtime_error("hermespy_rt.compute_taps failed (" + std::to_string(rc) + "): " + err);
+    run_pathsum("compute_taps", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_taps(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
+                                &spec, dst, nullptr);
+    });
     return out;
 }
 

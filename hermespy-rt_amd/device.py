@@ -378,6 +378,24 @@ class Tracer:
         return out
 
     # ------------------------------------------------------------------ channel
+    def _pathsum_buffers(self, shape, need, out, accumulate, cache):
+        """The output (`out` checked, or a new tensor), the scratch cache named `cache` grown to `need` bytes and the
+        current stream of one channel / array_channel / taps call."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            scratch = getattr(self, cache, None)
+            if scratch is None or scratch.numel() < int(need.value):
+                scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=self.device)
+                setattr(self, cache, scratch)
+        return out, scratch, torch.cuda.current_stream(self.device)
+
     def channel(self, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
                 accumulate=False):
         """Channel frequency response of the last trace, formed on the device (hrt_channel):
@@ -389,29 +407,17 @@ class Tracer:
         carrier phase).  Returns a complex64 tensor [nrx, ntx, 2, num_times, num_freqs] (pol 0 = TE, 1 = TM) on
         the device, enqueued on the current stream; `out` (such a tensor) is written in place, or added to with
         accumulate=True.  The error word is read first (counts()): a void step is traced again."""
-        torch = self.torch
         self.counts()
         spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
         need = C.c_uint64(0)
         _lib.check(self.L.hrt_channel_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need)),
                    "hrt_channel_scratch_bytes")
         shape = (self.nrx, self.ntx, 2, int(num_times), int(num_freqs))
-        with torch.cuda.device(self.device):
-            if out is None:
-                if accumulate:
-                    raise ValueError("accumulate=True needs `out`")
-                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
-                  or not out.is_contiguous()):
-                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
-            scratch = getattr(self, "_ch_scratch", None)
-            if scratch is None or scratch.numel() < int(need.value):
-                scratch = self._ch_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
-                                                         device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_ch_scratch")
         _lib.check(self.L.hrt_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
                                       C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
-                                      C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream)),
+                                      C.c_void_p(out.data_ptr()), 1 if accumulate else 0,
+                                      C.c_void_p(stream.cuda_stream)),
                    "hrt_channel")
         return out
 
@@ -447,19 +453,7 @@ class Tracer:
             raise ValueError("hrt_array_channel: " + self.L.hrt_last_error().decode())
         _lib.check(rc, "hrt_array_channel_scratch_bytes")
         shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_freqs))
-        with torch.cuda.device(self.device):
-            if out is None:
-                if accumulate:
-                    raise ValueError("accumulate=True needs `out`")
-                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
-                  or not out.is_contiguous()):
-                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
-            scratch = getattr(self, "_ac_scratch", None)
-            if scratch is None or scratch.numel() < int(need.value):
-                scratch = self._ac_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
-                                                         device=self.device)
-        stream = torch.cuda.current_stream(self.device)
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_ac_scratch")
         _lib.check(self.L.hrt_array_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
                                             C.byref(spec), C.byref(arr), C.c_void_p(scratch.data_ptr()),
                                             C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
@@ -479,7 +473,6 @@ class Tracer:
         around (Hz; None: the carrier, 0 the raw sum).  Its DTFT at |f| < fs / 2 is channel() at fc + f.  Returns a
         complex64 tensor [nrx, ntx, 2, num_times, num_taps] on the device, enqueued on the current stream; `out` is
         written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
-        torch = self.torch
         fc = self.f_ghz * 1e9 if fc is None else float(fc)
         spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
         self.counts()
@@ -489,22 +482,10 @@ class Tracer:
             raise ValueError("hrt_taps: " + self.L.hrt_last_error().decode())
         _lib.check(rc, "hrt_taps_scratch_bytes")
         shape = (self.nrx, self.ntx, 2, int(num_times), int(num_taps))
-        with torch.cuda.device(self.device):
-            if out is None:
-                if accumulate:
-                    raise ValueError("accumulate=True needs `out`")
-                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
-                  or not out.is_contiguous()):
-                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
-            scratch = getattr(self, "_tp_scratch", None)
-            if scratch is None or scratch.numel() < int(need.value):
-                scratch = self._tp_scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8,
-                                                         device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_tp_scratch")
         _lib.check(self.L.hrt_taps(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
                                    C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
-                                   C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream)),
+                                   C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
                    "hrt_taps")
         return out
 
