@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- the compute_paths hot path on N MI355X GPUs (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs
+and prints the line.  --full adds everything else the benchmark measures, all of it after the timed
+region: the per-kernel HIP events and the roofline, at N = 1 the figures below and the CPU baseline, at
+N > 1 the collection step (--collect, which --full defaults to `both`).
 
 With --gpus N > 1 and no torch.distributed environment, bench.py launches its own N rank
 processes (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1,
@@ -12,8 +17,8 @@ A "step" is one pass of the hot path over the whole launch set of the workload: 
 the (HBM-resident) launch directions, LoS pass, and num_bounces+1 launches of the trace / shade
 kernels.  SCOPE of `value`: inputs (scene, endpoints, launch directions in launch order) are
 resident in HBM before the timed region and outputs (compact path records) stay in HBM, sharded
-over the ranks -- it is the steady-state kernel rate.  What a caller of the drop-in pays on top is
-reported beside it, measured in the same process right after the timed region (N = 1):
+over the ranks -- it is the steady-state kernel rate.  With --full, what a caller of the drop-in pays
+on top is reported beside it, measured in the same process right after the timed region (N = 1):
 
     step_incl_launch_ms   the step with the launch directions and launch order generated inside it
                           (they are part of compute_paths in the reference, src/compute_paths.c:442-456)
@@ -26,8 +31,8 @@ N > 1: ray-sharded round-robin in 4096-path granules.  --scaling weak (default):
 N-times denser Fibonacci sphere (the workload's ray count per GPU); --scaling strong: the
 workload's ray count is the total -- `--workload c4 --gpus 4 --scaling strong` is BASELINE
 configs[3], `--workload c5 --gpus 8 --scaling strong` configs[4]; at N = 1 both are the same run.
-`value` has no exchange step in it (rays are independent); the collection of the records is
-measured right after and reported as first-class numbers:
+`value` has no exchange step in it (rays are independent); with --full (or --collect) the collection
+of the records is measured right after and reported as first-class numbers:
 
     value_with_gather     every rank's packed records -> rank 0 over RCCL (xGMI), serialised into the step
     value_with_d2h        every rank copies its own packed records to its host over its own PCIe link
@@ -202,6 +207,130 @@ def dropin_once(c, lib_, abi, W, with_rays=False):
                 records_unblocked=int(st.records_unblocked), dense_host_bytes=host_bytes)
 
 
+def kernel_figures(tr, step, args, w, unblocked, dt, world, local_rank):
+    """--full: the per-kernel HIP events of a separate pass after the timed region, the roofline of the
+    kernels they time and the packet-culling counters (`make STATS=1` builds only); every rank runs it."""
+    import torch
+    nrx, nb = tr.nrx, tr.nb
+    # per-kernel HIP events (one hrt_timer = the events of one step, recorded on the launch stream,
+    # read afterwards): a SEPARATE untimed pass right after the timed region, every step of it
+    # instrumented -- the timed steps carry no events (they cost ~4 % of a 1.6 ms step)
+    timers = [tr.new_timer() for _ in range(max(1, args.event_steps))]
+    for t in timers:
+        step(t)
+    torch.cuda.synchronize()
+    bounce_ms, los_ms, compact_ms, shade_ms, records_ms = [], [], [], [], []
+    for t in timers:
+        r = tr.read_timer(t)
+        los_ms.append(r["los_ms"])
+        bounce_ms.append(r["trace_ms"])
+        shade_ms.append(r["shade_ms"])
+        compact_ms.append(sum(r["scan_ms"]))
+        records_ms.append(r["records_ms"])
+
+    # ---- roofline of the dominant kernels, rank 0's launches.  One launch of "the bounce" is
+    # the pair hrt_trace_kernel (intersection) + hrt_shade_kernel (records, Fresnel, reflect):
+    # the algorithmic bytes of SURVEY 8(d) are those of the pair, so is the duration. ----
+    tm = np.asarray(bounce_ms, dtype=np.float64)          # [steps, nb+1] trace kernel (patch tables: primary rays only)
+    sm = np.asarray(shade_ms, dtype=np.float64)           # [steps, nb+1] shade kernel
+    rm = np.asarray(records_ms, dtype=np.float64)         # [steps, nb+1] records kernel (patch tables; else 0)
+    bm = tm + sm + rm
+    kern_ms_step = float(bm.sum(axis=1).mean())
+    n_launch = bm.shape[1]
+    unb_local = unblocked
+    B_local = algorithmic_bytes(w["live"], nrx, tr.num_local, unb_local, w["records"] - unb_local)
+    ach = B_local / (kern_ms_step * 1e-3) / 1e9
+    tests_local = w["tests"]
+    # HBM bytes per launch from PMC counters: collected by profiles/collect_pmc.sh (separate
+    # rocprofv3 passes) for exactly this workload at N = 1, committed in profiles/.  The JSON carries
+    # the hash of the kernel source it was measured on: `traffic_stale` says whether that is still
+    # the source of this run.
+    kern_sha = hashlib.sha256(b"".join(open(os.path.join(REPO, "hermespy-rt_amd", "csrc", f), "rb").read() for f in ("hrt_kernels.hip", "hrt_fused_body.inc"))).hexdigest()[:16]
+    traffic, traffic_src, traffic_stale = None, None, None
+    try:
+        pj = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
+        if world == 1 and args.workload in pj:
+            traffic = pj[args.workload]["hbm_bytes_per_launch_avg"]
+            traffic_src = pj[args.workload]["source"]
+            traffic_stale = pj[args.workload].get("kernels_sha16") != kern_sha
+    except (OSError, ValueError, KeyError):
+        pass
+    # VALU issue utilisation of the two kernels (SURVEY 8d asks for the VALU fraction next to the
+    # HBM one): from profiles/collect_valu.sh (own rocprofv3 --pmc pass), same workload, N = 1
+    valu = None
+    try:
+        vj = json.load(open(os.path.join(REPO, "profiles", "pmc_valu.json")))
+        if world == 1 and args.workload in vj:
+            valu = dict(vj[args.workload]["kernels"], source=vj[args.workload]["source"],
+                        stale=vj[args.workload].get("kernels_sha16") != kern_sha)
+    except (OSError, ValueError, KeyError):
+        pass
+    # which resource binds: the VALU issue rate of the dominant kernel (committed PMC pass) against
+    # the HBM fraction of the path -- C3 is VALU-bound (SURVEY H6), the tiny tables are nearer HBM
+    hbm_frac = ach / HBM_PEAK_GBS
+    valu_frac = None
+    if valu:
+        fr = [(v["valu_insts_per_step"], v["issue_frac_vs_simd32_peak"]) for k, v in valu.items()
+              if isinstance(v, dict) and "issue_frac_vs_simd32_peak" in v]
+        if fr:
+            valu_frac = max(fr)[1]   # of the kernel that issues the most instructions
+    fused0 = os.environ.get("HRT_FUSE", "") not in ("0",)
+    fused_all = fused0 and tr.num_tri <= 64
+    patched = 64 < tr.num_tri <= 256 and "no_patch" not in os.environ.get("HRT_TUNE", "")
+    kern_desc = ("hrt_fused_kernel (one kernel per launch: trace + shading + stable compaction)" if fused_all else
+                 ("launch 0: hrt_fused_kernel; later launches: " if fused0 else "") +
+                 ("hrt_records_kernel (shadow traces + scatter records; in the timed region on a second stream beside the "
+                  "others) + hrt_image_kernel / hrt_trace_kernel (primary rays) + hrt_shade_kernel (Fresnel, reflection, "
+                  "compaction): one bounce launch = the three; trace_kernel_ms = records + primary rays" if patched else
+                  "hrt_trace_kernel + hrt_shade_kernel (one bounce launch = the pair)"))
+    roofline = dict(bound=("valu" if (valu_frac is not None and valu_frac > hbm_frac) else "hbm"), kernel=kern_desc,
+                    achieved=ach, peak=HBM_PEAK_GBS,
+                    unit="GB/s", frac=hbm_frac, hbm_frac=hbm_frac, valu_frac=valu_frac,
+                    frac_of_step=B_local / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                    traffic=traffic, traffic_source=traffic_src,
+                    traffic_stale=traffic_stale, traffic_measured_in_run=False, kernels_sha16=kern_sha,
+                    algorithmic_bytes_per_launch=B_local / n_launch,
+                    avg_launch_ms=kern_ms_step / n_launch, launches_per_step=n_launch,
+                    steps_with_kernel_events=int(bm.shape[0]),
+                    kernel_events="separate untimed pass after the timed region, every step instrumented",
+                    per_launch_ms=[float(x) for x in bm.mean(axis=0)],
+                    trace_kernel_ms=[float(x) for x in tm.mean(axis=0)],
+                    shade_kernel_ms=[float(x) for x in sm.mean(axis=0)],
+                    records_kernel_ms=[float(x) for x in rm.mean(axis=0)],
+                    kernel_tests_per_s=tests_local / (kern_ms_step * 1e-3),
+                    compaction_ms_per_step=float(np.mean(compact_ms)), los_ms=float(np.mean(los_ms)),
+                    trace_variant=os.environ.get("HRT_TUNE", "auto (patch tables on 65-256 triangles; flat packet culling; trees on big sparse tables)"),
+                    valu=valu,
+                    note=("a fused launch reports its one kernel under trace_kernel_ms (shade_kernel_ms = 0); "
+                          "frac is the north-star's HBM figure (algorithmic bytes / SUM of the kernels' own durations, "
+                          "measured one after the other on one stream / 8 TB/s); frac_of_step the same bytes over the timed "
+                          "step, in which the records kernels run beside the others; "
+                          "valu_frac = VALU instructions issued x 2 cycles / SIMD-cycles of the busiest kernel"))
+
+    if rm.sum() > 0:
+        # the DOMINANT kernel on its own: hrt_records_kernel.  Algorithmic bytes of one launch b (SURVEY 8d, the part
+        # of the path this kernel performs): 44 B of state per entry in, 36 B per unblocked / 20 B per blocked record out
+        rec_launches = [b for b in range(1, nb + 1) if w["live"][b] > 0]
+        rec_bytes = 44.0 * sum(w["live"][b] for b in rec_launches) + 36.0 * unb_local + 20.0 * (w["records"] - unb_local)
+        rec_ms = float(rm.sum(axis=1).mean())
+        roofline["dominant_kernel"] = dict(
+            name="hrt_records_kernel", launches_per_step=len(rec_launches), avg_launch_ms=rec_ms / max(1, len(rec_launches)),
+            ms_per_step=rec_ms, algorithmic_bytes_per_step=rec_bytes,
+            achieved=rec_bytes / (rec_ms * 1e-3) / 1e9, unit="GB/s", frac=rec_bytes / (rec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            what="HIP events around the kernel, one stream (the event pass); its VALU issue fraction is roofline.valu.records")
+
+    kstats = None
+    try:
+        import ctypes
+        from hermespy_rt_amd import lib as _l2
+        arr = (ctypes.c_uint64 * 48)()
+        if _l2.load().hrt_debug_kernel_stats(local_rank, arr, 0) == 0 and any(arr):
+            kstats = [[int(arr[k * 16 + j]) for j in range(16)] for k in range(3)]
+    except Exception:
+        pass
+    return roofline, kstats
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -210,21 +339,26 @@ def main():
     ap.add_argument("--workload", default="c3")
     ap.add_argument("--gather-in-step", action="store_true",
                     help="N > 1: run the RCCL gather of all records to rank 0 inside every timed step")
-    ap.add_argument("--collect", choices=("gather", "d2h", "both", "none"), default="both",
-                    help="N > 1: which collection step(s) to measure after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond `value`, after the timed region: per-kernel HIP events and "
+                         "roofline; N = 1: sustained, launch-inclusive, shard and drop-in figures and the CPU "
+                         "baseline; N > 1: the collection step")
+    ap.add_argument("--collect", choices=("gather", "d2h", "both", "none"), default=None,
+                    help="N > 1: which collection step(s) to measure after the timed region "
+                         "(default: both with --full, none without)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="N > 1: weak = every GPU traces the workload's ray count (an N-times denser sphere in "
                          "all); strong = the workload's ray count is the TOTAL, ray-sharded over the N GPUs -- "
                          "`--workload c4 --gpus 4 --scaling strong` is BASELINE configs[3] (16 M rays in all), "
                          "`--workload c5 --gpus 8 --scaling strong` configs[4] (64 M)")
     ap.add_argument("--event-steps", type=int, default=10,
-                    help="steps of the separate, untimed pass that carries the per-kernel HIP events")
+                    help="--full: steps of the separate, untimed pass that carries the per-kernel HIP events")
     ap.add_argument("--no-gather", action="store_true", help="same as --collect none")
     ap.add_argument("--gather-timeout", type=float, default=120.0,
                     help="N > 1: give up on a collection measurement after this many seconds (exit code 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="N = 1: skip the drop-in / launch-inclusive / sustained measurements")
+                    help="--full, N = 1: skip the drop-in / launch-inclusive / sustained measurements")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--sustain-s", type=float, default=10.0,
                     help="GPU seconds of the sustained region (long enough for a utilisation sampler)")
@@ -243,6 +377,8 @@ def main():
         ap.error("--dump-outputs dumps the timed path; --dropin does not run it")
     if args.no_gather:
         args.collect = "none"
+    elif args.collect is None:
+        args.collect = "both" if args.full else "none"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -361,22 +497,6 @@ def main():
     dumped = None
     if args.dump_outputs:
         dumped = dump_outputs(tr, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank))
-    # per-kernel HIP events (one hrt_timer = the events of one step, recorded on the launch stream,
-    # read afterwards): a SEPARATE untimed pass right after the timed region, every step of it
-    # instrumented -- the timed steps carry no events (they cost ~4 % of a 1.6 ms step)
-    timers = [tr.new_timer() for _ in range(max(1, args.event_steps))]
-    for t in timers:
-        step(t)
-    torch.cuda.synchronize()
-    bounce_ms, los_ms, compact_ms, shade_ms, records_ms = [], [], [], [], []
-    for t in timers:
-        r = tr.read_timer(t)
-        los_ms.append(r["los_ms"])
-        bounce_ms.append(r["trace_ms"])
-        shade_ms.append(r["shade_ms"])
-        compact_ms.append(sum(r["scan_ms"]))
-        records_ms.append(r["records_ms"])
-
     # ---- work done (identical every step) ----
     counts = tr.counts()
     w = tr.work(counts)
@@ -393,106 +513,7 @@ def main():
     records, tests, unblk, live = tot[0], tot[1] + nrx * ntx * tr.num_tri, tot[2], tot[3:]
     paths = records + nrx * ntx
 
-    # ---- roofline of the dominant kernels, rank 0's launches.  One launch of "the bounce" is
-    # the pair hrt_trace_kernel (intersection) + hrt_shade_kernel (records, Fresnel, reflect):
-    # the algorithmic bytes of SURVEY 8(d) are those of the pair, so is the duration. ----
-    tm = np.asarray(bounce_ms, dtype=np.float64)          # [steps, nb+1] trace kernel (patch tables: primary rays only)
-    sm = np.asarray(shade_ms, dtype=np.float64)           # [steps, nb+1] shade kernel
-    rm = np.asarray(records_ms, dtype=np.float64)         # [steps, nb+1] records kernel (patch tables; else 0)
-    bm = tm + sm + rm
-    kern_ms_step = float(bm.sum(axis=1).mean())
-    n_launch = bm.shape[1]
-    unb_local = unblocked
-    B_local = algorithmic_bytes(w["live"], nrx, tr.num_local, unb_local, w["records"] - unb_local)
-    ach = B_local / (kern_ms_step * 1e-3) / 1e9
-    tests_local = w["tests"]
-    # HBM bytes per launch from PMC counters: collected by profiles/collect_pmc.sh (separate
-    # rocprofv3 passes) for exactly this workload at N = 1, committed in profiles/.  The JSON carries
-    # the hash of the kernel source it was measured on: `traffic_stale` says whether that is still
-    # the source of this run.
-    kern_sha = hashlib.sha256(b"".join(open(os.path.join(REPO, "hermespy-rt_amd", "csrc", f), "rb").read() for f in ("hrt_kernels.hip", "hrt_fused_body.inc"))).hexdigest()[:16]
-    traffic, traffic_src, traffic_stale = None, None, None
-    try:
-        pj = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
-        if world == 1 and args.workload in pj:
-            traffic = pj[args.workload]["hbm_bytes_per_launch_avg"]
-            traffic_src = pj[args.workload]["source"]
-            traffic_stale = pj[args.workload].get("kernels_sha16") != kern_sha
-    except (OSError, ValueError, KeyError):
-        pass
-    # VALU issue utilisation of the two kernels (SURVEY 8d asks for the VALU fraction next to the
-    # HBM one): from profiles/collect_valu.sh (own rocprofv3 --pmc pass), same workload, N = 1
-    valu = None
-    try:
-        vj = json.load(open(os.path.join(REPO, "profiles", "pmc_valu.json")))
-        if world == 1 and args.workload in vj:
-            valu = dict(vj[args.workload]["kernels"], source=vj[args.workload]["source"],
-                        stale=vj[args.workload].get("kernels_sha16") != kern_sha)
-    except (OSError, ValueError, KeyError):
-        pass
-    # which resource binds: the VALU issue rate of the dominant kernel (committed PMC pass) against
-    # the HBM fraction of the path -- C3 is VALU-bound, the tiny tables are nearer HBM
-    hbm_frac = ach / HBM_PEAK_GBS
-    valu_frac = None
-    if valu:
-        fr = [(v["valu_insts_per_step"], v["issue_frac_vs_simd32_peak"]) for k, v in valu.items()
-              if isinstance(v, dict) and "issue_frac_vs_simd32_peak" in v]
-        if fr:
-            valu_frac = max(fr)[1]   # of the kernel that issues the most instructions
-    fused0 = os.environ.get("HRT_FUSE", "") not in ("0",)
-    fused_all = fused0 and tr.num_tri <= 64
-    patched = 64 < tr.num_tri <= 256 and "no_patch" not in os.environ.get("HRT_TUNE", "")
-    kern_desc = ("hrt_fused_kernel (one kernel per launch: trace + shading + stable compaction)" if fused_all else
-                 ("launch 0: hrt_fused_kernel; later launches: " if fused0 else "") +
-                 ("hrt_records_kernel (shadow traces + scatter records; in the timed region on a second stream beside the "
-                  "others) + hrt_image_kernel / hrt_trace_kernel (primary rays) + hrt_shade_kernel (Fresnel, reflection, "
-                  "compaction): one bounce launch = the three; trace_kernel_ms = records + primary rays" if patched else
-                  "hrt_trace_kernel + hrt_shade_kernel (one bounce launch = the pair)"))
-    roofline = dict(bound=("valu" if (valu_frac is not None and valu_frac > hbm_frac) else "hbm"), kernel=kern_desc,
-                    achieved=ach, peak=HBM_PEAK_GBS,
-                    unit="GB/s", frac=hbm_frac, hbm_frac=hbm_frac, valu_frac=valu_frac,
-                    frac_of_step=B_local / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                    traffic=traffic, traffic_source=traffic_src,
-                    traffic_stale=traffic_stale, traffic_measured_in_run=False, kernels_sha16=kern_sha,
-                    algorithmic_bytes_per_launch=B_local / n_launch,
-                    avg_launch_ms=kern_ms_step / n_launch, launches_per_step=n_launch,
-                    steps_with_kernel_events=int(bm.shape[0]),
-                    kernel_events="separate untimed pass after the timed region, every step instrumented",
-                    per_launch_ms=[float(x) for x in bm.mean(axis=0)],
-                    trace_kernel_ms=[float(x) for x in tm.mean(axis=0)],
-                    shade_kernel_ms=[float(x) for x in sm.mean(axis=0)],
-                    records_kernel_ms=[float(x) for x in rm.mean(axis=0)],
-                    kernel_tests_per_s=tests_local / (kern_ms_step * 1e-3),
-                    compaction_ms_per_step=float(np.mean(compact_ms)), los_ms=float(np.mean(los_ms)),
-                    trace_variant=os.environ.get("HRT_TUNE", "auto (patch tables on 65-256 triangles; flat packet culling; trees on big sparse tables)"),
-                    valu=valu,
-                    note=("a fused launch reports its one kernel under trace_kernel_ms (shade_kernel_ms = 0); "
-                          "frac is the north-star's HBM figure (algorithmic bytes / SUM of the kernels' own durations, "
-                          "measured one after the other on one stream / 8 TB/s); frac_of_step the same bytes over the timed "
-                          "step, in which the records kernels run beside the others; "
-                          "valu_frac = VALU instructions issued x 2 cycles / SIMD-cycles of the busiest kernel"))
-
-    if rm.sum() > 0:
-        # the DOMINANT kernel on its own: hrt_records_kernel.  Algorithmic bytes of one launch b (the part
-        # of the path this kernel performs): 44 B of state per entry in, 36 B per unblocked / 20 B per blocked record out
-        rec_launches = [b for b in range(1, nb + 1) if w["live"][b] > 0]
-        rec_bytes = 44.0 * sum(w["live"][b] for b in rec_launches) + 36.0 * unb_local + 20.0 * (w["records"] - unb_local)
-        rec_ms = float(rm.sum(axis=1).mean())
-        roofline["dominant_kernel"] = dict(
-            name="hrt_records_kernel", launches_per_step=len(rec_launches), avg_launch_ms=rec_ms / max(1, len(rec_launches)),
-            ms_per_step=rec_ms, algorithmic_bytes_per_step=rec_bytes,
-            achieved=rec_bytes / (rec_ms * 1e-3) / 1e9, unit="GB/s", frac=rec_bytes / (rec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            what="HIP events around the kernel, one stream (the event pass); its VALU issue fraction is roofline.valu.records")
-
-    kstats = None
-    try:
-        import ctypes
-        from hermespy_rt_amd import lib as _l2
-        arr = (ctypes.c_uint64 * 48)()
-        if _l2.load().hrt_debug_kernel_stats(local_rank, arr, 0) == 0 and any(arr):
-            kstats = [[int(arr[k * 16 + j]) for j in range(16)] for k in range(3)]
-    except Exception:
-        pass
+    roofline, kstats = kernel_figures(tr, step, args, w, unblocked, dt, world, local_rank) if args.full else (None, None)
     out = None
     if rank == 0:
         out = dict(
@@ -509,8 +530,9 @@ def main():
                               "scatter are NOT in `value` -- see step_incl_launch_ms and end_to_end"),
             ray_tri_tests_per_sec=tests * args.steps / dt,
             nonzero_paths_per_sec=(unblk + nrx * ntx) * args.steps / dt,
-            work=dict(live=live, records=records, records_unblocked=unblk, tests=tests),
-            roofline=roofline)
+            work=dict(live=live, records=records, records_unblocked=unblk, tests=tests))
+        if roofline:
+            out["roofline"] = roofline
         # kernels this process switched off after a timeout (0: none; bit 0 fused launches, bit 1 the chain kernel:
         # the GPU was shared) and how often the timed region was timed again because a step in it was void
         out["fallback_state"] = int(_libm.load().hrt_fallback_state())
@@ -521,7 +543,7 @@ def main():
             out["kernel_stats_all_steps"] = dict(columns=["wave_traces", "usable_packets", "candidates", "stage2", "stage3", "exact", "c6", "c7"], primary0=kstats[0], primary=kstats[1], shadow=kstats[2])
 
     # ---- N = 1: what the steady-state number leaves out, measured in this process ----
-    if world == 1 and not args.no_end_to_end:
+    if args.full and world == 1 and not args.no_end_to_end:
         try:
             # (a) sustained: the same step for >= sustain_s of GPU time
             n_sus = max(args.steps, int(args.sustain_s / max(dt / args.steps, 1e-6)) + 1)
@@ -624,7 +646,7 @@ def main():
                 out["end_to_end"]["python_module_error"] = repr(e)
         except Exception as e:
             out["end_to_end_error"] = repr(e)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(base, args.cpu_budget_s)
 
     # ---- N > 1: the collection step, measured on its own, LAST and under a watchdog: the metric

@@ -10,7 +10,7 @@ tag=${1:-rXX}
 w=${2:-c3}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="python3 bench.py --workload $w --no-cpu-baseline --no-end-to-end --event-steps 1"
+B="python3 bench.py --workload $w --full --no-cpu-baseline --no-end-to-end --event-steps 1"
 d=gpurun_out/prof_${tag}_$w
 rm -rf $d
 # (one stream for the kernel-stats run, HRT_OVERLAP=0: a kernel's duration is then its own and can be held against the

@@ -10,7 +10,7 @@ for pass in A B; do
   d=gpurun_out/pq_${w}_$pass
   rm -rf $d
   timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -- \
-      python3 bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > $d.json 2> $d.err \
+      python3 bench.py --workload $w --steps 3 --warmup 1 --full --no-cpu-baseline --no-end-to-end > $d.json 2> $d.err \
       || (tail -20 $d.err; exit 1)
 done
 python3 - <<P

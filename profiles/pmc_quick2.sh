@@ -5,7 +5,7 @@ set -e
 tag=${1:-x}
 w=${2:-c3}
 export TMPDIR=/tmp
-B="python3 bench.py --workload $w --no-cpu-baseline --no-end-to-end --event-steps 1 --steps 3 --warmup 1"
+B="python3 bench.py --workload $w --full --no-cpu-baseline --no-end-to-end --event-steps 1 --steps 3 --warmup 1"
 d=gpurun_out/pmcq_${tag}_VALU; rm -rf $d
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAVES --kernel-trace --output-format csv -d $d -- $B > $d.json 2> $d.err || (tail -20 $d.err; exit 1)
 d=gpurun_out/pmcq_${tag}_WAVE; rm -rf $d
