@@ -396,3 +396,71 @@ def run_compute_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num
     nt, nl = int(spec.num_times), int(spec.num_taps)
     return _run_pathsum(lib, "hrt_compute_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, (2, nt, nl) if 0 < nt * nl <= (1 << 20) else None, (), stats)
+
+
+# hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
+(POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
+ POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)
+
+
+class PowerSpec(C.Structure):
+    """include/hermespy_rt.h hrt_power_spec"""
+    _fields_ = [("tau0_s", C.c_double), ("dtau_s", C.c_double), ("num_delay_bins", C.c_uint32),
+                ("num_zenith_bins", C.c_uint32), ("num_azimuth_bins", C.c_uint32), ("parts", C.c_uint32)]
+
+
+def power_spec(tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True, scatter=True,
+               parts=None):
+    if parts is None:
+        parts = (CHANNEL_LOS if los else 0) | (CHANNEL_SCATTER if scatter else 0)
+    return PowerSpec(float(tau0), float(dtau), int(num_delay_bins), int(num_zenith_bins), int(num_azimuth_bins),
+                     int(parts))
+
+
+def power_out_doubles(nrx, ntx, spec):
+    """the doubles of a power profiles output (hrt_power_out_doubles)"""
+    return nrx * ntx * 2 * (POWER_FIELDS + int(spec.num_delay_bins) +
+                            2 * int(spec.num_zenith_bins) * int(spec.num_azimuth_bins))
+
+
+def power_views(buf, nrx, ntx, spec):
+    """the regions of a flat power profiles buffer (numpy array or torch tensor) as views: moments [nrx, ntx, 2, F],
+    pdp [nrx, ntx, 2, Ld], arrival and departure [nrx, ntx, 2, Nth, Nph] (zero-sized where switched off), buffer"""
+    ld, nth, nph = int(spec.num_delay_bins), int(spec.num_zenith_bins), int(spec.num_azimuth_bins)
+    lp = nrx * ntx * 2
+    o1 = lp * POWER_FIELDS
+    o2 = o1 + lp * ld
+    o3 = o2 + lp * nth * nph
+    o4 = o3 + lp * nth * nph
+    return {"moments": buf[:o1].reshape(nrx, ntx, 2, POWER_FIELDS),
+            "pdp": buf[o1:o2].reshape(nrx, ntx, 2, ld),
+            "arrival": buf[o2:o3].reshape(nrx, ntx, 2, nth, nph),
+            "departure": buf[o3:o4].reshape(nrx, ntx, 2, nth, nph),
+            "buffer": buf}
+
+
+def run_compute_power_profiles(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                               stats=None):
+    """hrt_compute_power_profiles through ctypes -> power_views of a float64 numpy buffer.  Raises
+    RuntimeError("hrt_compute_power_profiles failed (<rc>): ...") on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    n = power_out_doubles(nrx, ntx, spec)
+    out = np.zeros(n if n <= 2 * (POWER_FIELDS * 65535 + (1 << 26)) else 1, np.float64)
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_power_profiles(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
+                                            C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+                                            C.byref(spec), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                            C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_power_profiles failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return power_views(out, nrx, ntx, spec)

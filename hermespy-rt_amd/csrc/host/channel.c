@@ -1,13 +1,13 @@
-/* channel.c -- channel frequency responses and impulse responses from traced paths, on the device
- * (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps; include/hermespy_rt.h: hrt_compute_channel,
- * hrt_compute_array_channel, hrt_compute_taps).
+/* channel.c -- channel frequency responses, impulse responses and power statistics from traced paths, on the
+ * device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_power_profiles; include/hermespy_rt.h:
+ * hrt_compute_channel, hrt_compute_array_channel, hrt_compute_taps, hrt_compute_power_profiles).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
- * csrc/hrt_array_channel.hip and csrc/hrt_taps.hip, over the workspace view of csrc/hrt_pathsum.h;
+ * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip and csrc/hrt_power.hip, over the workspace view of csrc/hrt_pathsum.h;
  * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
  * small download at the end.
  */
@@ -19,6 +19,7 @@
 #include "../hrt_array_channel.h"
 #include "../hrt_channel.h"
 #include "../hrt_pathsum.h"
+#include "../hrt_power.h"
 #include "../hrt_taps.h"
 
 /* ------------------------------------------------------------------ what the three path sums share (hrt_pathsum.h) */
@@ -84,7 +85,7 @@ static int ps_scratch_out(int rc, uint64_t bytes, uint64_t *out, const char *que
 
 /* the device buffers of one call, once its plan needs `need` bytes of scratch (`query` names the size query) */
 static int ps_bind(hrt_kview *v, uint64_t need, const void *d_workspace, void *d_scratch, uint64_t scratch_bytes,
-                   const float *d_out, int accumulate, const char *who, const char *query, float **partial)
+                   const void *d_out, int accumulate, const char *who, const char *query, float **partial)
 {
     if (!d_workspace || !d_out || !d_scratch)
         return hrt_fail(HRT_E_INVALID, "%s: NULL workspace, scratch or output", who);
@@ -173,20 +174,21 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
 struct ch_job {
-    const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel) or hrt_taps_spec */
+    const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel), hrt_taps_spec or
+                           hrt_power_spec */
     uint64_t out_bytes;
     const void *h_const;
     uint64_t const_bytes;
     void *d_const;
     int (*scratch_bytes)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out);
     int (*run)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
-               uint64_t scratch_bytes, float *d_out, int accumulate);
+               uint64_t scratch_bytes, void *d_out, int accumulate);
     uint32_t nr, nt;   /* the array call's element counts (hrt_compute_array_channel) */
     double fa;
 };
 
 static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
-                      float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, float *out,
+                      float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, void *out,
                       hrt_stats *stats, double t_begin)
 {
     hrt_stats st;
@@ -231,7 +233,7 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
         t0 = hrt_now_s();
         if ((rc = hrt_trace_batch(prob, &s, &L, w, &st))) goto done;   /* (batch.c) */
         /* batch 0 is rank 0 of the launch set: it adds the LoS term; the others add their records */
-        if ((rc = job->run(job, prob, &s, w->d_ws, d_scratch, scratch_bytes, (float *)d_out, first ? 0 : 1)))
+        if ((rc = job->run(job, prob, &s, w->d_ws, d_scratch, scratch_bytes, d_out, first ? 0 : 1)))
             goto done;
         first = 0;
         if ((rc = hrt_device_sync(device, NULL))) goto done;
@@ -268,7 +270,7 @@ static int ch_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard
 }
 
 static int ch_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
-                      uint64_t scratch_bytes, float *d_out, int accumulate)
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
 {
     return hrt_channel(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
 }
@@ -404,7 +406,7 @@ static int ac_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard
 }
 
 static int ac_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
-                      uint64_t scratch_bytes, float *d_out, int accumulate)
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
 {
     const hrt_array_spec a = ac_job_arrays(j);
     return hrt_array_channel(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
@@ -536,7 +538,7 @@ static int tp_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard
 }
 
 static int tp_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
-                      uint64_t scratch_bytes, float *d_out, int accumulate)
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
 {
     return hrt_taps(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
 }
@@ -556,5 +558,145 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
     job.out_bytes = (uint64_t)nrx * ntx * 2u * spec->num_times * spec->num_taps * 8u;
     job.scratch_bytes = tp_job_scratch;
     job.run = tp_job_run;
+    return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */
+
+#define HRT_PW_TARGET_GROUPS 2048u          /* workgroups of the moments pass worth launching (8 per CU) */
+#define HRT_PW_PARTIAL_MAX (512ull << 20)   /* partial moments beyond one chunk: at most this */
+
+static uint64_t align256(uint64_t n)
+{
+    return (n + 255u) / 256u * 256u;
+}
+
+/* the checks of a power spec that need no problem */
+static int power_check(const hrt_power_spec *spec)
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: NULL spec");
+    int rc = parts_check(spec->parts, "hrt_power_profiles");
+    if (rc) return rc;
+    const uint32_t Ld = spec->num_delay_bins, Nth = spec->num_zenith_bins, Nph = spec->num_azimuth_bins;
+    if (Ld > HRT_PW_MAX_DELAY_BINS)
+        return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: num_delay_bins = %u > 2^16", Ld);
+    if (Ld > 0 && !isfinite(spec->tau0_s))
+        return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: tau0 must be finite");
+    if (Ld > 0 && (!isfinite(spec->dtau_s) || !(spec->dtau_s > 0.0)))
+        return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: dtau must be finite and > 0");
+    if ((Nth == 0) != (Nph == 0))
+        return hrt_fail(HRT_E_INVALID,
+                        "hrt_power_profiles: num_zenith_bins = %u and num_azimuth_bins = %u (both 0 or both >= 1)",
+                        Nth, Nph);
+    if ((uint64_t)Nth * Nph > HRT_PW_MAX_ANGLE_BINS)
+        return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: num_zenith_bins * num_azimuth_bins = %llu > 2^14",
+                        (unsigned long long)Nth * Nph);
+    return HRT_OK;
+}
+
+/* the checks that need the link count */
+static int power_links_check(uint64_t nrx, uint64_t ntx, const hrt_power_spec *spec)
+{
+    if (nrx > 65535u || ntx > 65535u || nrx * ntx > 65535u)
+        return hrt_fail(HRT_E_INVALID, "hrt_power_profiles: num_rx * num_tx = %llu > 65535",
+                        (unsigned long long)(nrx * ntx));
+    const uint64_t bins = nrx * ntx * (spec->num_delay_bins + 2ull * spec->num_zenith_bins * spec->num_azimuth_bins);
+    if (bins > HRT_PW_MAX_LINK_BINS)
+        return hrt_fail(HRT_E_INVALID,
+                        "hrt_power_profiles: num_rx * num_tx * (num_delay_bins + 2 num_zenith_bins num_azimuth_bins)"
+                        " = %llu > 2^26", (unsigned long long)bins);
+    return HRT_OK;
+}
+
+uint64_t hrt_power_out_doubles(size_t num_rx, size_t num_tx, const hrt_power_spec *spec)
+{
+    if (!spec) return 0;
+    const uint64_t per_pol = HRT_POWER_FIELDS + (uint64_t)spec->num_delay_bins +
+                             2ull * spec->num_zenith_bins * spec->num_azimuth_bins;
+    return (uint64_t)num_rx * num_tx * 2u * per_pol;
+}
+
+/* the chunking and scratch of one power call: a pure function of the problem, the shard and the spec */
+static int pw_plan(const hrt_problem *p, const hrt_shard *s, const hrt_power_spec *spec, hrt_kpower *K,
+                   uint64_t *bytes, uint64_t *off_total, uint64_t *off_hist)
+{
+    int rc = power_check(spec);
+    if (rc) return rc;
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_power_profiles", &K->v))) return rc;
+    if ((rc = power_links_check(K->v.nrx, K->v.ntx, spec))) return rc;
+    K->num_paths = s->num_paths;
+    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
+    K->Ld = spec->num_delay_bins; K->Nth = spec->num_zenith_bins; K->Nph = spec->num_azimuth_bins;
+    K->nbins = K->Ld + 2u * K->Nth * K->Nph;
+    K->tau0 = spec->tau0_s; K->dtau = spec->dtau_s;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
+    const uint64_t per_chunk = links * 2u * HRT_POWER_FIELDS * 8u;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
+        K->v.nchunks = ps_nchunks(links, HRT_PW_TARGET_GROUPS, K->v.num_local, per_chunk, HRT_PW_PARTIAL_MAX,
+                                  UINT32_MAX);
+    *off_total = align256(K->v.nchunks * per_chunk);
+    *off_hist = *off_total + align256(links * 2u * 8u);
+    *bytes = ps_seg_bytes(&K->v) + *off_hist + links * 2u * K->nbins * 8u;
+    return HRT_OK;
+}
+
+int hrt_power_profiles_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_power_spec *spec,
+                                     uint64_t *out)
+{
+    hrt_kpower K;
+    uint64_t bytes = 0, ot, oh;
+    const int rc = pw_plan(p, s, spec, &K, &bytes, &ot, &oh);
+    return ps_scratch_out(rc, bytes, out, "hrt_power_profiles_scratch_bytes");
+}
+
+int hrt_power_profiles(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_power_spec *spec,
+                       void *d_scratch, uint64_t scratch_bytes, double *d_out, int accumulate, void *stream)
+{
+    hrt_kpower K;
+    uint64_t need = 0, off_total = 0, off_hist = 0;
+    int rc = pw_plan(p, s, spec, &K, &need, &off_total, &off_hist);
+    if (rc) return rc;
+    float *partial = NULL;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_power_profiles",
+                      "hrt_power_profiles_scratch_bytes", &partial)))
+        return rc;
+    K.partial = (double *)partial;
+    K.total = (double *)((uint8_t *)partial + off_total);
+    K.hist = (unsigned long long *)((uint8_t *)partial + off_hist);
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_power(&K, stream), "power kernels");
+    return HRT_OK;
+}
+
+static int pw_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    return hrt_power_profiles_scratch_bytes(p, s, j->spec, out);
+}
+
+static int pw_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
+{
+    return hrt_power_profiles(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                               const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                               const hrt_power_spec *spec, double *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = power_check(spec);
+    if (rc) return rc;
+    if ((rc = power_links_check(nrx, ntx, spec))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_power_profiles")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = hrt_power_out_doubles(nrx, ntx, spec) * 8u;
+    job.scratch_bytes = pw_job_scratch;
+    job.run = pw_job_run;
     return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
 }

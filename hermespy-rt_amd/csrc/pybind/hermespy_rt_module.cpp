@@ -383,6 +383,64 @@ py::array_t<std::complex<float>> compute_taps_py(
     return out;
 }
 
+// compute_power_profiles: per-link power statistics of the traced paths, formed on the device (extension; see
+// hrt_compute_power_profiles in hermespy_rt.h): a dict of float64 views of one flat buffer -- moments
+// (num_rx, num_tx, 2, HRT_POWER_FIELDS), pdp (num_rx, num_tx, 2, Ld), arrival and departure (num_rx, num_tx, 2, Nth,
+// Nph) -- and the buffer itself.
+py::dict compute_power_profiles_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double tau0, double dtau, unsigned long num_delay_bins, unsigned long num_zenith_bins,
+    unsigned long num_azimuth_bins, bool los, bool scatter)
+{
+    if (!num_rx || !num_tx || !num_paths || !num_bounces)
+        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    if (num_delay_bins > 0xffffffffUL || num_zenith_bins > 0xffffffffUL || num_azimuth_bins > 0xffffffffUL)
+        throw py::value_error("hermespy_rt.compute_power_profiles: num_delay_bins, num_zenith_bins and "
+                              "num_azimuth_bins must fit 32 bits");
+    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
+    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
+    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
+    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
+    check_scene_file(mesh_filepath);
+    hrt_power_spec spec{};
+    spec.tau0_s = tau0; spec.dtau_s = dtau;
+    spec.num_delay_bins = (uint32_t)num_delay_bins;
+    spec.num_zenith_bins = (uint32_t)num_zenith_bins; spec.num_azimuth_bins = (uint32_t)num_azimuth_bins;
+    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    // (the library validates the spec before it traces anything: a refused one raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t links = (size_t)num_rx * num_tx, Ld = spec.num_delay_bins;
+    const size_t Nth = spec.num_zenith_bins, Nph = spec.num_azimuth_bins;
+    const uint64_t n = hrt_power_out_doubles(num_rx, num_tx, &spec);
+    const bool fits = links <= 65535u && Ld <= (1u << 16) && Nth <= (1u << 14) && Nph <= (1u << 14) &&
+                      Nth * Nph <= (1u << 14) && links * (Ld + 2u * Nth * Nph) <= (1ull << 26);
+    py::array_t<double> buf(fits ? (size_t)n : (size_t)1);
+    double *dst = buf.mutable_data();
+    run_pathsum("compute_power_profiles", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_power_profiles(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                          num_bounces, &spec, dst, nullptr);
+    });
+    const size_t lp = links * 2u, o1 = lp * HRT_POWER_FIELDS, o2 = o1 + lp * Ld, o3 = o2 + lp * Nth * Nph;
+    auto view = [&](std::vector<size_t> shape, size_t off) {
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(double);
+        for (size_t k = shape.size(); k-- > 0;) {
+            strides[k] = st;
+            st *= (py::ssize_t)shape[k];
+        }
+        return py::array_t<double>(shape, strides, dst + off, buf);
+    };
+    const size_t R = num_rx, T = num_tx;
+    py::dict d;
+    d["moments"] = view({R, T, 2, (size_t)HRT_POWER_FIELDS}, 0);
+    d["pdp"] = view({R, T, 2, Ld}, o1);
+    d["arrival"] = view({R, T, 2, Nth, Nph}, o2);
+    d["departure"] = view({R, T, 2, Nth, Nph}, o3);
+    d["buffer"] = buf;
+    return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(hermespy_rt, m)
@@ -432,6 +490,14 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("l_min") = 0,
           py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
+    m.def("compute_power_profiles", &compute_power_profiles_py,
+          "Per-link power statistics of the traced paths, formed on the device: a dict of float64 arrays "
+          "(moments, pdp, arrival, departure, buffer)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("tau0"), py::arg("dtau"), py::arg("num_delay_bins"), py::arg("num_zenith_bins") = 0,
+          py::arg("num_azimuth_bins") = 0, py::arg("los") = true, py::arg("scatter") = true);
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

@@ -378,18 +378,20 @@ class Tracer:
         return out
 
     # ------------------------------------------------------------------ channel
-    def _pathsum_buffers(self, shape, need, out, accumulate, cache):
-        """The output (`out` checked, or a new tensor), the scratch cache named `cache` grown to `need` bytes and the
-        current stream of one channel / array_channel / taps call."""
+    def _pathsum_buffers(self, shape, need, out, accumulate, cache, dtype=None):
+        """The output (`out` checked, or a new tensor of `dtype`, default complex64), the scratch cache named `cache`
+        grown to `need` bytes and the current stream of one channel / array_channel / taps / power_profiles call."""
         torch = self.torch
+        dtype = torch.complex64 if dtype is None else dtype
         with torch.cuda.device(self.device):
             if out is None:
                 if accumulate:
                     raise ValueError("accumulate=True needs `out`")
-                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
-            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                out = torch.empty(shape, dtype=dtype, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device
                   or not out.is_contiguous()):
-                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+                raise ValueError("out must be a contiguous %s tensor of shape %s on %s"
+                                 % (str(dtype).replace("torch.", ""), shape, self.device))
             scratch = getattr(self, cache, None)
             if scratch is None or scratch.numel() < int(need.value):
                 scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=self.device)
@@ -488,6 +490,35 @@ class Tracer:
                                    C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
                    "hrt_taps")
         return out
+
+    def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
+                       scatter=True, out=None, accumulate=False):
+        """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums
+        of p = |a^pol|^2 over the paths and parts of channel() (include/hermespy_rt.h hrt_compute_power_profiles).
+
+            moments    [nrx, ntx, 2, POWER_FIELDS]  COUNT, P, P_TAU, P_TAU2, P_NU, P_NU2, P_URX_*, P_UTX_*, P_LOS
+            pdp        [nrx, ntx, 2, Ld]            p by delay bin floor((tau - tau0) / dtau)
+            arrival    [nrx, ntx, 2, Nth, Nph]      p by zenith x azimuth bin of u_rx
+            departure  [nrx, ntx, 2, Nth, Nph]      ... of u_tx (the launch direction of a record's ray)
+
+        Returns a dict of float64 views of one flat device tensor, itself under "buffer", enqueued on the current
+        stream; `out` (such a flat tensor) is written in place, or added to with accumulate=True.  hermespy_rt_amd.power
+        .summarize turns the moments into gains, spreads and K-factors.  Invalid arguments raise ValueError."""
+        spec = abi.power_spec(tau0, dtau, num_delay_bins, num_zenith_bins, num_azimuth_bins, los, scatter)
+        self.counts()
+        need = C.c_uint64(0)
+        rc = self.L.hrt_power_profiles_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need))
+        if rc == -1:
+            raise ValueError("hrt_power_profiles: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_power_profiles_scratch_bytes")
+        shape = (abi.power_out_doubles(self.nrx, self.ntx, spec),)
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_pw_scratch", self.torch.float64)
+        _lib.check(self.L.hrt_power_profiles(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
+                                             C.byref(spec), C.c_void_p(scratch.data_ptr()),
+                                             C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
+                                             1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
+                   "hrt_power_profiles")
+        return abi.power_views(out, self.nrx, self.ntx, spec)
 
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):

@@ -30,6 +30,7 @@ EXPORTED = (
     "hrt_channel_scratch_bytes", "hrt_channel", "hrt_compute_channel",
     "hrt_array_channel_scratch_bytes", "hrt_array_channel", "hrt_compute_array_channel",
     "hrt_taps_scratch_bytes", "hrt_taps", "hrt_compute_taps",
+    "hrt_power_out_doubles", "hrt_power_profiles_scratch_bytes", "hrt_power_profiles", "hrt_compute_power_profiles",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -229,6 +230,18 @@ def load():
     L.hrt_compute_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
                                    C.c_size_t, C.c_size_t, tpp, f32p, C.POINTER(Stats)]
     L.hrt_compute_taps.restype = C.c_int
+    # per-link power statistics (hrt_power_spec: abi.PowerSpec)
+    pwp = C.POINTER(abi.PowerSpec)
+    L.hrt_power_out_doubles.argtypes = [C.c_size_t, C.c_size_t, pwp]
+    L.hrt_power_out_doubles.restype = u64
+    L.hrt_power_profiles_scratch_bytes.argtypes = [vp, C.POINTER(Shard), pwp, C.POINTER(u64)]
+    L.hrt_power_profiles_scratch_bytes.restype = C.c_int
+    L.hrt_power_profiles.argtypes = [vp, C.POINTER(Shard), vp, pwp, vp, u64, vp, C.c_int, vp]
+    L.hrt_power_profiles.restype = C.c_int
+    L.hrt_compute_power_profiles.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                             C.c_size_t, C.c_size_t, C.c_size_t, pwp, C.POINTER(C.c_double),
+                                             C.POINTER(Stats)]
+    L.hrt_compute_power_profiles.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

@@ -252,6 +252,47 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
                      size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
                      float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
+ * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
+ *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);
+ *     clear a = HRT_LOS_A (TE = TM), tau = HRT_LOS_TAU, nu = HRT_LOS_FS, u_tx = HRT_LOS_DIR, u_rx = -u_tx;
+ *   scatter record: a = a_te / a_tm, tau, nu = the float difference FS0 - DFS (the path list's freq_shift),
+ *     u_rx = directions_rx, u_tx = the launch direction of the record's ray (as hrt_compute_array_channel).
+ * For pol 0 = TE, 1 = TM, p = |a^pol|^2 in FP64; every sum is FP64.  With L = num_rx * num_tx links, `out` holds
+ * four regions in this order (a region switched off is absent):
+ *   moments   [L][2][HRT_POWER_FIELDS]: COUNT (terms summed), P = sum p, P_TAU = sum p tau, P_TAU2 = sum p tau^2,
+ *             P_NU = sum p nu, P_NU2 = sum p nu^2, P_URX_X/Y/Z = sum p u_rx, P_UTX_X/Y/Z = sum p u_tx, P_LOS (the
+ *             LoS term's p);
+ *   pdp       [L][2][Ld]: bin i = floor((double(tau) - tau0) / dtau) (IEEE double division) gets p when
+ *             0 <= i < Ld; terms outside the window stay in the moments;
+ *   arrival   [L][2][Nth][Nph] and departure [L][2][Nth][Nph]: p by the direction of u_rx / u_tx, zenith
+ *             theta = acos(clamp(u_z, -1, 1)), bin min(floor(theta / pi * Nth), Nth - 1); azimuth
+ *             phi = atan2(u_y, u_x), bin floor((phi + pi) / (2 pi) * Nph), index Nph wrapping to 0.
+ * Ld = 0: no pdp; Nth = Nph = 0: no angular spectra.  Everything is additive: shards and batches add up to the whole.
+ * The histograms are formed in fixed point, rint(p 2^(62 - E)) with 2^E >= 2 P of the call: a bin is within
+ * N 2^-61 P of the FP64 sum of its N terms.  hrt_power_out_doubles gives the size of `out` (0 for a NULL spec).
+ * hrt_compute_power_profiles traces and batches like hrt_compute_channel (one device, one download at the end).
+ * HRT_E_INVALID, before the device is touched: parts 0 or with unknown bits; Ld > 2^16; tau0 or dtau not finite or
+ * dtau <= 0 when Ld > 0; exactly one of Nth, Nph 0; Nth * Nph > 2^14; num_rx * num_tx > 65535;
+ * num_rx * num_tx * (Ld + 2 Nth Nph) > 2^26. */
+enum {
+    HRT_POWER_COUNT = 0, HRT_POWER_P, HRT_POWER_P_TAU, HRT_POWER_P_TAU2, HRT_POWER_P_NU, HRT_POWER_P_NU2,
+    HRT_POWER_P_URX_X, HRT_POWER_P_URX_Y, HRT_POWER_P_URX_Z, HRT_POWER_P_UTX_X, HRT_POWER_P_UTX_Y, HRT_POWER_P_UTX_Z,
+    HRT_POWER_P_LOS,
+    HRT_POWER_FIELDS
+};
+typedef struct {
+    double tau0_s, dtau_s;                      /* delay bin i: [tau0 + i dtau, tau0 + (i + 1) dtau) */
+    uint32_t num_delay_bins;                    /* Ld */
+    uint32_t num_zenith_bins, num_azimuth_bins; /* Nth, Nph */
+    uint32_t parts;                             /* HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER */
+} hrt_power_spec;
+uint64_t hrt_power_out_doubles(size_t num_rx, size_t num_tx, const hrt_power_spec *spec);
+int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                               const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                               size_t num_rays, size_t num_bounces, const hrt_power_spec *spec,
+                               double *out /* hrt_power_out_doubles, layout above */, hrt_stats *stats);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

@@ -337,6 +337,21 @@ int hrt_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_t
 int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
              void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
 
+/* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
+ * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
+ * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
+ * device: no host synchronisation), asynchronous on `stream`, with the guarantees of hrt_taps: accumulate = 0
+ * overwrites d_out, 1 adds to it; only shard rank 0 adds the LoS term, so the outputs of the shards of one launch
+ * set sum to the whole result; the moments' partial sums go to the caller's scratch (hrt_power_profiles_scratch_bytes)
+ * and are reduced in a fixed order, the histograms are u64 fixed-point sums scaled by this call's own total power
+ * (never by what d_out holds); no floating-point atomics, so two calls with the same inputs give the same bits; the
+ * output is undefined if the trace's error word is set.
+ * HRT_E_INVALID, before the device is touched: every hrt_compute_power_profiles check, scratch too small. */
+int hrt_power_profiles_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_power_spec *spec,
+                                     uint64_t *out);
+int hrt_power_profiles(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_power_spec *spec,
+                       void *d_scratch, uint64_t scratch_bytes, double *d_out, int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
