@@ -1,0 +1,400 @@
+"""The path-sum families (Tracer.channel, array_channel, taps, power_profiles) record by record, on planted workspaces
+(tests/planted.py): after a real trace the test writes the records itself, so every reference sums values it chose.
+
+  a. poison: every slot a kernel must not read (blocked records, the slots past a block's count, mask bits past the
+     count, the fields of blocked and coincident LoS entries) is overwritten with NaN, then with 1e30; every output
+     must stay bit-identical.
+  b. planted sums: unit-sized dyadic terms on the exact grid of tests/planted.py.  The channel's inverse DFT over the
+     frequencies is the planted delay histogram; each tap is one record's term or 0; the power moments and every PDP
+     bin are exact; the array channel against a float64 sum.
+  c. structure: one, two and many record chunks, shards, the channel / array tilings, taps windows, power bins.
+  d. negative controls: every check of this module also runs against a reference changed in one record (dropped,
+     doubled, moved to the other polarisation) and must then fail, so every bound here is below one record.
+
+Bounds (planted |a_te| in {1, 2}, |a_tm| in {1/2, 1}): the channel's inverse DFT 1e-3 per bin; taps and the exact power
+fields 0; float32 direct sums (channel / array grids) UNIT_TOL = 0.05 absolute, a tenth of the weakest planted term.
+The float32 error of a sum of N <= 3e4 unit terms stays below 1e-2 (chunked sums of <= 10^3 terms, about sqrt(N)
+roundings of 2^-24 |sum| each, plus one f32 sincos per term)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from hermespy_rt_amd import abi
+
+from . import configs as K
+from . import planted as PL
+from . import scenes_gen as G
+from .test_gpu_power import _check as power_check
+from .test_gpu_power import _reference as power_reference
+
+pytestmark = pytest.mark.gpu
+
+UNIT_TOL = 0.05
+HIST_TOL = 1e-3
+PW_LDS_MAX = 80 << 10   # csrc/hrt_power.h HRT_PW_LDS_MAX: the hist kernel's LDS form up to this many bytes of bins
+PARTS = ((True, True), (True, False), (False, True))
+
+
+def _tracer(c, **kw):
+    from hermespy_rt_amd.device import Tracer
+    return Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"],
+                  c["num_paths"], c["num_bounces"], **kw)
+
+
+def _room(tmp_path_factory):
+    p = str(tmp_path_factory.mktemp("planted") / "room.hrt")
+    G.room_with_clutter(p, 120, seed=5)
+    return G.cfg(p, [[3.0, 2.0, 1.5], [-5.0, 4.0, 2.0]], [[-10.0, -6.0, 3.0], [12.0, 5.0, 4.0]], 6000, 3,
+                 tx_vel=[[1.0, 0.0, 0.0], [0.0, -2.0, 0.0]])
+
+
+CONFIGS = {"C3": lambda f: K.small(K.C3, 20000), "C4_DOPPLER": lambda f: K.small(K.C4_DOPPLER, 4000),
+           "COINCIDENT": lambda f: K.small(K.COINCIDENT, 8000), "room": _room}
+
+
+def _traced(name, tmp_path_factory, **kw):
+    c = CONFIGS[name](tmp_path_factory)
+    tr = _tracer(c, **kw)
+    if name == "room":
+        assert tr.num_tri > 1024   # the live list is re-sorted between bounces
+    tr.trace()
+    tr.torch.cuda.synchronize(tr.device)
+    return tr, c
+
+
+def _sel(T, los, scatter):
+    return PL.select(T, (T["los"] & los) | (~T["los"] & scatter))
+
+
+def _t(nt, t0=0.0, dt=PL.DT):
+    return t0 + np.arange(nt) * dt
+
+
+def _np(x):
+    return x.cpu().numpy()
+
+
+def _expect_failure(check, T, what):
+    """negative controls: check(T') must fail for T' = T changed in one record (PL.control_records x PL.MUTATIONS)"""
+    for name, k in PL.control_records(T):
+        for how in PL.MUTATIONS:
+            with pytest.raises(AssertionError):
+                check(PL.mutate(T, k, how))
+                print("%s: the check passed with record %s (%d) %s" % (what, name, k, how))
+
+
+# ------------------------------------------------------------------ a. poison
+def _bits(x):
+    import torch
+    x = torch.view_as_real(x) if x.is_complex() else x
+    return x.contiguous().view(torch.uint8).clone()
+
+
+def _run_all(tr, c, los, scatter):
+    """every family on the traced workspace, as raw output bytes"""
+    f0 = c["f_ghz"] * 1e9 - 32 * 30e3
+    rxe = np.array([[0, 0, 0], [0, 0.04, 0]], np.float32)
+    txe = np.array([[0, 0, 0], [0.04, 0, 0], [0, 0, 0.04]], np.float32)
+    out = {}
+    out["channel"] = _bits(tr.channel(f0, 30e3, 64, 1e-3, 2e-4, 2, los=los, scatter=scatter))
+    out["array"] = _bits(tr.array_channel(rxe, txe, f0, 30e3, 16, 1e-3, 2e-4, 2, los=los, scatter=scatter))
+    out["taps"] = _bits(tr.taps(122.88e6, 64, -8, t0=1e-3, dt=2e-4, num_times=2, los=los, scatter=scatter))
+    out["power_lds"] = _bits(tr.power_profiles(0.0, 5e-9, 256, 4, 8, los=los, scatter=scatter)["buffer"])
+    out["power_global"] = _bits(tr.power_profiles(0.0, 1e-10, 6000, 0, 0, los=los, scatter=scatter)["buffer"])
+    tr.torch.cuda.synchronize(tr.device)
+    return out
+
+
+def _force_los_classes(tr):
+    """give the poison a blocked and a coincident LoS entry where the trace has none (changing a clear entry's status
+    before the clean run: the kernels must then read nothing but that status)"""
+    st = PL.los_status(tr)
+    clear = [tuple(ix) for ix in np.argwhere(st == 2)]
+    S = PL.los_view(tr).view(tr.torch.int32)
+    for want in (1, 0):
+        if not (st == want).any() and clear:
+            rx, tx = clear.pop()
+            S[int(rx), int(tx), PL.LOS_STATUS] = want
+    tr.torch.cuda.synchronize(tr.device)
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_poison_does_not_change_any_output(name, tmp_path_factory):
+    tr, c = _traced(name, tmp_path_factory)
+    counts = tr.counts()
+    _force_los_classes(tr)
+    base = {parts: _run_all(tr, c, *parts) for parts in PARTS}
+    for parts, outs in base.items():
+        for fam, b in outs.items():
+            v = b.view(tr.torch.float64 if fam.startswith("power") else tr.torch.float32)
+            assert bool(tr.torch.isfinite(v).all()), (name, parts, fam)
+    for value in (float("nan"), 1e30):
+        hit = PL.poison(tr, counts, value)
+        for cls in ("blocked_records", "tail_slots", "tail_mask_bits"):
+            assert hit[cls] > 0, (name, cls, hit)
+        if tr.nrx * tr.ntx > 1:
+            assert hit["los_blocked"] > 0 and hit["los_coincident"] > 0, (name, hit)
+        else:
+            assert hit["los_blocked"] + hit["los_coincident"] > 0, (name, hit)
+        for parts in PARTS:
+            got = _run_all(tr, c, *parts)
+            for fam, b in base[parts].items():
+                assert bool(tr.torch.equal(got[fam], b)), "%s: %s with %s changed after poison %r" % (
+                    name, fam, parts, value)
+    tr.close()
+
+
+# ------------------------------------------------------------------ b. planted sums, with the negative controls
+@pytest.fixture(scope="module", params=["C3", "C4_DOPPLER"])
+def planted(request, tmp_path_factory):
+    tr, c = _traced(request.param, tmp_path_factory)
+    T = PL.plant(tr)
+    assert not PL.design_errors(T), PL.design_errors(T)
+    yield request.param, tr, T
+    tr.close()
+
+
+def _K(T):
+    return 1 << int(np.ceil(np.log2(T["n"].max() + 1)))
+
+
+@pytest.mark.parametrize("nt", [1, 3])
+def test_channel_inverse_dft_is_the_planted_histogram(planted, nt):
+    name, tr, T = planted
+    nk, t = _K(T), _t(nt)
+    full = None
+    for los, scatter in PARTS:
+        got = _np(tr.channel(PL.FC, PL.FS / nk, nk, 0.0, PL.DT, nt, los=los, scatter=scatter))
+        Ts = _sel(T, los, scatter)
+        err = PL.check_channel_hist(got, Ts, tr.nrx, tr.ntx, nk, t, HIST_TOL)
+        print(name, "channel", (los, scatter), "K", nk, "max |err|", err)
+        full = got if los and scatter else full
+    _expect_failure(lambda U: PL.check_channel_hist(full, U, tr.nrx, tr.ntx, nk, t, HIST_TOL), T, "channel")
+
+
+def test_taps_are_the_planted_terms(planted):
+    name, tr, T = planted
+    nmax, nt = int(T["n"].max()), 3
+    t = _t(nt)
+    full = None
+    for los, scatter in PARTS:
+        got = _np(tr.taps(PL.FS, nmax + 1, 0, fc=PL.FC, dt=PL.DT, num_times=nt, los=los, scatter=scatter))
+        PL.check_taps_planted(got, _sel(T, los, scatter), tr.nrx, tr.ntx, nmax + 1, 0, t)
+        full = got if los and scatter else full
+    _expect_failure(lambda U: PL.check_taps_planted(full, U, tr.nrx, tr.ntx, nmax + 1, 0, t), T, "taps")
+    # a window that cuts records off at both ends
+    lm, nl = 37, max(nmax // 2, 1)
+    got = _np(tr.taps(PL.FS, nl, lm, fc=PL.FC, dt=PL.DT, num_times=nt))
+    PL.check_taps_planted(got, T, tr.nrx, tr.ntx, nl, lm, t)
+    assert (T["n"] < lm).any() and (T["n"] >= lm + nl).any()
+
+
+@pytest.mark.parametrize("elements", ["2x2", "4x1"])
+def test_array_channel_against_float64(planted, elements):
+    name, tr, T = planted
+    lam = PL.C0 / (tr.f_ghz * 1e9)
+    if elements == "2x2":
+        rxe = np.array([[0, 0, 0], [0, lam / 2, 0]], np.float32)
+        txe = np.array([[0, 0, 0], [lam / 2, 0, lam / 3]], np.float32)
+    else:
+        rxe = (np.arange(4)[:, None] * np.array([[lam / 2, 0.0, 0.0]])).astype(np.float32)
+        txe = np.zeros((1, 3), np.float32)
+    fa = tr.f_ghz * 1e9
+    nk, nt, df = 16, 2, PL.FS / 4096
+    f, t = PL.FC + np.arange(nk) * df, _t(nt)
+    full = None
+    for los, scatter in PARTS:
+        got = _np(tr.array_channel(rxe, txe, PL.FC, df, nk, 0.0, PL.DT, nt, los=los, scatter=scatter))
+        Ts = _sel(T, los, scatter)
+        err = PL.check_close(got, PL.array_direct(Ts, tr.nrx, tr.ntx, rxe, txe, fa, f, t), UNIT_TOL, "array", Ts,
+                             tr.ntx)
+        print(name, "array", elements, (los, scatter), "max |err|", err)
+        full = got if los and scatter else full
+    _expect_failure(lambda U: PL.check_close(full, PL.array_direct(U, tr.nrx, tr.ntx, rxe, txe, fa, f, t), UNIT_TOL,
+                                             "array"), T, "array")
+
+
+def _power_checks(got, T, nrx, ntx, tau0, dtau, ld, nth, nph, tag, closure=True):
+    PL.check_power_exact(got, T, nrx, ntx, tau0, dtau, ld)
+    power_check(got, power_reference(PL.power_terms(T, nrx, ntx), tau0, dtau, ld, nth, nph), tag)
+    if closure:   # a window over every delay; sums of dyadic terms: exact
+        P = np.asarray(got["moments"])[..., abi.POWER_P]
+        assert np.array_equal(np.asarray(got["pdp"]).sum(axis=-1), P), tag
+        if nth:
+            for k in ("arrival", "departure"):
+                assert np.array_equal(np.asarray(got[k]).sum(axis=(-2, -1)), P), (tag, k)
+
+
+def test_power_moments_and_pdp_are_exact(planted):
+    name, tr, T = planted
+    tau0, dtau, ld = -0.5 / PL.FS, 1.0 / PL.FS, int(T["n"].max()) + 1
+    form = "global" if 2 * (ld + 2 * 15) * 8 > PW_LDS_MAX else "lds"
+    assert form == {"C3": "global", "C4_DOPPLER": "lds"}[name]   # both forms of hrt_power_hist_kernel
+    full = None
+    for los, scatter in PARTS:
+        got = {k: _np(v) for k, v in tr.power_profiles(tau0, dtau, ld, 3, 5, los=los, scatter=scatter).items()}
+        _power_checks(got, _sel(T, los, scatter), tr.nrx, tr.ntx, tau0, dtau, ld, 3, 5, (name, los, scatter))
+        full = got if los and scatter else full
+    _expect_failure(lambda U: PL.check_power_exact(full, U, tr.nrx, tr.ntx, tau0, dtau, ld), T, "power")
+
+
+# ------------------------------------------------------------------ c. structure
+def _channel_nchunks(tr, nk, nt):
+    spec = abi.channel_spec(PL.FC, 1.0, nk, 0.0, 0.0, nt)
+    need = C.c_uint64(0)
+    assert tr.L.hrt_channel_scratch_bytes(tr.problem, C.byref(tr.shard), C.byref(spec), C.byref(need)) == 0
+    seg = (tr.nb * (tr.ntx + 1) * 4 + 255) // 256 * 256
+    tiles = (nt * ((nk + 15) // 16) + 63) // 64
+    per = tr.nrx * tr.ntx * tiles * 64 * 16 * 4 * 4
+    assert (need.value - seg) % per == 0
+    return (need.value - seg) // per
+
+
+@pytest.mark.parametrize("rays,chunks", [(600, "one"), (1100, "two"), (20000, "many")])
+def test_record_chunks(rays, chunks):
+    """all four families where the TX segments are cut into one, two and many record chunks (host/channel.c
+    ps_nchunks: chunks of at least 512 records)"""
+    tr = _tracer(K.small(K.C4_DOPPLER, rays))
+    tr.trace()
+    n = _channel_nchunks(tr, 64, 2)
+    assert {"one": n == 1, "two": n == 2, "many": n > 2}[chunks], n
+    T = PL.plant(tr)
+    nrx, ntx, nt = tr.nrx, tr.ntx, 2
+    t = _t(nt, 3 * PL.DT)
+    f = PL.FC + np.arange(64) * 2.0 ** 22
+    got = _np(tr.channel(PL.FC, 2.0 ** 22, 64, t[0], PL.DT, nt))
+    PL.check_close(got, PL.channel_direct(T, nrx, ntx, f, t), UNIT_TOL, "channel", T, ntx)
+    nl = int(T["n"].max()) + 1
+    got = _np(tr.taps(PL.FS, nl, 0, fc=PL.FC, t0=t[0], dt=PL.DT, num_times=nt))
+    PL.check_taps_planted(got, T, nrx, ntx, nl, 0, t)
+    rxe = np.array([[0, 0, 0], [0, 0.05, 0]], np.float32)
+    txe = np.array([[0, 0, 0], [0.05, 0, 0]], np.float32)
+    got = _np(tr.array_channel(rxe, txe, PL.FC, 2.0 ** 22, 17, t[0], PL.DT, nt))
+    PL.check_close(got, PL.array_direct(T, nrx, ntx, rxe, txe, tr.f_ghz * 1e9, f[:17], t), UNIT_TOL, "array", T, ntx)
+    got = {k: _np(v) for k, v in tr.power_profiles(-0.5 / PL.FS, 1.0 / PL.FS, nl, 3, 5).items()}
+    _power_checks(got, T, nrx, ntx, -0.5 / PL.FS, 1.0 / PL.FS, nl, 3, 5, ("chunks", rays))
+    tr.close()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_shards_accumulate_to_the_whole(world):
+    """shards (chunk = 64) planted by global identity, summed with accumulate=True, against the whole's terms"""
+    c = K.small(K.C4_DOPPLER, 3000)
+    tr = _tracer(c)
+    tr.trace()
+    T = PL.plant(tr, keyed=True)
+    tr.close()
+    assert not PL.design_errors(T, keyed=True), PL.design_errors(T, keyed=True)
+    nrx, ntx, nt, nk, nl = len(c["rx_pos"]), len(c["tx_pos"]), 2, 33, PL.N_KEYED
+    t = _t(nt)
+    f = PL.FC + np.arange(nk) * 2.0 ** 21
+    rxe = np.array([[0, 0, 0], [0, 0.05, 0]], np.float32)
+    txe = np.array([[0, 0, 0], [0.05, 0, 0]], np.float32)
+    ch = ar = tp = pw = None
+    keys = []
+    for r in range(world):
+        ts = _tracer(c, rank=r, world=world, chunk=64)
+        ts.trace()
+        U = PL.plant(ts, keyed=True)
+        keys.append(U)
+        a = ch is not None
+        ch = ts.channel(PL.FC, 2.0 ** 21, nk, 0.0, PL.DT, nt, out=ch, accumulate=a)
+        ar = ts.array_channel(rxe, txe, PL.FC, 2.0 ** 21, nk, 0.0, PL.DT, nt, out=ar, accumulate=a)
+        tp = ts.taps(PL.FS, nl, 0, fc=PL.FC, dt=PL.DT, num_times=nt, out=tp, accumulate=a)
+        pw = ts.power_profiles(-0.5 / PL.FS, 1.0 / PL.FS, nl, 3, 5, out=pw["buffer"] if a else None, accumulate=a)
+        ts.torch.cuda.synchronize(ts.device)
+        ts.close()
+    # the shards planted the same terms as the whole (LoS on every shard's workspace, added by rank 0 only)
+    S = PL.concat(*[PL.select(U, ~U["los"]) for U in keys])
+    key = lambda X: np.lexsort((X["bounce"], X["path"], X["tx"], X["rx"]))   # noqa: E731
+    a, b = key(S), key(PL.select(T, ~T["los"]))
+    Tsc = PL.select(T, ~T["los"])
+    for k in ("rx", "tx", "path", "bounce", "n", "a_te", "a_tm", "nu"):
+        assert np.array_equal(S[k][a], Tsc[k][b]), k
+    PL.check_close(_np(ch), PL.channel_direct(T, nrx, ntx, f, t), UNIT_TOL, "channel shards", T, ntx)
+    PL.check_close(_np(ar), PL.array_direct(T, nrx, ntx, rxe, txe, c["f_ghz"] * 1e9, f, t), UNIT_TOL,
+                   "array shards", T, ntx)
+    PL.check_taps_planted(_np(tp), T, nrx, ntx, nl, 0, t)
+    got = {k: _np(v) for k, v in pw.items()}
+    _power_checks(got, T, nrx, ntx, -0.5 / PL.FS, 1.0 / PL.FS, nl, 3, 5, ("shards", world))
+
+
+@pytest.fixture(scope="module")
+def small_planted():
+    """C4_DOPPLER at 1100 rays: two record chunks, 2 x 2 links"""
+    tr = _tracer(K.small(K.C4_DOPPLER, 1100))
+    tr.trace()
+    T = PL.plant(tr)
+    yield tr, T
+    tr.close()
+
+
+GRID_K = [1, 15, 16, 17, 1023, 1024, 1025]
+
+
+@pytest.mark.parametrize("nt", [1, 4, 5])
+@pytest.mark.parametrize("nk", GRID_K)
+def test_channel_and_array_grids(small_planted, nk, nt):
+    """T ceil(K / 16) across the 64-row tile of the channel (HRT_CH_ROWS, HRT_CH_K2) and the array's row blocks"""
+    tr, T = small_planted
+    df = PL.FS / 2048
+    f, t = PL.FC + np.arange(nk) * df, _t(nt)
+    got = _np(tr.channel(PL.FC, df, nk, 0.0, PL.DT, nt))
+    PL.check_close(got, PL.channel_direct(T, tr.nrx, tr.ntx, f, t), UNIT_TOL, "channel", T, tr.ntx)
+    rxe = np.array([[0, 0, 0], [0, 0.05, 0]], np.float32)
+    txe = np.array([[0, 0, 0], [0.05, 0, 0.02]], np.float32)
+    got = _np(tr.array_channel(rxe, txe, PL.FC, df, nk, 0.0, PL.DT, nt))
+    PL.check_close(got, PL.array_direct(T, tr.nrx, tr.ntx, rxe, txe, tr.f_ghz * 1e9, f, t), UNIT_TOL, "array", T,
+                   tr.ntx)
+
+
+@pytest.mark.parametrize("case", ["negative_df", "negative_dt", "t0", "f0_70ghz", "all"])
+def test_channel_and_array_signs_and_offsets(small_planted, case):
+    tr, T = small_planted
+    f0, df, t0, dt = PL.FC, 30e3, 0.0, PL.DT
+    if case in ("negative_df", "all"):
+        df = -30e3
+    if case in ("negative_dt", "all"):
+        dt = -1e-3
+    if case in ("t0", "all"):
+        t0 = 0.0123
+    if case in ("f0_70ghz", "all"):
+        f0 = 71.5e9
+    nk, nt = 40, 3
+    f, t = f0 + np.arange(nk) * df, t0 + np.arange(nt) * dt
+    got = _np(tr.channel(f0, df, nk, t0, dt, nt))
+    PL.check_close(got, PL.channel_direct(T, tr.nrx, tr.ntx, f, t), UNIT_TOL, "channel " + case, T, tr.ntx)
+    rxe = np.array([[0, 0, 0], [0, 0.003, 0]], np.float32)
+    txe = np.array([[0, 0, 0], [0.003, 0, 0.001]], np.float32)
+    got = _np(tr.array_channel(rxe, txe, f0, df, nk, t0, dt, nt, array_frequency=f0))
+    PL.check_close(got, PL.array_direct(T, tr.nrx, tr.ntx, rxe, txe, f0, f, t), UNIT_TOL, "array " + case, T, tr.ntx)
+    _expect_failure(lambda U: PL.check_close(got, PL.array_direct(U, tr.nrx, tr.ntx, rxe, txe, f0, f, t), UNIT_TOL,
+                                             "array"), T, "array " + case)
+
+
+@pytest.mark.parametrize("l_min", [-100, 0, 37])
+@pytest.mark.parametrize("nl", [1, 63, 64, 65, 1025])
+def test_taps_windows(small_planted, nl, l_min):
+    tr, T = small_planted
+    nt = 2
+    t = _t(nt, -5 * PL.DT)
+    got = _np(tr.taps(PL.FS, nl, l_min, fc=PL.FC, t0=t[0], dt=PL.DT, num_times=nt))
+    PL.check_taps_planted(got, T, tr.nrx, tr.ntx, nl, l_min, t)
+
+
+@pytest.mark.parametrize("angles", [(1, 1), (3, 5)])
+@pytest.mark.parametrize("ld", [1, 3])
+def test_power_small_windows(small_planted, ld, angles):
+    """a delay window of 1 or 3 bins above some planted delays (tau0 past them), spectra of 1 x 1 and 3 x 5 bins"""
+    tr, T = small_planted
+    nth, nph = angles
+    n0 = int(np.median(T["n"]))
+    tau0, dtau = (n0 - 0.5) / PL.FS, 1.0 / PL.FS
+    assert (T["n"] < n0).any() and (T["n"] >= n0 + ld).any()
+    got = {k: _np(v) for k, v in tr.power_profiles(tau0, dtau, ld, nth, nph).items()}
+    PL.check_power_exact(got, T, tr.nrx, tr.ntx, tau0, dtau, ld)
+    power_check(got, power_reference(PL.power_terms(T, tr.nrx, tr.ntx), tau0, dtau, ld, nth, nph), ("small", ld))
+    P = np.asarray(got["moments"])[..., abi.POWER_P]
+    for k in ("arrival", "departure"):
+        assert np.array_equal(np.asarray(got[k]).sum(axis=(-2, -1)), P), k
