@@ -398,6 +398,23 @@ def run_compute_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num
                         num_bounces, spec, (2, nt, nl) if 0 < nt * nl <= (1 << 20) else None, (), stats)
 
 
+def run_compute_array_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                           rx_elements, tx_elements, array_frequency=None, stats=None):
+    """hrt_compute_array_taps through ctypes -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_taps] (array_frequency
+    defaults to the carrier).  Raises RuntimeError("hrt_compute_array_taps failed (<rc>): ...") on an error code."""
+    re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
+    nr, nt = re.shape[0], te.shape[0]
+    V3 = C.POINTER(Vec3)
+    fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    ntm, nl = int(spec.num_times), int(spec.num_taps)
+    pts = nr * nt * ntm * nl
+    fits = 0 < pts <= (1 << 24) and ntm * nl <= (1 << 20)
+    extra = (re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3), C.c_size_t(nt), C.c_double(fa))
+    return _run_pathsum(lib, "hrt_compute_array_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, (nr, nt, 2, ntm, nl) if fits else None, extra, stats)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

@@ -1,13 +1,15 @@
 /* channel.c -- channel frequency responses, impulse responses and power statistics from traced paths, on the
- * device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_power_profiles; include/hermespy_rt.h:
- * hrt_compute_channel, hrt_compute_array_channel, hrt_compute_taps, hrt_compute_power_profiles).
+ * device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps, hrt_power_profiles;
+ * include/hermespy_rt.h: hrt_compute_channel, hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps,
+ * hrt_compute_power_profiles).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
- * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip and csrc/hrt_power.hip, over the workspace view of csrc/hrt_pathsum.h;
+ * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip and csrc/hrt_power.hip, over the workspace
+ * view of csrc/hrt_pathsum.h;
  * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
  * small download at the end.
  */
@@ -17,6 +19,7 @@
 
 #include "hrt_internal.h"
 #include "../hrt_array_channel.h"
+#include "../hrt_array_taps.h"
 #include "../hrt_channel.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_power.h"
@@ -174,8 +177,8 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
 struct ch_job {
-    const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel), hrt_taps_spec or
-                           hrt_power_spec */
+    const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel), hrt_taps_spec
+                           (hrt_compute_taps, hrt_compute_array_taps) or hrt_power_spec */
     uint64_t out_bytes;
     const void *h_const;
     uint64_t const_bytes;
@@ -183,7 +186,7 @@ struct ch_job {
     int (*scratch_bytes)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out);
     int (*run)(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
                uint64_t scratch_bytes, void *d_out, int accumulate);
-    uint32_t nr, nt;   /* the array call's element counts (hrt_compute_array_channel) */
+    uint32_t nr, nt;   /* the array calls' element counts (hrt_compute_array_channel, hrt_compute_array_taps) */
     double fa;
 };
 
@@ -310,23 +313,51 @@ int hrt_compute_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, co
 #define HRT_AC_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
 #define HRT_SPEED_OF_LIGHT 299792458.0
 
+/* the checks of the arrays of a call (`who`) whose spec has `grid` points per element pair (`axes` names them);
+ * device pointers are not read */
+static int arrays_check(const hrt_array_spec *a, uint64_t grid, const char *axes, const char *who)
+{
+    if (!a) return hrt_fail(HRT_E_INVALID, "%s: NULL arrays", who);
+    if (a->num_rx_elements < 1 || a->num_rx_elements > HRT_AC_MAX_ELEMENTS || a->num_tx_elements < 1 ||
+        a->num_tx_elements > HRT_AC_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX elements (1 .. %u each)", who, a->num_rx_elements,
+                        a->num_tx_elements, HRT_AC_MAX_ELEMENTS);
+    const uint64_t pts = (uint64_t)a->num_rx_elements * a->num_tx_elements * grid;
+    if (pts > HRT_AC_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: Nr * Nt * %s = %llu > 2^24", who, axes, (unsigned long long)pts);
+    if (!isfinite(a->array_frequency_hz) || !(a->array_frequency_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "%s: the array frequency must be finite and > 0", who);
+    if (!a->rx_elements || !a->tx_elements) return hrt_fail(HRT_E_INVALID, "%s: NULL element offsets", who);
+    return HRT_OK;
+}
+
 /* the checks of an array call that need no problem (device pointers are not read) */
 static int array_check(const hrt_channel_spec *spec, const hrt_array_spec *a)
 {
     int rc = spec_check(spec);
     if (rc) return rc;
-    if (!a) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL arrays");
-    if (a->num_rx_elements < 1 || a->num_rx_elements > HRT_AC_MAX_ELEMENTS || a->num_tx_elements < 1 ||
-        a->num_tx_elements > HRT_AC_MAX_ELEMENTS)
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: %u RX and %u TX elements (1 .. %u each)",
-                        a->num_rx_elements, a->num_tx_elements, HRT_AC_MAX_ELEMENTS);
-    const uint64_t pts = (uint64_t)a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_freqs;
-    if (pts > HRT_AC_MAX_POINTS)
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: Nr * Nt * num_times * num_freqs = %llu > 2^24",
-                        (unsigned long long)pts);
-    if (!isfinite(a->array_frequency_hz) || !(a->array_frequency_hz > 0.0))
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: the array frequency must be finite and > 0");
-    if (!a->rx_elements || !a->tx_elements) return hrt_fail(HRT_E_INVALID, "hrt_array_channel: NULL element offsets");
+    return arrays_check(a, (uint64_t)spec->num_times * spec->num_freqs, "num_times * num_freqs",
+                        "hrt_array_channel");
+}
+
+/* the element counts of a drop-in array call (`who`), before they are narrowed to the spec's */
+static int ac_counts_check(size_t nr, size_t nt, const char *who)
+{
+    if (nr > HRT_AC_MAX_ELEMENTS || nt > HRT_AC_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: %zu RX and %zu TX elements (1 .. %u each)", who, nr, nt,
+                        HRT_AC_MAX_ELEMENTS);
+    return HRT_OK;
+}
+
+/* the host offsets of a drop-in array call (`who`): finite */
+static int ac_offsets_check(const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt, const char *who)
+{
+    for (size_t i = 0; i < nr; ++i)
+        if (!isfinite(rx_el[i].x) || !isfinite(rx_el[i].y) || !isfinite(rx_el[i].z))
+            return hrt_fail(HRT_E_INVALID, "%s: RX element %zu is not finite", who, i);
+    for (size_t j = 0; j < nt; ++j)
+        if (!isfinite(tx_el[j].x) || !isfinite(tx_el[j].y) || !isfinite(tx_el[j].z))
+            return hrt_fail(HRT_E_INVALID, "%s: TX element %zu is not finite", who, j);
     return HRT_OK;
 }
 
@@ -412,46 +443,50 @@ static int ac_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s,
     return hrt_array_channel(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
 }
 
+/* the offsets of a drop-in array call for ch_compute to upload (rx then tx; ac_job_arrays): *el is the host buffer,
+ * freed by the caller after the call */
+static int ac_job_elements(ch_job *job, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt, double f_a,
+                           float **el)
+{
+    *el = (float *)malloc((nr + nt) * 3u * sizeof(float));
+    if (!*el) return hrt_fail(HRT_E_NOMEM, "out of host memory");
+    float *e = *el;
+    for (size_t i = 0; i < nr; ++i) { e[3 * i] = rx_el[i].x; e[3 * i + 1] = rx_el[i].y; e[3 * i + 2] = rx_el[i].z; }
+    for (size_t j = 0; j < nt; ++j) {
+        float *q = e + 3u * (nr + j);
+        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
+    }
+    job->h_const = e;
+    job->const_bytes = (nr + nt) * 3u * sizeof(float);
+    job->nr = (uint32_t)nr;
+    job->nt = (uint32_t)nt;
+    job->fa = f_a;
+    return HRT_OK;
+}
+
 int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
                               const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
                               const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
                               size_t nt, double f_a, float *out, hrt_stats *stats)
 {
     const double t_begin = hrt_now_s();
-    if (nr > HRT_AC_MAX_ELEMENTS || nt > HRT_AC_MAX_ELEMENTS)
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: %zu RX and %zu TX elements (1 .. %u each)", nr, nt,
-                        HRT_AC_MAX_ELEMENTS);
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
     /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
     const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
-    int rc = array_check(spec, &a);
-    if (rc) return rc;
-    for (size_t i = 0; i < nr; ++i)
-        if (!isfinite(rx_el[i].x) || !isfinite(rx_el[i].y) || !isfinite(rx_el[i].z))
-            return hrt_fail(HRT_E_INVALID, "hrt_array_channel: RX element %zu is not finite", i);
-    for (size_t j = 0; j < nt; ++j)
-        if (!isfinite(tx_el[j].x) || !isfinite(tx_el[j].y) || !isfinite(tx_el[j].z))
-            return hrt_fail(HRT_E_INVALID, "hrt_array_channel: TX element %zu is not finite", j);
+    if ((rc = array_check(spec, &a))) return rc;
+    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_array_channel"))) return rc;
     if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
                                "hrt_compute_array_channel")))
         return rc;
-    float *el = (float *)malloc((nr + nt) * 3u * sizeof(float));
-    if (!el) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-    for (size_t i = 0; i < nr; ++i) { el[3 * i] = rx_el[i].x; el[3 * i + 1] = rx_el[i].y; el[3 * i + 2] = rx_el[i].z; }
-    for (size_t j = 0; j < nt; ++j) {
-        float *q = el + 3u * (nr + j);
-        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
-    }
     ch_job job;
     memset(&job, 0, sizeof job);
     job.spec = spec;
     job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
-    job.h_const = el;
-    job.const_bytes = (nr + nt) * 3u * sizeof(float);
     job.scratch_bytes = ac_job_scratch;
     job.run = ac_job_run;
-    job.nr = (uint32_t)nr;
-    job.nt = (uint32_t)nt;
-    job.fa = f_a;
+    float *el = NULL;
+    if ((rc = ac_job_elements(&job, rx_el, nr, tx_el, nt, f_a, &el))) return rc;
     rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
     free(el);
     return rc;
@@ -462,23 +497,29 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
 #define HRT_TP_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
 #define HRT_TP_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
 
-static int taps_check(const hrt_taps_spec *spec)
+/* the checks of a taps spec of a call (`who`) */
+static int taps_spec_check(const hrt_taps_spec *spec, const char *who)
 {
-    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_taps: NULL spec");
+    if (!spec) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
     if (spec->num_taps == 0 || spec->num_times == 0)
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: num_taps and num_times must be > 0");
+        return hrt_fail(HRT_E_INVALID, "%s: num_taps and num_times must be > 0", who);
     if ((uint64_t)spec->num_taps * spec->num_times > HRT_TP_MAX_POINTS)
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: num_taps * num_times = %llu > 2^20",
+        return hrt_fail(HRT_E_INVALID, "%s: num_taps * num_times = %llu > 2^20", who,
                         (unsigned long long)spec->num_taps * spec->num_times);
     if (!isfinite(spec->fs_hz) || !(spec->fs_hz > 0.0))
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: the sampling rate must be finite and > 0");
+        return hrt_fail(HRT_E_INVALID, "%s: the sampling rate must be finite and > 0", who);
     if (!isfinite(spec->fc_hz) || !isfinite(spec->t0_s) || !isfinite(spec->dt_s))
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: fc, t0 and dt must be finite");
+        return hrt_fail(HRT_E_INVALID, "%s: fc, t0 and dt must be finite", who);
     const int64_t lo = spec->l_min, hi = (int64_t)spec->l_min + spec->num_taps;
     if (lo < -HRT_TP_MAX_TAP || lo > HRT_TP_MAX_TAP || hi > HRT_TP_MAX_TAP)
-        return hrt_fail(HRT_E_INVALID, "hrt_taps: tap indices l_min = %lld .. %lld outside +-2^24", (long long)lo,
+        return hrt_fail(HRT_E_INVALID, "%s: tap indices l_min = %lld .. %lld outside +-2^24", who, (long long)lo,
                         (long long)hi);
-    return parts_check(spec->parts, "hrt_taps");
+    return parts_check(spec->parts, who);
+}
+
+static int taps_check(const hrt_taps_spec *spec)
+{
+    return taps_spec_check(spec, "hrt_taps");
 }
 
 /* the tiling of one taps call: a pure function of the problem, the shard and the spec */
@@ -559,6 +600,122 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
     job.scratch_bytes = tp_job_scratch;
     job.run = tp_job_run;
     return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ antenna-array impulse responses (hrt_array_taps) */
+
+#define HRT_AT_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_AT_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
+
+/* the checks of an array taps call that need no problem (device pointers are not read) */
+static int at_check(const hrt_taps_spec *spec, const hrt_array_spec *a)
+{
+    int rc = taps_spec_check(spec, "hrt_array_taps");
+    if (rc) return rc;
+    return arrays_check(a, (uint64_t)spec->num_times * spec->num_taps, "num_times * num_taps", "hrt_array_taps");
+}
+
+/* the tiling of one array taps call: a pure function of the problem, the shard, the spec and the array sizes */
+static int at_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, const hrt_array_spec *a,
+                   hrt_karray_taps *K, uint64_t *bytes)
+{
+    int rc = at_check(spec, a);
+    if (rc) return rc;
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_array_taps", &K->v))) return rc;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
+    if (links * 2u * a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_taps >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_taps: more than 2^39 outputs");
+    K->num_paths = s->num_paths;
+    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
+    K->nr = a->num_rx_elements; K->nt = a->num_tx_elements; K->npairs = K->nr * K->nt;
+    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
+    K->rows = K->npairs * K->T;
+    K->rtiles = (4u * K->rows + 15u) / 16u;
+    K->ctiles = (K->L + 15u) / 16u;
+    /* where the grid has four row tiles (Nr Nt T >= 13), 4 x 4 tiles per wave and the waves along the rows: a block
+     * of 16 x 4 tiles; otherwise hrt_taps' RT = 1 form: 1 x 4 tiles per wave, the waves along the columns */
+    K->rt = K->rtiles >= 4u ? 4u : 1u;
+    const uint32_t brows = K->rt == 4u ? 16u : 1u, bcols = K->rt == 4u ? 4u : 16u;   /* tiles of a block */
+    K->rblocks = (K->rtiles + brows - 1u) / brows;
+    K->cblocks = (K->ctiles + bcols - 1u) / bcols;
+    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
+    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
+    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->L * 8u;
+    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
+        K->v.nchunks = ps_nchunks(links * K->rblocks * K->cblocks, HRT_AT_TARGET_GROUPS, K->v.num_local, per_chunk,
+                                  HRT_AT_PARTIAL_MAX, 65535u);
+    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
+    return HRT_OK;
+}
+
+int hrt_array_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec,
+                                 const hrt_array_spec *arrays, uint64_t *out)
+{
+    hrt_karray_taps K;
+    uint64_t bytes = 0;
+    const int rc = at_plan(p, s, spec, arrays, &K, &bytes);
+    return ps_scratch_out(rc, bytes, out, "hrt_array_taps_scratch_bytes");
+}
+
+int hrt_array_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+                   const hrt_array_spec *arrays, void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate,
+                   void *stream)
+{
+    hrt_karray_taps K;
+    uint64_t need = 0;
+    int rc = at_plan(p, s, spec, arrays, &K, &need);
+    if (rc) return rc;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_array_taps",
+                      "hrt_array_taps_scratch_bytes", &K.partial)))
+        return rc;
+    K.rx_el = arrays->rx_elements;
+    K.tx_el = arrays->tx_elements;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_array_taps(&K, stream), "array taps kernels");
+    return HRT_OK;
+}
+
+static int at_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_taps_scratch_bytes(p, s, j->spec, &a, out);
+}
+
+static int at_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_taps(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                           const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                           const hrt_taps_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt,
+                           double f_a, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_taps");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: at_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = at_check(spec, &a))) return rc;
+    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_array_taps"))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_array_taps")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_taps * 8u;
+    job.scratch_bytes = at_job_scratch;
+    job.run = at_job_run;
+    float *el = NULL;
+    if ((rc = ac_job_elements(&job, rx_el, nr, tx_el, nt, f_a, &el))) return rc;
+    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+    free(el);
+    return rc;
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

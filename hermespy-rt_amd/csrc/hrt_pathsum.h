@@ -1,6 +1,7 @@
-/* hrt_pathsum.h -- what the three path-sum families (hrt_channel, hrt_array_channel, hrt_taps) share: the view of the
- * workspace of a finished hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray and
- * hrt_ktaps; filled by csrc/host/channel.c) and, for the .hip files, the device helpers that read it.
+/* hrt_pathsum.h -- what the path-sum families (hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
+ * hrt_power_profiles) share: the view of the workspace of a finished hrt_trace that their kernels read (plain C, the
+ * first member of hrt_kchannel, hrt_karray, hrt_ktaps, hrt_karray_taps and hrt_kpower; filled by csrc/host/channel.c)
+ * and, for the .hip files, the device helpers that read it.
  *
  * Every family sums, per link (rx, tx), the LoS entry (shard rank 0 only) and the scatter records of the link's TX
  * segment in every hit block.  The records of a segment are cut into nchunks chunks; a partial kernel writes one

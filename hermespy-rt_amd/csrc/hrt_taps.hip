@@ -5,7 +5,7 @@
 //
 // over the LoS entry (hrt_taps_reduce_kernel) and every unblocked scatter record (hrt_taps_partial_kernel) of the
 // link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip); the workspace
-// view, its readers and the batch fill are csrc/hrt_pathsum.h.
+// view, its readers and the batch fill are csrc/hrt_pathsum.h; the sinc weights csrc/hrt_sinc.h.
 //   hrt_taps_partial_kernel  one workgroup (4 waves) per (row block x column block, record chunk, link): the real
 //                            GEMM of csrc/hrt_taps.h on v_mfma_f32_16x16x4_f32, partial sums to the scratch.  The
 //                            unblocked records of the chunk are compacted by mask ballots and staged HRT_TP_BATCH at a
@@ -23,42 +23,10 @@
 #include <stdint.h>
 
 #include "hrt_pathsum.h"
+#include "hrt_sinc.h"
 #include "hrt_taps.h"
 
 typedef float hrt_f32x4 __attribute__((ext_vector_type(4)));
-
-namespace {
-
-// The sinc of one delay, x = f_s tau: sinc(l - x) = (-1)^l c / ((l - k) - r) with k = rint(x) clamped to
-// +-2^26 (so l - k is an exact int32 for |l| <= 2^24), r = x - k and c = -(-1)^n sin(pi (x - n)) / pi, n = rint(x).
-// Unclamped, |r| <= 1/2; clamped, r has the sign of k and l - k the other one, so (l - k) - r never vanishes.
-struct sinc_rec {
-    int32_t k;
-    float r, c;
-};
-
-__device__ __forceinline__ sinc_rec sinc_prep(double fs, float tau)
-{
-    const double x = fs * (double)tau;
-    const double n = rint(x);
-    const double k = fmin(fmax(n, -67108864.0), 67108864.0);
-    const double h = 0.5 * n;   // n odd <=> n / 2 has a fraction (exact below 2^53; beyond it x is even, f = 0)
-    const float s = sinpif((float)(x - n)) * 0.318309886183790672f;   // sin(pi f) / pi
-    sinc_rec q;
-    q.k = (int32_t)k;
-    q.r = (float)(x - k);
-    q.c = h != floor(h) ? s : -s;
-    return q;
-}
-
-__device__ __forceinline__ float sinc_tap(int32_t l, const sinc_rec &q)
-{
-    const float d = (float)(l - q.k) - q.r;
-    const float c = (l & 1) ? -q.c : q.c;
-    return fabsf(d) < 1e-4f ? 1.f : c * __builtin_amdgcn_rcpf(d);
-}
-
-}  // namespace
 
 // RT row tiles x (HRT_TP_WTILES / RT) column tiles per wave (csrc/hrt_taps.h)
 template <uint32_t RT>

@@ -383,6 +383,55 @@ py::array_t<std::complex<float>> compute_taps_py(
     return out;
 }
 
+// compute_array_taps: the antenna-array sampled impulse response of the traced paths, formed on the device
+// (extension; see hrt_compute_array_taps in hermespy_rt.h): complex64 (num_rx, num_tx, Nr, Nt, 2, num_times,
+// num_taps).  Element offsets are (Nr, 3) / (Nt, 3) metres from the traced RX / TX positions; center_frequency f_c
+// and array_frequency f_a (Hz) default to the carrier.
+py::array_t<std::complex<float>> compute_array_taps_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
+    long l_min, py::object center_frequency, double t0, double dt, unsigned long num_times, bool los, bool scatter,
+    py::object array_frequency)
+{
+    if (!num_rx || !num_tx || !num_paths || !num_bounces)
+        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_taps and num_times must fit 32 bits");
+    if (l_min < -(1L << 30) || l_min > (1L << 30))
+        throw py::value_error("hermespy_rt.compute_array_taps: tap indices l_min outside +-2^24");
+    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
+    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
+    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
+    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
+    if (rx_elements.size() % 3 || tx_elements.size() % 3)
+        throw std::invalid_argument("rx_elements and tx_elements must have shape (n, 3)");
+    const size_t nr = (size_t)rx_elements.size() / 3, nt = (size_t)tx_elements.size() / 3;
+    const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_taps_spec spec{};
+    spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
+    spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)num_times;
+    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
+    // beyond the limits would be refused, so only one within them is allocated.)
+    const unsigned long long pts = (unsigned long long)nr * nt * num_times * num_taps;
+    const bool fits = pts > 0 && pts <= (1ull << 24) && (uint64_t)num_taps * num_times <= (1ull << 20) && nr <= 1024 &&
+                      nt <= 1024;
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, nr, nt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_taps}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const Vec3 *rxe = reinterpret_cast<const Vec3 *>(rx_elements.data());
+    const Vec3 *txe = reinterpret_cast<const Vec3 *>(tx_elements.data());
+    run_pathsum("compute_array_taps", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_array_taps(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                      num_bounces, &spec, rxe, nr, txe, nt, fa, dst, nullptr);
+    });
+    return out;
+}
+
 // compute_power_profiles: per-link power statistics of the traced paths, formed on the device (extension; see
 // hrt_compute_power_profiles in hermespy_rt.h): a dict of float64 views of one flat buffer -- moments
 // (num_rx, num_tx, 2, HRT_POWER_FIELDS), pdp (num_rx, num_tx, 2, Ld), arrival and departure (num_rx, num_tx, 2, Nth,
@@ -490,6 +539,16 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("l_min") = 0,
           py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
+    m.def("compute_array_taps", &compute_array_taps_py,
+          "Antenna-array sampled channel impulse response of the traced paths, formed on the device: complex64 "
+          "(num_rx, num_tx, Nr, Nt, 2, num_times, num_taps)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("l_min") = 0, py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("array_frequency") = py::none());
     m.def("compute_power_profiles", &compute_power_profiles_py,
           "Per-link power statistics of the traced paths, formed on the device: a dict of float64 arrays "
           "(moments, pdp, arrival, departure, buffer)",

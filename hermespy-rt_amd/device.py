@@ -491,6 +491,48 @@ class Tracer:
                    "hrt_taps")
         return out
 
+    def array_taps(self, rx_elements, tx_elements, fs, num_taps, l_min=0, fc=None, t0=0.0, dt=0.0, num_times=1,
+                   los=True, scatter=True, array_frequency=None, out=None, accumulate=False):
+        """Antenna-array (MIMO) sampled impulse response of the last trace, formed on the device (hrt_array_taps):
+
+            h[rx, tx, i, j, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p))
+                                               * exp(j 2 pi f_a (r_i . u_p^rx + q_j . u_p^tx) / c) sinc(l_k - f_s tau_p)
+            t_m = t0 + m dt,  l_k = l_min + k
+
+        the taps of taps() between the elements of array_channel(): rx_elements (Nr, 3) / tx_elements (Nt, 3) element
+        offsets in metres (numpy or torch), f_a = array_frequency (Hz), fc the baseband centre (Hz); both default to
+        the carrier.  The paths, parts and directions are those of array_channel().  Returns a complex64 tensor
+        [nrx, ntx, Nr, Nt, 2, num_times, num_taps] on the device, enqueued on the current stream; `out` is written in
+        place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
+        te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
+        if not (np.isfinite(re).all() and np.isfinite(te).all()):
+            raise ValueError("element offsets must be finite")
+        nr, nt = re.shape[0], te.shape[0]
+        fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
+        fc = self.f_ghz * 1e9 if fc is None else float(fc)
+        spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
+        self.counts()
+        with torch.cuda.device(self.device):
+            d_el = torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
+        arr = abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa)
+        need = C.c_uint64(0)
+        rc = self.L.hrt_array_taps_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(arr),
+                                                 C.byref(need))
+        if rc == -1:
+            raise ValueError("hrt_array_taps: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_array_taps_scratch_bytes")
+        shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_taps))
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_at_scratch")
+        _lib.check(self.L.hrt_array_taps(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
+                                         C.byref(spec), C.byref(arr), C.c_void_p(scratch.data_ptr()),
+                                         C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
+                                         1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
+                   "hrt_array_taps")
+        d_el.record_stream(stream)   # (the kernels read the offsets after this call returns)
+        return out
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

@@ -30,6 +30,7 @@ EXPORTED = (
     "hrt_channel_scratch_bytes", "hrt_channel", "hrt_compute_channel",
     "hrt_array_channel_scratch_bytes", "hrt_array_channel", "hrt_compute_array_channel",
     "hrt_taps_scratch_bytes", "hrt_taps", "hrt_compute_taps",
+    "hrt_array_taps_scratch_bytes", "hrt_array_taps", "hrt_compute_array_taps",
     "hrt_power_out_doubles", "hrt_power_profiles_scratch_bytes", "hrt_power_profiles", "hrt_compute_power_profiles",
 )
 
@@ -230,6 +231,15 @@ def load():
     L.hrt_compute_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
                                    C.c_size_t, C.c_size_t, tpp, f32p, C.POINTER(Stats)]
     L.hrt_compute_taps.restype = C.c_int
+    # antenna-array impulse responses (hrt_taps_spec and hrt_array_spec)
+    L.hrt_array_taps_scratch_bytes.argtypes = [vp, C.POINTER(Shard), tpp, app, C.POINTER(u64)]
+    L.hrt_array_taps_scratch_bytes.restype = C.c_int
+    L.hrt_array_taps.argtypes = [vp, C.POINTER(Shard), vp, tpp, app, vp, u64, vp, C.c_int, vp]
+    L.hrt_array_taps.restype = C.c_int
+    L.hrt_compute_array_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                         C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                         f32p, C.POINTER(Stats)]
+    L.hrt_compute_array_taps.restype = C.c_int
     # per-link power statistics (hrt_power_spec: abi.PowerSpec)
     pwp = C.POINTER(abi.PowerSpec)
     L.hrt_power_out_doubles.argtypes = [C.c_size_t, C.c_size_t, pwp]

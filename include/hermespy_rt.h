@@ -252,6 +252,30 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
                      size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
                      float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Antenna-array (MIMO) sampled impulse responses of the traced paths, formed on the device (include/hrt_device.h:
+ * hrt_array_taps): the taps of hrt_compute_taps between the elements of hrt_compute_array_channel's arrays.  For every
+ * link, element pair (i, j), polarisation pol (0 = TE, 1 = TM), time sample m < num_times and tap l < num_taps:
+ *     h[rx][tx][i][j][pol][m][l] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p))
+ *                                         * exp(j 2 pi f_a (r_i . u_p^rx + q_j . u_p^tx) / c) sinc(l_min + l - f_s tau_p)
+ *     t_m = t0 + m dt,  sinc(x) = sin(pi x) / (pi x),  sinc(0) = 1,  c = 299 792 458 m/s
+ * over the paths hrt_channel sums (the same parts, LoS and scatter terms; blocked records add nothing).  u^rx is
+ * directions_rx; u^tx the launch direction of the record's ray; the LoS entry has u^tx = HRT_LOS_DIR and u^rx = -u^tx
+ * (coincident: u^rx = (1, 0, 0), u^tx = (-1, 0, 0)), a real amplitude and TE = TM.  The steering is narrowband, as in
+ * hrt_compute_array_channel: evaluated at f_a; one geometry is shared by all RX and one by all TX; the elements are
+ * isotropic.  Identities: for |f| < f_s / 2 the DTFT sum_l h[..., l] exp(-j 2 pi f (l_min + l) / f_s) is
+ * hrt_compute_array_channel's H at f_k = f_c + f (same f_a and elements), up to the taps cut off by the window; with
+ * Nr = Nt = 1 and zero offsets the result is hrt_compute_taps's; pair (i, j) is a call with the single pair (r_i, q_j).
+ * out: complex [num_rx][num_tx][Nr][Nt][2][num_times][num_taps], re/im interleaved (numpy complex64).
+ * rx_elements / tx_elements: HOST arrays of Nr / Nt offsets.  Traced and batched like hrt_compute_channel; only `out`
+ * is copied back.  HRT_E_INVALID, before the device is touched: every hrt_taps_spec check; Nr or Nt outside 1..1024;
+ * Nr * Nt * num_times * num_taps > 2^24; an offset or f_a not finite; f_a <= 0. */
+int hrt_compute_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                           const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                           size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
+                           const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                           size_t num_tx_elements, double array_frequency_hz,
+                           float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

@@ -337,6 +337,23 @@ int hrt_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_t
 int hrt_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
              void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
 
+/* ---- antenna-array impulse responses from the traced paths (csrc/host/channel.c, csrc/hrt_array_taps.hip) ----
+ * h[rx][tx][i][j][pol][m][l] as hermespy_rt.h defines it (hrt_compute_array_taps), formed from the workspace of a
+ * finished hrt_trace (its counts read on the device: no host synchronisation), asynchronous on `stream`, with the
+ * guarantees of hrt_taps: accumulate = 0 overwrites d_out, 1 adds to it; only shard rank 0 adds the LoS term, so the
+ * outputs of the shards of one launch set sum to the whole result; partial sums go to the caller's scratch
+ * (hrt_array_taps_scratch_bytes) and are reduced in a fixed order, no floating-point atomics, so two calls with the
+ * same inputs give the same bits; the output is undefined if the trace's error word is set.  The element offsets are
+ * DEVICE pointers, as in hrt_array_channel (their finiteness is the caller's to ensure; the host entries check it).
+ * HRT_E_INVALID, before the device is touched: every hrt_taps check; NULL arrays or element pointers; Nr or Nt
+ * outside 1..1024; Nr * Nt * num_times * num_taps > 2^24; f_a not finite or <= 0; num_rx * num_tx > 65535; 2^39
+ * outputs or more; scratch too small. */
+int hrt_array_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec,
+                                 const hrt_array_spec *arrays, uint64_t *out);
+int hrt_array_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+                   const hrt_array_spec *arrays, void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate,
+                   void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
