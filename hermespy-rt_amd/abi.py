@@ -312,9 +312,10 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 
 
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
-                 out_shape, extra, stats):
-    """One of hrt_compute_channel / _array_channel / _taps (`name`) through ctypes, into a complex64 numpy array of
-    shape (nrx, ntx) + out_shape (out_shape None: a placeholder the library refuses to write); `extra` are the
+                 out_shape, extra, stats, dtype=np.complex64):
+    """One of the five path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps or
+    _power_profiles) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape (a flat buffer of
+    out_shape doubles for float64; out_shape None: a placeholder the library refuses to write); `extra` are the
     arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
     tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
@@ -323,12 +324,17 @@ def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, n
     _, txp = _vec3_arg(tx_pos, ntx)
     rxv_a, rxv = _vec3_arg(rx_vel, nrx)
     txv_a, txv = _vec3_arg(tx_vel, ntx)
-    out = np.zeros((nrx, ntx) + tuple(out_shape) if out_shape is not None else (1,), np.complex64)
+    if out_shape is None:
+        out_shape = (1,)
+    elif dtype == np.complex64:
+        out_shape = (nrx, ntx) + tuple(out_shape)
+    out = np.zeros(out_shape, dtype)
     scene = lib.scene_load(str(scene_path).encode())
     try:
         rc = getattr(lib, name)(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx), C.c_size_t(ntx),
                                 C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)), C.byref(spec), *extra,
-                                out.ctypes.data_as(c_float_p), C.byref(stats) if stats is not None else None)
+                                out.ctypes.data_as(C.POINTER(C.c_double if dtype == np.float64 else C.c_float)),
+                                C.byref(stats) if stats is not None else None)
     finally:
         free_scene(scene)
     if rc != 0:
@@ -360,19 +366,25 @@ def elements(e, name):
     return a
 
 
+def _array_args(rx_elements, tx_elements, f_ghz, array_frequency):
+    """-> Nr, Nt and the arguments that follow the spec of hrt_compute_array_channel / _array_taps (array_frequency
+    defaults to the carrier)"""
+    re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
+    nr, nt = re.shape[0], te.shape[0]
+    V3 = C.POINTER(Vec3)
+    fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
+    return nr, nt, (re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3), C.c_size_t(nt), C.c_double(fa))
+
+
 def run_compute_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                               rx_elements, tx_elements, array_frequency=None, stats=None):
     """hrt_compute_array_channel through ctypes -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_freqs]
     (array_frequency defaults to the carrier).  Raises RuntimeError("hrt_compute_array_channel failed (<rc>): ...")
     on an error code."""
-    re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
-    nr, nt = re.shape[0], te.shape[0]
-    V3 = C.POINTER(Vec3)
-    fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
     # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
     pts = nr * nt * int(spec.num_times) * int(spec.num_freqs)
     shape = (max(nr, 1), max(nt, 1), 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
-    extra = (re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3), C.c_size_t(nt), C.c_double(fa))
     return _run_pathsum(lib, "hrt_compute_array_channel", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, shape if 0 < pts <= (1 << 24) else None, extra, stats)
 
@@ -402,15 +414,11 @@ def run_compute_array_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_gh
                            rx_elements, tx_elements, array_frequency=None, stats=None):
     """hrt_compute_array_taps through ctypes -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_taps] (array_frequency
     defaults to the carrier).  Raises RuntimeError("hrt_compute_array_taps failed (<rc>): ...") on an error code."""
-    re, te = elements(rx_elements, "rx_elements"), elements(tx_elements, "tx_elements")
-    nr, nt = re.shape[0], te.shape[0]
-    V3 = C.POINTER(Vec3)
-    fa = float(f_ghz) * 1e9 if array_frequency is None else float(array_frequency)
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
     # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
     ntm, nl = int(spec.num_times), int(spec.num_taps)
     pts = nr * nt * ntm * nl
     fits = 0 < pts <= (1 << 24) and ntm * nl <= (1 << 20)
-    extra = (re.ctypes.data_as(V3), C.c_size_t(nr), te.ctypes.data_as(V3), C.c_size_t(nt), C.c_double(fa))
     return _run_pathsum(lib, "hrt_compute_array_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, (nr, nt, 2, ntm, nl) if fits else None, extra, stats)
 
@@ -460,24 +468,10 @@ def run_compute_power_profiles(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, 
                                stats=None):
     """hrt_compute_power_profiles through ctypes -> power_views of a float64 numpy buffer.  Raises
     RuntimeError("hrt_compute_power_profiles failed (<rc>): ...") on an error code."""
-    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
-    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
-    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
-    _, rxp = _vec3_arg(rx_pos, nrx)
-    _, txp = _vec3_arg(tx_pos, ntx)
-    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
-    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
     # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
     n = power_out_doubles(nrx, ntx, spec)
-    out = np.zeros(n if n <= 2 * (POWER_FIELDS * 65535 + (1 << 26)) else 1, np.float64)
-    scene = lib.scene_load(str(scene_path).encode())
-    try:
-        rc = lib.hrt_compute_power_profiles(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx),
-                                            C.c_size_t(ntx), C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
-                                            C.byref(spec), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                            C.byref(stats) if stats is not None else None)
-    finally:
-        free_scene(scene)
-    if rc != 0:
-        raise RuntimeError("hrt_compute_power_profiles failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    out = _run_pathsum(lib, "hrt_compute_power_profiles", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                       num_bounces, spec, (n,) if n <= 2 * (POWER_FIELDS * 65535 + (1 << 26)) else None, (), stats,
+                       np.float64)
     return power_views(out, nrx, ntx, spec)

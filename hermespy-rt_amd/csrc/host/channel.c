@@ -25,7 +25,7 @@
 #include "../hrt_power.h"
 #include "../hrt_taps.h"
 
-/* ------------------------------------------------------------------ what the three path sums share (hrt_pathsum.h) */
+/* ------------------------------------------------------------------ what the path-sum families share (hrt_pathsum.h) */
 
 #define HRT_CH_MIN_CHUNK 512u                /* records of one TX segment per chunk, at least */
 
@@ -57,25 +57,36 @@ static int ps_view(const hrt_problem *p, const hrt_shard *s, uint32_t parts, con
     return HRT_OK;
 }
 
-/* record chunks per (link, block) of the scatter part: enough of the `groups` blocks per chunk to reach
- * target_groups, chunks of at least HRT_CH_MIN_CHUNK records, partial sums of at most partial_max bytes (but one
- * chunk always), and at most y_max (the chunks' grid dimension) */
-static uint32_t ps_nchunks(uint64_t groups, uint64_t target_groups, uint32_t num_local, uint64_t per_chunk,
-                           uint64_t partial_max, uint64_t y_max)
+/* the shard of the trace, for the kernels that form a record's departure direction from its global path */
+static void ps_shard(const hrt_shard *s, hrt_kshard *k)
 {
-    uint64_t nch = (target_groups + groups - 1) / groups;
-    const uint64_t by_recs = num_local / HRT_CH_MIN_CHUNK;
-    if (nch > by_recs) nch = by_recs;
-    if (nch > partial_max / per_chunk) nch = partial_max / per_chunk;
-    if (nch > y_max) nch = y_max;
-    if (nch < 1) nch = 1;
-    return (uint32_t)nch;
+    k->num_paths = s->num_paths;
+    k->rank = s->rank; k->count = s->count; k->chunk = s->chunk ? s->chunk : 4096u;
 }
 
 /* the scratch of one call: seg, then nchunks * per_chunk bytes of partial sums */
 static uint64_t ps_seg_bytes(const hrt_kview *v)
 {
     return ((uint64_t)v->nb * (v->ntx + 1u) * 4u + 255u) / 256u * 256u;
+}
+
+/* The record chunks per (link, block) of the scatter part, where the call has one (v->nchunks stays 0 otherwise):
+ * enough of the `groups` blocks per chunk to reach target_groups, chunks of at least HRT_CH_MIN_CHUNK records,
+ * partial sums of at most partial_max bytes (but one chunk always), and at most y_max (the chunks' grid dimension).
+ * Returns the scratch of the call: seg, then the partial sums. */
+static uint64_t ps_chunks(hrt_kview *v, uint32_t parts, uint64_t groups, uint64_t target_groups, uint64_t per_chunk,
+                          uint64_t partial_max, uint64_t y_max)
+{
+    if ((parts & HRT_CHANNEL_SCATTER) && v->nb > 0) {
+        uint64_t nch = (target_groups + groups - 1) / groups;
+        const uint64_t by_recs = v->num_local / HRT_CH_MIN_CHUNK;
+        if (nch > by_recs) nch = by_recs;
+        if (nch > partial_max / per_chunk) nch = partial_max / per_chunk;
+        if (nch > y_max) nch = y_max;
+        if (nch < 1) nch = 1;
+        v->nchunks = (uint32_t)nch;
+    }
+    return ps_seg_bytes(v) + v->nchunks * per_chunk;
 }
 
 static int ps_scratch_out(int rc, uint64_t bytes, uint64_t *out, const char *query)
@@ -141,10 +152,8 @@ static int ch_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_s
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     const uint64_t per_chunk = links * K->tiles * HRT_CH_TILE_FLOATS * 4u;
     /* (the chunks are grid x: no cap; HRT_CH_MIN_CHUNK keeps them below 2^23) */
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
-        K->v.nchunks = ps_nchunks(links * K->tiles, HRT_CH_TARGET_GROUPS, K->v.num_local, per_chunk,
-                                  HRT_CH_PARTIAL_MAX, UINT32_MAX);
-    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
+    *bytes = ps_chunks(&K->v, spec->parts, links * K->tiles, HRT_CH_TARGET_GROUPS, per_chunk, HRT_CH_PARTIAL_MAX,
+                       UINT32_MAX);
     return HRT_OK;
 }
 
@@ -172,7 +181,7 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-/* One drop-in call: what hrt_compute_channel and hrt_compute_array_channel share.  `scratch_bytes` and `run` are
+/* One drop-in call: what the five hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
@@ -361,6 +370,18 @@ static int ac_offsets_check(const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, siz
     return HRT_OK;
 }
 
+/* the array fields of hrt_karray / hrt_karray_taps (call `who`, `grid` points per element pair and `links` links) and
+ * the limit of the output index */
+static int ac_fields(const hrt_array_spec *a, uint64_t links, uint64_t grid, const char *who, uint32_t *nr,
+                     uint32_t *nt, uint32_t *npairs, double *fa_c)
+{
+    if (links * 2u * a->num_rx_elements * a->num_tx_elements * grid >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "%s: more than 2^39 outputs", who);
+    *nr = a->num_rx_elements; *nt = a->num_tx_elements; *npairs = *nr * *nt;
+    *fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
+    return HRT_OK;
+}
+
 /* the tiling of one array call: a pure function of the problem, the shard, the spec and the array sizes */
 static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, const hrt_array_spec *a,
                    hrt_karray *K, uint64_t *bytes)
@@ -370,23 +391,19 @@ static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_s
     memset(K, 0, sizeof *K);
     if ((rc = ps_view(p, s, spec->parts, "hrt_array_channel", &K->v))) return rc;
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
-    if (links * 2u * a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_freqs >= (1ull << 39))
-        return hrt_fail(HRT_E_INVALID, "hrt_array_channel: more than 2^39 outputs");
-    K->num_paths = s->num_paths;
-    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
-    K->nr = a->num_rx_elements; K->nt = a->num_tx_elements; K->npairs = K->nr * K->nt;
+    if ((rc = ac_fields(a, links, (uint64_t)spec->num_times * spec->num_freqs, "hrt_array_channel", &K->nr, &K->nt,
+                        &K->npairs, &K->fa_c)))
+        return rc;
+    ps_shard(s, &K->sh);
     K->K = spec->num_freqs; K->T = spec->num_times;
     K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
     K->rows = K->K1 * K->T;
     K->pblocks = (K->npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
     K->cblocks = (K->rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
     K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
     const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->K * 8u;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
-        K->v.nchunks = ps_nchunks(links * K->pblocks * K->cblocks, HRT_AC_TARGET_GROUPS, K->v.num_local, per_chunk,
-                                  HRT_AC_PARTIAL_MAX, 65535u);
-    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
+    *bytes = ps_chunks(&K->v, spec->parts, links * K->pblocks * K->cblocks, HRT_AC_TARGET_GROUPS, per_chunk,
+                       HRT_AC_PARTIAL_MAX, 65535u);
     return HRT_OK;
 }
 
@@ -443,14 +460,19 @@ static int ac_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s,
     return hrt_array_channel(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
 }
 
-/* the offsets of a drop-in array call for ch_compute to upload (rx then tx; ac_job_arrays): *el is the host buffer,
- * freed by the caller after the call */
-static int ac_job_elements(ch_job *job, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt, double f_a,
-                           float **el)
+/* What hrt_compute_array_channel and hrt_compute_array_taps (`who`, device entry `dev`) share once the counts and
+ * the spec are checked: the remaining checks in their order, the offsets for ch_compute to upload (rx then tx;
+ * ac_job_arrays), the call.  `job` has the spec, the output size and the device entry. */
+static int ac_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
+                      float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, const Vec3 *rx_el,
+                      size_t nr, const Vec3 *tx_el, size_t nt, double f_a, float *out, hrt_stats *stats,
+                      double t_begin, const char *dev, const char *who)
 {
-    *el = (float *)malloc((nr + nt) * 3u * sizeof(float));
-    if (!*el) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-    float *e = *el;
+    int rc = ac_offsets_check(rx_el, nr, tx_el, nt, dev);
+    if (rc) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, who))) return rc;
+    float *e = (float *)malloc((nr + nt) * 3u * sizeof(float));
+    if (!e) return hrt_fail(HRT_E_NOMEM, "out of host memory");
     for (size_t i = 0; i < nr; ++i) { e[3 * i] = rx_el[i].x; e[3 * i + 1] = rx_el[i].y; e[3 * i + 2] = rx_el[i].z; }
     for (size_t j = 0; j < nt; ++j) {
         float *q = e + 3u * (nr + j);
@@ -461,7 +483,9 @@ static int ac_job_elements(ch_job *job, const Vec3 *rx_el, size_t nr, const Vec3
     job->nr = (uint32_t)nr;
     job->nt = (uint32_t)nt;
     job->fa = f_a;
-    return HRT_OK;
+    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, job, out, stats, t_begin);
+    free(e);
+    return rc;
 }
 
 int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
@@ -475,21 +499,14 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
     /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
     const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
     if ((rc = array_check(spec, &a))) return rc;
-    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_array_channel"))) return rc;
-    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
-                               "hrt_compute_array_channel")))
-        return rc;
     ch_job job;
     memset(&job, 0, sizeof job);
     job.spec = spec;
     job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
     job.scratch_bytes = ac_job_scratch;
     job.run = ac_job_run;
-    float *el = NULL;
-    if ((rc = ac_job_elements(&job, rx_el, nr, tx_el, nt, f_a, &el))) return rc;
-    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
-    free(el);
-    return rc;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_array_channel");
 }
 
 /* ------------------------------------------------------------------ impulse responses (hrt_taps) */
@@ -517,16 +534,11 @@ static int taps_spec_check(const hrt_taps_spec *spec, const char *who)
     return parts_check(spec->parts, who);
 }
 
-static int taps_check(const hrt_taps_spec *spec)
-{
-    return taps_spec_check(spec, "hrt_taps");
-}
-
 /* the tiling of one taps call: a pure function of the problem, the shard and the spec */
 static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, hrt_ktaps *K,
                      uint64_t *bytes)
 {
-    int rc = taps_check(spec);
+    int rc = taps_spec_check(spec, "hrt_taps");
     if (rc) return rc;
     memset(K, 0, sizeof *K);
     if ((rc = ps_view(p, s, spec->parts, "hrt_taps", &K->v))) return rc;
@@ -542,10 +554,8 @@ static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_sp
     K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     const uint64_t per_chunk = links * 2u * K->T * K->L * 8u;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
-        K->v.nchunks = ps_nchunks(links * K->rblocks * K->cblocks, HRT_TP_TARGET_GROUPS, K->v.num_local, per_chunk,
-                                  HRT_TP_PARTIAL_MAX, 65535u);
-    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
+    *bytes = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_TP_TARGET_GROUPS, per_chunk,
+                       HRT_TP_PARTIAL_MAX, 65535u);
     return HRT_OK;
 }
 
@@ -589,7 +599,7 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
                      hrt_stats *stats)
 {
     const double t_begin = hrt_now_s();
-    int rc = taps_check(spec);
+    int rc = taps_spec_check(spec, "hrt_taps");
     if (rc) return rc;
     if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, "hrt_compute_taps")))
         return rc;
@@ -624,11 +634,10 @@ static int at_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec
     memset(K, 0, sizeof *K);
     if ((rc = ps_view(p, s, spec->parts, "hrt_array_taps", &K->v))) return rc;
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
-    if (links * 2u * a->num_rx_elements * a->num_tx_elements * spec->num_times * spec->num_taps >= (1ull << 39))
-        return hrt_fail(HRT_E_INVALID, "hrt_array_taps: more than 2^39 outputs");
-    K->num_paths = s->num_paths;
-    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
-    K->nr = a->num_rx_elements; K->nt = a->num_tx_elements; K->npairs = K->nr * K->nt;
+    if ((rc = ac_fields(a, links, (uint64_t)spec->num_times * spec->num_taps, "hrt_array_taps", &K->nr, &K->nt,
+                        &K->npairs, &K->fa_c)))
+        return rc;
+    ps_shard(s, &K->sh);
     K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
     K->rows = K->npairs * K->T;
     K->rtiles = (4u * K->rows + 15u) / 16u;
@@ -640,12 +649,9 @@ static int at_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec
     K->rblocks = (K->rtiles + brows - 1u) / brows;
     K->cblocks = (K->ctiles + bcols - 1u) / bcols;
     K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
     const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->L * 8u;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
-        K->v.nchunks = ps_nchunks(links * K->rblocks * K->cblocks, HRT_AT_TARGET_GROUPS, K->v.num_local, per_chunk,
-                                  HRT_AT_PARTIAL_MAX, 65535u);
-    *bytes = ps_seg_bytes(&K->v) + K->v.nchunks * per_chunk;
+    *bytes = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_AT_TARGET_GROUPS, per_chunk,
+                       HRT_AT_PARTIAL_MAX, 65535u);
     return HRT_OK;
 }
 
@@ -701,21 +707,14 @@ int hrt_compute_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
     /* (the element pointers stand in for the device ones: at_check tests them for NULL only) */
     const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
     if ((rc = at_check(spec, &a))) return rc;
-    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_array_taps"))) return rc;
-    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
-                               "hrt_compute_array_taps")))
-        return rc;
     ch_job job;
     memset(&job, 0, sizeof job);
     job.spec = spec;
     job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_taps * 8u;
     job.scratch_bytes = at_job_scratch;
     job.run = at_job_run;
-    float *el = NULL;
-    if ((rc = ac_job_elements(&job, rx_el, nr, tx_el, nt, f_a, &el))) return rc;
-    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
-    free(el);
-    return rc;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_taps", "hrt_compute_array_taps");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */
@@ -782,16 +781,13 @@ static int pw_plan(const hrt_problem *p, const hrt_shard *s, const hrt_power_spe
     memset(K, 0, sizeof *K);
     if ((rc = ps_view(p, s, spec->parts, "hrt_power_profiles", &K->v))) return rc;
     if ((rc = power_links_check(K->v.nrx, K->v.ntx, spec))) return rc;
-    K->num_paths = s->num_paths;
-    K->rank = s->rank; K->count = s->count; K->chunk = s->chunk ? s->chunk : 4096u;
+    ps_shard(s, &K->sh);
     K->Ld = spec->num_delay_bins; K->Nth = spec->num_zenith_bins; K->Nph = spec->num_azimuth_bins;
     K->nbins = K->Ld + 2u * K->Nth * K->Nph;
     K->tau0 = spec->tau0_s; K->dtau = spec->dtau_s;
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     const uint64_t per_chunk = links * 2u * HRT_POWER_FIELDS * 8u;
-    if ((spec->parts & HRT_CHANNEL_SCATTER) && s->num_bounces > 0)
-        K->v.nchunks = ps_nchunks(links, HRT_PW_TARGET_GROUPS, K->v.num_local, per_chunk, HRT_PW_PARTIAL_MAX,
-                                  UINT32_MAX);
+    (void)ps_chunks(&K->v, spec->parts, links, HRT_PW_TARGET_GROUPS, per_chunk, HRT_PW_PARTIAL_MAX, UINT32_MAX);
     *off_total = align256(K->v.nchunks * per_chunk);
     *off_hist = *off_total + align256(links * 2u * 8u);
     *bytes = ps_seg_bytes(&K->v) + *off_hist + links * 2u * K->nbins * 8u;

@@ -31,8 +31,7 @@ extern "C" {
 
 typedef struct {
     hrt_kview v;
-    uint64_t num_paths;             /* the shard's N: departure directions from the global path */
-    uint32_t rank, count, chunk;
+    hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t nr, nt, npairs;        /* elements; npairs = nr * nt */
     uint32_t K, T, K1, rows;        /* rows = T * K1 */
     uint32_t pblocks, cblocks;      /* ceil(npairs / HRT_AC_PAIRS), ceil(rows / HRT_AC_GROWS) */

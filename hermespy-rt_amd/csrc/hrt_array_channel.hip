@@ -26,13 +26,9 @@
 
 #include "hrt_array_channel.h"
 #include "hrt_channel.h"
-#include "hrt_launch_dir.h"
 #include "hrt_pathsum.h"
 
 typedef float hrt_f32x16 __attribute__((ext_vector_type(16)));
-
-// record fields staged per record: te re, te im, tm re, tm im, tau, nu, u_rx (3), u_tx (3)
-#define HRT_AC_REC_FLOATS 12u
 
 __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const hrt_karray P)
 {
@@ -43,7 +39,7 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t h = lane >> 5, k2 = lane & 15u, rsub = (lane >> 4) & 1u;
 
-    __shared__ float sRec[HRT_AC_BATCH][HRT_AC_REC_FLOATS];
+    __shared__ float sRec[HRT_AC_BATCH][HRT_PS_REC_FLOATS];
     __shared__ float4 sU[HRT_AC_BATCH][HRT_AC_GROWS];        // a_te U, a_tm U (complex) of the block's rows g
     __shared__ float4 sV[HRT_AC_BATCH][HRT_CH_K2];           // (Re V, -Im V, Im V, Re V): B = u . half h
     __shared__ float sA[HRT_AC_BATCH][2][64];                // the A operand of every lane, per pair tile
@@ -53,13 +49,7 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
     if (tid < HRT_AC_PAIRS) {
         const uint32_t a = pb * HRT_AC_PAIRS + tid;
         float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (a < P.npairs) {
-            const uint32_t i = a / P.nt, j = a - i * P.nt;
-            for (int q = 0; q < 3; ++q) {
-                e[q] = P.rx_el[3u * i + q];
-                e[3 + q] = P.tx_el[3u * j + q];
-            }
-        }
+        if (a < P.npairs) load_pair(P.rx_el, P.tx_el, P.nt, a, e);
         for (int q = 0; q < 6; ++q) sEl[tid][q] = e[q];
     }
 
@@ -109,7 +99,10 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
         }
         if (n == 0) break;
         __syncthreads();
-        if (tid < n) {   // the record's fields and its departure direction
+        if (tid < n) {
+            // stage_record (csrc/hrt_pathsum.h), written out like the batch fill: through the helper the compiler
+            // hoists the field addresses differently and this kernel ran 2.0 % slower on C3 (1 866.7 against
+            // 1 830.6 ms, run-to-run spread 0.01 %); this form compiles to the instructions it had before
             const uint32_t rb = sB[tid], i = sI[tid];
             float *R = sRec[tid];
             R[0] = rec_field(V, rb, rx, HRT_REC_A_TE_RE)[i];
@@ -121,8 +114,7 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
             R[6] = rec_field(V, rb, rx, HRT_REC_DIRX)[i];
             R[7] = rec_field(V, rb, rx, HRT_REC_DIRY)[i];
             R[8] = rec_field(V, rb, rx, HRT_REC_DIRZ)[i];
-            const uint32_t local = hit_field(V, rb, HRT_HIT_RAY)[i] - tx * V.num_local;
-            const hrt_launch_dir_t d = hrt_launch_dir(hrt_shard_path(local, P.chunk, P.count, P.rank), P.num_paths);
+            const hrt_launch_dir_t d = hit_launch_dir(V, P.sh, rb, tx, i);
             R[9] = d.fx;
             R[10] = d.fy;
             R[11] = d.fz;
@@ -156,8 +148,7 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_array_partial_kernel(const
             const float *R = sRec[j], *E = sEl[q];
             float sn = 0.f, cs = 0.f;
             if (pb * HRT_AC_PAIRS + q < P.npairs) {
-                const double pr = (double)E[0] * R[6] + (double)E[1] * R[7] + (double)E[2] * R[8];
-                const double pt = (double)E[3] * R[9] + (double)E[4] * R[10] + (double)E[5] * R[11];
+                const double pr = dot3(E, R + 6), pt = dot3(E + 3, R + 9);   // r_i . u_rx, q_j . u_tx
                 sincospif(half_revs(P.fa_c * (pr + pt)), &sn, &cs);
             }
             float *A = sA[j][q >> 4];
@@ -231,20 +222,14 @@ __global__ void hrt_array_reduce_kernel(const hrt_karray P)
     const uint32_t pair = (uint32_t)(e / (2u * tk)), pol = (uint32_t)(e / tk) & 1u;
     const uint64_t col = e % tk;
 
-    float2 s = make_float2(0.f, 0.f);
     const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link +
                         ((uint64_t)pol * P.npairs + pair) * tk + col;
-    for (uint32_t c = 0; c < V.nchunks; ++c) {
-        const float2 v = src[(uint64_t)c * per_link];
-        s.x += v.x;
-        s.y += v.y;
-    }
+    float2 s = sum_chunks(src, V.nchunks, per_link);
     hrt_los_entry L;
     if (V.los && los_entry(V, link, L)) {
         const uint32_t i = pair / P.nt, j = pair - i * P.nt;
-        const float *r = P.rx_el + 3u * i, *q = P.tx_el + 3u * j;
-        const double pr = (double)r[0] * -L.ux + (double)r[1] * -L.uy + (double)r[2] * -L.uz;   // r_i . u_rx
-        const double pt = (double)q[0] * L.ux + (double)q[1] * L.uy + (double)q[2] * L.uz;      // q_j . u_tx
+        const float u_tx[3] = {L.ux, L.uy, L.uz}, u_rx[3] = {-L.ux, -L.uy, -L.uz};
+        const double pr = dot3(P.rx_el + 3u * i, u_rx), pt = dot3(P.tx_el + 3u * j, u_tx);
         const uint32_t m = (uint32_t)(col / P.K), k = (uint32_t)(col % P.K);
         const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
         float sn, cs;
@@ -252,13 +237,7 @@ __global__ void hrt_array_reduce_kernel(const hrt_karray P)
         s.x += L.a * cs;
         s.y += L.a * sn;
     }
-    float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
-    if (V.accumulate) {
-        const float2 v = o[0];
-        s.x += v.x;
-        s.y += v.y;
-    }
-    o[0] = s;
+    store_out(reinterpret_cast<float2 *>(P.out) + gid, s, V.accumulate);
 }
 
 extern "C" int hrt_hip_launch_array_channel(const hrt_karray *P, void *stream)

@@ -26,14 +26,10 @@
 #include <stdint.h>
 
 #include "hrt_array_taps.h"
-#include "hrt_launch_dir.h"
 #include "hrt_pathsum.h"
 #include "hrt_sinc.h"
 
 typedef float hrt_f32x4 __attribute__((ext_vector_type(4)));
-
-// record fields staged per record: te re, te im, tm re, tm im, tau, nu, u_rx (3), u_tx (3)
-#define HRT_AT_REC_FLOATS 12u
 
 // RT row tiles x CT column tiles per wave; the 4 waves of the block stand WR along the rows and 4 / WR along the
 // columns (the two forms of csrc/hrt_array_taps.h: <4, 4, 4> and <1, 4, 1>)
@@ -51,7 +47,7 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_array_taps_partial_kernel(
     const uint32_t kq = lane >> 4, col = lane & 15u;   // A / B operand: record 4 g + kq; row / tap `col` of a tile
 
     __shared__ float sU[HRT_TP_BATCH][BR * 4u];   // U of the block's rows g = 4 mm + q
-    __shared__ float sRec[HRT_TP_BATCH][HRT_AT_REC_FLOATS];
+    __shared__ float sRec[HRT_TP_BATCH][HRT_PS_REC_FLOATS];
     __shared__ sinc_rec sS[HRT_TP_BATCH];
     __shared__ uint32_t sB[HRT_TP_BATCH], sI[HRT_TP_BATCH];   // (bounce, hit) of the staged records
     __shared__ float sEl[BR][6];                               // r_i, q_j of the block's rows
@@ -63,11 +59,7 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_array_taps_partial_kernel(
         double t = 0.0;
         if (row < P.rows) {
             const uint32_t a = row / P.T, m = row - a * P.T;
-            const uint32_t i = a / P.nt, j = a - i * P.nt;
-            for (int q = 0; q < 3; ++q) {
-                e[q] = P.rx_el[3u * i + q];
-                e[3 + q] = P.tx_el[3u * j + q];
-            }
+            load_pair(P.rx_el, P.tx_el, P.nt, a, e);
             t = P.t0 + (double)m * P.dt;
         }
         for (int q = 0; q < 6; ++q) sEl[tid][q] = e[q];
@@ -96,6 +88,10 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_array_taps_partial_kernel(
             float *R = sRec[tid];
             sinc_rec q = {0, 0.f, 0.f};
             if (tid < n) {
+                // stage_record (csrc/hrt_pathsum.h), written out as in hrt_array_partial_kernel: through the helper
+                // the <1, 4, 1> form ran 1.4 % slower on C3 (8.30 against 8.19 ms, run-to-run spread 0.1 %) and whole
+                // calls of the <4, 4, 4> form 0.2 % (T = 64, L = 64: 1 034.9 against 1 032.6 ms, spread 0.06 %); this
+                // form compiles to the instructions the kernel had before
                 const uint32_t bb = sB[tid], i = sI[tid];
                 R[0] = rec_field(V, bb, rx, HRT_REC_A_TE_RE)[i];
                 R[1] = rec_field(V, bb, rx, HRT_REC_A_TE_IM)[i];
@@ -106,14 +102,13 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_array_taps_partial_kernel(
                 R[6] = rec_field(V, bb, rx, HRT_REC_DIRX)[i];
                 R[7] = rec_field(V, bb, rx, HRT_REC_DIRY)[i];
                 R[8] = rec_field(V, bb, rx, HRT_REC_DIRZ)[i];
-                const uint32_t local = hit_field(V, bb, HRT_HIT_RAY)[i] - tx * V.num_local;
-                const hrt_launch_dir_t d = hrt_launch_dir(hrt_shard_path(local, P.chunk, P.count, P.rank), P.num_paths);
+                const hrt_launch_dir_t d = hit_launch_dir(V, P.sh, bb, tx, i);
                 R[9] = d.fx;
                 R[10] = d.fy;
                 R[11] = d.fz;
                 q = sinc_prep(P.fs, R[4]);
             } else {
-                for (uint32_t f = 0; f < HRT_AT_REC_FLOATS; ++f) R[f] = 0.f;
+                for (uint32_t f = 0; f < HRT_PS_REC_FLOATS; ++f) R[f] = 0.f;
             }
             sS[tid] = q;
         }
@@ -124,8 +119,7 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_array_taps_partial_kernel(
             const float *R = sRec[j], *E = sEl[mm];
             float u0 = 0.f, u1 = 0.f, u2 = 0.f, u3 = 0.f;
             if (j < n && rb * BR + mm < P.rows) {
-                const double pr = (double)E[0] * R[6] + (double)E[1] * R[7] + (double)E[2] * R[8];
-                const double pt = (double)E[3] * R[9] + (double)E[4] * R[10] + (double)E[5] * R[11];
+                const double pr = dot3(E, R + 6), pt = dot3(E + 3, R + 9);   // r_i . u_rx, q_j . u_tx
                 float sn, cs;
                 sincospif(half_revs((double)R[5] * sT[mm] - P.fc * (double)R[4] + P.fa_c * (pr + pt)), &sn, &cs);
                 u0 = R[0] * cs - R[1] * sn;
@@ -181,20 +175,14 @@ __global__ void hrt_array_taps_reduce_kernel(const hrt_karray_taps P)
     const uint32_t link = (uint32_t)(gid / per_link);
     const uint64_t e = gid - (uint64_t)link * per_link;   // = (pair * 2 + pol) * tl + m * L + i
 
-    float2 s = make_float2(0.f, 0.f);
     const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link + e;
-    for (uint32_t c = 0; c < V.nchunks; ++c) {
-        const float2 v = src[(uint64_t)c * per_link];
-        s.x += v.x;
-        s.y += v.y;
-    }
+    float2 s = sum_chunks(src, V.nchunks, per_link);
     hrt_los_entry L;
     if (V.los && los_entry(V, link, L)) {   // a real: TE = TM
         const uint32_t pair = (uint32_t)(e / (2u * tl));
         const uint32_t i = pair / P.nt, j = pair - i * P.nt;
-        const float *r = P.rx_el + 3u * i, *q = P.tx_el + 3u * j;
-        const double pr = (double)r[0] * -L.ux + (double)r[1] * -L.uy + (double)r[2] * -L.uz;   // r_i . u_rx
-        const double pt = (double)q[0] * L.ux + (double)q[1] * L.uy + (double)q[2] * L.uz;      // q_j . u_tx
+        const float u_tx[3] = {L.ux, L.uy, L.uz}, u_rx[3] = {-L.ux, -L.uy, -L.uz};
+        const double pr = dot3(P.rx_el + 3u * i, u_rx), pt = dot3(P.tx_el + 3u * j, u_tx);
         const uint64_t mi = e % tl;
         const uint32_t m = (uint32_t)(mi / P.L), k = (uint32_t)(mi % P.L);
         const double t = P.t0 + (double)m * P.dt;
@@ -204,13 +192,7 @@ __global__ void hrt_array_taps_reduce_kernel(const hrt_karray_taps P)
         s.x += v * cs;
         s.y += v * sn;
     }
-    float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
-    if (V.accumulate) {
-        const float2 v = o[0];
-        s.x += v.x;
-        s.y += v.y;
-    }
-    o[0] = s;
+    store_out(reinterpret_cast<float2 *>(P.out) + gid, s, V.accumulate);
 }
 
 extern "C" int hrt_hip_launch_array_taps(const hrt_karray_taps *P, void *stream)

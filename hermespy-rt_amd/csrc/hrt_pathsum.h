@@ -1,7 +1,9 @@
 /* hrt_pathsum.h -- what the path-sum families (hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles) share: the view of the workspace of a finished hrt_trace that their kernels read (plain C, the
  * first member of hrt_kchannel, hrt_karray, hrt_ktaps, hrt_karray_taps and hrt_kpower; filled by csrc/host/channel.c)
- * and, for the .hip files, the device helpers that read it.
+ * and, for the .hip files, the device helpers that read it: the field accessors, the chunk ranges and the batch fill,
+ * the staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the
+ * array families, the LoS entry, and the two halves the complex reduce kernels share.
  *
  * Every family sums, per link (rx, tx), the LoS entry (shard rank 0 only) and the scatter records of the link's TX
  * segment in every hit block.  The records of a segment are cut into nchunks chunks; a partial kernel writes one
@@ -25,6 +27,15 @@ typedef struct {
     uint32_t *seg;                  /* scratch: [nb][ntx + 1] first hit of every TX segment */
 } hrt_kview;
 
+/* The shard of the trace, for the families that need a record's departure direction: the member right after v in
+ * hrt_karray, hrt_karray_taps and hrt_kpower.  20 bytes, 4-aligned (not padded to 24): the fields that follow it
+ * in those structs keep the kernel-argument offsets they had when these four were written out there (new offsets
+ * alone moved hrt_array_partial_kernel's SGPR spills and its time: profiles/HISTORY.md). */
+typedef struct {
+    uint64_t num_paths;             /* the shard's N: departure directions from the global path */
+    uint32_t rank, count, chunk;
+} __attribute__((packed, aligned(4))) hrt_kshard;
+
 /* hrt_channel_segments_kernel: V->seg[b][t] for every bounce b and t <= ntx */
 int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
 
@@ -36,6 +47,12 @@ int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
 #include <hip/hip_runtime.h>
 
 #include "hrt_device.h"
+#include "hrt_launch_dir.h"
+
+static_assert(sizeof(hrt_kshard) == 20 && sizeof(hrt_kview) % 8 == 0, "hrt_kshard: the offsets after it");
+
+// floats of a staged record (stage_record): te re, te im, tm re, tm im, tau, nu, u_rx (3), u_tx (3)
+#define HRT_PS_REC_FLOATS 12u
 
 namespace {
 
@@ -71,6 +88,77 @@ __device__ __forceinline__ void chunk_range(const hrt_kview &V, uint32_t b, uint
     const uint64_t n = s1 - s0;
     start = s0 + (uint32_t)(n * c / V.nchunks);
     end = s0 + (uint32_t)(n * (c + 1u) / V.nchunks);
+}
+
+// u_tx of hit i of block b, a ray of TX tx: the launch direction of the ray's global path (csrc/hrt_launch_dir.h)
+__device__ __forceinline__ hrt_launch_dir_t hit_launch_dir(const hrt_kview &V, const hrt_kshard &S, uint32_t b,
+                                                           uint32_t tx, uint32_t i)
+{
+    const uint32_t local = hit_field(V, b, HRT_HIT_RAY)[i] - tx * V.num_local;
+    return hrt_launch_dir(hrt_shard_path(local, S.chunk, S.count, S.rank), S.num_paths);
+}
+
+// The HRT_PS_REC_FLOATS floats of record i of hit block b at receiver rx into R (a caller that sums in FP64 widens
+// them itself): nu is the float difference FS0 - DFS, u_rx the record's HRT_REC_DIR.  The two MFMA kernels that stage
+// into LDS (hrt_array_partial_kernel, hrt_array_taps_partial_kernel) write these lines out: see there.
+__device__ __forceinline__ void stage_record(const hrt_kview &V, const hrt_kshard &S, uint32_t b, uint32_t rx,
+                                             uint32_t tx, uint32_t i, float *R)
+{
+    R[0] = rec_field(V, b, rx, HRT_REC_A_TE_RE)[i];
+    R[1] = rec_field(V, b, rx, HRT_REC_A_TE_IM)[i];
+    R[2] = rec_field(V, b, rx, HRT_REC_A_TM_RE)[i];
+    R[3] = rec_field(V, b, rx, HRT_REC_A_TM_IM)[i];
+    R[4] = rec_field(V, b, rx, HRT_REC_TAU)[i];
+    R[5] = __uint_as_float(hit_field(V, b, HRT_HIT_FS0)[i]) - rec_field(V, b, rx, HRT_REC_DFS)[i];
+    R[6] = rec_field(V, b, rx, HRT_REC_DIRX)[i];
+    R[7] = rec_field(V, b, rx, HRT_REC_DIRY)[i];
+    R[8] = rec_field(V, b, rx, HRT_REC_DIRZ)[i];
+    const hrt_launch_dir_t d = hit_launch_dir(V, S, b, tx, i);
+    R[9] = d.fx;
+    R[10] = d.fy;
+    R[11] = d.fz;
+}
+
+// e[0..2] = r_i, e[3..5] = q_j of element pair a = i nt + j (the sEl rows of the array kernels)
+__device__ __forceinline__ void load_pair(const float *rx_el, const float *tx_el, uint32_t nt, uint32_t a, float *e)
+{
+    const uint32_t i = a / nt, j = a - i * nt;
+    for (int q = 0; q < 3; ++q) {
+        e[q] = rx_el[3u * i + q];
+        e[3 + q] = tx_el[3u * j + q];
+    }
+}
+
+// r . u in FP64 from float operands.  The steering path difference of an element pair (metres) is
+// dot3(r_i, u_rx) + dot3(q_j, u_tx); the LoS term has u_rx = -u_tx.
+__device__ __forceinline__ double dot3(const float *r, const float *u)
+{
+    return (double)r[0] * u[0] + (double)r[1] * u[1] + (double)r[2] * u[2];
+}
+
+// The two halves the complex reduce kernels share (one float2 per thread; hrt_channel_reduce_kernel carries both
+// polarisations in a float4 and stores them T * K apart: it keeps its own).  The partial sums of one output, chunk
+// 0's at src and the chunks `stride` apart, added in index order ...
+__device__ __forceinline__ float2 sum_chunks(const float2 *src, uint32_t nchunks, uint64_t stride)
+{
+    float2 s = make_float2(0.f, 0.f);
+    for (uint32_t c = 0; c < nchunks; ++c) {
+        const float2 v = src[(uint64_t)c * stride];
+        s.x += v.x;
+        s.y += v.y;
+    }
+    return s;
+}
+
+// ... and the store: s, added to what is there if accumulate
+__device__ __forceinline__ void store_out(float2 *o, float2 s, uint32_t accumulate)
+{
+    if (accumulate) {
+        const float2 v = o[0];
+        s.x += v.x;
+        s.y += v.y;
+    }
+    o[0] = s;
 }
 
 // The LoS entry of a link: a (real, TE = TM), tau, nu (the path list's freq_shift) and u = directions_tx

@@ -32,8 +32,7 @@ extern "C" {
 
 typedef struct {
     hrt_kview v;
-    uint64_t num_paths;             /* the shard's N: departure directions from the global path */
-    uint32_t rank, count, chunk;
+    hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t Ld, Nth, Nph;          /* delay bins; zenith x azimuth bins (0: no spectra) */
     uint32_t nbins;                 /* Ld + 2 Nth Nph */
     double tau0, dtau;

@@ -24,7 +24,6 @@
 
 #include <stdint.h>
 
-#include "hrt_launch_dir.h"
 #include "hrt_pathsum.h"
 #include "hrt_power.h"
 
@@ -61,21 +60,17 @@ __device__ __forceinline__ double term_field(const pw_term &t, uint32_t pol, uin
 __device__ __forceinline__ void scatter_term(const hrt_kpower &P, uint32_t b, uint32_t rx, uint32_t tx, uint32_t i,
                                              pw_term &t)
 {
-    const hrt_kview &V = P.v;
-    const double ter = rec_field(V, b, rx, HRT_REC_A_TE_RE)[i], tei = rec_field(V, b, rx, HRT_REC_A_TE_IM)[i];
-    const double tmr = rec_field(V, b, rx, HRT_REC_A_TM_RE)[i], tmi = rec_field(V, b, rx, HRT_REC_A_TM_IM)[i];
+    float R[HRT_PS_REC_FLOATS];
+    stage_record(P.v, P.sh, b, rx, tx, i, R);
+    const double ter = R[0], tei = R[1], tmr = R[2], tmi = R[3];
     t.p[0] = ter * ter + tei * tei;
     t.p[1] = tmr * tmr + tmi * tmi;
-    t.tau = rec_field(V, b, rx, HRT_REC_TAU)[i];
-    t.nu = (double)(__uint_as_float(hit_field(V, b, HRT_HIT_FS0)[i]) - rec_field(V, b, rx, HRT_REC_DFS)[i]);
-    t.ur[0] = rec_field(V, b, rx, HRT_REC_DIRX)[i];
-    t.ur[1] = rec_field(V, b, rx, HRT_REC_DIRY)[i];
-    t.ur[2] = rec_field(V, b, rx, HRT_REC_DIRZ)[i];
-    const uint32_t local = hit_field(V, b, HRT_HIT_RAY)[i] - tx * V.num_local;
-    const hrt_launch_dir_t d = hrt_launch_dir(hrt_shard_path(local, P.chunk, P.count, P.rank), P.num_paths);
-    t.ut[0] = d.fx;
-    t.ut[1] = d.fy;
-    t.ut[2] = d.fz;
+    t.tau = R[4];
+    t.nu = R[5];
+    for (int q = 0; q < 3; ++q) {
+        t.ur[q] = R[6 + q];
+        t.ut[q] = R[9 + q];
+    }
 }
 
 // the LoS entry of a link as a term (false where there is none: blocked)

@@ -142,13 +142,8 @@ __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
     const uint32_t link = (uint32_t)(gid / per_link);
     const uint64_t e = gid - (uint64_t)link * per_link;   // = pol * tl + m * L + i
 
-    float2 s = make_float2(0.f, 0.f);
     const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link + e;
-    for (uint32_t c = 0; c < V.nchunks; ++c) {
-        const float2 v = src[(uint64_t)c * per_link];
-        s.x += v.x;
-        s.y += v.y;
-    }
+    float2 s = sum_chunks(src, V.nchunks, per_link);
     hrt_los_entry L;
     if (V.los && los_entry(V, link, L)) {   // a real: TE = TM
         const uint64_t mi = e % tl;
@@ -160,13 +155,7 @@ __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
         s.x += v * cs;
         s.y += v * sn;
     }
-    float2 *o = reinterpret_cast<float2 *>(P.out) + gid;
-    if (V.accumulate) {
-        const float2 v = o[0];
-        s.x += v.x;
-        s.y += v.y;
-    }
-    o[0] = s;
+    store_out(reinterpret_cast<float2 *>(P.out) + gid, s, V.accumulate);
 }
 
 extern "C" int hrt_hip_launch_taps(const hrt_ktaps *P, void *stream)

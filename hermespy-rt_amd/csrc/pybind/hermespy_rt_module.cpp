@@ -248,8 +248,49 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
-// the call of a compute_channel / compute_array_channel / compute_taps entry (`name`): the scene loaded and freed
-// around `call` without the GIL; a refused argument raises ValueError, any other error RuntimeError
+// What the five path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
+// compute_power_profiles) share.  The counts and the four position / velocity arguments, checked ...
+struct endpoints {
+    const Vec3 *rxp, *txp, *rxv, *txv;
+    endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
+              const farr &tx_velocities, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+              unsigned long num_bounces)
+    {
+        if (!num_rx || !num_tx || !num_paths || !num_bounces)
+            throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+        rxp = as_vec3(rx_positions, num_rx, "rx_positions");
+        txp = as_vec3(tx_positions, num_tx, "tx_positions");
+        rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
+        txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
+    }
+};
+
+// ... the element arguments of the two array entries, and whether Nr * Nt * grid points are within the library's
+// limits (an output it would refuse is not allocated), the `parts` word ...
+struct array_elements {
+    const Vec3 *rxe, *txe;
+    size_t nr, nt;
+    array_elements(const farr &rx_elements, const farr &tx_elements)
+        : rxe(reinterpret_cast<const Vec3 *>(rx_elements.data())),
+          txe(reinterpret_cast<const Vec3 *>(tx_elements.data())), nr((size_t)rx_elements.size() / 3),
+          nt((size_t)tx_elements.size() / 3)
+    {
+        if (rx_elements.size() % 3 || tx_elements.size() % 3)
+            throw std::invalid_argument("rx_elements and tx_elements must have shape (n, 3)");
+    }
+    bool fits(unsigned long long grid) const
+    {
+        const unsigned long long pts = (unsigned long long)nr * nt * grid;
+        return pts > 0 && pts <= (1ull << 24) && nr <= 1024 && nt <= 1024;
+    }
+};
+
+uint32_t parts_word(bool los, bool scatter)
+{
+    return (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+}
+
+// ... and the call of the entry (`name`): the scene loaded and freed around `call` without the GIL; a refused argument raises ValueError, any other error RuntimeError
 template <typename F>
 void run_pathsum(const char *name, const std::string &mesh_filepath, F call)
 {
@@ -276,25 +317,20 @@ py::array_t<std::complex<float>> compute_channel_py(
     unsigned long num_bounces, double f0, double df, unsigned long num_freqs, double t0, double dt,
     unsigned long num_times, bool los, bool scatter)
 {
-    if (!num_rx || !num_tx || !num_paths || !num_bounces)
-        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
         throw std::invalid_argument("num_freqs and num_times must fit 32 bits");
-    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
-    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
-    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
-    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
     check_scene_file(mesh_filepath);
     hrt_channel_spec spec{};
     spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
     spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
-    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    spec.parts = parts_word(los, scatter);
     // (the library validates the spec before it traces anything: a refused one raises ValueError)
     py::array_t<std::complex<float>> out({(size_t)num_rx, (size_t)num_tx, (size_t)2, (size_t)num_times,
                                           (size_t)num_freqs});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
     run_pathsum("compute_channel", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_channel(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+        return hrt_compute_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                    num_bounces, &spec, dst, nullptr);
     });
     return out;
@@ -309,36 +345,26 @@ py::array_t<std::complex<float>> compute_array_channel_py(
     unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
     double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency)
 {
-    if (!num_rx || !num_tx || !num_paths || !num_bounces)
-        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
         throw std::invalid_argument("num_freqs and num_times must fit 32 bits");
-    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
-    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
-    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
-    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
-    if (rx_elements.size() % 3 || tx_elements.size() % 3)
-        throw std::invalid_argument("rx_elements and tx_elements must have shape (n, 3)");
-    const size_t nr = (size_t)rx_elements.size() / 3, nt = (size_t)tx_elements.size() / 3;
+    const array_elements a(rx_elements, tx_elements);
     const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
     check_scene_file(mesh_filepath);
     hrt_channel_spec spec{};
     spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
     spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
-    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    spec.parts = parts_word(los, scatter);
     // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
     // beyond the 2^24 points of the limit would be refused, so only one within it is allocated.)
-    const unsigned long long pts = (unsigned long long)nr * nt * num_times * num_freqs;
-    const bool fits = pts > 0 && pts <= (1ull << 24) && nr <= 1024 && nt <= 1024;
-    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, nr, nt, (size_t)2,
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, a.nr, a.nt, (size_t)2,
                                                                     (size_t)num_times, (size_t)num_freqs}
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
-    const Vec3 *rxe = reinterpret_cast<const Vec3 *>(rx_elements.data());
-    const Vec3 *txe = reinterpret_cast<const Vec3 *>(tx_elements.data());
     run_pathsum("compute_array_channel", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_array_channel(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
-                                         num_bounces, &spec, rxe, nr, txe, nt, fa, dst, nullptr);
+        return hrt_compute_array_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                         num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
     });
     return out;
 }
@@ -353,22 +379,17 @@ py::array_t<std::complex<float>> compute_taps_py(
     unsigned long num_bounces, double sampling_rate, unsigned long num_taps, long l_min, py::object center_frequency,
     double t0, double dt, unsigned long num_times, bool los, bool scatter)
 {
-    if (!num_rx || !num_tx || !num_paths || !num_bounces)
-        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
         throw std::invalid_argument("num_taps and num_times must fit 32 bits");
     if (l_min < -(1L << 30) || l_min > (1L << 30))
         throw py::value_error("hermespy_rt.compute_taps: tap indices l_min outside +-2^24");
-    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
-    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
-    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
-    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
     const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
     check_scene_file(mesh_filepath);
     hrt_taps_spec spec{};
     spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
     spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)num_times;
-    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    spec.parts = parts_word(los, scatter);
     // (the library validates the spec before it traces anything: a refused one raises ValueError; an output too
     // large for its limits is not allocated)
     const bool fits = num_taps && num_times && (uint64_t)num_taps * num_times <= (1ull << 20);
@@ -377,7 +398,7 @@ py::array_t<std::complex<float>> compute_taps_py(
                                               : std::vector<size_t>{(size_t)1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
     run_pathsum("compute_taps", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_taps(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
+        return hrt_compute_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
                                 &spec, dst, nullptr);
     });
     return out;
@@ -394,40 +415,29 @@ py::array_t<std::complex<float>> compute_array_taps_py(
     long l_min, py::object center_frequency, double t0, double dt, unsigned long num_times, bool los, bool scatter,
     py::object array_frequency)
 {
-    if (!num_rx || !num_tx || !num_paths || !num_bounces)
-        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
         throw std::invalid_argument("num_taps and num_times must fit 32 bits");
     if (l_min < -(1L << 30) || l_min > (1L << 30))
         throw py::value_error("hermespy_rt.compute_array_taps: tap indices l_min outside +-2^24");
-    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
-    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
-    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
-    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
-    if (rx_elements.size() % 3 || tx_elements.size() % 3)
-        throw std::invalid_argument("rx_elements and tx_elements must have shape (n, 3)");
-    const size_t nr = (size_t)rx_elements.size() / 3, nt = (size_t)tx_elements.size() / 3;
+    const array_elements a(rx_elements, tx_elements);
     const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
     const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
     check_scene_file(mesh_filepath);
     hrt_taps_spec spec{};
     spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
     spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)num_times;
-    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    spec.parts = parts_word(los, scatter);
     // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
     // beyond the limits would be refused, so only one within them is allocated.)
-    const unsigned long long pts = (unsigned long long)nr * nt * num_times * num_taps;
-    const bool fits = pts > 0 && pts <= (1ull << 24) && (uint64_t)num_taps * num_times <= (1ull << 20) && nr <= 1024 &&
-                      nt <= 1024;
-    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, nr, nt, (size_t)2,
+    const bool fits = a.fits((unsigned long long)num_times * num_taps) && (uint64_t)num_taps * num_times <= (1ull << 20);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, a.nr, a.nt, (size_t)2,
                                                                     (size_t)num_times, (size_t)num_taps}
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
-    const Vec3 *rxe = reinterpret_cast<const Vec3 *>(rx_elements.data());
-    const Vec3 *txe = reinterpret_cast<const Vec3 *>(tx_elements.data());
     run_pathsum("compute_array_taps", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_array_taps(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
-                                      num_bounces, &spec, rxe, nr, txe, nt, fa, dst, nullptr);
+        return hrt_compute_array_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                      num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
     });
     return out;
 }
@@ -442,21 +452,16 @@ py::dict compute_power_profiles_py(
     unsigned long num_bounces, double tau0, double dtau, unsigned long num_delay_bins, unsigned long num_zenith_bins,
     unsigned long num_azimuth_bins, bool los, bool scatter)
 {
-    if (!num_rx || !num_tx || !num_paths || !num_bounces)
-        throw std::invalid_argument("num_rx, num_tx, num_paths, num_bounces must be > 0");
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_delay_bins > 0xffffffffUL || num_zenith_bins > 0xffffffffUL || num_azimuth_bins > 0xffffffffUL)
         throw py::value_error("hermespy_rt.compute_power_profiles: num_delay_bins, num_zenith_bins and "
                               "num_azimuth_bins must fit 32 bits");
-    const Vec3 *rxp = as_vec3(rx_positions, num_rx, "rx_positions");
-    const Vec3 *txp = as_vec3(tx_positions, num_tx, "tx_positions");
-    const Vec3 *rxv = as_vec3(rx_velocities, num_rx, "rx_velocities");
-    const Vec3 *txv = as_vec3(tx_velocities, num_tx, "tx_velocities");
     check_scene_file(mesh_filepath);
     hrt_power_spec spec{};
     spec.tau0_s = tau0; spec.dtau_s = dtau;
     spec.num_delay_bins = (uint32_t)num_delay_bins;
     spec.num_zenith_bins = (uint32_t)num_zenith_bins; spec.num_azimuth_bins = (uint32_t)num_azimuth_bins;
-    spec.parts = (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
+    spec.parts = parts_word(los, scatter);
     // (the library validates the spec before it traces anything: a refused one raises ValueError; an output beyond
     // its limits is not allocated)
     const size_t links = (size_t)num_rx * num_tx, Ld = spec.num_delay_bins;
@@ -467,7 +472,7 @@ py::dict compute_power_profiles_py(
     py::array_t<double> buf(fits ? (size_t)n : (size_t)1);
     double *dst = buf.mutable_data();
     run_pathsum("compute_power_profiles", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_power_profiles(scene, rxp, txp, rxv, txv, carrier_frequency, num_rx, num_tx, num_paths,
+        return hrt_compute_power_profiles(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                           num_bounces, &spec, dst, nullptr);
     });
     const size_t lp = links * 2u, o1 = lp * HRT_POWER_FIELDS, o2 = o1 + lp * Ld, o3 = o2 + lp * Nth * Nph;

@@ -380,7 +380,7 @@ class Tracer:
     # ------------------------------------------------------------------ channel
     def _pathsum_buffers(self, shape, need, out, accumulate, cache, dtype=None):
         """The output (`out` checked, or a new tensor of `dtype`, default complex64), the scratch cache named `cache`
-        grown to `need` bytes and the current stream of one channel / array_channel / taps / power_profiles call."""
+        grown to `need` bytes and the current stream of one path-sum call (_pathsum)."""
         torch = self.torch
         dtype = torch.complex64 if dtype is None else dtype
         with torch.cuda.device(self.device):
@@ -398,6 +398,44 @@ class Tracer:
                 setattr(self, cache, scratch)
         return out, scratch, torch.cuda.current_stream(self.device)
 
+    def _pathsum(self, name, spec, shape, cache, out, accumulate, arrays=None, dtype=None, value_error=True):
+        """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps or
+        hrt_power_profiles): the scratch query, the buffers (scratch cache `cache`) and the entry on the current
+        stream.  `arrays`: what _elements prepared for the two array families.  A spec the library refuses raises
+        ValueError, or HrtError where value_error is False."""
+        extra = () if arrays is None else (C.byref(arrays[0]),)
+        need = C.c_uint64(0)
+        rc = getattr(self.L, name + "_scratch_bytes")(self.problem, C.byref(self.shard), C.byref(spec), *extra,
+                                                      C.byref(need))
+        if rc == -1 and value_error:
+            raise ValueError(name + ": " + self.L.hrt_last_error().decode())
+        _lib.check(rc, name + "_scratch_bytes")
+        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, cache, dtype)
+        _lib.check(getattr(self.L, name)(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
+                                         C.byref(spec), *extra, C.c_void_p(scratch.data_ptr()),
+                                         C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
+                                         1 if accumulate else 0, C.c_void_p(stream.cuda_stream)), name)
+        if arrays is not None:
+            arrays[1].record_stream(stream)   # (the kernels read the offsets after this call returns)
+        return out
+
+    def _elements(self, rx_elements, tx_elements, array_frequency):
+        """The element arguments of an array call, checked -> (Nr, Nt, upload): upload() puts the offsets on the
+        device and returns the (ArraySpec, device tensor it points into) that _pathsum takes."""
+        re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
+        te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
+        if not (np.isfinite(re).all() and np.isfinite(te).all()):
+            raise ValueError("element offsets must be finite")
+        nr, nt = re.shape[0], te.shape[0]
+        fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
+
+        def upload():
+            with self.torch.cuda.device(self.device):
+                d_el = self.torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
+            return abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa), d_el
+
+        return nr, nt, upload
+
     def channel(self, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
                 accumulate=False):
         """Channel frequency response of the last trace, formed on the device (hrt_channel):
@@ -411,17 +449,8 @@ class Tracer:
         accumulate=True.  The error word is read first (counts()): a void step is traced again."""
         self.counts()
         spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
-        need = C.c_uint64(0)
-        _lib.check(self.L.hrt_channel_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need)),
-                   "hrt_channel_scratch_bytes")
         shape = (self.nrx, self.ntx, 2, int(num_times), int(num_freqs))
-        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_ch_scratch")
-        _lib.check(self.L.hrt_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
-                                      C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
-                                      C.c_void_p(out.data_ptr()), 1 if accumulate else 0,
-                                      C.c_void_p(stream.cuda_stream)),
-                   "hrt_channel")
-        return out
+        return self._pathsum("hrt_channel", spec, shape, "_ch_scratch", out, accumulate, value_error=False)
 
     def array_channel(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
                       scatter=True, array_frequency=None, out=None, accumulate=False):
@@ -436,33 +465,11 @@ class Tracer:
         direction (directions_tx for LoS, the launch direction of the ray for a scatter record).  Returns a complex64
         tensor [nrx, ntx, Nr, Nt, 2, num_times, num_freqs] on the device, enqueued on the current stream; `out` is
         written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
-        torch = self.torch
-        re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
-        te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
-        if not (np.isfinite(re).all() and np.isfinite(te).all()):
-            raise ValueError("element offsets must be finite")
-        nr, nt = re.shape[0], te.shape[0]
-        fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
         spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
         self.counts()
-        with torch.cuda.device(self.device):
-            d_el = torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
-        arr = abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa)
-        need = C.c_uint64(0)
-        rc = self.L.hrt_array_channel_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(arr),
-                                                    C.byref(need))
-        if rc == -1:
-            raise ValueError("hrt_array_channel: " + self.L.hrt_last_error().decode())
-        _lib.check(rc, "hrt_array_channel_scratch_bytes")
         shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_freqs))
-        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_ac_scratch")
-        _lib.check(self.L.hrt_array_channel(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
-                                            C.byref(spec), C.byref(arr), C.c_void_p(scratch.data_ptr()),
-                                            C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
-                                            1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
-                   "hrt_array_channel")
-        d_el.record_stream(stream)   # (the kernels read the offsets after this call returns)
-        return out
+        return self._pathsum("hrt_array_channel", spec, shape, "_ac_scratch", out, accumulate, upload())
 
     def taps(self, fs, num_taps, l_min=0, fc=None, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
              accumulate=False):
@@ -478,18 +485,8 @@ class Tracer:
         fc = self.f_ghz * 1e9 if fc is None else float(fc)
         spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
         self.counts()
-        need = C.c_uint64(0)
-        rc = self.L.hrt_taps_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need))
-        if rc == -1:
-            raise ValueError("hrt_taps: " + self.L.hrt_last_error().decode())
-        _lib.check(rc, "hrt_taps_scratch_bytes")
         shape = (self.nrx, self.ntx, 2, int(num_times), int(num_taps))
-        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_tp_scratch")
-        _lib.check(self.L.hrt_taps(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()), C.byref(spec),
-                                   C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch.numel()),
-                                   C.c_void_p(out.data_ptr()), 1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
-                   "hrt_taps")
-        return out
+        return self._pathsum("hrt_taps", spec, shape, "_tp_scratch", out, accumulate)
 
     def array_taps(self, rx_elements, tx_elements, fs, num_taps, l_min=0, fc=None, t0=0.0, dt=0.0, num_times=1,
                    los=True, scatter=True, array_frequency=None, out=None, accumulate=False):
@@ -504,34 +501,12 @@ class Tracer:
         the carrier.  The paths, parts and directions are those of array_channel().  Returns a complex64 tensor
         [nrx, ntx, Nr, Nt, 2, num_times, num_taps] on the device, enqueued on the current stream; `out` is written in
         place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
-        torch = self.torch
-        re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
-        te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
-        if not (np.isfinite(re).all() and np.isfinite(te).all()):
-            raise ValueError("element offsets must be finite")
-        nr, nt = re.shape[0], te.shape[0]
-        fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
         fc = self.f_ghz * 1e9 if fc is None else float(fc)
         spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
         self.counts()
-        with torch.cuda.device(self.device):
-            d_el = torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
-        arr = abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa)
-        need = C.c_uint64(0)
-        rc = self.L.hrt_array_taps_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(arr),
-                                                 C.byref(need))
-        if rc == -1:
-            raise ValueError("hrt_array_taps: " + self.L.hrt_last_error().decode())
-        _lib.check(rc, "hrt_array_taps_scratch_bytes")
         shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_taps))
-        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_at_scratch")
-        _lib.check(self.L.hrt_array_taps(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
-                                         C.byref(spec), C.byref(arr), C.c_void_p(scratch.data_ptr()),
-                                         C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
-                                         1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
-                   "hrt_array_taps")
-        d_el.record_stream(stream)   # (the kernels read the offsets after this call returns)
-        return out
+        return self._pathsum("hrt_array_taps", spec, shape, "_at_scratch", out, accumulate, upload())
 
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
@@ -548,18 +523,9 @@ class Tracer:
         .summarize turns the moments into gains, spreads and K-factors.  Invalid arguments raise ValueError."""
         spec = abi.power_spec(tau0, dtau, num_delay_bins, num_zenith_bins, num_azimuth_bins, los, scatter)
         self.counts()
-        need = C.c_uint64(0)
-        rc = self.L.hrt_power_profiles_scratch_bytes(self.problem, C.byref(self.shard), C.byref(spec), C.byref(need))
-        if rc == -1:
-            raise ValueError("hrt_power_profiles: " + self.L.hrt_last_error().decode())
-        _lib.check(rc, "hrt_power_profiles_scratch_bytes")
         shape = (abi.power_out_doubles(self.nrx, self.ntx, spec),)
-        out, scratch, stream = self._pathsum_buffers(shape, need, out, accumulate, "_pw_scratch", self.torch.float64)
-        _lib.check(self.L.hrt_power_profiles(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
-                                             C.byref(spec), C.c_void_p(scratch.data_ptr()),
-                                             C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
-                                             1 if accumulate else 0, C.c_void_p(stream.cuda_stream)),
-                   "hrt_power_profiles")
+        out = self._pathsum("hrt_power_profiles", spec, shape, "_pw_scratch", out, accumulate,
+                            dtype=self.torch.float64)
         return abi.power_views(out, self.nrx, self.ntx, spec)
 
     # ------------------------------------------------------------------ dense (host) view

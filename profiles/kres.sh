@@ -1,8 +1,10 @@
 #!/bin/bash
-# kernel resource usage of hrt_kernels.hip (VGPRs, SGPRs, scratch, occupancy) -- compile-only, no GPU
+# kernel resource usage (VGPRs, SGPRs, LDS, scratch, occupancy) of the given files of csrc/ (default:
+# hrt_kernels.hip), e.g. profiles/kres.sh hrt_channel.hip hrt_power.hip -- compile-only, no GPU
 cd "$(dirname "$0")/../hermespy-rt_amd"
+for f in "${@:-hrt_kernels.hip}"; do
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -fno-slp-vectorize -I../include -Icsrc $EXTRA \
-  -c csrc/hrt_kernels.hip -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
+  -c "csrc/$f" -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re
 cur=None
 for l in sys.stdin:
@@ -18,3 +20,4 @@ for l in sys.stdin:
         cur+=' '+t.replace(' [bytes/lane]','').replace(' [waves/SIMD]','').replace(' [bytes/block]','')
 if cur: print(cur)
 "
+done

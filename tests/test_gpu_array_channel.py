@@ -5,7 +5,6 @@ hermespy_rt.compute_array_channel) against float64 numpy sums over the same floa
 
 u_rx: Tracer.paths()' direction_rx (LoS: -HRT_LOS_DIR); u_tx: hrt_launch_dirs_host of the record's global path
 (LoS: HRT_LOS_DIR).  Tolerance per (link, i, j, pol), over all (m, k): |H - H64| <= 1e-5 * sum_p |a_p^pol|."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -13,52 +12,15 @@ import sys
 import numpy as np
 import pytest
 
-from hermespy_rt_amd import lib
-
 from . import configs as K
 from . import scenes_gen as G
-from .test_gpu_channel import DF, _cfg, _grid, _tracer
+from . import planted as PL
+from .pathsum_util import ARRAY_CASES as CASES
+from .pathsum_util import C0, DF, _cfg, _geometries, _grid, _lam, _tracer, _ula, _upa
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C0 = 299792458.0
-
-
-def _lam(c):
-    return C0 / (c["f_ghz"] * 1e9)
-
-
-def _ula(n, d, axis=1):
-    e = np.zeros((n, 3))
-    e[:, axis] = np.arange(n) * d
-    return e
-
-
-def _upa(n1, n2, d):
-    e = np.zeros((n1 * n2, 3))
-    e[:, 0] = np.repeat(np.arange(n1), n2) * d
-    e[:, 2] = np.tile(np.arange(n2), n1) * d
-    return e
-
-
-def _random(n, radius, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(-radius, radius, (n, 3)) / np.sqrt(3.0)
-
-
-def _geometries(c):
-    lam = _lam(c)
-    return [("ula2_upa3x5", _ula(2, lam / 2), _upa(3, 5, lam / 2)),
-            ("random7_ula2", _random(7, 4 * lam, 11), _ula(2, lam / 2, axis=0))]
-
-
-def _launch_dirs(tr):
-    """departure directions of every global path (host libm: the reference's floats)"""
-    s = lib.Shard(tr.num_paths, 0, 1, 0, tr.nb)
-    d = np.empty((tr.num_paths, 3), np.float32)
-    lib.check(tr.L.hrt_launch_dirs_host(C.byref(s), d.ctypes.data_as(C.POINTER(C.c_float)), 0))
-    return d
 
 
 def _sum(H, S, link, a_te, a_tm, tau, nu, urx, utx, rxe, txe, fa, f, t, chunk=512):
@@ -86,7 +48,7 @@ def _reference_ft(tr, f, t, rxe, txe, fa, los=True, scatter=True):
     if scatter:
         P = {k: v.cpu().numpy() for k, v in tr.paths(nonzero_only=False).items()}
         ub = P["unblocked"]
-        dirs = _launch_dirs(tr)
+        dirs = PL.launch_dirs(tr).astype(np.float32)
         for rx in range(tr.nrx):
             for tx in range(tr.ntx):
                 s = (P["rx"] == rx) & (P["tx"] == tx) & ub
@@ -123,15 +85,6 @@ def _check(got, H, S):
     err = np.abs(got.astype(np.complex128) - H).reshape(*H.shape[:5], -1).max(axis=-1)   # (rx, tx, i, j, pol)
     bound = 1e-5 * S[:, :, None, None, :] + 1e-30
     assert (err <= bound).all(), (err / np.maximum(S[:, :, None, None, :], 1e-30)).max()
-
-
-CASES = [
-    ("C1", None, 1, 100),
-    ("C3", 20000, 1, 257),
-    ("C4_DOPPLER", 4000, 4, 100),
-    ("COINCIDENT", 8000, 1, 64),
-    ("IN_PLANE_canyon", None, 1, 100),
-]
 
 
 @pytest.mark.parametrize("name,n,nt,nk", CASES, ids=[c[0] for c in CASES])

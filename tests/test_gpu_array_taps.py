@@ -23,10 +23,9 @@ from hermespy_rt_amd import abi
 from . import configs as K
 from . import planted as PL
 from . import scenes_gen as G
-from .test_gpu_array_channel import CASES, C0, _geometries, _lam, _launch_dirs, _ula, _upa
-from .test_gpu_channel import _cfg, _tracer
-from .test_gpu_pathsum_planted import CONFIGS, PARTS, _bits, _expect_failure, _force_los_classes, _traced
-from .test_gpu_taps import FS, _los_status
+from .pathsum_util import ARRAY_CASES as CASES
+from .pathsum_util import (C0, CONFIGS, FS, PARTS, _bits, _cfg, _expect_failure, _force_los_classes, _geometries, _lam,
+                           _los_status, _traced, _tracer, _ula, _upa)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,7 +61,7 @@ def _reference_lt(tr, fs, l, t, rxe, txe, fa=None, fc=None, los=True, scatter=Tr
     if scatter:
         P = {k: v.cpu().numpy() for k, v in tr.paths(nonzero_only=False).items()}
         ub = P["unblocked"]
-        dirs = _launch_dirs(tr)
+        dirs = PL.launch_dirs(tr).astype(np.float32)
         for rx in range(tr.nrx):
             for tx in range(tr.ntx):
                 s = (P["rx"] == rx) & (P["tx"] == tx) & ub

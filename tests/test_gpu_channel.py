@@ -16,21 +16,11 @@ from oracle import oracle
 
 from . import configs as K
 from . import scenes_gen as G
+from .pathsum_util import DF, _cfg, _grid, _tracer
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DF = 30e3
-
-
-def _tracer(c, **kw):
-    from hermespy_rt_amd.device import Tracer
-    return Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"],
-                  c["num_paths"], c["num_bounces"], **kw)
-
-
-def _grid(c, nk):
-    return c["f_ghz"] * 1e9 - (nk // 2) * DF   # f0: an OFDM grid of nk subcarriers around the carrier
 
 
 def _phase_sum(H, S, rx, tx, a_te, a_tm, tau, nu, f, t, chunk=1024):
@@ -98,11 +88,6 @@ CASES = [
     ("COINCIDENT", 8000, 1, [1000]),
     ("IN_PLANE_canyon", None, 1, [7, 1000]),
 ]
-
-
-def _cfg(name, n):
-    c = K.IN_PLANE["canyon"] if name == "IN_PLANE_canyon" else K.ALL[name]
-    return K.small(c, n) if n else c
 
 
 @pytest.mark.parametrize("name,n,nt,ks", CASES, ids=[c[0] for c in CASES])

@@ -24,43 +24,13 @@ from hermespy_rt_amd import abi
 
 from . import configs as K
 from . import planted as PL
-from . import scenes_gen as G
-from .test_gpu_power import _check as power_check
-from .test_gpu_power import _reference as power_reference
+from .pathsum_util import CONFIGS, PARTS, _bits, _expect_failure, _force_los_classes, _traced, _tracer, power_check, power_reference
 
 pytestmark = pytest.mark.gpu
 
 UNIT_TOL = 0.05
 HIST_TOL = 1e-3
 PW_LDS_MAX = 80 << 10   # csrc/hrt_power.h HRT_PW_LDS_MAX: the hist kernel's LDS form up to this many bytes of bins
-PARTS = ((True, True), (True, False), (False, True))
-
-
-def _tracer(c, **kw):
-    from hermespy_rt_amd.device import Tracer
-    return Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"],
-                  c["num_paths"], c["num_bounces"], **kw)
-
-
-def _room(tmp_path_factory):
-    p = str(tmp_path_factory.mktemp("planted") / "room.hrt")
-    G.room_with_clutter(p, 120, seed=5)
-    return G.cfg(p, [[3.0, 2.0, 1.5], [-5.0, 4.0, 2.0]], [[-10.0, -6.0, 3.0], [12.0, 5.0, 4.0]], 6000, 3,
-                 tx_vel=[[1.0, 0.0, 0.0], [0.0, -2.0, 0.0]])
-
-
-CONFIGS = {"C3": lambda f: K.small(K.C3, 20000), "C4_DOPPLER": lambda f: K.small(K.C4_DOPPLER, 4000),
-           "COINCIDENT": lambda f: K.small(K.COINCIDENT, 8000), "room": _room}
-
-
-def _traced(name, tmp_path_factory, **kw):
-    c = CONFIGS[name](tmp_path_factory)
-    tr = _tracer(c, **kw)
-    if name == "room":
-        assert tr.num_tri > 1024   # the live list is re-sorted between bounces
-    tr.trace()
-    tr.torch.cuda.synchronize(tr.device)
-    return tr, c
 
 
 def _sel(T, los, scatter):
@@ -73,22 +43,6 @@ def _t(nt, t0=0.0, dt=PL.DT):
 
 def _np(x):
     return x.cpu().numpy()
-
-
-def _expect_failure(check, T, what):
-    """negative controls: check(T') must fail for T' = T changed in one record (PL.control_records x PL.MUTATIONS)"""
-    for name, k in PL.control_records(T):
-        for how in PL.MUTATIONS:
-            with pytest.raises(AssertionError):
-                check(PL.mutate(T, k, how))
-                print("%s: the check passed with record %s (%d) %s" % (what, name, k, how))
-
-
-# ------------------------------------------------------------------ a. poison
-def _bits(x):
-    import torch
-    x = torch.view_as_real(x) if x.is_complex() else x
-    return x.contiguous().view(torch.uint8).clone()
 
 
 def _run_all(tr, c, los, scatter):
@@ -104,19 +58,6 @@ def _run_all(tr, c, los, scatter):
     out["power_global"] = _bits(tr.power_profiles(0.0, 1e-10, 6000, 0, 0, los=los, scatter=scatter)["buffer"])
     tr.torch.cuda.synchronize(tr.device)
     return out
-
-
-def _force_los_classes(tr):
-    """give the poison a blocked and a coincident LoS entry where the trace has none (changing a clear entry's status
-    before the clean run: the kernels must then read nothing but that status)"""
-    st = PL.los_status(tr)
-    clear = [tuple(ix) for ix in np.argwhere(st == 2)]
-    S = PL.los_view(tr).view(tr.torch.int32)
-    for want in (1, 0):
-        if not (st == want).any() and clear:
-            rx, tx = clear.pop()
-            S[int(rx), int(tx), PL.LOS_STATUS] = want
-    tr.torch.cuda.synchronize(tr.device)
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))

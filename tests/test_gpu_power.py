@@ -18,18 +18,14 @@ from hermespy_rt_amd import abi, power
 
 from . import configs as K
 from . import scenes_gen as G
-from .test_gpu_array_channel import _launch_dirs
+from . import planted as PL
+from .pathsum_util import F, _cfg, _tracer
+from .pathsum_util import power_check as _check
+from .pathsum_util import power_reference as _reference
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = abi.POWER_FIELDS
-
-
-def _tracer(c, **kw):
-    from hermespy_rt_amd.device import Tracer
-    return Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"],
-                  c["num_paths"], c["num_bounces"], **kw)
 
 
 def _terms(tr, los=True, scatter=True):
@@ -38,7 +34,7 @@ def _terms(tr, los=True, scatter=True):
     if scatter:
         P = {k: v.cpu().numpy() for k, v in tr.paths(nonzero_only=False).items()}
         ub = P["unblocked"]
-        dirs = _launch_dirs(tr)
+        dirs = PL.launch_dirs(tr).astype(np.float32)
         pw = lambda a: a.real.astype(np.float64) ** 2 + a.imag.astype(np.float64) ** 2   # noqa: E731
         cols["link"].append((P["rx"] * tr.ntx + P["tx"])[ub])
         cols["p"].append(np.stack([pw(P["a_te"][ub]), pw(P["a_tm"][ub])], axis=1))
@@ -75,86 +71,6 @@ def _terms(tr, los=True, scatter=True):
     return out
 
 
-def _zen(u, n):
-    x = np.arccos(np.clip(u[:, 2], -1.0, 1.0)) / np.pi * n
-    return np.minimum(np.floor(x), n - 1).astype(np.int64), x
-
-
-def _azi(u, n):
-    x = (np.arctan2(u[:, 1], u[:, 0]) + np.pi) / (2 * np.pi) * n
-    i = np.floor(x).astype(np.int64)
-    return np.where(i >= n, 0, i), x
-
-
-def _near_edge(x):
-    return np.abs(x - np.rint(x)) < 1e-6
-
-
-def _reference(T, tau0, dtau, ld, nth, nph):
-    """moments [L, 2, F], |moments| [L, 2, F], pdp [L, 2, ld], arrival / departure [L, 2, nth, nph], the count N
-    [L] and the edge slack of arrival / departure [L, 2]"""
-    nl, link, p = T["nlinks"], T["link"], T["p"]
-    tau, nu, urx, utx = T["tau"], T["nu"], T["urx"], T["utx"]
-    M = np.zeros((nl, 2, F))
-    A = np.zeros((nl, 2, F))
-    N = np.bincount(link, minlength=nl).astype(np.float64)
-
-    def add(dst, w, idx=link, n=nl):
-        return dst + np.bincount(idx, weights=w, minlength=n)
-
-    for pol in range(2):
-        q = p[:, pol]
-        M[:, pol, abi.POWER_COUNT] = N
-        A[:, pol, abi.POWER_COUNT] = N
-        fields = {abi.POWER_P: q, abi.POWER_P_TAU: q * tau, abi.POWER_P_TAU2: q * tau * tau, abi.POWER_P_NU: q * nu,
-                  abi.POWER_P_NU2: q * nu * nu, abi.POWER_P_LOS: q * T["los"]}
-        for c in range(3):
-            fields[abi.POWER_P_URX_X + c] = q * urx[:, c]
-            fields[abi.POWER_P_UTX_X + c] = q * utx[:, c]
-        for f, w in fields.items():
-            M[:, pol, f] = add(0.0, w)
-            A[:, pol, f] = add(0.0, np.abs(w))
-    pdp = np.zeros((nl, 2, ld))
-    if ld:
-        x = (tau - tau0) / dtau
-        ok = (x >= 0) & (x < ld)
-        b = np.floor(x[ok]).astype(np.int64)
-        for pol in range(2):
-            pdp[:, pol] = np.bincount(link[ok] * ld + b, weights=p[ok, pol], minlength=nl * ld).reshape(nl, ld)
-    arr = np.zeros((nl, 2, nth, nph))
-    dep = np.zeros((nl, 2, nth, nph))
-    slack = np.zeros((2, nl, 2))
-    if nth:
-        for k, (u, H) in enumerate(((urx, arr), (utx, dep))):
-            zi, zx = _zen(u, nth)
-            ai, ax = _azi(u, nph)
-            edge = _near_edge(zx) | _near_edge(ax)
-            for pol in range(2):
-                H[:, pol] = np.bincount(link * nth * nph + zi * nph + ai, weights=p[:, pol],
-                                        minlength=nl * nth * nph).reshape(nl, nth, nph)
-                slack[k, :, pol] = np.bincount(link[edge], weights=p[edge, pol], minlength=nl)
-    return M, A, pdp, arr, dep, N, slack
-
-
-def _check(got, ref, tag=""):
-    M, A, pdp, arr, dep, N, slack = ref
-    nl = M.shape[0]
-    m = np.asarray(got["moments"]).reshape(nl, 2, F)
-    P = M[:, :, abi.POWER_P]
-    tol = 1e-9 * A + 1e-300
-    tol[:, :, abi.POWER_P_UTX_X:abi.POWER_P_UTX_Z + 1] += 2.0 ** -22 * P[:, :, None]
-    err = np.abs(m - M)
-    assert (err <= tol).all(), (tag, "moments", np.unravel_index(np.argmax(err / tol), err.shape), (err / tol).max())
-    hb = ((1e-12 + N * 2.0 ** -61)[:, None] * P)   # [L, 2]
-    g = np.asarray(got["pdp"]).reshape(pdp.shape)
-    e = np.abs(g - pdp).reshape(nl, 2, -1).max(axis=-1, initial=0.0)
-    assert (e <= hb + 1e-300).all(), (tag, "pdp", (e / np.maximum(hb, 1e-300)).max())
-    for k, (name, H) in enumerate((("arrival", arr), ("departure", dep))):
-        g = np.asarray(got[name]).reshape(H.shape)
-        e = np.abs(g - H).reshape(nl, 2, -1).max(axis=-1, initial=0.0)
-        assert (e <= hb + slack[k] + 1e-300).all(), (tag, name, e.max(), (hb + slack[k]).max())
-
-
 def _np(d):
     return {k: v.cpu().numpy() for k, v in d.items()}
 
@@ -163,11 +79,6 @@ def _np(d):
 SPECS = [(0.0, 0.0, 1024, 0, 0), (0.0, 0.0, 300, 7, 13), (1e-7, 2e-9, 1024, 32, 64)]
 CASES = [("C1", None), ("TEST_PY", None), ("COINCIDENT", 8000), ("C3", 20000), ("C4_DOPPLER", 4000),
          ("IN_PLANE_canyon", None)]
-
-
-def _cfg(name, n):
-    c = K.IN_PLANE["canyon"] if name == "IN_PLANE_canyon" else K.ALL[name]
-    return K.small(c, n) if n else c
 
 
 def _window(T, ld):

@@ -18,17 +18,11 @@ from hermespy_rt_amd import abi
 
 from . import configs as K
 from . import scenes_gen as G
+from .pathsum_util import FS, _cfg, _los_status, _tracer
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS = 122.88e6
-
-
-def _tracer(c, **kw):
-    from hermespy_rt_amd.device import Tracer
-    return Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"],
-                  c["num_paths"], c["num_bounces"], **kw)
 
 
 def _taps_sum(h, S, rx, tx, a_te, a_tm, tau, nu, fs, fc, l, t, chunk=2048):
@@ -43,10 +37,6 @@ def _taps_sum(h, S, rx, tx, a_te, a_tm, tau, nu, fs, fc, l, t, chunk=2048):
             h[rx, tx, pol] += u.T @ v
     S[rx, tx, 0] += np.abs(a_te.astype(np.complex128)).sum()
     S[rx, tx, 1] += np.abs(a_tm.astype(np.complex128)).sum()
-
-
-def _los_status(L):
-    return int(L[0:1].view(np.uint32)[0])
 
 
 def _los_sum(h, S, los, fs, fc, l, t):
@@ -105,11 +95,6 @@ CASES = [
     ("C4_DOPPLER", 4000, [(3, 64, 0, FS), (1, 300, -7, 1e9)]),
     ("IN_PLANE_canyon", None, [(1, 300, -7, FS), (3, 64, 0, 1e9)]),
 ]
-
-
-def _cfg(name, n):
-    c = K.IN_PLANE["canyon"] if name == "IN_PLANE_canyon" else K.ALL[name]
-    return K.small(c, n) if n else c
 
 
 @pytest.mark.parametrize("name,n,grids", CASES, ids=[c[0] for c in CASES])
