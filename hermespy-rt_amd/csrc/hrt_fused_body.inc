@@ -120,34 +120,9 @@
     };
 
     if constexpr (CHAIN) __syncthreads();   // (the previous chunk's readers of L.wcnt are done)
-    if (TRI_IN_LDS && !CHAIN) {
-        // (four loads in flight per thread: a load -> store -> load chain costs a round trip per 4 KB)
-        const uint32_t n4 = HRT_ROW * T;
-        for (uint32_t k0 = tid; k0 < n4; k0 += 4u * HRT_BLOCK) {
-            const uint32_t k1 = k0 + HRT_BLOCK, k2 = k0 + 2u * HRT_BLOCK, k3 = k0 + 3u * HRT_BLOCK;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 t0 = g_tri[k0], t1 = k1 < n4 ? g_tri[k1] : z, t2 = k2 < n4 ? g_tri[k2] : z,
-                         t3 = k3 < n4 ? g_tri[k3] : z;
-            L.tri[k0] = t0;
-            if (k1 < n4) L.tri[k1] = t1;
-            if (k2 < n4) L.tri[k2] = t2;
-            if (k3 < n4) L.tri[k3] = t3;
-        }
-        if constexpr (VARIANT >= 4) {
-            for (uint32_t k = tid; k < T; k += HRT_BLOCK) L.tg[k] = g_tg[k];
-            for (uint32_t k = tid; k < 2u * n_leaf; k += HRT_BLOCK) L.leaf[k] = g_leaf[k];
-        }
-    }
     if constexpr (!CHAIN) {
-        if (!FIRST)
-            for (uint32_t k = tid; k < P.num_rx; k += HRT_BLOCK)
-                L.rx[k] = make_float4(P.rx_pos[3 * k], P.rx_pos[3 * k + 1], P.rx_pos[3 * k + 2], 0.f);
-        else if (tid < min(P.num_tx, kLdsTx))
-            L.tx[tid] = make_float4(P.tx_pos[3 * tid], P.tx_pos[3 * tid + 1], P.tx_pos[3 * tid + 2], 0.f);
-        {
-            const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
-            for (uint32_t k = tid; k < 4u * HRT_NUM_MATERIALS; k += HRT_BLOCK) L.mat[k] = g_mat[k];
-        }
+        // (the tables behind the state in one flight: a load -> store -> load chain costs a round trip per 4 KB)
+        fused_stage<TRI_IN_LDS, (VARIANT >= 4), FIRST>(P, L, T, n_leaf, tid);
         __syncthreads();
     }
     auto tri = [&]() {

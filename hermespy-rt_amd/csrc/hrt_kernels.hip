@@ -770,15 +770,24 @@ __device__ __forceinline__ F3 image_of(F3 t, float4 q0, float4 q2)
 // (apex, patch), any other lane of the list the whole table; the wave walks the union through the staged
 // test.  ALL lanes must call (uniform control flow).  apex_k: k (shadow rays to RX k) or num_rx + tx.
 struct PatchRef { bool served; uint32_t off; };   // off: byte offset of the patch's masks inside one apex's table
+// the two definition rows of triangle htri's grid (global memory; a request only: they need the entry's triangle and
+// nothing from LDS, so a kernel asks for them before the barrier behind its table staging)
+__device__ __forceinline__ void patch_fetch(const hrt_kpatch &X, uint32_t num_tri, uint32_t htri, bool valid, float4 &p0, float4 &p1)
+{
+    p0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    p1 = p0;
+    if (valid && htri < num_tri) {
+        p0 = reinterpret_cast<const float4 *>(X.pdef)[2u * htri];
+        p1 = reinterpret_cast<const float4 *>(X.pdef)[2u * htri + 1u];
+    }
+}
 template <typename TriPtr>
 __device__ __forceinline__ PatchRef patch_locate(TriPtr tri, const hrt_kpatch &X, uint32_t num_tri, uint32_t htri, F3 o,
-                                                 const bool image, F3 apex, F3 d)
+                                                 const bool image, F3 apex, F3 d, const float4 p0, const float4 p1)
 {
     PatchRef R = {false, 0u};
     if (htri < num_tri) {
         const float4 q0 = tri[HRT_ROW * htri], q2 = tri[HRT_ROW * htri + 2];
-        const float4 p0 = reinterpret_cast<const float4 *>(X.pdef)[2u * htri];
-        const float4 p1 = reinterpret_cast<const float4 *>(X.pdef)[2u * htri + 1u];
         const F3 sv = sub3(o, {q0.x, q0.y, q0.z});
         const float fu = fdot3(sv, {p0.x, p0.y, p0.z}), fv = fdot3(sv, {p1.x, p1.y, p1.z});
         const float hh = fdot3(sv, {q2.y, q2.z, q2.w});
@@ -1776,6 +1785,62 @@ __device__ __forceinline__ Rsrc res_blk(const hrt_kparams &P, uint32_t k)
     return make_rsrc(P.ws + P.off_res + (uint64_t)(2u * k) * P.cap * 4u);
 }
 
+// ---- table staging ----
+// Every kernel copies the per-problem tables (triangle rows, RX / TX positions, materials, ...) into LDS before
+// its first barrier.  Written as `for (k = tid; k < n; k += HRT_BLOCK) lds[k] = g[k]` such a copy compiles to load ->
+// s_waitcnt vmcnt(0) -> ds_write -> branch: one memory round trip per 4 KB, and one more per table behind it.
+// Here a thread requests a whole batch -- of every table -- before the first wait: stage_load fills registers with
+// items tid, tid + HRT_BLOCK, ... (those below n), the caller requests whatever else it wants in flight (its
+// first entry's state), stage_store writes the batch, stage_rest copies what a long table has behind its first
+// batch.  `ld(k)` forms item k from global memory, so the LDS image is whatever the plain loop stored.
+constexpr int kStageTri = 5;   // float4 per thread in the triangle table's batch: C3's 1 170 float4 are one batch
+template <int N, typename V, typename Ld>
+__device__ __forceinline__ void stage_load(V (&v)[N], const uint32_t n, const uint32_t k0, const Ld ld)
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t k = k0 + (uint32_t)j * HRT_BLOCK;
+        v[j] = V{};
+        if (k < n) v[j] = ld(k);
+    }
+}
+template <int N, typename V>
+__device__ __forceinline__ void stage_store(V *l, const V (&v)[N], const uint32_t n, const uint32_t k0)
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t k = k0 + (uint32_t)j * HRT_BLOCK;
+        if (k < n) l[k] = v[j];
+    }
+}
+// items [N * HRT_BLOCK, n): M per thread and round (M >= 2: never a load -> wait -> store chain)
+template <int N, int M, typename V, typename Ld>
+__device__ __forceinline__ void stage_rest(V *l, const uint32_t n, const uint32_t tid, const Ld ld)
+{
+    for (uint32_t k0 = (uint32_t)N * HRT_BLOCK + tid; k0 < n; k0 += (uint32_t)M * HRT_BLOCK) {
+        V v[M];
+        stage_load(v, n, k0, ld);
+        stage_store(l, v, n, k0);
+    }
+}
+// a table of float4 copied as it is: request (beside the other tables' stage_load) and commit (beside their stage_store)
+template <int N>
+__device__ __forceinline__ void copy16_request(float4 (&v)[N], const float4 *g, const uint32_t n, const uint32_t tid)
+{
+    stage_load(v, n, tid, [&](uint32_t k) { return g[k]; });
+}
+template <int N>
+__device__ __forceinline__ void copy16_commit(const float4 (&v)[N], float4 *l, const float4 *g, const uint32_t n, const uint32_t tid)
+{
+    stage_store(l, v, n, tid);
+    stage_rest<N, (N > 1 ? N : 2)>(l, n, tid, [&](uint32_t k) { return g[k]; });
+}
+// item k of a position table (3 floats per row) as the float4 the kernels keep in LDS
+__device__ __forceinline__ float4 stage_pos(const float *pos, const uint32_t k)
+{
+    return make_float4(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.f);
+}
+
 // ---- workspace addressing (include/hrt_device.h) ----
 __device__ __forceinline__ float *hit_field(const hrt_kparams &P, uint32_t b, uint32_t f)
 {
@@ -1900,15 +1965,25 @@ __global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VA
     uint32_t *l_wcnt = reinterpret_cast<uint32_t *>(
         reinterpret_cast<float4 *>(reinterpret_cast<unsigned long long *>(l_rx + P.num_rx) +
                                    (HRT_BLOCK / 64u) * kMaskRounds) + (HRT_BLOCK / 64u) * wave_scratch4(VARIANT == 9));
-    if (TRI_IN_LDS) {
-        for (uint32_t k = tid; k < HRT_ROW * T; k += HRT_BLOCK) l_tri[k] = g_tri[k];
-        if constexpr (VARIANT >= 4) {   // guard pairs and leaf records: only the tree variants read them
-            for (uint32_t k = tid; k < T; k += HRT_BLOCK) l_tg[k] = g_tg[k];
-            for (uint32_t k = tid; k < 2u * n_leaf; k += HRT_BLOCK) l_leaf[k] = g_leaf[k];
-        }
+    {   // the tables: one flight (stage_load), guard pairs and leaf records only for the tree variants, which read them
+        constexpr bool kTree = TRI_IN_LDS && VARIANT >= 4;
+        const uint32_t n_tri4 = TRI_IN_LDS ? HRT_ROW * T : 0u;
+        const uint32_t n_tg = kTree ? T : 0u, n_leaf4 = kTree ? 2u * n_leaf : 0u;
+        const auto ld_tg = [&](uint32_t k) { return g_tg[k]; };
+        const auto ld_rx = [&](uint32_t k) { return stage_pos(P.rx_pos, k); };
+        float4 s_tri[kStageTri], s_leaf[2], s_rx[1];
+        float2 s_tg[2];
+        copy16_request(s_tri, g_tri, n_tri4, tid);
+        stage_load(s_tg, n_tg, tid, ld_tg);
+        copy16_request(s_leaf, g_leaf, n_leaf4, tid);
+        stage_load(s_rx, P.num_rx, tid, ld_rx);
+        copy16_commit(s_tri, l_tri, g_tri, n_tri4, tid);
+        stage_store(l_tg, s_tg, n_tg, tid);
+        copy16_commit(s_leaf, l_leaf, g_leaf, n_leaf4, tid);
+        stage_store(l_rx, s_rx, P.num_rx, tid);
+        stage_rest<2, 2>(l_tg, n_tg, tid, ld_tg);
+        stage_rest<1, 2>(l_rx, P.num_rx, tid, ld_rx);
     }
-    for (uint32_t k = tid; k < P.num_rx; k += HRT_BLOCK)
-        l_rx[k] = make_float4(P.rx_pos[3 * k], P.rx_pos[3 * k + 1], P.rx_pos[3 * k + 2], 0.f);
     __syncthreads();
     auto tri = [&]() {
         if constexpr (TRI_IN_LDS) return (const float4 *)l_tri;
@@ -2433,19 +2508,34 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
     uint32_t *l_wcnt = reinterpret_cast<uint32_t *>(l_rx + P.num_rx);
     float4 *l_trin = reinterpret_cast<float4 *>(l_wcnt + 8);   // [T]: n.xyz, mesh id (bits)
     float4 *l_mesh = l_trin + P.num_tri;                         // [M]: velocity, material (bits)
-    {
+    // the bounce's own trace result of an entry (see below); the first chunk's is requested with the tables
+    const uint64_t base0 = (uint64_t)blockIdx.x * HRT_BLOCK;
+    uint32_t ptri0 = HRT_NO_HIT;
+    float pt0 = 0.f;
+    {   // the tables: one flight (stage_load)
         const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
-        for (uint32_t k = tid; k < 4u * HRT_NUM_MATERIALS; k += HRT_BLOCK) l_mat[k] = g_mat[k];
-        for (uint32_t k = tid; k < P.num_rx; k += HRT_BLOCK)
-            l_rx[k] = make_float4(P.rx_pos[3 * k], P.rx_pos[3 * k + 1], P.rx_pos[3 * k + 2], 0.f);
-        if constexpr (NLDS) {
-            for (uint32_t k = tid; k < P.num_tri; k += HRT_BLOCK) {
-                const float *row = P.tri + (size_t)k * HRT_TRI_FLOATS;
-                l_trin[k] = make_float4(row[9], row[10], row[11], row[19]);
-            }
-            const float4 *g_mesh = reinterpret_cast<const float4 *>(P.mesh);
-            for (uint32_t k = tid; k < P.num_mesh; k += HRT_BLOCK) l_mesh[k] = g_mesh[k];
+        const float4 *g_mesh = reinterpret_cast<const float4 *>(P.mesh);
+        const uint32_t n_trin = NLDS ? P.num_tri : 0u, n_mesh = NLDS ? P.num_mesh : 0u;
+        const auto ld_rx = [&](uint32_t k) { return stage_pos(P.rx_pos, k); };
+        const auto ld_trin = [&](uint32_t k) {
+            const float *row = P.tri + (size_t)k * HRT_TRI_FLOATS;
+            return make_float4(row[9], row[10], row[11], row[19]);
+        };
+        float4 s_mat[1], s_rx[1], s_trin[2], s_mesh[1];
+        copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        stage_load(s_rx, P.num_rx, tid, ld_rx);
+        stage_load(s_trin, n_trin, tid, ld_trin);
+        copy16_request(s_mesh, g_mesh, n_mesh, tid);
+        if (do_trace && (uint32_t)base0 + tid < n_in) {
+            ptri0 = ldu(res_blk(P, P.num_rx), 0u, ((uint32_t)base0 + tid) * 4u);
+            pt0 = ldf(res_blk(P, P.num_rx), cap4, ((uint32_t)base0 + tid) * 4u);
         }
+        copy16_commit(s_mat, l_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        stage_store(l_rx, s_rx, P.num_rx, tid);
+        stage_store(l_trin, s_trin, n_trin, tid);
+        copy16_commit(s_mesh, l_mesh, g_mesh, n_mesh, tid);
+        stage_rest<1, 2>(l_rx, P.num_rx, tid, ld_rx);
+        stage_rest<2, 2>(l_trin, n_trin, tid, ld_trin);
     }
     __syncthreads();
     const uint32_t lane = tid & 63u, wave = tid >> 6;
@@ -2465,8 +2555,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
         else return gather4(mesh_r, HRT_MESH_FLOATS * 4u, m, 0u);
     };
 
-    for (uint64_t base = (uint64_t)blockIdx.x * HRT_BLOCK; base < n_in;
-         base += (uint64_t)gridDim.x * HRT_BLOCK) {
+    for (uint64_t base = base0; base < n_in; base += (uint64_t)gridDim.x * HRT_BLOCK) {
         const uint32_t i = (uint32_t)base + tid;
         const uint32_t i4 = i * 4u;
         const bool valid = i < n_in;
@@ -2481,7 +2570,10 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
         // not, and the kernel is bound by its traffic.)
         uint32_t ptri = HRT_NO_HIT;
         float pt = 0.f;
-        if (do_trace && valid) {
+        if (base == base0) {   // (requested in front of the table staging)
+            ptri = ptri0;
+            pt = pt0;
+        } else if (do_trace && valid) {
             ptri = ldu(res_blk(P, P.num_rx), 0u, i4);
             pt = ldf(res_blk(P, P.num_rx), cap4, i4);
         }
@@ -2720,27 +2812,45 @@ __global__ __launch_bounds__(HRT_BLOCK, 8) void hrt_image_kernel(const hrt_kpara
     const uint32_t cap4 = (uint32_t)P.cap * 4u;
     float4 *l_tri = lds;
     uint32_t *l_wcnt = reinterpret_cast<uint32_t *>(lds + HRT_ROW * T);
-    {
+    const uint32_t pb = b - 1;
+    // an entry's state (nothing of it depends on LDS): the first chunk's is requested with the table
+    F3 o, d;
+    uint32_t htri, hray;
+    float4 pd0, pd1;   // (patch_fetch: the definition rows of the entry's triangle, requested as soon as htri is there)
+    const auto load_state = [&](const uint32_t chunk) {
+        const uint32_t i = chunk * HRT_BLOCK + tid;
+        const uint32_t i4 = i * 4u;
+        o = {0.f, 0.f, 0.f};
+        d = {0.f, 0.f, 1.f};
+        htri = 0u;
+        hray = 0u;
+        if (i < n_in) {
+            htri = ldu(hit_blk(P, pb), H_TRI * cap4, i4);
+            o = {ldf(hit_blk(P, pb), H_OX * cap4, i4), ldf(hit_blk(P, pb), H_OY * cap4, i4), ldf(hit_blk(P, pb), H_OZ * cap4, i4)};
+            d = {ldf(hit_blk(P, pb), H_DX * cap4, i4), ldf(hit_blk(P, pb), H_DY * cap4, i4), ldf(hit_blk(P, pb), H_DZ * cap4, i4)};
+            if (P.num_tx != 1u) hray = ldu(hit_blk(P, pb), H_RAY * cap4, i4);
+        }
+        patch_fetch(P.patch, T, htri, i < n_in, pd0, pd1);
+    };
+    {   // the table and the first entry's state: one flight (stage_load)
         const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
-        for (uint32_t k = tid; k < HRT_ROW * T; k += HRT_BLOCK) l_tri[k] = g_tri[k];
+        float4 s_tri[kStageTri];
+        copy16_request(s_tri, g_tri, HRT_ROW * T, tid);
+        load_state(blockIdx.x);
+        copy16_commit(s_tri, l_tri, g_tri, HRT_ROW * T, tid);
     }
     __syncthreads();
     const float4 *tri = l_tri;
-    const uint32_t pb = b - 1;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const uint32_t i = chunk * HRT_BLOCK + tid;
         const uint32_t i4 = i * 4u;
         const bool valid = i < n_in;
-        F3 o = {0.f, 0.f, 0.f}, d = {0.f, 0.f, 1.f};
         uint32_t tx = 0u;
         PatchRef ref = {false, 0u};
         if (valid) {
-            o = {ldf(hit_blk(P, pb), H_OX * cap4, i4), ldf(hit_blk(P, pb), H_OY * cap4, i4), ldf(hit_blk(P, pb), H_OZ * cap4, i4)};
-            d = {ldf(hit_blk(P, pb), H_DX * cap4, i4), ldf(hit_blk(P, pb), H_DY * cap4, i4), ldf(hit_blk(P, pb), H_DZ * cap4, i4)};
-            const uint32_t htri = ldu(hit_blk(P, pb), H_TRI * cap4, i4);
-            if (P.num_tx != 1u) tx = min(ldu(hit_blk(P, pb), H_RAY * cap4, i4) / P.num_local, P.num_tx - 1u);
+            if (P.num_tx != 1u) tx = min(hray / P.num_local, P.num_tx - 1u);
             // the apex: the image of the lane's own TX in the plane of the triangle it left
-            ref = patch_locate(tri, P.patch, T, htri, o, true, {P.tx_pos[3 * tx], P.tx_pos[3 * tx + 1], P.tx_pos[3 * tx + 2]}, d);
+            ref = patch_locate(tri, P.patch, T, htri, o, true, {P.tx_pos[3 * tx], P.tx_pos[3 * tx + 1], P.tx_pos[3 * tx + 2]}, d, pd0, pd1);
         }
         const Hit h = closest_hit_patch(tri, P.acc.orig, P.patch, ref, P.num_rx + tx, T, o, d, valid, lane, 1);
         if (valid) {
@@ -2757,6 +2867,7 @@ __global__ __launch_bounds__(HRT_BLOCK, 8) void hrt_image_kernel(const hrt_kpara
             atomicAdd(reinterpret_cast<uint32_t *>(P.ws + P.off_super_cnt) + (uint64_t)b * P.num_super + (chunk >> HRT_SUPER_SHIFT), c);
         }
         __syncthreads();
+        if (chunk + gridDim.x < n_chunks) load_state(chunk + gridDim.x);   // (the next chunk's, where its iteration begins)
     }
 }
 
@@ -2785,27 +2896,20 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
     // (the reference-order index of every row, for the tie rule: in LDS, so that the exact stage of the walk has no
     // global load -- whose s_waitcnt vmcnt(0) would also wait for the masks requested ahead)
     uint32_t *l_orig = reinterpret_cast<uint32_t *>(l_mat + 4u * HRT_NUM_MATERIALS);
-    {
-        const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
-        const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
-        for (uint32_t k = tid; k < HRT_ROW * T; k += HRT_BLOCK) l_tri[k] = g_tri[k];
-        for (uint32_t k = tid; k < P.num_rx; k += HRT_BLOCK)
-            l_rx[k] = make_float4(P.rx_pos[3 * k], P.rx_pos[3 * k + 1], P.rx_pos[3 * k + 2], 0.f);
-        for (uint32_t k = tid; k < 4u * HRT_NUM_MATERIALS; k += HRT_BLOCK) l_mat[k] = g_mat[k];
-        for (uint32_t k = tid; k < T; k += HRT_BLOCK) l_orig[k] = P.acc.orig[k];
-    }
-    __syncthreads();
-    const float4 *tri = l_tri;
     const uint32_t pb = b - 1;
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    // an entry's state (nothing of it depends on LDS): the first chunk's is requested with the tables
+    F3 o, d;
+    uint32_t htri;
+    float theta, tau, a0, a1, a2, a3;
+    const auto load_state = [&](const uint32_t chunk) {
         const uint32_t i = chunk * HRT_BLOCK + tid;
         const uint32_t i4 = i * 4u;
-        const bool valid = i < n_in;
-        F3 o = {0.f, 0.f, 0.f}, d = {0.f, 0.f, 1.f}, n = {0.f, 0.f, 1.f}, mvel = {0.f, 0.f, 0.f};
-        float theta = 0.f, tau = 0.f, a0 = 1.f, a1 = 0.f, a2 = 1.f, a3 = 0.f, mat_s = 0.f, mat_alpha = 1.f;
-        PatchRef ref = {false, 0u};
-        if (valid) {
-            const uint32_t htri = ldu(hit_blk(P, pb), H_TRI * cap4, i4);
+        o = {0.f, 0.f, 0.f};
+        d = {0.f, 0.f, 1.f};
+        htri = 0u;
+        theta = 0.f; tau = 0.f; a0 = 1.f; a1 = 0.f; a2 = 1.f; a3 = 0.f;
+        if (i < n_in) {
+            htri = ldu(hit_blk(P, pb), H_TRI * cap4, i4);
             theta = ldf(hit_blk(P, pb), H_THETA * cap4, i4);
             o = {ldf(hit_blk(P, pb), H_OX * cap4, i4), ldf(hit_blk(P, pb), H_OY * cap4, i4),
                  ldf(hit_blk(P, pb), H_OZ * cap4, i4)};
@@ -2816,11 +2920,47 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
             a2 = ldf(hit_blk(P, pb), H_A2 * cap4, i4);
             a3 = ldf(hit_blk(P, pb), H_A3 * cap4, i4);
             tau = ldf(hit_blk(P, pb), H_TAU * cap4, i4);
-            ref = patch_locate(tri, P.patch, T, htri, o, false, o, o);
+        }
+    };
+    {   // the tables and the first entry's state: one flight (stage_load)
+        const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
+        const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
+        const auto ld_rx = [&](uint32_t k) { return stage_pos(P.rx_pos, k); };
+        const auto ld_orig = [&](uint32_t k) { return P.acc.orig[k]; };
+        float4 s_tri[kStageTri], s_rx[1], s_mat[1];
+        uint32_t s_orig[1];
+        copy16_request(s_tri, g_tri, HRT_ROW * T, tid);
+        stage_load(s_rx, P.num_rx, tid, ld_rx);
+        copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        stage_load(s_orig, T, tid, ld_orig);
+        load_state(blockIdx.x);
+        copy16_commit(s_tri, l_tri, g_tri, HRT_ROW * T, tid);
+        stage_store(l_rx, s_rx, P.num_rx, tid);
+        copy16_commit(s_mat, l_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        stage_store(l_orig, s_orig, T, tid);
+        stage_rest<1, 2>(l_rx, P.num_rx, tid, ld_rx);
+        stage_rest<1, 2>(l_orig, T, tid, ld_orig);
+    }
+    __syncthreads();
+    const float4 *tri = l_tri;
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t i = chunk * HRT_BLOCK + tid;
+        const uint32_t i4 = i * 4u;
+        const bool valid = i < n_in;
+        F3 n = {0.f, 0.f, 1.f}, mvel = {0.f, 0.f, 0.f};
+        float mat_s = 0.f, mat_alpha = 1.f;
+        PatchRef ref = {false, 0u};
+        if (valid) {
+            // (the patch's definition rows and the mesh row are requested together: patch_locate waits for the former.
+            // Requested in front of the barrier, as the image kernel does, the rows are spilled here: 80 registers)
+            float4 pd0, pd1;
+            patch_fetch(P.patch, T, htri, true, pd0, pd1);
+            float4 mm = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (htri < T) mm = gather4(mesh_r, HRT_MESH_FLOATS * 4u, __float_as_uint(tri[HRT_ROW * htri + 4].w), 0u);
+            ref = patch_locate(tri, P.patch, T, htri, o, false, o, o, pd0, pd1);
             if (htri < T) {   // (always: the list holds rows of the table; never fault)
                 const float4 q2 = tri[HRT_ROW * htri + 2];
                 n = {q2.y, q2.z, q2.w};
-                const float4 mm = gather4(mesh_r, HRT_MESH_FLOATS * 4u, __float_as_uint(tri[HRT_ROW * htri + 4].w), 0u);
                 mvel = {mm.x, mm.y, mm.z};
                 const float4 m3 = l_mat[4u * __float_as_uint(mm.w) + 3u];
                 mat_s = m3.x;
@@ -2882,6 +3022,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
             const unsigned long long m = __ballot(unblocked);
             if (lane == 0 && valid) mask_words(P, pb, rx)[i >> 6] = m;
         }
+        if (chunk + gridDim.x < n_chunks) load_state(chunk + gridDim.x);   // (the next chunk's, where its iteration begins)
     }
 }
 
@@ -3035,6 +3176,37 @@ __device__ __forceinline__ FusedLds fused_lds(float4 *lds, uint32_t T, uint32_t 
     L.mat = reinterpret_cast<float4 *>(L.wcnt + 64);
     L.tx = L.mat + 4u * HRT_NUM_MATERIALS;   // the first kLdsTx TX positions (launch 0)
     return L;
+}
+// The tables of that image, in one flight (stage_load): triangle rows, guard pairs and leaf records (TREE: the tree
+// variants read them) if staged, the RX positions -- FIRST: the TX positions instead --, the materials.  No barrier.
+template <bool TRI_IN_LDS, bool TREE, bool FIRST>
+__device__ __forceinline__ void fused_stage(const hrt_kparams &P, const FusedLds &L, const uint32_t T, const uint32_t n_leaf,
+                                            const uint32_t tid)
+{
+    const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
+    const float2 *g_tg = reinterpret_cast<const float2 *>(P.acc.tg);
+    const float4 *g_leaf = reinterpret_cast<const float4 *>(P.acc.leaf);
+    const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
+    const uint32_t n_tri4 = TRI_IN_LDS ? HRT_ROW * T : 0u;
+    const uint32_t n_tg = (TRI_IN_LDS && TREE) ? T : 0u, n_leaf4 = (TRI_IN_LDS && TREE) ? 2u * n_leaf : 0u;
+    const uint32_t n_pos = FIRST ? min(P.num_tx, kLdsTx) : P.num_rx;
+    float4 *l_pos = FIRST ? L.tx : L.rx;
+    const auto ld_tg = [&](uint32_t k) { return g_tg[k]; };
+    const auto ld_pos = [&](uint32_t k) { return stage_pos(FIRST ? P.tx_pos : P.rx_pos, k); };
+    float4 s_tri[kStageTri], s_leaf[2], s_pos[1], s_mat[1];
+    float2 s_tg[2];
+    copy16_request(s_tri, g_tri, n_tri4, tid);
+    stage_load(s_tg, n_tg, tid, ld_tg);
+    copy16_request(s_leaf, g_leaf, n_leaf4, tid);
+    stage_load(s_pos, n_pos, tid, ld_pos);
+    copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+    copy16_commit(s_tri, L.tri, g_tri, n_tri4, tid);
+    stage_store(L.tg, s_tg, n_tg, tid);
+    copy16_commit(s_leaf, L.leaf, g_leaf, n_leaf4, tid);
+    stage_store(l_pos, s_pos, n_pos, tid);
+    copy16_commit(s_mat, L.mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+    stage_rest<2, 2>(L.tg, n_tg, tid, ld_tg);
+    stage_rest<1, 2>(l_pos, n_pos, tid, ld_pos);
 }
 
 // The bounce itself for a ray that hit triangle `ptri` at distance `pt` (src/compute_paths.c:
@@ -3215,20 +3387,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_FUSED_WAVESB) void hrt_chain_kernel(
     const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9)>(lds, P.num_tri, P.acc.num_leaf, P.num_rx, tid >> 6);
     {   // the tables, once
         const uint32_t T = P.num_tri, n_leaf = P.acc.num_leaf;
-        if (TRI_IN_LDS) {
-            const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
-            for (uint32_t k = tid; k < HRT_ROW * T; k += HRT_BLOCK) L.tri[k] = g_tri[k];
-            if constexpr (VARIANT >= 4) {
-                const float2 *g_tg = reinterpret_cast<const float2 *>(P.acc.tg);
-                const float4 *g_leaf = reinterpret_cast<const float4 *>(P.acc.leaf);
-                for (uint32_t k = tid; k < T; k += HRT_BLOCK) L.tg[k] = g_tg[k];
-                for (uint32_t k = tid; k < 2u * n_leaf; k += HRT_BLOCK) L.leaf[k] = g_leaf[k];
-            }
-        }
-        for (uint32_t k = tid; k < P.num_rx; k += HRT_BLOCK)
-            L.rx[k] = make_float4(P.rx_pos[3 * k], P.rx_pos[3 * k + 1], P.rx_pos[3 * k + 2], 0.f);
-        const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
-        for (uint32_t k = tid; k < 4u * HRT_NUM_MATERIALS; k += HRT_BLOCK) L.mat[k] = g_mat[k];
+        fused_stage<TRI_IN_LDS, (VARIANT >= 4), false>(P, L, T, n_leaf, tid);
     }
     // Roll call before any work: is the whole grid resident?  Alone on the GPU it is within microseconds; when
     // other kernels hold the slots (processes sharing the GPU, a long kernel on another stream) it may never be,
