@@ -313,10 +313,10 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                  out_shape, extra, stats, dtype=np.complex64):
-    """One of the five path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps or
-    _power_profiles) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape (a flat buffer of
-    out_shape doubles for float64; out_shape None: a placeholder the library refuses to write); `extra` are the
-    arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
+    """One of the six path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
+    _power_profiles or _dominant_paths) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
+    (a flat buffer of out_shape doubles for float64 or bytes for uint8; out_shape None: a placeholder the library
+    refuses to write); `extra` are the arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
     tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
     nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
@@ -333,7 +333,8 @@ def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, n
     try:
         rc = getattr(lib, name)(C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx), C.c_size_t(ntx),
                                 C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)), C.byref(spec), *extra,
-                                out.ctypes.data_as(C.POINTER(C.c_double if dtype == np.float64 else C.c_float)),
+                                out.ctypes.data_as(C.c_void_p if dtype == np.uint8 else
+                                                   C.POINTER(C.c_double if dtype == np.float64 else C.c_float)),
                                 C.byref(stats) if stats is not None else None)
     finally:
         free_scene(scene)
@@ -475,3 +476,80 @@ def run_compute_power_profiles(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, 
                        num_bounces, spec, (n,) if n <= 2 * (POWER_FIELDS * 65535 + (1 << 26)) else None, (), stats,
                        np.float64)
     return power_views(out, nrx, ntx, spec)
+
+
+DOMINANT_MAX_PATHS = 1024   # hrt_dominant_spec.max_paths; and num_rx * num_tx * max_paths <= 2^22
+
+
+class DominantSpec(C.Structure):
+    """include/hermespy_rt.h hrt_dominant_spec"""
+    _fields_ = [("max_paths", C.c_uint32), ("parts", C.c_uint32)]
+
+
+class DominantPath(C.Structure):
+    """include/hermespy_rt.h hrt_dominant_path"""
+    _fields_ = [("power", C.c_double), ("path", C.c_uint64), ("bounce", C.c_int32), ("tri", C.c_uint32),
+                ("a_te_re", C.c_float), ("a_te_im", C.c_float), ("a_tm_re", C.c_float), ("a_tm_im", C.c_float),
+                ("tau", C.c_float), ("freq_shift", C.c_float), ("u_rx", C.c_float * 3), ("u_tx", C.c_float * 3)]
+
+
+assert C.sizeof(DominantSpec) == 8 and C.sizeof(DominantPath) == 72
+
+
+def dominant_spec(max_paths, los=True, scatter=True, parts=None):
+    if parts is None:
+        parts = (CHANNEL_LOS if los else 0) | (CHANNEL_SCATTER if scatter else 0)
+    return DominantSpec(int(max_paths), int(parts))
+
+
+def dominant_out_bytes(nrx, ntx, spec):
+    """the bytes of a dominant paths output (hrt_dominant_out_bytes; 0 for a spec the library refuses)"""
+    k, links = int(spec.max_paths), nrx * ntx
+    if not 0 < k <= DOMINANT_MAX_PATHS or not int(spec.parts) or int(spec.parts) & ~3:
+        return 0
+    if max(nrx, ntx, links) > 65535 or links * k > (1 << 22):
+        return 0
+    return links * (16 + k * C.sizeof(DominantPath))
+
+
+def dominant_views(buf, nrx, ntx, K):
+    """the fields of a dominant paths buffer (a flat uint8 numpy array or torch tensor, 8-byte aligned) as views, no
+    copies: kept, eligible [nrx, ntx]; power, path, bounce, tri, tau, freq_shift [nrx, ntx, K]; a_te, a_tm complex64
+    [nrx, ntx, K]; u_rx, u_tx [nrx, ntx, K, 3]; buffer"""
+    links, K = nrx * ntx, int(K)
+    is_np = isinstance(buf, np.ndarray)
+    if is_np:
+        i32, u32, i64, u64, f32, f64 = np.int32, np.uint32, np.int64, np.uint64, np.float32, np.float64
+    else:
+        import torch
+        i32, i64, f32, f64 = torch.int32, torch.int64, torch.float32, torch.float64
+        u32, u64 = i32, i64   # (torch: the unsigned fields as their signed bit patterns)
+    hdr = buf[:16 * links].view(u64).reshape(nrx, ntx, 2)
+    rec = buf[16 * links:16 * links + 72 * links * K]
+    w64 = rec.view(i64).reshape(nrx, ntx, K, 9)
+    w32 = rec.view(i32).reshape(nrx, ntx, K, 18)
+
+    def cplx(lo):
+        pair = w32[..., lo:lo + 2].view(f32)   # [nrx, ntx, K, 2]: re, im next to each other
+        if is_np:
+            return pair.view(np.complex64)[..., 0]
+        return torch.view_as_complex(pair)
+
+    return {"kept": hdr[..., 0], "eligible": hdr[..., 1],
+            "power": w64[..., 0].view(f64), "path": w64[..., 1].view(u64),
+            "bounce": w32[..., 4], "tri": w32[..., 5].view(u32),
+            "a_te": cplx(6), "a_tm": cplx(8),
+            "tau": w32[..., 10].view(f32), "freq_shift": w32[..., 11].view(f32),
+            "u_rx": w32[..., 12:15].view(f32), "u_tx": w32[..., 15:18].view(f32), "buffer": buf}
+
+
+def run_compute_dominant_paths(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                               stats=None):
+    """hrt_compute_dominant_paths through ctypes -> dominant_views of a uint8 numpy buffer.  Raises
+    RuntimeError("hrt_compute_dominant_paths failed (<rc>): ...") on an error code."""
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    n = dominant_out_bytes(nrx, ntx, spec)
+    out = _run_pathsum(lib, "hrt_compute_dominant_paths", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                       num_bounces, spec, (n,) if n else None, (), stats, np.uint8)
+    return dominant_views(out, nrx, ntx, spec.max_paths)

@@ -1,15 +1,15 @@
-/* channel.c -- channel frequency responses, impulse responses and power statistics from traced paths, on the
- * device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps, hrt_power_profiles;
- * include/hermespy_rt.h: hrt_compute_channel, hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps,
- * hrt_compute_power_profiles).
+/* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
+ * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
+ * hrt_power_profiles, hrt_dominant_paths; include/hermespy_rt.h: hrt_compute_channel, hrt_compute_array_channel,
+ * hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles, hrt_compute_dominant_paths).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
  * over the LoS entry and the scatter records of every (rx, tx) -- the sum a HermesPy caller forms on the host
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
- * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip and csrc/hrt_power.hip, over the workspace
- * view of csrc/hrt_pathsum.h;
+ * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip, csrc/hrt_power.hip and
+ * csrc/hrt_dominant.hip, over the workspace view of csrc/hrt_pathsum.h;
  * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
  * small download at the end.
  */
@@ -21,6 +21,7 @@
 #include "../hrt_array_channel.h"
 #include "../hrt_array_taps.h"
 #include "../hrt_channel.h"
+#include "../hrt_dominant.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_power.h"
 #include "../hrt_taps.h"
@@ -181,13 +182,13 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-/* One drop-in call: what the five hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
+/* One drop-in call: what the six hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
 struct ch_job {
     const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel), hrt_taps_spec
-                           (hrt_compute_taps, hrt_compute_array_taps) or hrt_power_spec */
+                           (hrt_compute_taps, hrt_compute_array_taps), hrt_power_spec or hrt_dominant_spec */
     uint64_t out_bytes;
     const void *h_const;
     uint64_t const_bytes;
@@ -197,6 +198,8 @@ struct ch_job {
                uint64_t scratch_bytes, void *d_out, int accumulate);
     uint32_t nr, nt;   /* the array calls' element counts (hrt_compute_array_channel, hrt_compute_array_taps) */
     double fa;
+    /* optional: runs on the downloaded output while the problem still exists (NULL: nothing to do) */
+    int (*finish)(const ch_job *j, const hrt_problem *p, void *out);
 };
 
 static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
@@ -254,6 +257,7 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
     {
         const double t0 = hrt_now_s();
         if ((rc = hrt_device_download(device, out, d_out, out_bytes))) goto done;
+        if (job->finish && (rc = job->finish(job, prob, out))) goto done;
         st.t_readback_s = hrt_now_s() - t0;
     }
     st.num_batches = G;
@@ -851,5 +855,144 @@ int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
     job.out_bytes = hrt_power_out_doubles(nrx, ntx, spec) * 8u;
     job.scratch_bytes = pw_job_scratch;
     job.run = pw_job_run;
+    return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ the K strongest paths per link (hrt_dominant_paths) */
+
+#define HRT_DM_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_DM_PARTIAL_MAX (512ull << 20)   /* candidate lists beyond one chunk: at most this */
+
+/* the checks of a dominant spec that need no problem */
+static int dominant_check(const hrt_dominant_spec *spec)
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_dominant_paths: NULL spec");
+    if (spec->max_paths == 0 || spec->max_paths > HRT_DM_MAX_PATHS)
+        return hrt_fail(HRT_E_INVALID, "hrt_dominant_paths: max_paths = %u (1 .. %u)", spec->max_paths,
+                        HRT_DM_MAX_PATHS);
+    return parts_check(spec->parts, "hrt_dominant_paths");
+}
+
+/* the checks that need the link count */
+static int dominant_links_check(uint64_t nrx, uint64_t ntx, const hrt_dominant_spec *spec)
+{
+    if (nrx > 65535u || ntx > 65535u || nrx * ntx > 65535u)
+        return hrt_fail(HRT_E_INVALID, "hrt_dominant_paths: num_rx * num_tx = %llu > 65535",
+                        (unsigned long long)(nrx * ntx));
+    if (nrx * ntx * spec->max_paths > HRT_DM_MAX_LINK_PATHS)
+        return hrt_fail(HRT_E_INVALID, "hrt_dominant_paths: num_rx * num_tx * max_paths = %llu > 2^22",
+                        (unsigned long long)(nrx * ntx * spec->max_paths));
+    return HRT_OK;
+}
+
+uint64_t hrt_dominant_out_bytes(size_t num_rx, size_t num_tx, const hrt_dominant_spec *spec)
+{
+    if (dominant_check(spec) || dominant_links_check(num_rx, num_tx, spec)) return 0;
+    return (uint64_t)num_rx * num_tx * (16u + (uint64_t)spec->max_paths * sizeof(hrt_dominant_path));
+}
+
+/* the chunking and scratch of one dominant call: a pure function of the problem, the shard and the spec; off[0 .. 3]
+ * are where la, ca, lb and cb start behind seg (hrt_dominant.h) */
+static int dm_plan(const hrt_problem *p, const hrt_shard *s, const hrt_dominant_spec *spec, hrt_kdominant *K,
+                   uint64_t *bytes, uint64_t off[4])
+{
+    int rc = dominant_check(spec);
+    if (rc) return rc;
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_dominant_paths", &K->v))) return rc;
+    if ((rc = dominant_links_check(K->v.nrx, K->v.ntx, spec))) return rc;
+    if (s->num_paths >> HRT_DM_PATH_BITS)
+        return hrt_fail(HRT_E_INVALID, "hrt_dominant_paths: num_paths = %llu >= 2^48",
+                        (unsigned long long)s->num_paths);
+    ps_shard(s, &K->sh);
+    K->K = spec->max_paths;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
+    const uint64_t per_chunk = links * (K->K * sizeof(hrt_dm_cand) + 8u);
+    (void)ps_chunks(&K->v, spec->parts, links, HRT_DM_TARGET_GROUPS, per_chunk, HRT_DM_PARTIAL_MAX,
+                    HRT_DM_MAX_CHUNKS);
+    K->nmid = K->v.nchunks > HRT_DM_FANIN ? (K->v.nchunks + HRT_DM_FANIN - 1u) / HRT_DM_FANIN : 0u;
+    off[0] = 0;
+    off[1] = off[0] + align256(links * K->v.nchunks * K->K * sizeof(hrt_dm_cand));
+    off[2] = off[1] + align256(links * K->v.nchunks * 8u);
+    off[3] = off[2] + align256(links * K->nmid * K->K * sizeof(hrt_dm_cand));
+    *bytes = ps_seg_bytes(&K->v) + off[3] + align256(links * K->nmid * 8u);
+    return HRT_OK;
+}
+
+int hrt_dominant_paths_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_dominant_spec *spec,
+                                     uint64_t *out)
+{
+    hrt_kdominant K;
+    uint64_t bytes = 0, off[4];
+    const int rc = dm_plan(p, s, spec, &K, &bytes, off);
+    return ps_scratch_out(rc, bytes, out, "hrt_dominant_paths_scratch_bytes");
+}
+
+int hrt_dominant_paths(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                       const hrt_dominant_spec *spec, void *d_scratch, uint64_t scratch_bytes, void *d_out,
+                       int accumulate, void *stream)
+{
+    hrt_kdominant K;
+    uint64_t need = 0, off[4];
+    int rc = dm_plan(p, s, spec, &K, &need, off);
+    if (rc) return rc;
+    float *partial = NULL;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_dominant_paths",
+                      "hrt_dominant_paths_scratch_bytes", &partial)))
+        return rc;
+    K.la = (hrt_dm_cand *)((uint8_t *)partial + off[0]);
+    K.ca = (uint64_t *)((uint8_t *)partial + off[1]);
+    K.lb = (hrt_dm_cand *)((uint8_t *)partial + off[2]);
+    K.cb = (uint64_t *)((uint8_t *)partial + off[3]);
+    K.out = (uint8_t *)d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_dominant(&K, stream), "dominant kernels");
+    return HRT_OK;
+}
+
+static int dm_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    return hrt_dominant_paths_scratch_bytes(p, s, j->spec, out);
+}
+
+static int dm_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
+{
+    return hrt_dominant_paths(p, s, d_ws, j->spec, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+/* the kept records' tri: the row of the device table -> the flat index of the reference's (mesh, face) loop */
+static int dm_job_finish(const ch_job *j, const hrt_problem *p, void *out)
+{
+    const hrt_dominant_spec *spec = j->spec;
+    const uint64_t links = (uint64_t)p->num_rx * p->num_tx;
+    const uint64_t *hdr = out;
+    hrt_dominant_path *recs = (hrt_dominant_path *)((uint8_t *)out + 16u * links);
+    for (uint64_t l = 0; l < links; ++l)
+        for (uint64_t k = 0; k < hdr[2 * l] && k < spec->max_paths; ++k) {
+            hrt_dominant_path *r = recs + l * spec->max_paths + k;
+            if (r->bounce >= 0 && r->tri < p->num_tri) r->tri = p->accel.orig[r->tri];
+        }
+    return HRT_OK;
+}
+
+int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                               const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                               const hrt_dominant_spec *spec, void *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = dominant_check(spec);
+    if (rc) return rc;
+    if ((rc = dominant_links_check(nrx, ntx, spec))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_dominant_paths")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = hrt_dominant_out_bytes(nrx, ntx, spec);
+    job.scratch_bytes = dm_job_scratch;
+    job.run = dm_job_run;
+    job.finish = dm_job_finish;
     return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
 }

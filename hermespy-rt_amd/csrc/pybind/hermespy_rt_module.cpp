@@ -29,6 +29,7 @@
 #include <pybind11/pybind11.h>
 
 #include <complex>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -248,8 +249,8 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
-// What the five path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
-// compute_power_profiles) share.  The counts and the four position / velocity arguments, checked ...
+// What the six path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
+// compute_power_profiles, compute_dominant_paths) share.  The counts and the four position / velocity arguments, checked ...
 struct endpoints {
     const Vec3 *rxp, *txp, *rxv, *txv;
     endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
@@ -495,6 +496,61 @@ py::dict compute_power_profiles_py(
     return d;
 }
 
+// compute_dominant_paths: the max_paths strongest paths of every link, selected on the device (extension; see
+// hrt_compute_dominant_paths in hermespy_rt.h): a dict of views of one buffer -- kept, eligible (num_rx, num_tx);
+// power, path, bounce, tri, tau, freq_shift (num_rx, num_tx, K); a_te, a_tm complex64 (num_rx, num_tx, K); u_rx, u_tx
+// (num_rx, num_tx, K, 3) -- and the buffer itself (uint8).
+py::dict compute_dominant_paths_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, unsigned long max_paths, bool los, bool scatter)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (max_paths > 0xffffffffUL)
+        throw py::value_error("hermespy_rt.compute_dominant_paths: max_paths must fit 32 bits");
+    check_scene_file(mesh_filepath);
+    hrt_dominant_spec spec{};
+    spec.max_paths = (uint32_t)max_paths;
+    spec.parts = parts_word(los, scatter);
+    // (the library validates the spec before it traces anything: a refused one raises ValueError and has no output)
+    const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &spec);
+    py::array_t<uint64_t> buf((size_t)(n ? n / 8u : 1u));   // (8-byte aligned words; 72 and 16 are multiples of 8)
+    uint8_t *dst = reinterpret_cast<uint8_t *>(buf.mutable_data());
+    run_pathsum("compute_dominant_paths", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_dominant_paths(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                          num_paths, num_bounces, &spec, dst, nullptr);
+    });
+    const py::ssize_t R = (py::ssize_t)num_rx, T = (py::ssize_t)num_tx, K = (py::ssize_t)max_paths;
+    const py::ssize_t rec = (py::ssize_t)sizeof(hrt_dominant_path);
+    uint8_t *recs = dst + 16 * R * T;
+    auto field = [&](auto *proto, size_t off) {
+        using V = std::remove_pointer_t<decltype(proto)>;
+        return py::array_t<V>({R, T, K}, {T * K * rec, K * rec, rec}, reinterpret_cast<V *>(recs + off), buf);
+    };
+    auto vec3 = [&](size_t off) {
+        return py::array_t<float>({R, T, K, (py::ssize_t)3}, {T * K * rec, K * rec, rec, (py::ssize_t)4},
+                                  reinterpret_cast<float *>(recs + off), buf);
+    };
+    auto header = [&](size_t word) {
+        return py::array_t<uint64_t>({R, T}, {T * 16, (py::ssize_t)16}, reinterpret_cast<uint64_t *>(dst) + word, buf);
+    };
+    py::dict d;
+    d["kept"] = header(0);
+    d["eligible"] = header(1);
+    d["power"] = field((double *)nullptr, offsetof(hrt_dominant_path, power));
+    d["path"] = field((uint64_t *)nullptr, offsetof(hrt_dominant_path, path));
+    d["bounce"] = field((int32_t *)nullptr, offsetof(hrt_dominant_path, bounce));
+    d["tri"] = field((uint32_t *)nullptr, offsetof(hrt_dominant_path, tri));
+    d["a_te"] = field((std::complex<float> *)nullptr, offsetof(hrt_dominant_path, a_te_re));
+    d["a_tm"] = field((std::complex<float> *)nullptr, offsetof(hrt_dominant_path, a_tm_re));
+    d["tau"] = field((float *)nullptr, offsetof(hrt_dominant_path, tau));
+    d["freq_shift"] = field((float *)nullptr, offsetof(hrt_dominant_path, freq_shift));
+    d["u_rx"] = vec3(offsetof(hrt_dominant_path, u_rx));
+    d["u_tx"] = vec3(offsetof(hrt_dominant_path, u_tx));
+    d["buffer"] = py::array_t<uint8_t>({(py::ssize_t)n}, {(py::ssize_t)1}, dst, buf);
+    return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(hermespy_rt, m)
@@ -562,6 +618,13 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("tau0"), py::arg("dtau"), py::arg("num_delay_bins"), py::arg("num_zenith_bins") = 0,
           py::arg("num_azimuth_bins") = 0, py::arg("los") = true, py::arg("scatter") = true);
+    m.def("compute_dominant_paths", &compute_dominant_paths_py,
+          "The max_paths strongest paths of every link, selected on the device: a dict of arrays (kept, eligible, "
+          "power, path, bounce, tri, a_te, a_tm, tau, freq_shift, u_rx, u_tx, buffer)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("max_paths"), py::arg("los") = true, py::arg("scatter") = true);
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

@@ -399,8 +399,8 @@ class Tracer:
         return out, scratch, torch.cuda.current_stream(self.device)
 
     def _pathsum(self, name, spec, shape, cache, out, accumulate, arrays=None, dtype=None, value_error=True):
-        """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps or
-        hrt_power_profiles): the scratch query, the buffers (scratch cache `cache`) and the entry on the current
+        """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
+        hrt_power_profiles or hrt_dominant_paths): the scratch query, the buffers (scratch cache `cache`) and the entry on the current
         stream.  `arrays`: what _elements prepared for the two array families.  A spec the library refuses raises
         ValueError, or HrtError where value_error is False."""
         extra = () if arrays is None else (C.byref(arrays[0]),)
@@ -527,6 +527,28 @@ class Tracer:
         out = self._pathsum("hrt_power_profiles", spec, shape, "_pw_scratch", out, accumulate,
                             dtype=self.torch.float64)
         return abi.power_views(out, self.nrx, self.ntx, spec)
+
+    def dominant_paths(self, max_paths, los=True, scatter=True, out=None, accumulate=False):
+        """The max_paths strongest paths of every link of the last trace, selected on the device (hrt_dominant_paths;
+        include/hermespy_rt.h hrt_dominant_path): the eligible terms are those of channel() (the LoS entry, shard rank
+        0 only, and every unblocked scatter record), ranked by the FP64 power |a_te|^2 + |a_tm|^2, ties by bounce
+        (LoS: -1) and then by global path, so the list does not depend on shards or on the device's record order.
+
+            kept, eligible                          [nrx, ntx]      records in the list / eligible terms
+            power, path, bounce, tri, tau, freq_shift  [nrx, ntx, K]   (tri: row of the device table, tri_order maps it)
+            a_te, a_tm                              [nrx, ntx, K]   complex64
+            u_rx, u_tx                              [nrx, ntx, K, 3]
+
+        Returns a dict of views of one flat uint8 device tensor (abi.dominant_views), itself under "buffer", enqueued
+        on the current stream; the slots past `kept` are zero bytes.  `out` (such a flat tensor) is written in place,
+        or, with accumulate=True, MERGED with: the first K of its records and this trace's terms, which is how the
+        shards of one launch set combine into the unsharded list.  Invalid arguments raise ValueError."""
+        spec = abi.dominant_spec(max_paths, los, scatter)
+        self.counts()
+        shape = (abi.dominant_out_bytes(self.nrx, self.ntx, spec),)
+        out = self._pathsum("hrt_dominant_paths", spec, shape, "_dm_scratch", out, accumulate,
+                            dtype=self.torch.uint8)
+        return abi.dominant_views(out, self.nrx, self.ntx, spec.max_paths)
 
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):

@@ -32,6 +32,7 @@ EXPORTED = (
     "hrt_taps_scratch_bytes", "hrt_taps", "hrt_compute_taps",
     "hrt_array_taps_scratch_bytes", "hrt_array_taps", "hrt_compute_array_taps",
     "hrt_power_out_doubles", "hrt_power_profiles_scratch_bytes", "hrt_power_profiles", "hrt_compute_power_profiles",
+    "hrt_dominant_out_bytes", "hrt_dominant_paths_scratch_bytes", "hrt_dominant_paths", "hrt_compute_dominant_paths",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -252,6 +253,17 @@ def load():
                                              C.c_size_t, C.c_size_t, C.c_size_t, pwp, C.POINTER(C.c_double),
                                              C.POINTER(Stats)]
     L.hrt_compute_power_profiles.restype = C.c_int
+    # the K strongest paths per link (hrt_dominant_spec: abi.DominantSpec)
+    dmp = C.POINTER(abi.DominantSpec)
+    L.hrt_dominant_out_bytes.argtypes = [C.c_size_t, C.c_size_t, dmp]
+    L.hrt_dominant_out_bytes.restype = u64
+    L.hrt_dominant_paths_scratch_bytes.argtypes = [vp, C.POINTER(Shard), dmp, C.POINTER(u64)]
+    L.hrt_dominant_paths_scratch_bytes.restype = C.c_int
+    L.hrt_dominant_paths.argtypes = [vp, C.POINTER(Shard), vp, dmp, vp, u64, vp, C.c_int, vp]
+    L.hrt_dominant_paths.restype = C.c_int
+    L.hrt_compute_dominant_paths.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                             C.c_size_t, C.c_size_t, C.c_size_t, dmp, vp, C.POINTER(Stats)]
+    L.hrt_compute_dominant_paths.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

@@ -317,6 +317,48 @@ int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
                                size_t num_rays, size_t num_bounces, const hrt_power_spec *spec,
                                double *out /* hrt_power_out_doubles, layout above */, hrt_stats *stats);
 
+/* The K strongest paths of every link, selected on the device (include/hrt_device.h: hrt_dominant_paths): the short
+ * list of (gain, delay, Doppler, arrival and departure direction) a link-level simulator builds a sparse channel
+ * from, instead of the full path list.  The ELIGIBLE terms of a link are exactly the terms hrt_channel sums (the same
+ * `parts`): the LoS entry (shard rank 0, LoS not blocked) and every unblocked scatter record of every bounce; blocked
+ * records are not eligible and are not counted.  The ranking quantity is the FP64 value
+ *     power = ((double)te_re*te_re + (double)te_im*te_im) + ((double)tm_re*tm_re + (double)tm_im*tm_im)
+ * of the float amplitudes (every product exact, denormal amplitudes kept; the LoS entry has a_te = a_tm = (a, 0)).
+ * Term A precedes term B if power_A > power_B, or the powers are equal and bounce_A < bounce_B, or powers and bounces
+ * are equal and path_A < path_B; bounce is -1 for the LoS entry and path is the GLOBAL path index (the one
+ * hrt_compute_paths_list reports), so within a link the order is strict and does not depend on shards, batches or
+ * the order the device visits the records in.
+ * A kept term is a record of 72 bytes.  Its float fields are bit for bit the floats the other families sum:
+ * freq_shift the float difference FS0 - DFS, u_rx the record's directions_rx, u_tx the launch direction of the
+ * record's ray; the LoS entry has u_tx = HRT_LOS_DIR and u_rx = -u_tx (the sign bit of every component flipped), a
+ * coincident one a = 1, tau = freq_shift = 0, u_tx = (-1, 0, 0), u_rx = (1, -0, -0).  `tri` is the triangle the ray left towards the RX: here the flat index in
+ * the reference's (mesh, face) loop order (in the device-resident entry: the row of the device table, see
+ * hrt_device.h).
+ * out: hrt_dominant_out_bytes bytes (0 for a NULL or refused spec): a header uint64_t [L][2] = {kept, eligible} per
+ * link (L = num_rx * num_tx), then hrt_dominant_path [L][K], K = max_paths.  Within a link the first
+ * kept = min(K, eligible) slots are the first `kept` eligible terms in the order above and the remaining slots are
+ * all-zero bytes: the whole buffer is a function of the inputs.
+ * hrt_compute_dominant_paths traces and batches like hrt_compute_channel (one device, one download at the end; the
+ * batches are merged on the device).  HRT_E_INVALID, before the device is touched: NULL spec; max_paths 0 or > 1024;
+ * parts 0 or with unknown bits; num_rx * num_tx > 65535; num_rx * num_tx * max_paths > 2^22. */
+typedef struct {
+    double power;
+    uint64_t path;            /* global path; LoS: UINT64_MAX */
+    int32_t bounce;           /* LoS: -1 */
+    uint32_t tri;             /* LoS: UINT32_MAX */
+    float a_te_re, a_te_im, a_tm_re, a_tm_im, tau, freq_shift;
+    float u_rx[3], u_tx[3];
+} hrt_dominant_path;
+typedef struct {
+    uint32_t max_paths;                         /* K */
+    uint32_t parts;                             /* HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER */
+} hrt_dominant_spec;
+uint64_t hrt_dominant_out_bytes(size_t num_rx, size_t num_tx, const hrt_dominant_spec *spec);
+int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                               const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                               size_t num_rays, size_t num_bounces, const hrt_dominant_spec *spec,
+                               void *out /* hrt_dominant_out_bytes, layout above */, hrt_stats *stats);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

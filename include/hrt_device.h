@@ -369,6 +369,26 @@ int hrt_power_profiles_scratch_bytes(const hrt_problem *p, const hrt_shard *s, c
 int hrt_power_profiles(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_power_spec *spec,
                        void *d_scratch, uint64_t scratch_bytes, double *d_out, int accumulate, void *stream);
 
+/* ---- the K strongest paths per link from the traced paths (csrc/host/channel.c, csrc/hrt_dominant.hip) ----
+ * header and records as hermespy_rt.h defines them (hrt_dominant_spec, hrt_dominant_path,
+ * hrt_compute_dominant_paths), hrt_dominant_out_bytes bytes at d_out, selected from the workspace of a finished
+ * hrt_trace (its counts read on the device: no host synchronisation), asynchronous on `stream`.  Here `tri` is the
+ * ROW of the device table (HRT_HIT_TRI; hrt_problem_tri_order translates it to the reference's flat index).
+ * accumulate = 0 overwrites d_out; accumulate = 1 MERGES: the new list of a link is the first K of (the records
+ * d_out already holds, united with this call's eligible terms) and `eligible` is added to what d_out holds.  A term
+ * in the first K of a union is in the first K of its part, and only shard rank 0 contributes the LoS entry, so the
+ * shards and batches of one launch set, merged in any order, give byte for byte the unsharded result.  The candidate
+ * lists go to the caller's scratch (hrt_dominant_paths_scratch_bytes); no floating-point atomics, and the result is
+ * a function of the set of terms only, so two calls with the same inputs give the same bits; the output is
+ * undefined if the trace's error word is set.
+ * HRT_E_INVALID, before the device is touched: every hrt_compute_dominant_paths check; num_paths of the shard
+ * >= 2^48; scratch too small. */
+int hrt_dominant_paths_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_dominant_spec *spec,
+                                     uint64_t *out);
+int hrt_dominant_paths(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                       const hrt_dominant_spec *spec, void *d_scratch, uint64_t scratch_bytes, void *d_out,
+                       int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
