@@ -254,7 +254,7 @@
                         stf(rec, R_A1 * cap4, i4, o1);
                         stf(rec, R_A2 * cap4, i4, o2);
                         stf(rec, R_A3 * cap4, i4, o3);
-                        stf(rec, R_TAU * cap4, i4, tau[k] + d2rx / kC);
+                        stf(rec, R_TAU * cap4, i4, tau[k] + div_c(d2rx));
                         stf(rec, R_DX * cap4, i4, -w.x);
                         stf(rec, R_DY * cap4, i4, -w.y);
                         stf(rec, R_DZ * cap4, i4, -w.z);

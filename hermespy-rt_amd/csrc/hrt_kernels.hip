@@ -64,6 +64,16 @@ constexpr float kEps = 1.1920928955078125e-07f;             // FLT_EPSILON
 constexpr float kOnePlusEps = 1.00000011920928955078125f;   // next float after 1
 constexpr float kPi = 3.14159265358979323846f;              // src/compute_paths.c:18 (float)
 constexpr float kC = 299792458.0f;                          // src/compute_paths.c:19
+constexpr float kInvC = 1.0f / kC;
+// a / kC for a distance: the rounded product with 1/kC, corrected once by its exact residual, is the correctly
+// rounded quotient -- compared with `/` for every float of [2^-60, 2^40) and for 0 (tests/test_division_by_c.py);
+// three instructions instead of the eleven of an IEEE division
+__device__ __forceinline__ float div_c(float a)
+{
+    const float q = a * kInvC;
+    const float r = __builtin_fmaf(-q, kC, a);
+    return __builtin_fmaf(r, kInvC, q);
+}
 constexpr uint32_t kErrFuseTimeout = HRT_ERR_FUSE_TIMEOUT;   // bit of the trace's error word (counts[nb + 1]): see lb_exclusive
 constexpr uint32_t kErrChainTimeout = HRT_ERR_CHAIN_TIMEOUT;   // ... the same from hrt_chain_kernel (its grid was not resident)
 constexpr uint32_t kErrVoid = kErrFuseTimeout | kErrChainTimeout;   // either: the step is void, every kernel of it returns at once
@@ -729,28 +739,40 @@ __device__ __forceinline__ Rsrc make_rsrc(const uint8_t *base)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, 0xffffffff, 0x00020000);
 }
 
-// bitwise OR of eight 32-bit words over the wave (eight interleaved in-place DPP chains: the chains fill
-// each other's read-after-write wait states), wave-uniform results
+// bitwise OR of eight 32-bit words over the wave, wave-uniform results.  The eight registers are folded into two
+// first: a half-wave swap (v_permlane32_swap: the upper 32 lanes of one register against the lower 32 of the other)
+// and an OR leave word k in the lower and word k + 4 in the upper half of one register, a row swap
+// (v_permlane16_swap: the odd 16-lane rows of one against the even rows of the other) and an OR then leave words
+// k, k + 2, k + 4, k + 6 in the four rows of one.  Four row-shift DPP steps on the two registers that remain put a
+// row's union into its last lane: 8 DPP + 6 swaps + 6 ORs instead of 48 DPP steps.
 __device__ __forceinline__ void wave_or256(uint32_t (&w)[8])
 {
-#define HRT_OR8(CTRL)                                                   \
-        "v_or_b32_dpp %0, %0, %0 " CTRL "\n" "v_or_b32_dpp %1, %1, %1 " CTRL "\n"  \
-        "v_or_b32_dpp %2, %2, %2 " CTRL "\n" "v_or_b32_dpp %3, %3, %3 " CTRL "\n"  \
-        "v_or_b32_dpp %4, %4, %4 " CTRL "\n" "v_or_b32_dpp %5, %5, %5 " CTRL "\n"  \
-        "v_or_b32_dpp %6, %6, %6 " CTRL "\n" "v_or_b32_dpp %7, %7, %7 " CTRL "\n"
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // c[k]: lanes 0-31 hold w[k] of lanes i and i + 32, lanes 32-63 w[k + 4]
+        const auto r = __builtin_amdgcn_permlane32_swap(w[k], w[k + 4], false, false);
+        c[k] = (uint32_t)r[0] | (uint32_t)r[1];
+    }
+    uint32_t e[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {   // e[k]: row q holds w[k + 2q] of four lanes
+        const auto r = __builtin_amdgcn_permlane16_swap(c[k], c[k + 2], false, false);
+        e[k] = (uint32_t)r[0] | (uint32_t)r[1];
+    }
+    // (two chains only: an s_nop 0 beside the other chain's step makes the two wait states between a write and the
+    // DPP read of it)
+#define HRT_OR2(CTRL) "v_or_b32_dpp %0, %0, %0 " CTRL "\n" "v_or_b32_dpp %1, %1, %1 " CTRL "\n" "s_nop 0\n"
     asm volatile(
         "s_nop 4\n"
-        HRT_OR8("row_shr:1 row_mask:0xf bank_mask:0xf")
-        HRT_OR8("row_shr:2 row_mask:0xf bank_mask:0xf")
-        HRT_OR8("row_shr:4 row_mask:0xf bank_mask:0xf")
-        HRT_OR8("row_shr:8 row_mask:0xf bank_mask:0xf")
-        HRT_OR8("row_bcast:15 row_mask:0xa bank_mask:0xf")
-        HRT_OR8("row_bcast:31 row_mask:0xc bank_mask:0xf")
+        HRT_OR2("row_shr:1 row_mask:0xf bank_mask:0xf")
+        HRT_OR2("row_shr:2 row_mask:0xf bank_mask:0xf")
+        HRT_OR2("row_shr:4 row_mask:0xf bank_mask:0xf")
+        HRT_OR2("row_shr:8 row_mask:0xf bank_mask:0xf")
         "s_nop 1\n"
-        : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
-#undef HRT_OR8
+        : "+v"(e[0]), "+v"(e[1]));
+#undef HRT_OR2
 #pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = (uint32_t)__builtin_amdgcn_readlane((int)w[k], 63);
+    for (int k = 0; k < 8; ++k) w[k] = (uint32_t)__builtin_amdgcn_readlane((int)e[k & 1], 15 + 16 * (k >> 1));
 }
 
 // image of the point t in the plane of the triangle (v1 = q0.xyz, unit normal n = q2.yzw) -- the kernel
@@ -810,32 +832,28 @@ __device__ __forceinline__ PatchRef patch_locate(TriPtr tri, const hrt_kpatch &X
     return R;
 }
 
-// the mask words of a located lane for apex `apex_k` (a lane that is not served: the whole table; a lane past the
-// end of the list: nothing) -- a request only: nothing waits for the loads here
-__device__ __forceinline__ void patch_load(const hrt_kpatch &X, const PatchRef R, uint32_t apex_k, uint32_t num_tri, bool valid,
-                                           uint32_t (&w)[8])
+// the mask words of a located lane for apex `apex_k` (a lane that is not served or past the end of the list: nothing
+// -- a wave with a valid lane that is not served walks the whole table, which closest_hit_words adds to the union
+// from `patch_whole`) -- a request only: nothing waits for the loads here
+__device__ __forceinline__ void patch_load(const hrt_kpatch &X, const PatchRef R, uint32_t apex_k, bool valid, uint32_t (&w)[8])
 {
 #pragma unroll
     for (int k = 0; k < 8; ++k) w[k] = 0u;
-    if (valid) {
-        if (R.served) {
-            const Rsrc mr = make_rsrc(reinterpret_cast<const uint8_t *>(X.mask));
-            const uint32_t off = R.off + apex_k * X.num_patch * (HRT_PATCH_WORDS * 8u);
-            const auto a = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)off, 0, 0);
-            const auto b = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)(off + 16u), 0, 0);
-            w[0] = (uint32_t)a[0]; w[1] = (uint32_t)a[1]; w[2] = (uint32_t)a[2]; w[3] = (uint32_t)a[3];
-            w[4] = (uint32_t)b[0]; w[5] = (uint32_t)b[1]; w[6] = (uint32_t)b[2]; w[7] = (uint32_t)b[3];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                w[k] = num_tri >= 32u * (uint32_t)(k + 1) ? ~0u : (num_tri > 32u * (uint32_t)k ? (1u << (num_tri - 32u * (uint32_t)k)) - 1u : 0u);
-        }
+    if (valid && R.served) {
+        const Rsrc mr = make_rsrc(reinterpret_cast<const uint8_t *>(X.mask));
+        const uint32_t off = R.off + apex_k * X.num_patch * (HRT_PATCH_WORDS * 8u);
+        const auto a = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)off, 0, 0);
+        const auto b = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)(off + 16u), 0, 0);
+        w[0] = (uint32_t)a[0]; w[1] = (uint32_t)a[1]; w[2] = (uint32_t)a[2]; w[3] = (uint32_t)a[3];
+        w[4] = (uint32_t)b[0]; w[5] = (uint32_t)b[1]; w[6] = (uint32_t)b[2]; w[7] = (uint32_t)b[3];
     }
 }
+// some valid lane of the wave is not served (wave-uniform; it holds for every apex of the entry)
+__device__ __forceinline__ bool patch_whole(const PatchRef R, bool valid) { return HRT_BALLOT(valid && !R.served) != 0ull; }
 
 // the trace of a wave from its lanes' mask words: the union over the wave, walked through the staged test
 template <typename TriPtr, typename OrigPtr>
-__device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint32_t (&w)[8], uint32_t num_tri,
+__device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint32_t (&w)[8], const bool whole, uint32_t num_tri,
                                                  F3 o, F3 d, bool valid, uint32_t lane, [[maybe_unused]] int kind)
 {
     float best = 1e9f;
@@ -843,6 +861,11 @@ __device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint3
     const unsigned long long inval = HRT_BALLOT(!valid);
     if (inval == ~0ull) return {who, best};
     wave_or256(w);
+    if (whole) {   // (wave-uniform, on the union in scalar registers: every row of the table)
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            w[k] |= num_tri >= 32u * (uint32_t)(k + 1) ? ~0u : (num_tri > 32u * (uint32_t)k ? (1u << (num_tri - 32u * (uint32_t)k)) - 1u : 0u);
+    }
     HRT_STAT(kind, 0, 1);
     HRT_STAT(kind, 1, 1);
 #pragma unroll
@@ -855,7 +878,6 @@ __device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint3
             HRT_STAGED_BODY(j)
         }
     }
-    (void)num_tri;
     return {who, best};
 }
 
@@ -866,9 +888,9 @@ __device__ __forceinline__ Hit closest_hit_patch(TriPtr tri, OrigPtr orig, const
                                                  bool valid, uint32_t lane, [[maybe_unused]] int kind)
 {
     uint32_t w[8];
-    patch_load(X, R, apex_k, num_tri, valid, w);
+    patch_load(X, R, apex_k, valid, w);
     HRT_STAT(kind, 6, (valid && R.served) ? 1 : 0);
-    return closest_hit_words(tri, orig, w, num_tri, o, d, valid, lane, kind);
+    return closest_hit_words(tri, orig, w, patch_whole(R, valid), num_tri, o, d, valid, lane, kind);
 }
 
 // launch 0 on patch-table problems: the ray leaves TX `tx` exactly (o == its position), so its candidates are the
@@ -888,7 +910,7 @@ __device__ __forceinline__ Hit closest_hit_txcell(TriPtr tri, OrigPtr orig, cons
         w[0] = (uint32_t)a[0]; w[1] = (uint32_t)a[1]; w[2] = (uint32_t)a[2]; w[3] = (uint32_t)a[3];
         w[4] = (uint32_t)b[0]; w[5] = (uint32_t)b[1]; w[6] = (uint32_t)b[2]; w[7] = (uint32_t)b[3];
     }
-    return closest_hit_words(tri, orig, w, num_tri, o, d, valid, lane, 0);
+    return closest_hit_words(tri, orig, w, false, num_tri, o, d, valid, lane, 0);
 }
 
 template <bool MULTI, typename TriPtr>
@@ -2681,7 +2703,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
                             stf(rec_blk(P, pb, rx), R_A1 * cap4, i4, o1);
                             stf(rec_blk(P, pb, rx), R_A2 * cap4, i4, o2);
                             stf(rec_blk(P, pb, rx), R_A3 * cap4, i4, o3);
-                            stf(rec_blk(P, pb, rx), R_TAU * cap4, i4, tau + d2rx / kC);
+                            stf(rec_blk(P, pb, rx), R_TAU * cap4, i4, tau + div_c(d2rx));
                             stf(rec_blk(P, pb, rx), R_DX * cap4, i4, -w.x);
                             stf(rec_blk(P, pb, rx), R_DY * cap4, i4, -w.y);
                             stf(rec_blk(P, pb, rx), R_DZ * cap4, i4, -w.z);
@@ -2969,7 +2991,10 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
         }
 #if HRT_RECORDS_PREFETCH
         uint32_t wnext[8];   // the masks of the NEXT RX are requested before this RX's walk (a global gather: ~1-2 us)
-        patch_load(P.patch, ref, 0u, T, valid, wnext);
+        patch_load(P.patch, ref, 0u, valid, wnext);
+        // (once per entry: the whole table for a wave with a valid lane that is not served.  Taking two register sets
+        // in turn in a loop unrolled by two, to spare the copy below, costs 48 B of scratch)
+        const bool whole = patch_whole(ref, valid);
 #endif
         for (uint32_t rx = 0; rx < P.num_rx; ++rx) {
             const float4 rp = l_rx[rx];
@@ -2980,8 +3005,8 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
             uint32_t wcur[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) wcur[q] = wnext[q];
-            if (rx + 1u < P.num_rx) patch_load(P.patch, ref, rx + 1u, T, valid, wnext);
-            const Hit h = closest_hit_words(tri, l_orig, wcur, T, o, w, valid, lane, 2);
+            if (rx + 1u < P.num_rx) patch_load(P.patch, ref, rx + 1u, valid, wnext);
+            const Hit h = closest_hit_words(tri, l_orig, wcur, whole, T, o, w, valid, lane, 2);
 #else
             const Hit h = closest_hit_patch(tri, l_orig, P.patch, ref, rx, T, o, w, valid, lane, 2);
 #endif
@@ -3012,7 +3037,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
                     stf(rec_blk(P, pb, rx), R_A1 * cap4, i4, o1);
                     stf(rec_blk(P, pb, rx), R_A2 * cap4, i4, o2);
                     stf(rec_blk(P, pb, rx), R_A3 * cap4, i4, o3);
-                    stf(rec_blk(P, pb, rx), R_TAU * cap4, i4, tau + d2rx / kC);
+                    stf(rec_blk(P, pb, rx), R_TAU * cap4, i4, tau + div_c(d2rx));
                     stf(rec_blk(P, pb, rx), R_DX * cap4, i4, -w.x);
                     stf(rec_blk(P, pb, rx), R_DY * cap4, i4, -w.y);
                     stf(rec_blk(P, pb, rx), R_DZ * cap4, i4, -w.z);
@@ -4031,11 +4056,50 @@ __global__ void hrt_fs0_kernel(const float *dirs, uint64_t n, float vx, float vy
     out[i] = dot3(tv, d) * mult;
 }
 
+// fn >= 8 of the selftest: thread i works on item i of n / K, floats [K i, K i + K) of `in` and of `out` (words are
+// carried as the bits of floats).  Whole waves call the wave primitives: a lane past the last item brings zeros.
+//    8  K = 8  wave_or256: the lane's eight mask words -> the wave's union (the same in every lane of the wave)
+//    9  K = 1  div_c
+//   10  K = 4  (s, alpha, th_s, th_i) -> scatter_pattern
+__device__ __forceinline__ void selftest_items(int fn, const float *in, float *out, uint64_t n, uint64_t i)
+{
+    const uint64_t K = fn == 8 ? 8u : (fn == 9 ? 1u : 4u);
+    const uint64_t items = n / K;
+    if ((i & ~(uint64_t)63) >= items) return;   // (a whole wave)
+    const bool live = i < items;
+    float x[8];
+#pragma unroll
+    for (uint64_t k = 0; k < 8; ++k) x[k] = (live && k < K) ? in[K * i + k] : 0.f;
+    float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (fn == 8) {
+        uint32_t w[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = __float_as_uint(x[k]);
+        wave_or256(w);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) y[k] = __uint_as_float(w[k]);
+    } else if (fn == 9) {
+        y[0] = div_c(x[0]);
+    } else if (live) {
+        const float4 S = scatter_pattern(x[0], x[1], x[2], x[3]);
+        y[0] = S.x; y[1] = S.y; y[2] = S.z; y[3] = S.w;
+    }
+    if (live) {
+#pragma unroll
+        for (uint64_t k = 0; k < 8; ++k)
+            if (k < K) out[K * i + k] = y[k];
+    }
+}
+
 // evaluates one of the hrt_libm.h functions (or the incidence-angle acos) over an array: the
 // GPU side of tests/test_gpu_libm.py
 __global__ void hrt_selftest_math_kernel(int fn, const float *in, float *out, uint64_t n)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (fn >= 8) {   // the primitives of the patch-mask and record kernels: K floats in and K floats out per item
+        selftest_items(fn, in, out, n, i);
+        return;
+    }
     if (i >= n) return;
     const float x = in[i];
     float y;

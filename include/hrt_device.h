@@ -415,7 +415,12 @@ int hrt_scene_import_sionna(const char *xml_path, Scene *out);
  * -- or, fn 4, the incidence angle of src/compute_paths.c:281-283 for dot(n, d) = in[i]
  * ((float)acos((double)x) folded to [0, pi/2]); fn 5 / 6 the sine / cosine of the fused
  * hrt_sincosf and fn 7 hrt_cosf_nb (the branch-free forms the shade kernel calls).  Tests compare
- * the result with the host libm. */
+ * the result with the host libm.
+ * fn 8 .. 10 evaluate primitives of the patch-mask and record kernels on items of K floats, n / K items,
+ * floats [K i, K i + K) of `in` and of `out` belonging to item i (64 consecutive items share a wave):
+ * fn 8, K = 8: the bitwise OR over the wave of the item's eight 32-bit words (carried as float bits);
+ * fn 9, K = 1: in / c, c the float speed of light; fn 10, K = 4: (s, alpha, theta_s, theta_i) -> the
+ * four scattering pattern terms of src/compute_paths.c:359-415. */
 int hrt_selftest_math(int device, int fn, const float *in, float *out, uint64_t n);
 
 /* Diagnostic counters of the trace kernel; all zero unless the library was built with
