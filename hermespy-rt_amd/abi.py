@@ -313,8 +313,8 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                  out_shape, extra, stats, dtype=np.complex64):
-    """One of the six path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
-    _power_profiles or _dominant_paths) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
+    """One of the seven path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
+    _power_profiles, _dominant_paths or _beam_channel) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
     (a flat buffer of out_shape doubles for float64 or bytes for uint8; out_shape None: a placeholder the library
     refuses to write); `extra` are the arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
@@ -388,6 +388,42 @@ def run_compute_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f
     shape = (max(nr, 1), max(nt, 1), 2, max(int(spec.num_times), 1), max(int(spec.num_freqs), 1))
     return _run_pathsum(lib, "hrt_compute_array_channel", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, shape if 0 < pts <= (1 << 24) else None, extra, stats)
+
+class BeamSpec(C.Structure):
+    """include/hrt_device.h hrt_beam_spec (the weight pointers are device pointers)"""
+    _fields_ = [("num_rx_beams", C.c_uint32), ("num_tx_beams", C.c_uint32),
+                ("rx_weights", C.c_void_p), ("tx_weights", C.c_void_p)]
+
+
+def weights(w, n_elements, name):
+    """a codebook as a contiguous complex64 [beams, n_elements] numpy array (beams >= 0; the library checks the
+    limits): one row per beam; a 1-D array of n_elements weights is one beam"""
+    a = np.asarray(w)
+    if a.dtype.kind not in "fc":
+        raise ValueError("%s must be a real or complex floating-point array, got %s" % (name, a.dtype))
+    a = np.ascontiguousarray(a, np.complex64)
+    if a.ndim == 1 and a.size == n_elements:
+        a = a.reshape(1, n_elements)
+    if a.ndim != 2 or a.shape[1] != n_elements:
+        raise ValueError("%s must have shape (beams, %d), got %s" % (name, n_elements, a.shape))
+    return a
+
+
+def run_compute_beam_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                             rx_elements, tx_elements, rx_weights, tx_weights, array_frequency=None, stats=None):
+    """hrt_compute_beam_channel through ctypes -> complex64 [nrx, ntx, Br, Bt, 2, num_times, num_freqs]: rx_weights
+    (Br, Nr) is applied conjugated (the combiner w^H), tx_weights (Bt, Nt) as it is; array_frequency defaults to the
+    carrier.  Raises RuntimeError("hrt_compute_beam_channel failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    wr, wt = weights(rx_weights, nr, "rx_weights"), weights(tx_weights, nt, "tx_weights")
+    br, bt = wr.shape[0], wt.shape[0]
+    extra += (wr.ctypes.data_as(c_float_p), C.c_size_t(br), wt.ctypes.data_as(c_float_p), C.c_size_t(bt))
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    pts = br * bt * int(spec.num_times) * int(spec.num_freqs)
+    shape = (br, bt, 2, int(spec.num_times), int(spec.num_freqs))
+    return _run_pathsum(lib, "hrt_compute_beam_channel", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, shape if 0 < pts <= (1 << 24) else None, extra, stats)
+
 
 class TapsSpec(C.Structure):
     """include/hermespy_rt.h hrt_taps_spec"""

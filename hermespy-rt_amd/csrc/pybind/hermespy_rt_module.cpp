@@ -249,8 +249,8 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
-// What the six path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
-// compute_power_profiles, compute_dominant_paths) share.  The counts and the four position / velocity arguments, checked ...
+// What the seven path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
+// compute_power_profiles, compute_dominant_paths, compute_beam_channel) share.  The counts and the four position / velocity arguments, checked ...
 struct endpoints {
     const Vec3 *rxp, *txp, *rxv, *txv;
     endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
@@ -366,6 +366,55 @@ py::array_t<std::complex<float>> compute_array_channel_py(
     run_pathsum("compute_array_channel", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_array_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                          num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
+    });
+    return out;
+}
+
+// a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
+using carr = py::array_t<std::complex<float>, py::array::c_style>;
+carr as_weights(const py::array &w, size_t n_elements, const char *name)
+{
+    if (!py::isinstance<py::array_t<std::complex<float>>>(w) || w.ndim() != 2 || (size_t)w.shape(1) != n_elements)
+        throw std::invalid_argument(std::string(name) + " must be a complex64 array of shape (beams, " +
+                                    std::to_string(n_elements) + ")");
+    return carr::ensure(w);
+}
+
+// compute_beam_channel: the beamformed (codebook) channel of the traced paths, formed on the device (extension; see
+// hrt_compute_beam_channel in hermespy_rt.h): complex64 (num_rx, num_tx, Br, Bt, 2, num_times, num_freqs) =
+// sum_ij conj(rx_weights[a, i]) H[..., i, j, ...] tx_weights[b, j] of compute_array_channel's H, which is never formed.
+py::array_t<std::complex<float>> compute_beam_channel_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    py::array rx_weights, py::array tx_weights, double t0, double dt, unsigned long num_times, bool los, bool scatter,
+    py::object array_frequency)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_freqs and num_times must fit 32 bits");
+    const array_elements a(rx_elements, tx_elements);
+    const carr wr = as_weights(rx_weights, a.nr, "rx_weights"), wt = as_weights(tx_weights, a.nt, "tx_weights");
+    const size_t br = (size_t)wr.shape(0), bt = (size_t)wt.shape(0);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
+    // beyond the 2^24 points of the limit would be refused, so only one within it is allocated.)
+    const unsigned long long pts = (unsigned long long)br * bt * num_times * num_freqs;
+    const bool fits = pts > 0 && pts <= (1ull << 24) && br <= 256 && bt <= 256;
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, br, bt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_freqs}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const float *pwr = reinterpret_cast<const float *>(wr.data()), *pwt = reinterpret_cast<const float *>(wt.data());
+    run_pathsum("compute_beam_channel", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_beam_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                        num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, pwr, br, pwt, bt, dst,
+                                        nullptr);
     });
     return out;
 }
@@ -591,6 +640,17 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
           py::arg("scatter") = true, py::arg("array_frequency") = py::none());
+    m.def("compute_beam_channel", &compute_beam_channel_py,
+          "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
+          "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "
+          "(Bt, Nt) as it is",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("rx_weights"), py::arg("tx_weights"), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("array_frequency") = py::none());
     m.def("compute_taps", &compute_taps_py,
           "Sampled channel impulse response of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, 2, num_times, num_taps)",

@@ -400,10 +400,11 @@ class Tracer:
 
     def _pathsum(self, name, spec, shape, cache, out, accumulate, arrays=None, dtype=None, value_error=True):
         """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
-        hrt_power_profiles or hrt_dominant_paths): the scratch query, the buffers (scratch cache `cache`) and the entry on the current
-        stream.  `arrays`: what _elements prepared for the two array families.  A spec the library refuses raises
+        hrt_power_profiles, hrt_dominant_paths or hrt_beam_channel): the scratch query, the buffers (scratch cache
+        `cache`) and the entry on the current stream.  `arrays`: what _elements prepared for the array families, the
+        specs that follow `spec` and last the device tensor they point into.  A spec the library refuses raises
         ValueError, or HrtError where value_error is False."""
-        extra = () if arrays is None else (C.byref(arrays[0]),)
+        extra = () if arrays is None else tuple(C.byref(a) for a in arrays[:-1])
         need = C.c_uint64(0)
         rc = getattr(self.L, name + "_scratch_bytes")(self.problem, C.byref(self.shard), C.byref(spec), *extra,
                                                       C.byref(need))
@@ -416,12 +417,13 @@ class Tracer:
                                          C.c_uint64(scratch.numel()), C.c_void_p(out.data_ptr()),
                                          1 if accumulate else 0, C.c_void_p(stream.cuda_stream)), name)
         if arrays is not None:
-            arrays[1].record_stream(stream)   # (the kernels read the offsets after this call returns)
+            arrays[-1].record_stream(stream)   # (the kernels read the offsets after this call returns)
         return out
 
     def _elements(self, rx_elements, tx_elements, array_frequency):
         """The element arguments of an array call, checked -> (Nr, Nt, upload): upload() puts the offsets on the
-        device and returns the (ArraySpec, device tensor it points into) that _pathsum takes."""
+        device and returns the (ArraySpec, device tensor it points into) that _pathsum takes; with a codebook pair,
+        (ArraySpec, BeamSpec, device tensor)."""
         re = abi.elements(rx_elements.cpu().numpy() if hasattr(rx_elements, "cpu") else rx_elements, "rx_elements")
         te = abi.elements(tx_elements.cpu().numpy() if hasattr(tx_elements, "cpu") else tx_elements, "tx_elements")
         if not (np.isfinite(re).all() and np.isfinite(te).all()):
@@ -429,10 +431,19 @@ class Tracer:
         nr, nt = re.shape[0], te.shape[0]
         fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
 
-        def upload():
+        def upload(weights=None):
+            """weights: (W_rx [Br, Nr], W_tx [Bt, Nt]) complex64, uploaded behind the offsets (beam_channel)"""
+            parts = [re.reshape(-1), te.reshape(-1)]
+            if weights is not None:
+                parts += [w.view(np.float32).reshape(-1) for w in weights]
             with self.torch.cuda.device(self.device):
-                d_el = self.torch.from_numpy(np.concatenate([re, te]).reshape(-1)).to(self.device)
-            return abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa), d_el
+                d_el = self.torch.from_numpy(np.concatenate(parts)).to(self.device)
+            arrays = abi.ArraySpec(nr, nt, d_el.data_ptr(), d_el.data_ptr() + 12 * nr, fa)
+            if weights is None:
+                return arrays, d_el
+            at = d_el.data_ptr() + 12 * (nr + nt)
+            beams = abi.BeamSpec(weights[0].shape[0], weights[1].shape[0], at, at + 8 * weights[0].size)
+            return arrays, beams, d_el
 
         return nr, nt, upload
 
@@ -470,6 +481,31 @@ class Tracer:
         self.counts()
         shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_freqs))
         return self._pathsum("hrt_array_channel", spec, shape, "_ac_scratch", out, accumulate, upload())
+
+    def beam_channel(self, rx_elements, tx_elements, rx_weights, tx_weights, f0, df, num_freqs, t0=0.0, dt=0.0,
+                     num_times=1, los=True, scatter=True, array_frequency=None, out=None, accumulate=False):
+        """Beamformed (codebook) channel of the last trace, formed on the device (hrt_beam_channel): the channel after
+        the combiner w^H = conj(W_rx[a]) and the precoder f = W_tx[b],
+
+            B[rx, tx, a, b, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) g_rx[a](u_p^rx) g_tx[b](u_p^tx)
+            g_rx[a](u) = sum_i conj(W_rx[a, i]) exp(j 2 pi f_a r_i . u / c)
+            g_tx[b](u) = sum_j      W_tx[b, j]  exp(j 2 pi f_a q_j . u / c)
+
+        = sum_ij conj(W_rx[a, i]) H[rx, tx, i, j, pol, m, k] W_tx[b, j] with array_channel()'s H for the same elements,
+        without H being formed: the cost follows Br * Bt, not Nr * Nt (hermespy_rt_amd.beams.apply is the host form).
+        rx_elements (Nr, 3) / tx_elements (Nt, 3) as in array_channel(); rx_weights (Br, Nr) / tx_weights (Bt, Nt)
+        complex (numpy or torch), one codebook for all RX and one for all TX, not normalised.  Returns a complex64
+        tensor [nrx, ntx, Br, Bt, 2, num_times, num_freqs] on the device, enqueued on the current stream; `out` is
+        written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        wr = abi.weights(rx_weights.cpu().numpy() if hasattr(rx_weights, "cpu") else rx_weights, nr, "rx_weights")
+        wt = abi.weights(tx_weights.cpu().numpy() if hasattr(tx_weights, "cpu") else tx_weights, nt, "tx_weights")
+        if not (np.isfinite(wr.view(np.float32)).all() and np.isfinite(wt.view(np.float32)).all()):
+            raise ValueError("beam weights must be finite")
+        spec = abi.channel_spec(f0, df, num_freqs, t0, dt, num_times, los, scatter)
+        self.counts()
+        shape = (self.nrx, self.ntx, wr.shape[0], wt.shape[0], 2, int(num_times), int(num_freqs))
+        return self._pathsum("hrt_beam_channel", spec, shape, "_bm_scratch", out, accumulate, upload((wr, wt)))
 
     def taps(self, fs, num_taps, l_min=0, fc=None, t0=0.0, dt=0.0, num_times=1, los=True, scatter=True, out=None,
              accumulate=False):

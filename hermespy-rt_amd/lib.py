@@ -33,6 +33,7 @@ EXPORTED = (
     "hrt_array_taps_scratch_bytes", "hrt_array_taps", "hrt_compute_array_taps",
     "hrt_power_out_doubles", "hrt_power_profiles_scratch_bytes", "hrt_power_profiles", "hrt_compute_power_profiles",
     "hrt_dominant_out_bytes", "hrt_dominant_paths_scratch_bytes", "hrt_dominant_paths", "hrt_compute_dominant_paths",
+    "hrt_beam_channel_scratch_bytes", "hrt_beam_channel", "hrt_compute_beam_channel",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -264,6 +265,16 @@ def load():
     L.hrt_compute_dominant_paths.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
                                              C.c_size_t, C.c_size_t, C.c_size_t, dmp, vp, C.POINTER(Stats)]
     L.hrt_compute_dominant_paths.restype = C.c_int
+    # beamformed channel responses (hrt_array_spec and hrt_beam_spec: abi.BeamSpec)
+    bmp = C.POINTER(abi.BeamSpec)
+    L.hrt_beam_channel_scratch_bytes.argtypes = [vp, C.POINTER(Shard), spp, app, bmp, C.POINTER(u64)]
+    L.hrt_beam_channel_scratch_bytes.restype = C.c_int
+    L.hrt_beam_channel.argtypes = [vp, C.POINTER(Shard), vp, spp, app, bmp, vp, u64, vp, C.c_int, vp]
+    L.hrt_beam_channel.restype = C.c_int
+    L.hrt_compute_beam_channel.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                           C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                           f32p, C.c_size_t, f32p, C.c_size_t, f32p, C.POINTER(Stats)]
+    L.hrt_compute_beam_channel.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

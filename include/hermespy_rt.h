@@ -228,6 +228,30 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
                               size_t num_tx_elements, double array_frequency_hz,
                               float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Beamformed (codebook) channel responses of the traced paths, formed on the device (include/hrt_device.h:
+ * hrt_beam_channel): the channel after a combiner and a precoder from a codebook.  For every link, RX beam a < Br,
+ * TX beam b < Bt, polarisation and grid point:
+ *     B[rx][tx][a][b][pol][m][k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) g_rx[a](u_p^rx) g_tx[b](u_p^tx)
+ *     g_rx[a](u) = sum_i conj(W_rx[a][i]) exp(j 2 pi f_a r_i . u / c)      (combiner  w^H)
+ *     g_tx[b](u) = sum_j      W_tx[b][j]  exp(j 2 pi f_a q_j . u / c)      (precoder  f)
+ * which is sum_ij conj(W_rx[a][i]) H[rx][tx][i][j][pol][m][k] W_tx[b][j] with hrt_compute_array_channel's H for the
+ * same elements and f_a: the paths, parts, u^rx and u^tx are exactly its.  The weights are folded into each path's
+ * steering term, so H is never formed: the cost follows Br * Bt, not Nr * Nt, and Nr * Nt is not limited.  One
+ * codebook is shared by all RX and one by all TX (as the element geometries are); the weights are not normalised.
+ * out: complex [num_rx][num_tx][Br][Bt][2][num_times][num_freqs], re/im interleaved (numpy complex64).
+ * rx_elements / tx_elements: HOST arrays of Nr / Nt offsets; rx_weights / tx_weights: HOST arrays [Br][Nr][2] /
+ * [Bt][Nt][2] of (re, im) floats (numpy complex64 (Br, Nr) / (Bt, Nt)).  Traced and batched like hrt_compute_channel;
+ * only `out` is copied back.  HRT_E_INVALID, before the device is touched: every hrt_channel_spec check; Nr or Nt
+ * outside 1..256; Br or Bt outside 1..256; Br * Bt * num_times * num_freqs > 2^24; an offset, a weight or f_a not
+ * finite; f_a <= 0; a NULL pointer. */
+int hrt_compute_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                             const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                             size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                             const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                             size_t num_tx_elements, double array_frequency_hz, const float *rx_weights,
+                             size_t num_rx_beams, const float *tx_weights, size_t num_tx_beams,
+                             float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Sampled channel impulse responses (taps) of the traced paths, formed on the device (include/hrt_device.h:
  * hrt_taps).  For every (rx, tx), polarisation pol (0 = TE, 1 = TM), time sample m < num_times and tap i < num_taps:
  *     h[rx][tx][pol][m][i] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) sinc(l_i - f_s tau_p)

@@ -324,6 +324,29 @@ int hrt_array_channel(const hrt_problem *p, const hrt_shard *s, const void *d_wo
                       const hrt_channel_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
                       uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
 
+/* ---- beamformed (codebook) channel responses from the traced paths (csrc/host/channel.c, csrc/hrt_beam_channel.hip) ----
+ * B[rx][tx][a][b][pol][m][k] as hermespy_rt.h defines it (hrt_compute_beam_channel): hrt_array_channel's H contracted
+ * with the combiner conj(W_rx[a]) and the precoder W_tx[b], with the weights folded into every path's steering term on
+ * the device, so H is never formed and Nr * Nt is not limited.  Formed from the workspace of a finished hrt_trace,
+ * asynchronous on `stream`, with the guarantees of hrt_channel: accumulate = 0 overwrites d_out, 1 adds to it; only
+ * shard rank 0 adds the LoS term; partial sums and the LoS gains go to the caller's scratch
+ * (hrt_beam_channel_scratch_bytes) and are reduced in a fixed order, no floating-point atomics, so two calls with the
+ * same inputs give the same bits.  The element offsets (hrt_array_spec) and the weights are DEVICE pointers and are not
+ * read on the host: their finiteness is the caller's to ensure (the host entries check it).  One codebook is shared by
+ * all RX and one by all TX; the weights are not normalised.  HRT_E_INVALID, before the device is touched: every
+ * hrt_channel check; NULL arrays, beams, element or weight pointers; Nr or Nt outside 1..256; Br or Bt outside
+ * 1..256; Br * Bt * num_times * num_freqs > 2^24; f_a not finite or <= 0; 2^39 outputs or more; scratch too small. */
+typedef struct {
+    uint32_t num_rx_beams, num_tx_beams;         /* Br, Bt: 1 .. 256 */
+    const float *rx_weights;                     /* device [Br][Nr][2] (re, im): W_rx, applied conjugated (w^H) */
+    const float *tx_weights;                     /* device [Bt][Nt][2] (re, im): W_tx, applied as it is (f) */
+} hrt_beam_spec;
+int hrt_beam_channel_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec,
+                                   const hrt_array_spec *arrays, const hrt_beam_spec *beams, uint64_t *out);
+int hrt_beam_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                     const hrt_channel_spec *spec, const hrt_array_spec *arrays, const hrt_beam_spec *beams,
+                     void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
+
 /* ---- sampled channel impulse responses from the traced paths (csrc/host/channel.c, csrc/hrt_taps.hip) ----
  * h[rx][tx][pol][m][i] as hermespy_rt.h defines it (hrt_taps_spec, hrt_compute_taps), formed from the workspace of
  * a finished hrt_trace (its counts read on the device: no host synchronisation), asynchronous on `stream`, with the
