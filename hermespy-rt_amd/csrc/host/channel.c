@@ -10,9 +10,11 @@
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
  * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip, csrc/hrt_power.hip,
- * csrc/hrt_dominant.hip and csrc/hrt_beam_channel.hip, over the workspace view of csrc/hrt_pathsum.h;
- * the drop-in entries run the batch loop of batch.c, with one device output accumulated over the batches and one
- * small download at the end.
+ * csrc/hrt_dominant.hip and csrc/hrt_beam_channel.hip, over the workspace view of csrc/hrt_pathsum.h.  The two pair
+ * families (hrt_array_channel: element pairs, hrt_beam_channel: beam pairs) share one grid (hrt_kgrid, pair_grid) as
+ * their kernels share one GEMM body (csrc/hrt_pair_gemm.inc), and the array and beam drop-ins one packing of the
+ * element offsets (ac_pack_offsets).  The drop-in entries run the batch loop of batch.c, with one device output
+ * accumulated over the batches and one small download at the end.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -378,6 +380,17 @@ static int ac_offsets_check(const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, siz
     return HRT_OK;
 }
 
+/* the host offsets of a drop-in array or beam call as ch_compute uploads them: [nr + nt][3] floats, rx then tx
+ * (ac_job_arrays) */
+static void ac_pack_offsets(const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt, float *e)
+{
+    for (size_t i = 0; i < nr; ++i) { e[3 * i] = rx_el[i].x; e[3 * i + 1] = rx_el[i].y; e[3 * i + 2] = rx_el[i].z; }
+    for (size_t j = 0; j < nt; ++j) {
+        float *q = e + 3u * (nr + j);
+        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
+    }
+}
+
 /* the array fields of hrt_karray / hrt_karray_taps (call `who`, `grid` points per element pair and `links` links) and
  * the limit of the output index */
 static int ac_fields(const hrt_array_spec *a, uint64_t links, uint64_t grid, const char *who, uint32_t *nr,
@@ -390,6 +403,26 @@ static int ac_fields(const hrt_array_spec *a, uint64_t links, uint64_t grid, con
     return HRT_OK;
 }
 
+/* The grid of one call of a pair family (hrt_kgrid, csrc/hrt_pathsum.h: hrt_array_channel's element pairs,
+ * hrt_beam_channel's beam pairs) and its record chunks, v->nchunks.  Returns the bytes of one chunk's partial sums;
+ * *bytes is the scratch: seg, then the partial sums. */
+static uint64_t pair_grid(hrt_kview *v, const hrt_channel_spec *spec, uint32_t npairs, double fa_hz, hrt_kgrid *g,
+                          uint64_t *bytes)
+{
+    g->K = spec->num_freqs; g->T = spec->num_times;
+    g->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
+    g->rows = g->K1 * g->T;
+    g->pblocks = (npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
+    g->cblocks = (g->rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
+    g->f0 = spec->f0_hz; g->df = spec->df_hz; g->t0 = spec->t0_s; g->dt = spec->dt_s;
+    g->fa_c = fa_hz / HRT_SPEED_OF_LIGHT;
+    const uint64_t links = (uint64_t)v->nrx * v->ntx;
+    const uint64_t per_chunk = links * 2u * npairs * g->T * g->K * 8u;
+    *bytes = ps_chunks(v, spec->parts, links * g->pblocks * g->cblocks, HRT_AC_TARGET_GROUPS, per_chunk,
+                       HRT_AC_PARTIAL_MAX, 65535u);
+    return per_chunk;
+}
+
 /* the tiling of one array call: a pure function of the problem, the shard, the spec and the array sizes */
 static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_spec *spec, const hrt_array_spec *a,
                    hrt_karray *K, uint64_t *bytes)
@@ -400,18 +433,10 @@ static int ac_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel_s
     if ((rc = ps_view(p, s, spec->parts, "hrt_array_channel", &K->v))) return rc;
     const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
     if ((rc = ac_fields(a, links, (uint64_t)spec->num_times * spec->num_freqs, "hrt_array_channel", &K->nr, &K->nt,
-                        &K->npairs, &K->fa_c)))
+                        &K->npairs, &K->g.fa_c)))
         return rc;
     ps_shard(s, &K->sh);
-    K->K = spec->num_freqs; K->T = spec->num_times;
-    K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
-    K->rows = K->K1 * K->T;
-    K->pblocks = (K->npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
-    K->cblocks = (K->rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
-    K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->K * 8u;
-    *bytes = ps_chunks(&K->v, spec->parts, links * K->pblocks * K->cblocks, HRT_AC_TARGET_GROUPS, per_chunk,
-                       HRT_AC_PARTIAL_MAX, 65535u);
+    (void)pair_grid(&K->v, spec, K->npairs, a->array_frequency_hz, &K->g, bytes);
     return HRT_OK;
 }
 
@@ -481,11 +506,7 @@ static int ac_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
     if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, who))) return rc;
     float *e = (float *)malloc((nr + nt) * 3u * sizeof(float));
     if (!e) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-    for (size_t i = 0; i < nr; ++i) { e[3 * i] = rx_el[i].x; e[3 * i + 1] = rx_el[i].y; e[3 * i + 2] = rx_el[i].z; }
-    for (size_t j = 0; j < nt; ++j) {
-        float *q = e + 3u * (nr + j);
-        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
-    }
+    ac_pack_offsets(rx_el, nr, tx_el, nt, e);
     job->h_const = e;
     job->const_bytes = (nr + nt) * 3u * sizeof(float);
     job->nr = (uint32_t)nr;
@@ -1003,8 +1024,7 @@ int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
 
 /* ------------------------------------------------------------------ beamformed channel responses (hrt_beam_channel) */
 
-#define HRT_BM_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
-#define HRT_BM_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
+/* (the grid, the chunks and the bound of the partial sums are the array channel's: pair_grid) */
 
 /* the checks of a beam call that need no problem (device pointers are not read).  There is no limit on Nr * Nt: the
  * element-domain matrix is never formed */
@@ -1076,16 +1096,8 @@ static int beam_plan(const hrt_problem *p, const hrt_shard *s, const hrt_channel
     ps_shard(s, &K->sh);
     K->nr = a->num_rx_elements; K->nt = a->num_tx_elements;
     K->br = bm->num_rx_beams; K->bt = bm->num_tx_beams; K->npairs = K->br * K->bt;
-    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
-    K->K = spec->num_freqs; K->T = spec->num_times;
-    K->K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
-    K->rows = K->K1 * K->T;
-    K->pblocks = (K->npairs + HRT_BM_PAIRS - 1) / HRT_BM_PAIRS;
-    K->cblocks = (K->rows + HRT_BM_GROWS - 1) / HRT_BM_GROWS;
-    K->f0 = spec->f0_hz; K->df = spec->df_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->K * 8u;
-    const uint64_t sums = ps_chunks(&K->v, spec->parts, links * K->pblocks * K->cblocks, HRT_BM_TARGET_GROUPS,
-                                    per_chunk, HRT_BM_PARTIAL_MAX, 65535u);
+    uint64_t sums = 0;
+    const uint64_t per_chunk = pair_grid(&K->v, spec, K->npairs, a->array_frequency_hz, &K->g, &sums);
     *off_los = align256(K->v.nchunks * per_chunk);
     *bytes = sums - K->v.nchunks * per_chunk + *off_los + beam_los_bytes(K);
     return HRT_OK;
@@ -1171,11 +1183,7 @@ int hrt_compute_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_po
     const size_t n_el = (nr + nt) * 3u, n_wr = n_rx_beams * nr * 2u, n_wt = n_tx_beams * nt * 2u;
     float *e = (float *)malloc((n_el + n_wr + n_wt) * sizeof(float));
     if (!e) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-    for (size_t i = 0; i < nr; ++i) { e[3 * i] = rx_el[i].x; e[3 * i + 1] = rx_el[i].y; e[3 * i + 2] = rx_el[i].z; }
-    for (size_t j = 0; j < nt; ++j) {
-        float *q = e + 3u * (nr + j);
-        q[0] = tx_el[j].x; q[1] = tx_el[j].y; q[2] = tx_el[j].z;
-    }
+    ac_pack_offsets(rx_el, nr, tx_el, nt, e);
     memcpy(e + n_el, rx_weights, n_wr * sizeof(float));
     memcpy(e + n_el + n_wr, tx_weights, n_wt * sizeof(float));
     ch_job job;

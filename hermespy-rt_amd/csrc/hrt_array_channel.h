@@ -14,6 +14,7 @@
 #ifndef HRT_ARRAY_CHANNEL_H
 #define HRT_ARRAY_CHANNEL_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "hrt_pathsum.h"
@@ -33,14 +34,14 @@ typedef struct {
     hrt_kview v;
     hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t nr, nt, npairs;        /* elements; npairs = nr * nt */
-    uint32_t K, T, K1, rows;        /* rows = T * K1 */
-    uint32_t pblocks, cblocks;      /* ceil(npairs / HRT_AC_PAIRS), ceil(rows / HRT_AC_GROWS) */
-    double f0, df, t0, dt;
-    double fa_c;                    /* f_a / c: revolutions per metre of path difference */
+    hrt_kgrid g;                    /* K .. fa_c (csrc/hrt_pathsum.h) */
     const float *rx_el, *tx_el;     /* device [nr][3], [nt][3] element offsets (m) */
     float *partial;                 /* scratch: complex [link][chunk][pol][pair][T * K] */
     float *out;                     /* complex [nrx][ntx][nr][nt][2][T][K] */
 } hrt_karray;
+
+/* kernel-argument offsets alone have moved the partial kernel's SGPR spills and its time (hrt_kshard) */
+_Static_assert(offsetof(hrt_karray, g) == 144 && offsetof(hrt_karray, rx_el) == 208, "hrt_karray: the argument offsets");
 
 int hrt_hip_launch_array_channel(const hrt_karray *P, void *stream);
 

@@ -9,27 +9,26 @@
  * W is the two-level factorisation of csrc/hrt_channel.h; the A operand of v_mfma_f32_32x32x2_f32 is the 2x2 real
  * embedding (Re G, -Im G; Im G, Re G), which holds for any complex G.  The weights are folded into every record's
  * steering term before the GEMM, so the element-domain matrix is never formed and the cost does not grow with Nr Nt.
- * A workgroup (4 waves) forms HRT_BM_PAIRS beam pairs x 256 padded columns of one link from one chunk of the link's
+ * A workgroup (4 waves) forms HRT_AC_PAIRS beam pairs x 256 padded columns of one link from one chunk of the link's
  * records.  Per batch of staged records it forms the element phase factors HRT_BM_ETILE elements at a time in LDS and
  * accumulates the gains of the beams its pairs touch: the RX beams a0 .. a0 + na - 1 and, of the TX beams, all Bt of
- * them where Bt <= HRT_BM_PAIRS and (p0 + slot) mod Bt otherwise -- at most HRT_BM_PAIRS a side.  Within an element
+ * them where Bt <= HRT_AC_PAIRS and (p0 + slot) mod Bt otherwise -- at most HRT_AC_PAIRS a side.  Within an element
  * tile the sum is FP32, across the tiles FP64.  The LoS gains of every (link, pair) are formed once by
  * hrt_beam_los_kernel into the scratch (behind the partial sums) and read by the reduce kernel. */
 #ifndef HRT_BEAM_CHANNEL_H
 #define HRT_BEAM_CHANNEL_H
 
+#include <stddef.h>
 #include <stdint.h>
 
+#include "hrt_array_channel.h"
 #include "hrt_pathsum.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define HRT_BM_THREADS 256u   /* 4 waves per workgroup */
-#define HRT_BM_PAIRS 32u      /* beam pairs per workgroup: 2 MFMA row tiles of 16 */
-#define HRT_BM_GROWS 16u      /* rows g per workgroup: 256 padded columns, 2 tiles of 32 a wave */
-#define HRT_BM_BATCH 32u      /* unblocked records staged in LDS at a time */
+/* (the tile of a workgroup is csrc/hrt_array_channel.h's: HRT_AC_THREADS, HRT_AC_PAIRS, HRT_AC_GROWS, HRT_AC_BATCH) */
 #define HRT_BM_ETILE 32u      /* elements whose phase factors are in LDS at a time */
 #define HRT_BM_MAX_ELEMENTS 256u
 #define HRT_BM_MAX_BEAMS 256u
@@ -39,16 +38,15 @@ typedef struct {
     hrt_kview v;
     hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t nr, nt, br, bt, npairs;   /* elements, beams; npairs = br * bt */
-    uint32_t K, T, K1, rows;        /* rows = T * K1 */
-    uint32_t pblocks, cblocks;      /* ceil(npairs / HRT_BM_PAIRS), ceil(rows / HRT_BM_GROWS) */
-    double f0, df, t0, dt;
-    double fa_c;                    /* f_a / c: revolutions per metre of path difference */
+    hrt_kgrid g;                    /* K .. fa_c (csrc/hrt_pathsum.h) */
     const float *rx_el, *tx_el;     /* device [nr][3], [nt][3] element offsets (m) */
     const float *rx_w, *tx_w;       /* device [br][nr][2], [bt][nt][2] weights (re, im) */
     float *partial;                 /* scratch: complex [link][chunk][pol][pair][T * K] */
     float *los;                     /* scratch: complex [link][pair] gains at the LoS directions */
     float *out;                     /* complex [nrx][ntx][br][bt][2][T][K] */
 } hrt_kbeam;
+
+_Static_assert(offsetof(hrt_kbeam, g) == 152 && offsetof(hrt_kbeam, rx_el) == 216, "hrt_kbeam: the argument offsets");
 
 int hrt_hip_launch_beam_channel(const hrt_kbeam *P, void *stream);
 

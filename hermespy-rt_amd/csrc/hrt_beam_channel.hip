@@ -23,11 +23,9 @@
 #include "hrt_channel.h"
 #include "hrt_pathsum.h"
 
-typedef float hrt_f32x16 __attribute__((ext_vector_type(16)));
+#define HRT_BM_SLOTS (HRT_AC_BATCH * HRT_AC_PAIRS / HRT_AC_THREADS)   // (record, beam) gains per thread and side
 
-#define HRT_BM_SLOTS (HRT_BM_BATCH * HRT_BM_PAIRS / HRT_BM_THREADS)   // (record, beam) gains per thread and side
-
-static_assert(HRT_BM_BATCH == 32u && HRT_BM_PAIRS == 32u && HRT_BM_ETILE == 32u, "the index arithmetic of the S stage");
+static_assert(HRT_AC_BATCH == 32u && HRT_AC_PAIRS == 32u && HRT_BM_ETILE == 32u, "the index arithmetic of the S stage");
 
 namespace {
 
@@ -40,75 +38,44 @@ __device__ __forceinline__ float2 beam_weight(const float *w, uint32_t n, uint32
 
 }  // namespace
 
-__global__ void __launch_bounds__(HRT_BM_THREADS) hrt_beam_partial_kernel(const hrt_kbeam P)
+__global__ void __launch_bounds__(HRT_AC_THREADS) hrt_beam_partial_kernel(const hrt_kbeam P)
 {
     const hrt_kview &V = P.v;
     const uint32_t blk = blockIdx.x, c = blockIdx.y, link = blockIdx.z;
-    const uint32_t pb = blk % P.pblocks, cb = blk / P.pblocks;
+    const uint32_t pb = blk % P.g.pblocks, cb = blk / P.g.pblocks;
     const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t h = lane >> 5, k2 = lane & 15u, rsub = (lane >> 4) & 1u;
 
-    __shared__ float sRec[HRT_BM_BATCH][HRT_PS_REC_FLOATS];
-    __shared__ float4 sU[HRT_BM_BATCH][HRT_BM_GROWS];        // a_te U, a_tm U (complex) of the block's rows g
-    __shared__ float4 sV[HRT_BM_BATCH][HRT_CH_K2];           // (Re V, -Im V, Im V, Re V): B = u . half h
-    __shared__ float sA[HRT_BM_BATCH][2][64];                // the A operand of every lane, per pair tile
-    __shared__ float2 sE[HRT_BM_ETILE][HRT_BM_BATCH];        // phase factors of one element tile: [element][record]
-    __shared__ float2 sW[HRT_BM_PAIRS][HRT_BM_ETILE + 1u];   // weights of the touched beams: [beam slot][element]
-    __shared__ float2 sG[2][HRT_BM_PAIRS][HRT_BM_BATCH + 1u];   // gains: [side][beam slot][record]
-    __shared__ uint32_t sB[HRT_BM_BATCH], sI[HRT_BM_BATCH];  // (bounce, hit) of the staged records
+    __shared__ float sRec[HRT_AC_BATCH][HRT_PS_REC_FLOATS];
+    __shared__ float4 sU[HRT_AC_BATCH][HRT_AC_GROWS];        // a_te U, a_tm U (complex) of the block's rows g
+    __shared__ float4 sV[HRT_AC_BATCH][HRT_CH_K2];           // (Re V, -Im V, Im V, Re V): B = u . half h
+    __shared__ float sA[HRT_AC_BATCH][2][64];                // the A operand of every lane, per pair tile
+    __shared__ float2 sE[HRT_BM_ETILE][HRT_AC_BATCH];        // phase factors of one element tile: [element][record]
+    __shared__ float2 sW[HRT_AC_PAIRS][HRT_BM_ETILE + 1u];   // weights of the touched beams: [beam slot][element]
+    __shared__ float2 sG[2][HRT_AC_PAIRS][HRT_AC_BATCH + 1u];   // gains: [side][beam slot][record]
+    __shared__ uint32_t sB[HRT_AC_BATCH], sI[HRT_AC_BATCH];  // (bounce, hit) of the staged records
 
     // the beams of this block's pairs p0 .. p0 + 31: RX slot s is beam a0 + s; TX slot s is beam s where every TX
     // beam fits (Bt <= 32), else the beam of pair p0 + s
-    const uint32_t p0 = pb * HRT_BM_PAIRS;
+    const uint32_t p0 = pb * HRT_AC_PAIRS;
     const uint32_t a0 = p0 / P.bt;
-    const uint32_t na = (min(p0 + HRT_BM_PAIRS, P.npairs) - 1u) / P.bt - a0 + 1u, nb = min(P.bt, HRT_BM_PAIRS);
-    const bool tx_all = P.bt <= HRT_BM_PAIRS;
+    const uint32_t na = (min(p0 + HRT_AC_PAIRS, P.npairs) - 1u) / P.bt - a0 + 1u, nb = min(P.bt, HRT_AC_PAIRS);
+    const bool tx_all = P.bt <= HRT_AC_PAIRS;
 
-    // the MFMA tiles of this wave: pair tiles 0, 1 of the block; column tiles 2w, 2w + 1 (rows g 4w .. 4w + 3)
-    const bool live_p1 = p0 + 16u < P.npairs;
-    const bool live_c0 = cb * HRT_BM_GROWS + 4u * w < P.rows;
-    const bool live_c1 = cb * HRT_BM_GROWS + 4u * w + 2u < P.rows;
-    hrt_f32x16 acc[2][2][2];   // [pair tile][column tile][pol]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][t][q][r] = 0.f;
+#define HRT_PG_PART 1
+#include "hrt_pair_gemm.inc"
 
     uint32_t b = 0, cur = 0, end = 0;
     chunk_range(V, 0, tx, c, cur, end);
     for (;;) {
-        const uint32_t n = fill_batch<HRT_BM_BATCH>(V, rx, tx, c, lane, w, b, cur, end, sB, sI);
+        const uint32_t n = fill_batch<HRT_AC_BATCH>(V, rx, tx, c, lane, w, b, cur, end, sB, sI);
         if (n == 0) break;
         __syncthreads();
         if (tid < n) stage_record(V, P.sh, sB[tid], rx, tx, sI[tid], sRec[tid]);
         __syncthreads();
-#pragma unroll 1
-        for (uint32_t e = tid; e < n * HRT_BM_GROWS; e += HRT_BM_THREADS) {   // U
-            const uint32_t j = e / HRT_BM_GROWS, r = e % HRT_BM_GROWS, g = cb * HRT_BM_GROWS + r;
-            const float *R = sRec[j];
-            float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (g < P.rows) {
-                const uint32_t m = g / P.K1, k1 = g - m * P.K1;
-                const double t = P.t0 + (double)m * P.dt;
-                const double f = P.f0 + (double)(k1 * HRT_CH_K2) * P.df;
-                float sn, cs;
-                sincospif(half_revs((double)R[5] * t - f * (double)R[4]), &sn, &cs);
-                u = make_float4(R[0] * cs - R[1] * sn, R[0] * sn + R[1] * cs, R[2] * cs - R[3] * sn, R[2] * sn + R[3] * cs);
-            }
-            sU[j][r] = u;
-        }
-#pragma unroll 1
-        for (uint32_t e = tid; e < n * HRT_CH_K2; e += HRT_BM_THREADS) {   // V
-            const uint32_t j = e / HRT_CH_K2, q = e % HRT_CH_K2;
-            float sn, cs;
-            sincospif(half_revs(-(double)q * P.df * (double)sRec[j][4]), &sn, &cs);
-            sV[j][q] = make_float4(cs, -sn, sn, cs);
-        }
+#define HRT_PG_PART 2
+#include "hrt_pair_gemm.inc"
         // S: the gains of the touched beams at every staged record, side 0 = RX (u_rx, conj W_rx), 1 = TX
 #pragma unroll 1
         for (uint32_t side = 0; side < 2u; ++side) {
@@ -122,16 +89,16 @@ __global__ void __launch_bounds__(HRT_BM_THREADS) hrt_beam_partial_kernel(const 
                 const uint32_t ne = min(HRT_BM_ETILE, N - e0);
                 __syncthreads();   // the readers of the tile before are done
 #pragma unroll 1
-                for (uint32_t x = tid; x < ne * HRT_BM_BATCH; x += HRT_BM_THREADS) {   // phase factors
+                for (uint32_t x = tid; x < ne * HRT_AC_BATCH; x += HRT_AC_THREADS) {   // phase factors
                     const uint32_t j = x & 31u, e = x >> 5;
                     if (j < n) {
                         float sn, cs;
-                        sincospif(half_revs(P.fa_c * dot3(el + 3u * (e0 + e), sRec[j] + 6u + 3u * side)), &sn, &cs);
+                        sincospif(half_revs(P.g.fa_c * dot3(el + 3u * (e0 + e), sRec[j] + 6u + 3u * side)), &sn, &cs);
                         sE[e][j] = make_float2(cs, sn);
                     }
                 }
 #pragma unroll 1
-                for (uint32_t x = tid; x < ns * HRT_BM_ETILE; x += HRT_BM_THREADS) {   // weights
+                for (uint32_t x = tid; x < ns * HRT_BM_ETILE; x += HRT_AC_THREADS) {   // weights
                     const uint32_t e = x & 31u, s = x >> 5;
                     const uint32_t beam = side == 0u ? a0 + s : (tx_all ? s : (p0 + s) % P.bt);
                     if (e < ne) sW[s][e] = beam_weight(wt, N, beam, e0 + e, side == 0u);
@@ -139,7 +106,7 @@ __global__ void __launch_bounds__(HRT_BM_THREADS) hrt_beam_partial_kernel(const 
                 __syncthreads();
 #pragma unroll
                 for (uint32_t s = 0; s < HRT_BM_SLOTS; ++s) {
-                    const uint32_t x = tid + s * HRT_BM_THREADS, j = x & 31u, slot = x >> 5;
+                    const uint32_t x = tid + s * HRT_AC_THREADS, j = x & 31u, slot = x >> 5;
                     if (j < n && slot < ns) {
                         float re = 0.f, im = 0.f;
                         for (uint32_t e = 0; e < ne; ++e) {
@@ -156,14 +123,14 @@ __global__ void __launch_bounds__(HRT_BM_THREADS) hrt_beam_partial_kernel(const 
             }
 #pragma unroll
             for (uint32_t s = 0; s < HRT_BM_SLOTS; ++s) {
-                const uint32_t x = tid + s * HRT_BM_THREADS, j = x & 31u, slot = x >> 5;
+                const uint32_t x = tid + s * HRT_AC_THREADS, j = x & 31u, slot = x >> 5;
                 if (j < n && slot < ns) sG[side][slot][j] = make_float2((float)gre[s], (float)gim[s]);
             }
         }
         __syncthreads();
 #pragma unroll 1
-        for (uint32_t e = tid; e < n * HRT_BM_PAIRS; e += HRT_BM_THREADS) {   // G, as the A operand of each lane
-            const uint32_t j = e / HRT_BM_PAIRS, q = e % HRT_BM_PAIRS, pair = p0 + q;
+        for (uint32_t e = tid; e < n * HRT_AC_PAIRS; e += HRT_AC_THREADS) {   // G, as the A operand of each lane
+            const uint32_t j = e / HRT_AC_PAIRS, q = e % HRT_AC_PAIRS, pair = p0 + q;
             float gr = 0.f, gi = 0.f;   // padded pairs: A = 0
             if (pair < P.npairs) {
                 const uint32_t a = pair / P.bt, bb = pair - a * P.bt;
@@ -179,54 +146,13 @@ __global__ void __launch_bounds__(HRT_BM_THREADS) hrt_beam_partial_kernel(const 
             A[row + 48u] = gr;  // Im B row, k = 1: Re G
         }
         __syncthreads();
-        const float2 *sV2 = reinterpret_cast<const float2 *>(&sV[0][0]);
-        for (uint32_t j = 0; j < n; ++j) {
-            const float2 v = sV2[(j * HRT_CH_K2 + k2) * 2u + h];
-            const float4 u0 = sU[j][4u * w + rsub], u1 = sU[j][4u * w + 2u + rsub];
-            // lane (k = h, column): h = 0 Re(U V), h = 1 Im(U V)
-            const float b00 = fmaf(u0.x, v.x, u0.y * v.y), b01 = fmaf(u0.z, v.x, u0.w * v.y);
-            const float b10 = fmaf(u1.x, v.x, u1.y * v.y), b11 = fmaf(u1.z, v.x, u1.w * v.y);
-            const float a0v = sA[j][0][lane], a1v = sA[j][1][lane];
-            if (live_c0) {
-                acc[0][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v, b00, acc[0][0][0], 0, 0, 0);
-                acc[0][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v, b01, acc[0][0][1], 0, 0, 0);
-                if (live_p1) {
-                    acc[1][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b00, acc[1][0][0], 0, 0, 0);
-                    acc[1][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b01, acc[1][0][1], 0, 0, 0);
-                }
-            }
-            if (live_c1) {
-                acc[0][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v, b10, acc[0][1][0], 0, 0, 0);
-                acc[0][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v, b11, acc[0][1][1], 0, 0, 0);
-                if (live_p1) {
-                    acc[1][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b10, acc[1][1][0], 0, 0, 0);
-                    acc[1][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b11, acc[1][1][1], 0, 0, 0);
-                }
-            }
-        }
+#define HRT_PG_PART 3
+#include "hrt_pair_gemm.inc"
         __syncthreads();
     }
 
-    // D: lane = column, register r = row (r & 3) + 8 (r >> 2) + 4 h; rows 0..15 Re B, 16..31 Im B of 16 pairs
-    const uint64_t tk = (uint64_t)P.T * P.K;
-    float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * V.nchunks + c) * 2u * P.npairs * tk;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const uint32_t g = cb * HRT_BM_GROWS + 4u * w + 2u * t + rsub;
-        const uint32_t m = g / P.K1, k = (g - m * P.K1) * HRT_CH_K2 + k2;
-        const bool col_ok = g < P.rows && k < P.K;
-        float2 *d = dst + (uint64_t)m * P.K + k;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const uint32_t pair = p0 + 16u * a + (r & 3) + 8u * (r >> 2) + 4u * h;
-                    if (col_ok && pair < P.npairs)
-                        d[((uint64_t)q * P.npairs + pair) * tk] = make_float2(acc[a][t][q][r], acc[a][t][q][r + 8]);
-                }
-    }
+#define HRT_PG_PART 4
+#include "hrt_pair_gemm.inc"
 }
 
 // one thread per (link, pair): G = g_rx[a](-u) g_tx[b](u) at the LoS entry's u = directions_tx (the coincident
@@ -248,7 +174,7 @@ __global__ void hrt_beam_los_kernel(const hrt_kbeam P)
         for (uint32_t e = 0; e < N; ++e) {
             const float2 wv = beam_weight(wt, N, beam, e, side == 0u);
             float sn, cs;
-            sincospif(half_revs(P.fa_c * dot3(el + 3u * e, u)), &sn, &cs);
+            sincospif(half_revs(P.g.fa_c * dot3(el + 3u * e, u)), &sn, &cs);
             g[side][0] += (double)wv.x * cs - (double)wv.y * sn;
             g[side][1] += (double)wv.x * sn + (double)wv.y * cs;
         }
@@ -261,25 +187,15 @@ __global__ void hrt_beam_los_kernel(const hrt_kbeam P)
 __global__ void hrt_beam_reduce_kernel(const hrt_kbeam P)
 {
     const hrt_kview &V = P.v;
-    const uint64_t tk = (uint64_t)P.T * P.K;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t per_link = (uint64_t)P.npairs * 2u * tk;
-    if (gid >= per_link * V.nrx * V.ntx) return;
-    const uint32_t link = (uint32_t)(gid / per_link);
-    const uint64_t e = gid - (uint64_t)link * per_link;   // = (pair * 2 + pol) * tk + col
-    const uint32_t pair = (uint32_t)(e / (2u * tk)), pol = (uint32_t)(e / tk) & 1u;
-    const uint64_t col = e % tk;
-
-    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link +
-                        ((uint64_t)pol * P.npairs + pair) * tk + col;
-    float2 s = sum_chunks(src, V.nchunks, per_link);
+    hrt_pair_output o;
+    if (!pair_output(V, P.g, P.npairs, P.partial, gid, o)) return;
+    float2 s = o.s;
     hrt_los_entry L;
-    if (V.los && los_entry(V, link, L)) {
-        const float2 G = reinterpret_cast<const float2 *>(P.los)[(uint64_t)link * P.npairs + pair];
-        const uint32_t m = (uint32_t)(col / P.K), k = (uint32_t)(col % P.K);
-        const double t = P.t0 + (double)m * P.dt, f = P.f0 + (double)k * P.df;
+    if (V.los && los_entry(V, o.link, L)) {
+        const float2 G = reinterpret_cast<const float2 *>(P.los)[(uint64_t)o.link * P.npairs + o.pair];
         float sn, cs;
-        sincospif(half_revs((double)L.nu * t - f * (double)L.tau), &sn, &cs);
+        sincospif(half_revs(pair_los_phase(P.g, o.col, L.tau, L.nu)), &sn, &cs);
         s.x += L.a * fmaf(cs, G.x, -(sn * G.y));
         s.y += L.a * fmaf(cs, G.y, sn * G.x);
     }
@@ -288,19 +204,6 @@ __global__ void hrt_beam_reduce_kernel(const hrt_kbeam P)
 
 extern "C" int hrt_hip_launch_beam_channel(const hrt_kbeam *P, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t links = P->v.nrx * P->v.ntx;
-    if (P->v.nchunks) {
-        const int e = hrt_hip_launch_segments(&P->v, stream);
-        if (e) return e;
-        hipLaunchKernelGGL(hrt_beam_partial_kernel, dim3(P->pblocks * P->cblocks, P->v.nchunks, links),
-                           dim3(HRT_BM_THREADS), 0, st, *P);
-    }
-    if (P->v.los) {
-        const uint64_t g = (uint64_t)links * P->npairs;
-        hipLaunchKernelGGL(hrt_beam_los_kernel, dim3((unsigned)((g + 255u) / 256u)), dim3(256), 0, st, *P);
-    }
-    const uint64_t n = (uint64_t)links * P->npairs * 2u * P->T * P->K;
-    hipLaunchKernelGGL(hrt_beam_reduce_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
-    return (int)hipGetLastError();
+    return launch_pair_family<hrt_kbeam>(P, HRT_AC_THREADS, hrt_beam_partial_kernel, hrt_beam_los_kernel,
+                                         hrt_beam_reduce_kernel, stream);
 }

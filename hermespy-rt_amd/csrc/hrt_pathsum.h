@@ -1,9 +1,11 @@
 /* hrt_pathsum.h -- what the path-sum families (hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles) share: the view of the workspace of a finished hrt_trace that their kernels read (plain C, the
- * first member of hrt_kchannel, hrt_karray, hrt_ktaps, hrt_karray_taps and hrt_kpower; filled by csrc/host/channel.c)
- * and, for the .hip files, the device helpers that read it: the field accessors, the chunk ranges and the batch fill,
- * the staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the
- * array families, the LoS entry, and the two halves the complex reduce kernels share.
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel) share: the view of the workspace of a finished hrt_trace
+ * that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray, hrt_ktaps, hrt_karray_taps, hrt_kpower,
+ * hrt_kdominant and hrt_kbeam; filled by csrc/host/channel.c), the grid of the two pair families (hrt_kgrid), and, for
+ * the .hip files, the device helpers that read them: the field accessors, the chunk ranges and the batch fill, the
+ * staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the array
+ * families, the LoS entry, the two halves the complex reduce kernels share, and the reduce walk and the launch of the
+ * pair families.
  *
  * Every family sums, per link (rx, tx), the LoS entry (shard rank 0 only) and the scatter records of the link's TX
  * segment in every hit block.  The records of a segment are cut into nchunks chunks; a partial kernel writes one
@@ -28,13 +30,23 @@ typedef struct {
 } hrt_kview;
 
 /* The shard of the trace, for the families that need a record's departure direction: the member right after v in
- * hrt_karray, hrt_karray_taps and hrt_kpower.  20 bytes, 4-aligned (not padded to 24): the fields that follow it
+ * hrt_karray, hrt_karray_taps, hrt_kpower, hrt_kdominant and hrt_kbeam.  20 bytes, 4-aligned (not padded to 24): the fields that follow it
  * in those structs keep the kernel-argument offsets they had when these four were written out there (new offsets
  * alone moved hrt_array_partial_kernel's SGPR spills and its time: profiles/HISTORY.md). */
 typedef struct {
     uint64_t num_paths;             /* the shard's N: departure directions from the global path */
     uint32_t rank, count, chunk;
 } __attribute__((packed, aligned(4))) hrt_kshard;
+
+/* The grid of the pair families (hrt_array_channel: element pairs, hrt_beam_channel: beam pairs), a member of hrt_karray
+ * and hrt_kbeam at the offsets these fields had when they were written out there (8-aligned in both; asserted in the
+ * two headers).  csrc/hrt_pair_gemm.inc and pair_output read it as P.g. */
+typedef struct {
+    uint32_t K, T, K1, rows;        /* rows = T * K1 */
+    uint32_t pblocks, cblocks;      /* ceil(npairs / HRT_AC_PAIRS), ceil(rows / HRT_AC_GROWS) */
+    double f0, df, t0, dt;
+    double fa_c;                    /* f_a / c: revolutions per metre of path difference */
+} hrt_kgrid;
 
 /* hrt_channel_segments_kernel: V->seg[b][t] for every bounce b and t <= ntx */
 int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
@@ -161,6 +173,39 @@ __device__ __forceinline__ void store_out(float2 *o, float2 s, uint32_t accumula
     o[0] = s;
 }
 
+// What the reduce kernels of the pair families share (one thread per output gid = ((link * npairs + pair) * 2 + pol)
+// * T K + col; partial sums [link][chunk][pol][pair][T K]): the output's link, pair and column and the sum s of its
+// chunks (false past the last output), and the W phase of a LoS entry (tau, nu) at a column, in revolutions.
+struct hrt_pair_output {
+    uint32_t link, pair;
+    uint64_t col;
+    float2 s;
+};
+
+__device__ __forceinline__ bool pair_output(const hrt_kview &V, const hrt_kgrid &G, uint32_t npairs, const float *partial,
+                                            uint64_t gid, hrt_pair_output &o)
+{
+    const uint64_t tk = (uint64_t)G.T * G.K;
+    const uint64_t per_link = (uint64_t)npairs * 2u * tk;
+    if (gid >= per_link * V.nrx * V.ntx) return false;
+    o.link = (uint32_t)(gid / per_link);
+    const uint64_t e = gid - (uint64_t)o.link * per_link;   // = (pair * 2 + pol) * tk + col
+    const uint32_t pol = (uint32_t)(e / tk) & 1u;
+    o.pair = (uint32_t)(e / (2u * tk));
+    o.col = e % tk;
+    const float2 *src = reinterpret_cast<const float2 *>(partial) + (uint64_t)o.link * V.nchunks * per_link +
+                        ((uint64_t)pol * npairs + o.pair) * tk + o.col;
+    o.s = sum_chunks(src, V.nchunks, per_link);
+    return true;
+}
+
+__device__ __forceinline__ double pair_los_phase(const hrt_kgrid &G, uint64_t col, float tau, float nu)
+{
+    const uint32_t m = (uint32_t)(col / G.K), k = (uint32_t)(col % G.K);
+    const double t = G.t0 + (double)m * G.dt, f = G.f0 + (double)k * G.df;
+    return (double)nu * t - f * (double)tau;
+}
+
 // The LoS entry of a link: a (real, TE = TM), tau, nu (the path list's freq_shift) and u = directions_tx
 // (directions_rx = -u).  False where the LoS is blocked.  Coincident: a = 1, tau = nu = 0, directions_rx = (1, 0, 0),
 // directions_tx = (-1, 0, 0) (src/compute_paths.c:533-534).
@@ -215,6 +260,29 @@ __device__ __forceinline__ uint32_t fill_batch(const hrt_kview &V, uint32_t rx, 
         n += take;
     }
     return n;
+}
+
+// The launch of a pair family (P: hrt_karray or hrt_kbeam): the TX segments and the partial kernel where the call has
+// a scatter part, the family's LoS pre-pass where it has one (`los`, one thread per (link, pair); may be NULL) and
+// the call a LoS part, then the reduce kernel, one thread per output.
+template <typename KP>
+int launch_pair_family(const KP *P, uint32_t threads, void (*partial)(const KP), void (*los)(const KP),
+                       void (*reduce)(const KP), void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t links = P->v.nrx * P->v.ntx;
+    if (P->v.nchunks) {
+        const int e = hrt_hip_launch_segments(&P->v, stream);
+        if (e) return e;
+        hipLaunchKernelGGL(partial, dim3(P->g.pblocks * P->g.cblocks, P->v.nchunks, links), dim3(threads), 0, st, *P);
+    }
+    if (los && P->v.los) {
+        const uint64_t g = (uint64_t)links * P->npairs;
+        hipLaunchKernelGGL(los, dim3((unsigned)((g + 255u) / 256u)), dim3(256), 0, st, *P);
+    }
+    const uint64_t n = (uint64_t)links * P->npairs * 2u * P->g.T * P->g.K;
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
