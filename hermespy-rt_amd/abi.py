@@ -589,3 +589,32 @@ def run_compute_dominant_paths(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, 
     out = _run_pathsum(lib, "hrt_compute_dominant_paths", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                        num_bounces, spec, (n,) if n else None, (), stats, np.uint8)
     return dominant_views(out, nrx, ntx, spec.max_paths)
+
+
+# ---- test-only entries (include/hrt_device.h): a lane's own candidate lookup, what the tables were built with ----
+CAND_KINDS = dict(patch=1, image=2, txcell=4, cell_mask=8)
+
+
+def debug_candidates(lib, problem, mode, queries):
+    """hrt_debug_candidates: queries float32 [n][8] (o, d, row and apex as u32 bits) -> uint32 [n][10] (served, patch
+    index, eight mask words).  Raises RuntimeError on an error code (e.g. no table for the mode)."""
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, 8)
+    out = np.zeros((q.shape[0], 10), np.uint32)
+    rc = lib.hrt_debug_candidates(problem, int(mode), q.shape[0], q.ctypes.data_as(c_float_p),
+                                  out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0:
+        raise RuntimeError("hrt_debug_candidates failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return out
+
+
+def debug_table_info(lib, problem):
+    """hrt_debug_table_info -> dict(nuv uint32 [T][2], hmax, ro_rx, ro_img, num_patch, kinds)."""
+    T = int(lib.hrt_problem_num_triangles(problem))
+    nuv = np.zeros((max(T, 1), 2), np.uint32)
+    f3 = np.zeros(3, np.float32)
+    npatch, kinds = C.c_uint64(0), C.c_uint32(0)
+    rc = lib.hrt_debug_table_info(problem, nuv.ctypes.data_as(C.POINTER(C.c_uint32)), f3.ctypes.data_as(c_float_p),
+                                  C.byref(npatch), C.byref(kinds))
+    if rc != 0:
+        raise RuntimeError("hrt_debug_table_info failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    return dict(nuv=nuv[:T], hmax=f3[0], ro_rx=f3[1], ro_img=f3[2], num_patch=int(npatch.value), kinds=int(kinds.value))

@@ -1469,6 +1469,67 @@ int hrt_selftest_math(int device, int fn, const float *in, float *out, uint64_t 
     return rc;
 }
 
+/* ------------------------------------------------------------------ candidate tables (test entries) */
+
+/* which table a mode of hrt_debug_candidates looks up: NULL = this problem has none */
+static const void *cand_table(const hrt_problem *p, int mode)
+{
+    switch (mode) {
+    case 0: return p->kpatch.mask;
+    case 1: return p->kpatch.num_img ? p->kpatch.mask : NULL;
+    case 2: return p->kpatch.txcell;
+    case 3: return p->krxt.cell_mask;
+    default: return NULL;
+    }
+}
+
+int hrt_debug_candidates(const hrt_problem *p, int mode, uint64_t n, const float *in, uint32_t *out)
+{
+    if (!p || !in || !out || mode < 0 || mode > 3) return hrt_fail(HRT_E_INVALID, "hrt_debug_candidates: bad argument");
+    if (n > (1ull << 26)) return hrt_fail(HRT_E_INVALID, "hrt_debug_candidates: more than 2^26 queries");
+    if (!cand_table(p, mode)) return hrt_fail(HRT_E_INVALID, "hrt_debug_candidates: the problem has no table for mode %d", mode);
+    if (n == 0) return HRT_OK;
+    void *d_in = NULL, *d_out = NULL;
+    int rc = hrt_device_malloc(p->device, &d_in, n * 32);
+    if (rc) return rc;
+    if ((rc = hrt_device_malloc(p->device, &d_out, n * 40))) { hrt_device_free(p->device, d_in); return rc; }
+    if (!(rc = hrt_device_upload(p->device, d_in, in, n * 32))) {
+        int e = hrt_hip_debug_candidates(p->d_tri, p->num_tri, p->d_tx_pos, p->num_rx, p->num_tx, &p->kpatch, &p->krxt, mode, n,
+                                         (const float *)d_in, (uint32_t *)d_out, NULL);
+        if (e) rc = hrt_fail_hip(e, "hrt_debug_candidates_kernel");
+        else if (!(rc = hrt_device_sync(p->device, NULL))) rc = hrt_device_download(p->device, out, d_out, n * 40);
+    }
+    hrt_device_free(p->device, d_in);
+    hrt_device_free(p->device, d_out);
+    return rc;
+}
+
+int hrt_debug_table_info(const hrt_problem *p, uint32_t *nuv, float *hmax_ro_rx_ro_img, uint64_t *num_patch, uint32_t *kinds)
+{
+    if (!p || !nuv || !hmax_ro_rx_ro_img || !num_patch || !kinds) return hrt_fail(HRT_E_INVALID, "hrt_debug_table_info: bad argument");
+    memset(nuv, 0, (size_t)p->num_tri * 8);
+    hmax_ro_rx_ro_img[0] = p->kpatch.hmax;
+    hmax_ro_rx_ro_img[1] = p->kpatch.ro_rx;
+    hmax_ro_rx_ro_img[2] = p->kpatch.ro_img;
+    *num_patch = p->kpatch.mask ? p->kpatch.num_patch : 0u;
+    *kinds = (p->kpatch.mask ? 1u : 0u) | (p->kpatch.mask && p->kpatch.num_img ? 2u : 0u) | (p->kpatch.txcell ? 4u : 0u) |
+             (p->krxt.cell_mask ? 8u : 0u);
+    if (p->kpatch.mask) {   /* the grids as the kernels read them: the definition rows on the device */
+        float *pdef = (float *)malloc((size_t)p->num_tri * 32);
+        if (!pdef) return hrt_fail(HRT_E_NOMEM, "out of host memory");
+        const int rc = hrt_device_download(p->device, pdef, p->kpatch.pdef, (uint64_t)p->num_tri * 32);
+        for (uint32_t j = 0; !rc && j < p->num_tri; ++j) {
+            uint32_t bits;
+            memcpy(&bits, &pdef[8 * (size_t)j + 7], 4);
+            nuv[2 * j] = bits & 0xffffu;
+            nuv[2 * j + 1] = bits >> 16;
+        }
+        free(pdef);
+        if (rc) return rc;
+    }
+    return HRT_OK;
+}
+
 /* Diagnostic counters of the packet-culling loop (all zero unless built with `make STATS=1`):
  * out[kind][16], kind 0 = primary traces of launch 0, 1 = primary traces of later launches,
  * 2 = shadow traces; columns: see include/hrt_device.h. */

@@ -705,6 +705,17 @@ __device__ __forceinline__ uint32_t rxt_cell(F3 a)
 // `apex_k` is per lane (a wave of the launch set may straddle two TXs).  A lane whose origin is not
 // inside the ball the tables were built for (cannot happen for hit points and TXs; NaNs) asks for
 // every triangle.
+// the two halves of a lane's lookup (the hot kernels through closest_hit_masked; hrt_debug_candidates_kernel): is the
+// origin inside the ball the tables were built for, and the mask of the cell of the lane's own direction
+__device__ __forceinline__ bool rxt_inside(const hrt_krxt &X, F3 o)
+{
+    const F3 dc = sub3(o, {X.cx, X.cy, X.cz});
+    return fast_sqrt(fdot3(dc, dc)) * 1.0001f <= X.region_r;   // NaN: false
+}
+__device__ __forceinline__ unsigned long long rxt_cell_load(const hrt_krxt &X, uint32_t apex_k, F3 d)
+{
+    return X.cell_mask[(uint64_t)apex_k * HRT_RXT_BINS + rxt_cell(d)];
+}
 template <typename TriPtr>
 __device__ __forceinline__ Hit closest_hit_masked(TriPtr tri, const uint32_t *__restrict__ orig, const hrt_krxt &X,
                                                   uint32_t apex_k, uint32_t num_tri, F3 o, F3 d, bool valid,
@@ -716,10 +727,8 @@ __device__ __forceinline__ Hit closest_hit_masked(TriPtr tri, const uint32_t *__
     if (inval == ~0ull) return {who, best};
     unsigned long long mine = 0ull;
     if (valid) {
-        const F3 dc = sub3(o, {X.cx, X.cy, X.cz});
-        const bool inside = fast_sqrt(fdot3(dc, dc)) * 1.0001f <= X.region_r;   // NaN: false
-        mine = inside ? X.cell_mask[(uint64_t)apex_k * HRT_RXT_BINS + rxt_cell(d)]
-                      : (num_tri >= 64u ? ~0ull : ((1ull << num_tri) - 1ull));
+        mine = rxt_inside(X, o) ? rxt_cell_load(X, apex_k, d)
+                                : (num_tri >= 64u ? ~0ull : ((1ull << num_tri) - 1ull));
     }
     unsigned long long m = wave_or64(mine);
     HRT_STAT(kind, 0, 1);
@@ -893,6 +902,18 @@ __device__ __forceinline__ Hit closest_hit_patch(TriPtr tri, OrigPtr orig, const
     return closest_hit_words(tri, orig, w, patch_whole(R, valid), num_tri, o, d, valid, lane, kind);
 }
 
+// the mask words of the cube-map cell of direction d in TX tx's table (hrt_kpatch.txcell) -- the hot kernels through
+// closest_hit_txcell; hrt_debug_candidates_kernel
+__device__ __forceinline__ void txcell_load(const hrt_kpatch &X, uint32_t tx, F3 d, uint32_t (&w)[8])
+{
+    const Rsrc mr = make_rsrc(reinterpret_cast<const uint8_t *>(X.txcell));
+    const uint32_t off = (tx * HRT_RXT_BINS + rxt_cell(d)) * (HRT_PATCH_WORDS * 8u);
+    const auto a = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)off, 0, 0);
+    const auto b = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)(off + 16u), 0, 0);
+    w[0] = (uint32_t)a[0]; w[1] = (uint32_t)a[1]; w[2] = (uint32_t)a[2]; w[3] = (uint32_t)a[3];
+    w[4] = (uint32_t)b[0]; w[5] = (uint32_t)b[1]; w[6] = (uint32_t)b[2]; w[7] = (uint32_t)b[3];
+}
+
 // launch 0 on patch-table problems: the ray leaves TX `tx` exactly (o == its position), so its candidates are the
 // mask of the cube-map cell of its own direction (hrt_kpatch.txcell); the wave ORs and walks the union
 template <typename TriPtr, typename OrigPtr>
@@ -902,14 +923,7 @@ __device__ __forceinline__ Hit closest_hit_txcell(TriPtr tri, OrigPtr orig, cons
     uint32_t w[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) w[k] = 0u;
-    if (valid) {
-        const Rsrc mr = make_rsrc(reinterpret_cast<const uint8_t *>(X.txcell));
-        const uint32_t off = (tx * HRT_RXT_BINS + rxt_cell(d)) * (HRT_PATCH_WORDS * 8u);
-        const auto a = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)off, 0, 0);
-        const auto b = __builtin_amdgcn_raw_buffer_load_b128(mr, (int)(off + 16u), 0, 0);
-        w[0] = (uint32_t)a[0]; w[1] = (uint32_t)a[1]; w[2] = (uint32_t)a[2]; w[3] = (uint32_t)a[3];
-        w[4] = (uint32_t)b[0]; w[5] = (uint32_t)b[1]; w[6] = (uint32_t)b[2]; w[7] = (uint32_t)b[3];
-    }
+    if (valid) txcell_load(X, tx, d, w);
     return closest_hit_words(tri, orig, w, false, num_tri, o, d, valid, lane, 0);
 }
 
@@ -4120,6 +4134,59 @@ __global__ void hrt_selftest_math_kernel(int fn, const float *in, float *out, ui
     out[i] = y;
 }
 
+// TEST ENTRY (hrt_debug_candidates, include/hrt_device.h): one query per lane, the lane's OWN lookup through the device
+// functions the hot kernels call -- no wave union, no walk.  in [n][8]: o, d, row, apex (u32 bits); out [n][10]:
+// served, patch index, eight mask words (zero when not served).  mode 0 / 1: the patch table for RX `apex` / for the
+// image of TX `apex` (d enters the line test); 2: TX `apex`'s cell mask of launch 0; 3: the per-cell mask of apex
+// `apex` (RX k or num_rx + t) on tables of at most 64 triangles, served = the origin is inside the region ball.
+// An apex past the tables is not served (and nothing is loaded).
+__global__ __launch_bounds__(256) void hrt_debug_candidates_kernel(const float *tri_f, uint32_t num_tri, const float *tx_pos,
+                                                                   uint32_t num_rx, uint32_t num_tx, const hrt_kpatch X,
+                                                                   const hrt_krxt R, int mode, uint64_t n, const float *in,
+                                                                   uint32_t *out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 *tri = reinterpret_cast<const float4 *>(tri_f);
+    const float *q = in + 8u * i;
+    const F3 o = {q[0], q[1], q[2]}, d = {q[3], q[4], q[5]};
+    const uint32_t row = __float_as_uint(q[6]), apex = __float_as_uint(q[7]);
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = 0u;
+    uint32_t served = 0u, pidx = 0u;
+    if (mode <= 1) {
+        const bool image = mode == 1;
+        const bool ok = apex < (image ? X.num_img : num_rx);
+        float4 p0, p1;
+        patch_fetch(X, num_tri, row, true, p0, p1);
+        F3 ap = o;
+        if (image && ok) ap = {tx_pos[3u * apex], tx_pos[3u * apex + 1u], tx_pos[3u * apex + 2u]};
+        PatchRef ref = patch_locate(tri, X, num_tri, row, o, image, ap, image ? d : o, p0, p1);
+        ref.served = ref.served && ok;
+        patch_load(X, ref, image ? num_rx + apex : apex, true, w);
+        served = ref.served ? 1u : 0u;
+        pidx = ref.served ? ref.off / (HRT_PATCH_WORDS * 8u) : 0u;
+    } else if (mode == 2) {
+        if (apex < num_tx) {
+            txcell_load(X, apex, d, w);
+            served = 1u;
+        }
+    } else {
+        if (apex < num_rx + num_tx && rxt_inside(R, o)) {
+            const unsigned long long m = rxt_cell_load(R, apex, d);
+            w[0] = (uint32_t)m;
+            w[1] = (uint32_t)(m >> 32);
+            served = 1u;
+        }
+    }
+    uint32_t *y = out + 10u * i;
+    y[0] = served;
+    y[1] = pidx;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) y[2 + k] = w[k];
+}
+
 template <bool LDS, int V>
 static void launch_trace_t(const hrt_kparams *P, uint32_t bounce, uint32_t blocks, size_t lds,
                            hipStream_t st, hipError_t *err)
@@ -4730,6 +4797,16 @@ int hrt_hip_selftest_math(int fn, const float *d_in, float *d_out, uint64_t n, v
     if (n == 0) return 0;
     hipLaunchKernelGGL(hrt_selftest_math_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, fn, d_in, d_out, n);
+    return (int)hipGetLastError();
+}
+
+int hrt_hip_debug_candidates(const float *d_tri, uint32_t num_tri, const float *d_tx_pos, uint32_t num_rx, uint32_t num_tx,
+                             const hrt_kpatch *patch, const hrt_krxt *rxt, int mode, uint64_t n, const float *d_in,
+                             uint32_t *d_out, void *stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(hrt_debug_candidates_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       d_tri, num_tri, d_tx_pos, num_rx, num_tx, *patch, *rxt, mode, n, d_in, d_out);
     return (int)hipGetLastError();
 }
 

@@ -284,6 +284,9 @@ int hrt_hip_launch_order(const uint32_t *d_seg_start, const uint32_t *d_seg_band
                          uint32_t *d_order, void *stream);
 int hrt_hip_h2d_async(void *dst, const void *src, uint64_t bytes, void *stream);
 int hrt_hip_selftest_math(int fn, const float *d_in, float *d_out, uint64_t n, void *stream);
+int hrt_hip_debug_candidates(const float *d_tri, uint32_t num_tri, const float *d_tx_pos, uint32_t num_rx, uint32_t num_tx,
+                             const hrt_kpatch *patch, const hrt_krxt *rxt, int mode, uint64_t n, const float *d_in,
+                             uint32_t *d_out, void *stream);
 #define HRT_STATS_COLS 16
 int hrt_hip_read_stats(unsigned long long *out3xCOLS, int reset);
 /* events: opaque handles */

@@ -455,6 +455,29 @@ int hrt_selftest_math(int device, int fn, const float *in, float *out, uint64_t 
  * leaves judged, 11 of them with flagged triangles, 12 flagged triangles, 13-15 unused. */
 int hrt_debug_kernel_stats(int device, uint64_t *out48, int reset);
 
+/* TEST ONLY -- a lane's own candidate lookup, for tests/test_gpu_candidates.py.  Every kernel that traces a ray on
+ * tables of at most 256 triangles takes its candidates from bit masks built once per problem (csrc/hrt_kparams.h:
+ * hrt_kpatch, hrt_krxt) and walks the UNION over its wave; this entry returns what ONE lane looks up, before any
+ * union and without a walk, through the device functions the hot kernels call (patch_fetch, patch_locate, patch_load,
+ * txcell_load, rxt_inside, rxt_cell_load).  One query per lane of one small kernel:
+ *   in  [n][8]   origin xyz, direction xyz, table row (u32 bits), apex (u32 bits)
+ *   out [n][10]  served (0 / 1), patch index, 8 mask words (bit j of word k = table row 32 k + j); all zero words
+ *                and patch index 0 when not served
+ *   mode 0  apex = RX k     the patch table of `row` for shadow rays to RX k (the direction is not used)
+ *   mode 1  apex = TX t     the patch table of `row` for the image of TX t; the direction enters the line test
+ *   mode 2  apex = TX t     the TX cell mask of launch 0 (origin and row are not used)
+ *   mode 3  apex = RX k or num_rx + t: the per-cell mask on tables of at most 64 triangles (words 0, 1);
+ *           served = the origin lies inside the region ball (a hot lane outside it asks for the whole table)
+ * An apex past the tables is not served.  HRT_E_INVALID, nothing launched: the problem has no table for the mode;
+ * mode outside 0 .. 3; NULL pointers; n > 2^26.  Host arrays; blocks until done. */
+int hrt_debug_candidates(const hrt_problem *p, int mode, uint64_t n, const float *in, uint32_t *out);
+/* TEST ONLY -- what the candidate tables were built with: nuv [T][2] the grid of every table row as the kernels
+ * read it (0 0 = not served), {hmax, ro_rx, ro_img}, the number of patches (patch indices of row j:
+ * [base_j, base_j + nu nv), base_j = the sum over the rows before it), kinds = bit 0 patch tables, bit 1 their
+ * image-apex part, bit 2 TX cell masks, bit 3 per-cell masks (tables of at most 64 triangles). */
+int hrt_debug_table_info(const hrt_problem *p, uint32_t *nuv, float *hmax_ro_rx_ro_img, uint64_t *num_patch,
+                         uint32_t *kinds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,11 +192,12 @@ typedef struct {
 /* src/compute_paths.c:237-287.  Closest hit over all triangles in (mesh, face) order; the
  * strict '<' keeps the lowest index on equal distance.  theta depends only on the final
  * winner, so it is evaluated once after the loop. */
-static hit_t closest_hit(const tri_t *tris, uint32_t nt, v3 o, v3 d)
+static inline hit_t closest_hit_sel(const tri_t *tris, uint32_t nt, v3 o, v3 d, const uint8_t *visit)
 {
     float best = 1e9f;
     uint32_t who = HRT_NO_HIT;
     for (uint32_t j = 0; j < nt; ++j) {
+        if (visit && !visit[j]) continue;   /* (hrt_oracle_closest_hits: a scan of the marked triangles only) */
         const tri_t *T = &tris[j];
         v3 pv = cross3(d, T->e2);
         float det = dot3(T->e1, pv);
@@ -220,6 +221,7 @@ static hit_t closest_hit(const tri_t *tris, uint32_t nt, v3 o, v3 d)
     }
     return h;
 }
+static hit_t closest_hit(const tri_t *tris, uint32_t nt, v3 o, v3 d) { return closest_hit_sel(tris, nt, o, d, NULL); }
 
 /* src/compute_paths.c:300-344 */
 static void fresnel(const mat_pre *m, float th, float out[4])
@@ -606,4 +608,99 @@ void hrt_oracle_libm(int fn, const float *in, float *out, size_t n)
         }
         out[i] = y;
     }
+}
+
+/* Prepared triangles of a scene as hrt_oracle_compute_paths forms them (:438, :208-224, :259-260). */
+static tri_t *prepare_tris(const hrt_oracle_scene *sc)
+{
+    const uint32_t T = sc->num_tri;
+    tri_t *tris = (tri_t *)malloc((size_t)(T ? T : 1) * sizeof(tri_t));
+    if (!tris) return NULL;
+    for (uint32_t j = 0; j < T; ++j) {
+        v3 a = ld3(sc->tri_vtx + 9 * j), b = ld3(sc->tri_vtx + 9 * j + 3), c = ld3(sc->tri_vtx + 9 * j + 6);
+        tris[j].v1 = a;
+        tris[j].e1 = sub3(b, a);
+        tris[j].e2 = sub3(c, a);
+        tris[j].n = unit3(cross3(tris[j].e1, tris[j].e2));
+    }
+    return tris;
+}
+
+/* The full scan of src/compute_paths.c:237-287 (closest_hit above) for n rays of the caller's own: tri_out[i] = the
+ * winner's flat index (HRT_NO_HIT: none), dist_bits_out[i] = the bits of its distance (of 1e9f on a miss).
+ * row_masks != NULL restricts ray i's scan to the triangles marked in row_masks[i * mask_words ..]: bit r of the
+ * 64-bit words marks ROW r of some other table, orig_of_row[r] its flat index here (rows >= num_rows must not be
+ * marked: -2); the scan still runs in flat-index order, so the tie rule is the same (strict <, lowest flat index).
+ * For tests/test_gpu_candidates.py: a candidate mask is sound when the restricted scan equals the full one. */
+int hrt_oracle_closest_hits(const hrt_oracle_scene *sc, const float *o, const float *d, size_t n,
+                            const uint64_t *row_masks, uint32_t mask_words, const uint32_t *orig_of_row,
+                            uint32_t num_rows, uint32_t *tri_out, uint32_t *dist_bits_out)
+{
+    const uint32_t T = sc->num_tri;
+    tri_t *tris = prepare_tris(sc);
+    if (!tris) return -1;
+    int bad = 0;
+#pragma omp parallel
+    {
+        uint8_t *visit = row_masks ? (uint8_t *)malloc(T ? T : 1) : NULL;
+#pragma omp for schedule(dynamic, 256)
+        for (size_t i = 0; i < n; ++i) {
+            if (row_masks) {
+                if (!visit) {
+#pragma omp atomic write
+                    bad = -1;
+                    continue;
+                }
+                memset(visit, 0, T ? T : 1);
+                for (uint32_t w = 0; w < mask_words; ++w) {
+                    uint64_t m = row_masks[i * mask_words + w];
+                    while (m) {
+                        const uint32_t r = w * 64u + (uint32_t)__builtin_ctzll(m);
+                        m &= m - 1;
+                        if (r >= num_rows || orig_of_row[r] >= T) {
+#pragma omp atomic write
+                            bad = -2;
+                        } else {
+                            visit[orig_of_row[r]] = 1;
+                        }
+                    }
+                }
+            }
+            const hit_t h = closest_hit_sel(tris, T, ld3(o + 3 * i), ld3(d + 3 * i), visit);
+            tri_out[i] = h.tri;
+            memcpy(&dist_bits_out[i], &h.t, 4);
+        }
+        free(visit);
+    }
+    free(tris);
+    return bad;
+}
+
+/* The shadow direction as the reference forms it (src/compute_paths.c:517-519 of this restatement's bounce loop:
+ * w = rx - o, normalised by unit3) for n (origin, rx) pairs. */
+void hrt_oracle_shadow_dirs(const float *o, const float *rx, size_t n, float *w_out)
+{
+    for (size_t i = 0; i < n; ++i) st3(w_out + 3 * i, unit3(sub3(ld3(rx + 3 * i), ld3(o + 3 * i))));
+}
+
+/* What a bounce leaves behind (:502-505 above; src/compute_paths.c:654-659) for n rays that left `from` towards
+ * `through` and were mirrored by triangle tri[i]: d0 = unit3(through - from), d = d0 - n 2 dot(d0, n), and the origin
+ * o_in advanced 1e-4 along d. */
+int hrt_oracle_mirror(const hrt_oracle_scene *sc, const uint32_t *tri, const float *from, const float *through,
+                      const float *o_in, size_t n, float *d_out, float *o_out)
+{
+    tri_t *tris = prepare_tris(sc);
+    if (!tris) return -1;
+    int bad = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (tri[i] >= sc->num_tri) { bad = -2; continue; }
+        const v3 nn = tris[tri[i]].n;
+        v3 dd = unit3(sub3(ld3(through + 3 * i), ld3(from + 3 * i)));
+        const float dn = dot3(dd, nn);
+        dd = sub3(dd, mul3(nn, 2.f * dn));
+        st3(d_out + 3 * i, dd);
+        st3(o_out + 3 * i, add3(ld3(o_in + 3 * i), mul3(dd, 1e-4f)));
+    }
+    free(tris);
+    return bad;
 }

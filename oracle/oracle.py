@@ -78,6 +78,13 @@ def lib():
         _lib.hrt_oracle_set_threads(int(os.environ.get("HRT_ORACLE_THREADS", min(16, cores))))
         _lib.hrt_oracle_libm.argtypes = [C.c_int, _f32p, _f32p, C.c_size_t]
         _lib.hrt_oracle_libm.restype = None
+        _lib.hrt_oracle_closest_hits.restype = C.c_int
+        _lib.hrt_oracle_closest_hits.argtypes = [C.POINTER(_Scene), _f32p, _f32p, C.c_size_t, _u64p, C.c_uint32,
+                                                 _u32p, C.c_uint32, _u32p, _u32p]
+        _lib.hrt_oracle_shadow_dirs.restype = None
+        _lib.hrt_oracle_shadow_dirs.argtypes = [_f32p, _f32p, C.c_size_t, _f32p]
+        _lib.hrt_oracle_mirror.restype = C.c_int
+        _lib.hrt_oracle_mirror.argtypes = [C.POINTER(_Scene), _u32p, _f32p, _f32p, _f32p, C.c_size_t, _f32p, _f32p]
     return _lib
 
 
@@ -285,3 +292,60 @@ def host_libm(fn, x):
     out = np.empty_like(x)
     lib().hrt_oracle_libm(LIBM_FN[fn], _p(x), _p(out), x.size)
     return out
+
+
+def _scene_arg(scene):
+    """`scene`: a .hrt path or the dict flatten() returns -> (flat, _Scene)"""
+    flat = scene if isinstance(scene, dict) else flatten(read_hrt(scene))
+    sc = _Scene(len(flat["mesh_material"]), flat["tri_vtx"].shape[0], _p(flat["tri_vtx"]), _p(flat["tri_mesh"], _u32p),
+                _p(flat["mesh_material"], _u32p), _p(flat["mesh_velocity"]))
+    return flat, sc
+
+
+def _rows3(a):
+    return np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))
+
+
+def closest_hits(scene, o, d, row_masks=None, orig_of_row=None):
+    """The oracle's full scan (closest_hit) for n rays of the caller's own -> (tri [n] flat indices, NO_HIT on a miss;
+    dist bits [n] uint32).  With row_masks (uint64 [n][W]: bit r of a ray's words marks ROW r of the product's device
+    table) the scan visits only the marked triangles; orig_of_row (hrt_problem_tri_order) maps rows to the flat
+    indices of this scene; the tie rule is the same (strict <, lowest flat index)."""
+    flat, sc = _scene_arg(scene)
+    o, d = _rows3(o), _rows3(d)
+    n = o.shape[0]
+    assert d.shape[0] == n
+    tri, dist = np.empty(n, np.uint32), np.empty(n, np.uint32)
+    if row_masks is None:
+        rc = lib().hrt_oracle_closest_hits(C.byref(sc), _p(o), _p(d), n, None, 0, None, 0, _p(tri, _u32p), _p(dist, _u32p))
+    else:
+        m = np.ascontiguousarray(np.asarray(row_masks, np.uint64).reshape(n, -1))
+        oo = np.ascontiguousarray(np.asarray(orig_of_row, np.uint32))
+        rc = lib().hrt_oracle_closest_hits(C.byref(sc), _p(o), _p(d), n, _p(m, _u64p), m.shape[1], _p(oo, _u32p), oo.size,
+                                           _p(tri, _u32p), _p(dist, _u32p))
+    if rc != 0:
+        raise RuntimeError("hrt_oracle_closest_hits failed: %d" % rc)
+    return tri, dist
+
+
+def shadow_dirs(o, rx):
+    """unit3(rx - o) as the reference forms the shadow direction, per row."""
+    o, rx = _rows3(o), _rows3(rx)
+    assert o.shape == rx.shape
+    w = np.empty_like(o)
+    lib().hrt_oracle_shadow_dirs(_p(o), _p(rx), o.shape[0], _p(w))
+    return w
+
+
+def mirror(scene, tri, src, through, o):
+    """Rays that left `src` towards `through` and were mirrored by triangle tri[i] (flat index): -> (d, o advanced
+    1e-4 along d), the reference's sequence of a bounce."""
+    flat, sc = _scene_arg(scene)
+    src, through, o = _rows3(src), _rows3(through), _rows3(o)
+    tri = np.ascontiguousarray(np.asarray(tri, np.uint32))
+    assert src.shape == through.shape == o.shape and tri.size == o.shape[0]
+    d, o2 = np.empty_like(o), np.empty_like(o)
+    rc = lib().hrt_oracle_mirror(C.byref(sc), _p(tri, _u32p), _p(src), _p(through), _p(o), tri.size, _p(d), _p(o2))
+    if rc != 0:
+        raise RuntimeError("hrt_oracle_mirror failed: %d" % rc)
+    return d, o2
