@@ -127,3 +127,154 @@ def check(got, B, S, wr, wt, scale=1e-5, what=""):
     print("%s: max |err| / bound = %.3g" % (what, worst))
     assert (err <= lim).all(), (what, worst, np.unravel_index(np.argmax(err / lim), err.shape))
     return worst
+
+
+# ------------------------------------------------------------------ planted workspaces: the unit bound
+UNIT_TOL = 0.05   # per element pair: a tenth of the weakest planted term (tests/test_gpu_beam_planted.py)
+
+
+def check_unit(got, ref, wr, wt, what):
+    """|got - ref| <= UNIT_TOL ||W_rx[a]||_1 ||W_tx[b]||_1 everywhere; returns the largest error over bound"""
+    got = np.asarray(got).astype(np.complex128)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    tol = UNIT_TOL * np.abs(wr).sum(axis=1)[:, None] * np.abs(wt).sum(axis=1)[None, :]
+    err = np.abs(got - ref)
+    err = np.where(np.isnan(err), np.inf, err).reshape(*ref.shape[:4], -1).max(axis=-1)   # (rx, tx, a, b)
+    worst = float((err / tol).max())
+    assert (err <= tol).all(), "%s: |err| / bound = %.3g at (rx, tx, a, b) = %s" % (
+        what, worst, np.unravel_index(np.argmax(err / tol), err.shape))
+    return worst
+
+
+def planted_codebooks(nr, nt):
+    """3 RX and 5 TX random beams; beam 0 of either side has one non-zero weight (tests/test_gpu_beam_planted.py)"""
+    wr, wt = random_weights(3, nr, 21), random_weights(5, nt, 22)
+    wr[0], wt[0] = 0, 0
+    wr[0, nr - 1], wt[0, 0] = 0.8 - 0.6j, -0.5j   # beam 0: one element
+    return wr, wt
+
+
+# ------------------------------------------------------------------ the S stage's edges (tests/test_gpu_beam_edges.py)
+PAIRS = 32   # csrc/hrt_array_channel.h HRT_AC_PAIRS: beam pairs of one workgroup
+ETILE = 32   # csrc/hrt_beam_channel.h HRT_BM_ETILE: elements whose phase factors are in LDS at a time
+
+
+def probe_weights(beams, elements, seed=0):
+    """complex64 [beams, elements], sparse: beam a has 1 + (a + seed) % 4 weights of modulus 1 (fewer where the side
+    has fewer elements), all phases distinct (a golden-ratio sequence: no symmetry).  The first sits at element
+    (37 a + 5) % elements, the others on tile borders (0, 31, 32, 63, 64, elements - 1), those of another tile than the
+    first one's taken first: every beam with two weights or more spans two tiles where the side has two.  With
+    ||W[a]||_1 <= 4 a weight read from the wrong beam, element or slot moves the output by many times the bound."""
+    n = int(elements)
+    borders = sorted({e for e in (0, ETILE - 1, ETILE, 2 * ETILE - 1, 2 * ETILE, n - 1) if 0 <= e < n})
+    W = np.zeros((beams, n), np.complex64)
+    k = 0
+    for a in range(beams):
+        first = (37 * a + 5) % n
+        els = [first]
+        r = a % len(borders)
+        order = sorted(borders[r:] + borders[:r], key=lambda e: e // ETILE == first // ETILE)   # (stable)
+        for e in order:
+            if len(els) == 1 + (a + seed) % 4:
+                break
+            if e not in els:
+                els.append(e)
+        for e in els:
+            k += 1
+            W[a, e] = np.exp(2j * np.pi * ((0.137 + 0.6180339887498949 * k) % 1.0))
+    return W
+
+
+def block_slots(pb, br, bt):
+    """(a0, na, [TX beam of slot s], pairs) of pair block pb, restated from the S stage of hrt_beam_partial_kernel: RX
+    slot s is beam a0 + s, s < na; TX slot s is beam s where Bt <= 32, else the beam of pair p0 + s"""
+    p0, npairs = pb * PAIRS, br * bt
+    assert p0 < npairs
+    last = min(p0 + PAIRS, npairs) - 1
+    a0 = p0 // bt
+    tx = list(range(bt)) if bt <= PAIRS else [(p0 + s) % bt for s in range(PAIRS)]
+    return a0, last // bt - a0 + 1, tx, last - p0 + 1
+
+
+def pick_weight(W, beam=None, element=None):
+    """(beam, element) of the first non-zero weight of W with that beam and / or element"""
+    for b, e in np.argwhere(np.asarray(W) != 0):
+        if (beam is None or b == beam) and (element is None or e == element):
+            return int(b), int(e)
+    raise AssertionError("no weight at beam %s, element %s" % (beam, element))
+
+
+def change_weight(wr, wt, side, beam, element, how):
+    """the codebooks with W_side[beam, element] zeroed ("zero") or moved to the next beam ("move")"""
+    wr, wt = np.array(wr), np.array(wt)
+    W = wt if side == "tx" else wr
+    w = W[beam, element]
+    assert w != 0 and how in ("zero", "move") and (how == "zero" or W.shape[0] > 1), (side, beam, element, how)
+    W[beam, element] = 0
+    if how == "move":
+        W[(beam + 1) % W.shape[0], element] += w
+    return wr, wt
+
+
+def edge_grid(K, T, t0=0.0):
+    """(f0, df, f [K], t [T]) on the planted grid"""
+    df = PL.FS / 4096
+    return PL.FC, df, PL.FC + np.arange(K) * df, t0 + np.arange(T) * PL.DT
+
+
+HEAVY = 8.0   # modulus of the weights the controls of case F change (see edge_cases)
+
+
+def edge_cases(lam):
+    """The cases of tests/test_gpu_beam_edges.py by name: dict(rxe, txe, wr, wt, probe, controls), elements for the
+    wavelength lam.  controls: (name, side, beam, element, how) for change_weight, at the positions where an index of
+    the S stage can go wrong: the last element of the last tile, element 32, the last beam of a block's RX slots, the
+    first TX beam after a wrap.  probe: the codebooks have single-weight beams, so one planted record is seen too.
+
+    F has 256 dense weights a beam on both sides.  The bound follows ||W_rx[a]||_1 ||W_tx[b]||_1, about 200 * 200,
+    while one weight of modulus 1 moves a sum over N records with unrelated phases by about sqrt(N) |g_tx|, far less.
+    So the weights F's controls change have modulus HEAVY: the sums stay dense, and those weights are sharp."""
+    from .pathsum_util import _random, _upa
+    one = np.zeros((1, 3))
+    u256, u64, u33 = _upa(16, 16, lam / 2), _upa(8, 8, lam / 2), _upa(3, 11, lam / 2)
+    r65, r256 = _random(65, 6 * lam, 12), _random(256, 8 * lam, 14)
+    w1 = np.array([[0.6 - 0.8j]], np.complex64)
+    cases = {
+        "A": dict(rxe=u256, txe=one, wr=probe_weights(256, 256), wt=w1, probe=True,
+                  sel=[("last element of the last tile", "rx", None, 255, "zero"), ("element 32", "rx", None, 32, "move"),
+                       ("last RX slot of block 1", "rx", 63, None, "move"), ("RX slot 16 of block 0", "rx", 16, None, "zero")]),
+        "B": dict(rxe=one, txe=u256, wr=np.conj(w1) * 1j, wt=probe_weights(256, 256, 1), probe=True,
+                  sel=[("last element of the last tile", "tx", None, 255, "zero"), ("element 32", "tx", None, 32, "move"),
+                       ("last TX slot of block 1", "tx", 63, None, "move"), ("first TX slot of block 2", "tx", 64, None, "zero")]),
+        "C": dict(rxe=_random(2, 4 * lam, 11), txe=r65, wr=probe_weights(3, 2), wt=random_weights(33, 65, 31), probe=True,
+                  sel=[("last element of the last tile", "tx", 32, 64, "zero"), ("element 32", "tx", 31, 32, "move"),
+                       ("last RX slot of block 1", "rx", 1, None, "move"),
+                       ("first TX beam after the wrap of block 1", "tx", 0, 33, "zero")]),
+        "D32": dict(rxe=u64, txe=u33, wr=probe_weights(2, 64, 2), wt=probe_weights(32, 33), probe=True,
+                    sel=[("last element of the last RX tile", "rx", None, 63, "zero"),
+                         ("element 32 (the last TX tile)", "tx", None, 32, "move"),
+                         ("the RX beam of block 1", "rx", 1, None, "move"), ("last TX slot", "tx", 31, None, "move")]),
+        "D31": dict(rxe=u64, txe=u33, wr=probe_weights(3, 64, 1), wt=probe_weights(31, 33), probe=True,
+                    sel=[("last element of the last RX tile", "rx", None, 63, "move"),
+                         ("element 32 (the last TX tile)", "tx", None, 32, "zero"),
+                         ("last RX slot of block 0", "rx", 1, None, "zero"), ("last TX slot", "tx", 30, None, "move")]),
+        "E": dict(rxe=u33, txe=r65, wr=random_weights(2, 33, 41), wt=random_weights(40, 65, 42), probe=False,
+                  sel=[("last element of the last RX tile", "rx", 1, 32, "zero"),
+                       ("last element of the last TX tile", "tx", 39, 64, "zero"), ("element 32", "tx", 7, 32, "move"),
+                       ("first TX beam after the wrap of block 1", "tx", 0, 33, "move"),
+                       ("last RX slot of block 1", "rx", 1, 0, "zero")]),
+        "F": dict(rxe=u256, txe=r256, wr=random_weights(4, 256, 51), wt=random_weights(8, 256, 52), probe=False,
+                  sel=[("last element of the last RX tile, last RX slot", "rx", 3, 255, "zero"),
+                       ("last element of the last TX tile", "tx", 7, 255, "move"), ("element 32", "rx", 1, 32, "move"),
+                       ("element 32", "tx", 2, 32, "zero")]),
+    }
+    for name, c in cases.items():
+        c["wr"], c["wt"] = np.asarray(c["wr"], np.complex64), np.asarray(c["wt"], np.complex64)
+        c["controls"] = []
+        for what, side, beam, element, how in c.pop("sel"):
+            W = c["wt"] if side == "tx" else c["wr"]
+            beam, element = pick_weight(W, beam, element)
+            if name == "F":
+                W[beam, element] *= HEAVY / abs(W[beam, element])
+            c["controls"].append((what, side, beam, element, how))
+    return cases

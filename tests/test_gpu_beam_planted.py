@@ -18,35 +18,15 @@ from hermespy_rt_amd import beams
 
 from . import beam_util as BU
 from . import planted as PL
+from .beam_util import check_unit as _check
+from .beam_util import planted_codebooks as _codebooks
 from .pathsum_util import PARTS, _bits, _expect_failure, _force_los_classes, _traced
 
 pytestmark = pytest.mark.gpu
 
-UNIT_TOL = 0.05
-
-
-def _codebooks(nr, nt):
-    wr, wt = BU.random_weights(3, nr, 21), BU.random_weights(5, nt, 22)
-    wr[0], wt[0] = 0, 0
-    wr[0, nr - 1], wt[0, 0] = 0.8 - 0.6j, -0.5j   # beam 0: one element
-    return wr, wt
-
 
 def _sel(T, los, scatter):
     return PL.select(T, (T["los"] & los) | (~T["los"] & scatter))
-
-
-def _check(got, ref, wr, wt, what):
-    """|got - ref| <= UNIT_TOL ||W_rx[a]||_1 ||W_tx[b]||_1 everywhere"""
-    got = np.asarray(got).astype(np.complex128)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    tol = UNIT_TOL * np.abs(wr).sum(axis=1)[:, None] * np.abs(wt).sum(axis=1)[None, :]
-    err = np.abs(got - ref)
-    err = np.where(np.isnan(err), np.inf, err).reshape(*ref.shape[:4], -1).max(axis=-1)   # (rx, tx, a, b)
-    worst = float((err / tol).max())
-    assert (err <= tol).all(), "%s: |err| / bound = %.3g at (rx, tx, a, b) = %s" % (
-        what, worst, np.unravel_index(np.argmax(err / tol), err.shape))
-    return worst
 
 
 @pytest.fixture(scope="module", params=["C3", "room"])

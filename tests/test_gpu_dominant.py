@@ -15,7 +15,7 @@ from hermespy_rt_amd import abi, dominant
 from . import configs as K
 from . import planted as PL
 from .dominant_util import check_bytes, expected, to_numpy, trace_terms
-from .pathsum_util import CONFIGS, PARTS, _bits, _cfg, _expect_failure, _force_los_classes, _traced, _tracer
+from .pathsum_util import CONFIGS, PARTS, _bits, _cfg, _expect_failure, _force_los_classes, _thin, _traced, _tracer
 
 pytestmark = pytest.mark.gpu
 
@@ -79,44 +79,6 @@ def _planted_check(tr, k):
         got["tri"][got["bounce"] >= 0] = 0   # (a planted term list has no triangles: reference() leaves 0 there)
         check_bytes(got, dominant.reference(terms, tr.nrx, tr.ntx, k), ("planted", k))
     return check
-
-
-def _thin(tr, per_link, seed=3):
-    """clear unblocked bits of tr's last trace until every link has at most about per_link unblocked records; the last
-    unblocked record of every (block, rx) stays (PL.control_records picks it)"""
-    torch = tr.torch
-    counts = tr.counts()
-    rng = np.random.default_rng(seed)
-    most = 1
-    blocks = []
-    for b in range(tr.nb):
-        n = int(counts[b + 1])
-        if n == 0:
-            continue
-        ray = tr.hit_block(b)[PL.HIT_RAY, :n].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
-        tx, _ = tr.global_path(ray)
-        ub = PL._mask_bits(tr, b, n)
-        blocks.append((b, n, tx, ub))
-    per = np.zeros((tr.nrx, tr.ntx), np.int64)
-    for b, n, tx, ub in blocks:
-        for rx in range(tr.nrx):
-            per[rx] += np.bincount(tx[ub[rx]], minlength=tr.ntx)
-    p = min(1.0, per_link / max(int(per.max()), 1))
-    for b, n, tx, ub in blocks:
-        keep = ub & (rng.random(ub.shape) < p)
-        for rx in range(tr.nrx):
-            i = np.nonzero(ub[rx])[0]
-            if i.size:
-                keep[rx, i[-1]] = True
-        pad = (-n) % 64
-        bits = np.pad(keep, ((0, 0), (0, pad))).reshape(tr.nrx, -1, 64).astype(np.uint64)
-        words = (bits << np.arange(64, dtype=np.uint64)).sum(axis=-1, dtype=np.uint64)   # [nrx, ceil(n / 64)]
-        m = tr.mask_block(b).view(torch.int64)   # [nrx, cap / 64]
-        if n % 64:   # the bits at and beyond n of the last word stay as they are
-            old = m[:, words.shape[1] - 1].cpu().numpy().view(np.uint64)
-            words[:, -1] |= old & ~np.uint64((1 << (n % 64)) - 1)
-        m[:, :words.shape[1]] = torch.from_numpy(words.view(np.int64)).to(tr.device)
-    torch.cuda.synchronize(tr.device)
 
 
 @pytest.mark.parametrize("name", sorted(CONFIGS))
