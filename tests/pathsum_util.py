@@ -223,6 +223,10 @@ def power_reference(T, tau0, dtau, ld, nth, nph):
 
 
 def power_check(got, ref, tag=""):
+    """got against power_reference within float64 rounding.  The edge slack (the whole power of every term whose bin
+    coordinate lies within 1e-6 of an edge) is for TRACED directions, where numpy's and the device's libm may fall on
+    either side of an edge; it waives the rule at the edge itself.  tests/test_gpu_power_edges.py pins the edges: it
+    plants records on them and compares every bin at tolerance 0."""
     M, A, pdp, arr, dep, N, slack = ref
     nl = M.shape[0]
     m = np.asarray(got["moments"]).reshape(nl, 2, F)

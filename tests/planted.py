@@ -13,7 +13,8 @@ The planted values make the references exact or FFT-cheap:
     a_te in {1, 2} j^k, a_tm = a_te j / 2    |a|^2 dyadic (TE 1 or 4, TM 1/4 or 1); a swapped polarisation shows
     nu in NUS, FS0 = 0, DFS = -nu            with dt = DT, nu t_m is a whole number of quarter revolutions
 
-Directions stay as traced.  Only plant() and poison() need a device; the rest is plain numpy."""
+Directions stay as traced (tests/power_edges_util.py plants delays and directions on the bin edges of the power
+profiles on top of this).  Only plant() and poison() need a device; the rest is plain numpy."""
 import numpy as np
 
 FS = 2.0 ** 30                 # sampling rate of the planted delay grid (Hz)
