@@ -313,8 +313,8 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                  out_shape, extra, stats, dtype=np.complex64):
-    """One of the seven path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
-    _power_profiles, _dominant_paths or _beam_channel) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
+    """One of the eight path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
+    _power_profiles, _dominant_paths, _beam_channel or _beam_taps) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
     (a flat buffer of out_shape doubles for float64 or bytes for uint8; out_shape None: a placeholder the library
     refuses to write); `extra` are the arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
@@ -458,6 +458,22 @@ def run_compute_array_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_gh
     fits = 0 < pts <= (1 << 24) and ntm * nl <= (1 << 20)
     return _run_pathsum(lib, "hrt_compute_array_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, (nr, nt, 2, ntm, nl) if fits else None, extra, stats)
+
+
+def run_compute_beam_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                          rx_elements, tx_elements, rx_weights, tx_weights, array_frequency=None, stats=None):
+    """hrt_compute_beam_taps through ctypes -> complex64 [nrx, ntx, Br, Bt, 2, num_times, num_taps]: rx_weights
+    (Br, Nr) is applied conjugated (the combiner w^H), tx_weights (Bt, Nt) as it is; array_frequency defaults to the
+    carrier.  Raises RuntimeError("hrt_compute_beam_taps failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    wr, wt = weights(rx_weights, nr, "rx_weights"), weights(tx_weights, nt, "tx_weights")
+    br, bt = wr.shape[0], wt.shape[0]
+    extra += (wr.ctypes.data_as(c_float_p), C.c_size_t(br), wt.ctypes.data_as(c_float_p), C.c_size_t(bt))
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    ntm, nl = int(spec.num_times), int(spec.num_taps)
+    fits = 0 < br * bt * ntm * nl <= (1 << 24) and ntm * nl <= (1 << 20)
+    return _run_pathsum(lib, "hrt_compute_beam_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                        num_bounces, spec, (br, bt, 2, ntm, nl) if fits else None, extra, stats)
 
 
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)

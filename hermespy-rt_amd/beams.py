@@ -1,9 +1,11 @@
-"""Host side of the beamformed channel (Tracer.beam_channel, hermespy_rt.compute_beam_channel): codebooks, steering
-vectors and the contraction the device folds into the path sum, in plain numpy.
+"""Host side of the beamformed channel and taps (Tracer.beam_channel, Tracer.beam_taps, hermespy_rt.compute_beam_channel,
+hermespy_rt.compute_beam_taps): codebooks, steering vectors and the contraction the device folds into the path sum, in
+plain numpy.
 
     dft_codebook   the unitary DFT codebook of an n-element uniform linear array (one beam per row)
     steering       the plane-wave response of an array towards given directions
-    apply          B = conj(W_rx) H W_tx^T on an array_channel result: what beam_channel computes without forming H
+    apply          B = conj(W_rx) H W_tx^T on an array_channel or array_taps result: what beam_channel and beam_taps
+                   compute without forming H
 
 The convention is that of include/hermespy_rt.h (hrt_compute_beam_channel): the RX codebook is a combiner and is
 applied conjugated (w^H), the TX codebook is a precoder and is applied as it is (f); nothing is normalised.  With
@@ -38,7 +40,8 @@ def steering(elements, directions, frequency):
 
 def apply(H, rx_weights, tx_weights):
     """B[rx, tx, a, b, ...] = sum_ij conj(W_rx[a, i]) H[rx, tx, i, j, ...] W_tx[b, j] of an array channel
-    [nrx, ntx, Nr, Nt, ...] (numpy; complex128 unless everything is complex64) with W_rx [Br, Nr] and W_tx [Bt, Nt]"""
+    (array_channel) or of array taps (array_taps: the trailing axes are then pol, time, tap) [nrx, ntx, Nr, Nt, ...]
+    (numpy; complex128 unless everything is complex64) with W_rx [Br, Nr] and W_tx [Bt, Nt]"""
     H = np.asarray(H)
     wr, wt = np.asarray(rx_weights), np.asarray(tx_weights)
     if wr.ndim != 2 or wt.ndim != 2 or H.ndim < 4 or H.shape[2] != wr.shape[1] or H.shape[3] != wt.shape[1]:

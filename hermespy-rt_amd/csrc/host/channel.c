@@ -1,8 +1,8 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel; include/hermespy_rt.h: hrt_compute_channel,
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps; include/hermespy_rt.h: hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
- * hrt_compute_dominant_paths, hrt_compute_beam_channel).
+ * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -10,7 +10,8 @@
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
  * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip, csrc/hrt_power.hip,
- * csrc/hrt_dominant.hip and csrc/hrt_beam_channel.hip, over the workspace view of csrc/hrt_pathsum.h.  The two pair
+ * csrc/hrt_dominant.hip, csrc/hrt_beam_channel.hip and csrc/hrt_beam_taps.hip, over the workspace view of
+ * csrc/hrt_pathsum.h.  The two pair
  * families (hrt_array_channel: element pairs, hrt_beam_channel: beam pairs) share one grid (hrt_kgrid, pair_grid) as
  * their kernels share one GEMM body (csrc/hrt_pair_gemm.inc), and the array and beam drop-ins one packing of the
  * element offsets (ac_pack_offsets).  The drop-in entries run the batch loop of batch.c, with one device output
@@ -24,6 +25,7 @@
 #include "../hrt_array_channel.h"
 #include "../hrt_array_taps.h"
 #include "../hrt_beam_channel.h"
+#include "../hrt_beam_taps.h"
 #include "../hrt_channel.h"
 #include "../hrt_dominant.h"
 #include "../hrt_pathsum.h"
@@ -186,7 +188,7 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-/* One drop-in call: what the seven hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
+/* One drop-in call: what the eight hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
@@ -203,7 +205,7 @@ struct ch_job {
     uint32_t nr, nt;   /* the array calls' element counts (hrt_compute_array_channel, hrt_compute_array_taps,
                           hrt_compute_beam_channel) */
     double fa;
-    uint32_t nbr, nbt; /* the beam call's beam counts (hrt_compute_beam_channel) */
+    uint32_t nbr, nbt; /* the beam calls' beam counts (hrt_compute_beam_channel, hrt_compute_beam_taps) */
     /* optional: runs on the downloaded output while the problem still exists (NULL: nothing to do) */
     int (*finish)(const ch_job *j, const hrt_problem *p, void *out);
 };
@@ -1054,24 +1056,24 @@ static int beam_check(const hrt_channel_spec *spec, const hrt_array_spec *a, con
     return HRT_OK;
 }
 
-/* the counts of a drop-in beam call, before they are narrowed to the specs' */
-static int beam_counts_check(size_t nr, size_t nt, size_t nbr, size_t nbt)
+/* the counts of a drop-in beam call (`who`), before they are narrowed to the specs' */
+static int beam_counts_check(size_t nr, size_t nt, size_t nbr, size_t nbt, const char *who)
 {
     if (nr > HRT_BM_MAX_ELEMENTS || nt > HRT_BM_MAX_ELEMENTS)
-        return hrt_fail(HRT_E_INVALID, "hrt_beam_channel: %zu RX and %zu TX elements (1 .. %u each)", nr, nt,
+        return hrt_fail(HRT_E_INVALID, "%s: %zu RX and %zu TX elements (1 .. %u each)", who, nr, nt,
                         HRT_BM_MAX_ELEMENTS);
     if (nbr > HRT_BM_MAX_BEAMS || nbt > HRT_BM_MAX_BEAMS)
-        return hrt_fail(HRT_E_INVALID, "hrt_beam_channel: %zu RX and %zu TX beams (1 .. %u each)", nbr, nbt,
+        return hrt_fail(HRT_E_INVALID, "%s: %zu RX and %zu TX beams (1 .. %u each)", who, nbr, nbt,
                         HRT_BM_MAX_BEAMS);
     return HRT_OK;
 }
 
-/* the host weights of a drop-in beam call ([beams][elements][2]): finite */
-static int beam_weights_check(const float *w, size_t beams, size_t elements, const char *side)
+/* the host weights of a drop-in beam call (`who`; [beams][elements][2]): finite */
+static int beam_weights_check(const float *w, size_t beams, size_t elements, const char *side, const char *who)
 {
     for (size_t i = 0; i < beams * elements * 2u; ++i)
         if (!isfinite(w[i]))
-            return hrt_fail(HRT_E_INVALID, "hrt_beam_channel: %s weight (%zu, %zu) is not finite", side,
+            return hrt_fail(HRT_E_INVALID, "%s: %s weight (%zu, %zu) is not finite", who, side,
                             i / (2u * elements), i / 2u % elements);
     return HRT_OK;
 }
@@ -1160,6 +1162,31 @@ static int beam_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *
     return hrt_beam_channel(p, s, d_ws, j->spec, &a, &b, d_scratch, scratch_bytes, d_out, accumulate, NULL);
 }
 
+/* What hrt_compute_beam_channel and hrt_compute_beam_taps share once everything is checked: the offsets (rx then tx;
+ * ac_job_arrays) and behind them the weights (rx then tx; beam_job_beams) for ch_compute to upload, the call.  `job`
+ * has the spec, the output size and the device entry. */
+static int beam_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
+                        float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, const Vec3 *rx_el,
+                        size_t nr, const Vec3 *tx_el, size_t nt, double f_a, const float *rx_weights,
+                        size_t n_rx_beams, const float *tx_weights, size_t n_tx_beams, void *out, hrt_stats *stats,
+                        double t_begin)
+{
+    const size_t n_el = (nr + nt) * 3u, n_wr = n_rx_beams * nr * 2u, n_wt = n_tx_beams * nt * 2u;
+    float *e = (float *)malloc((n_el + n_wr + n_wt) * sizeof(float));
+    if (!e) return hrt_fail(HRT_E_NOMEM, "out of host memory");
+    ac_pack_offsets(rx_el, nr, tx_el, nt, e);
+    memcpy(e + n_el, rx_weights, n_wr * sizeof(float));
+    memcpy(e + n_el + n_wr, tx_weights, n_wt * sizeof(float));
+    job->h_const = e;
+    job->const_bytes = (n_el + n_wr + n_wt) * sizeof(float);
+    job->nr = (uint32_t)nr; job->nt = (uint32_t)nt;
+    job->nbr = (uint32_t)n_rx_beams; job->nbt = (uint32_t)n_tx_beams;
+    job->fa = f_a;
+    const int rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, job, out, stats, t_begin);
+    free(e);
+    return rc;
+}
+
 int hrt_compute_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
                              const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
                              const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt,
@@ -1167,37 +1194,167 @@ int hrt_compute_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_po
                              size_t n_tx_beams, float *out, hrt_stats *stats)
 {
     const double t_begin = hrt_now_s();
-    int rc = beam_counts_check(nr, nt, n_rx_beams, n_tx_beams);
+    int rc = beam_counts_check(nr, nt, n_rx_beams, n_tx_beams, "hrt_beam_channel");
     if (rc) return rc;
     /* (the host pointers stand in for the device ones: beam_check tests them for NULL only) */
     const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
     const hrt_beam_spec bm = {(uint32_t)n_rx_beams, (uint32_t)n_tx_beams, rx_weights, tx_weights};
     if ((rc = beam_check(spec, &a, &bm))) return rc;
     if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_beam_channel"))) return rc;
-    if ((rc = beam_weights_check(rx_weights, n_rx_beams, nr, "RX"))) return rc;
-    if ((rc = beam_weights_check(tx_weights, n_tx_beams, nt, "TX"))) return rc;
+    if ((rc = beam_weights_check(rx_weights, n_rx_beams, nr, "RX", "hrt_beam_channel"))) return rc;
+    if ((rc = beam_weights_check(tx_weights, n_tx_beams, nt, "TX", "hrt_beam_channel"))) return rc;
     if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
                                "hrt_compute_beam_channel")))
         return rc;
-    /* h_const: the offsets (rx then tx), then the weights (rx then tx) */
-    const size_t n_el = (nr + nt) * 3u, n_wr = n_rx_beams * nr * 2u, n_wt = n_tx_beams * nt * 2u;
-    float *e = (float *)malloc((n_el + n_wr + n_wt) * sizeof(float));
-    if (!e) return hrt_fail(HRT_E_NOMEM, "out of host memory");
-    ac_pack_offsets(rx_el, nr, tx_el, nt, e);
-    memcpy(e + n_el, rx_weights, n_wr * sizeof(float));
-    memcpy(e + n_el + n_wr, tx_weights, n_wt * sizeof(float));
     ch_job job;
     memset(&job, 0, sizeof job);
     job.spec = spec;
     job.out_bytes = (uint64_t)nrx * ntx * n_rx_beams * n_tx_beams * 2u * spec->num_times * spec->num_freqs * 8u;
     job.scratch_bytes = beam_job_scratch;
     job.run = beam_job_run;
-    job.h_const = e;
-    job.const_bytes = (n_el + n_wr + n_wt) * sizeof(float);
-    job.nr = (uint32_t)nr; job.nt = (uint32_t)nt;
-    job.nbr = (uint32_t)n_rx_beams; job.nbt = (uint32_t)n_tx_beams;
-    job.fa = f_a;
-    rc = ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
-    free(e);
-    return rc;
+    return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                        rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ beamformed impulse responses (hrt_beam_taps) */
+
+#define HRT_BT_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_BT_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
+
+/* the checks of a beam taps call that need no problem (device pointers are not read).  There is no limit on Nr * Nt:
+ * the element-domain taps are never formed */
+static int bt_check(const hrt_taps_spec *spec, const hrt_array_spec *a, const hrt_beam_spec *bm)
+{
+    const char *who = "hrt_beam_taps";
+    int rc = taps_spec_check(spec, who);
+    if (rc) return rc;
+    if (!a) return hrt_fail(HRT_E_INVALID, "%s: NULL arrays", who);
+    if (!bm) return hrt_fail(HRT_E_INVALID, "%s: NULL beams", who);
+    if (a->num_rx_elements < 1 || a->num_rx_elements > HRT_BM_MAX_ELEMENTS || a->num_tx_elements < 1 ||
+        a->num_tx_elements > HRT_BM_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX elements (1 .. %u each)", who, a->num_rx_elements,
+                        a->num_tx_elements, HRT_BM_MAX_ELEMENTS);
+    if (bm->num_rx_beams < 1 || bm->num_rx_beams > HRT_BM_MAX_BEAMS || bm->num_tx_beams < 1 ||
+        bm->num_tx_beams > HRT_BM_MAX_BEAMS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX beams (1 .. %u each)", who, bm->num_rx_beams,
+                        bm->num_tx_beams, HRT_BM_MAX_BEAMS);
+    const uint64_t pts = (uint64_t)bm->num_rx_beams * bm->num_tx_beams * spec->num_times * spec->num_taps;
+    if (pts > HRT_BM_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: Br * Bt * num_times * num_taps = %llu > 2^24", who,
+                        (unsigned long long)pts);
+    if (!isfinite(a->array_frequency_hz) || !(a->array_frequency_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "%s: the array frequency must be finite and > 0", who);
+    if (!a->rx_elements || !a->tx_elements) return hrt_fail(HRT_E_INVALID, "%s: NULL element offsets", who);
+    if (!bm->rx_weights || !bm->tx_weights) return hrt_fail(HRT_E_INVALID, "%s: NULL beam weights", who);
+    return HRT_OK;
+}
+
+/* the tiling of one beam taps call: a pure function of the problem, the shard, the spec and the array and codebook
+ * sizes (hrt_array_taps' rule with Br Bt for Nr Nt).  The scratch is seg, the partial sums (*off_los bytes of them)
+ * and the LoS gains of every (link, pair) */
+static int bt_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, const hrt_array_spec *a,
+                   const hrt_beam_spec *bm, hrt_kbeam_taps *K, uint64_t *bytes, uint64_t *off_los)
+{
+    int rc = bt_check(spec, a, bm);
+    if (rc) return rc;
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_beam_taps", &K->v))) return rc;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
+    if (links * 2u * bm->num_rx_beams * bm->num_tx_beams * spec->num_times * spec->num_taps >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "hrt_beam_taps: more than 2^39 outputs");
+    ps_shard(s, &K->sh);
+    K->nr = a->num_rx_elements; K->nt = a->num_tx_elements;
+    K->br = bm->num_rx_beams; K->bt = bm->num_tx_beams; K->npairs = K->br * K->bt;
+    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
+    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
+    K->rows = K->npairs * K->T;
+    K->rtiles = (4u * K->rows + 15u) / 16u;
+    K->ctiles = (K->L + 15u) / 16u;
+    /* where the grid has four row tiles (Br Bt T >= 13), 4 x 4 tiles per wave and the waves along the rows: a block
+     * of 16 x 4 tiles (64 rows: up to 64 beam pairs); otherwise 1 x 4 tiles per wave, the waves along the columns */
+    K->rt = K->rtiles >= 4u ? 4u : 1u;
+    const uint32_t brows = K->rt == 4u ? 16u : 1u, bcols = K->rt == 4u ? 4u : 16u;   /* tiles of a block */
+    K->rblocks = (K->rtiles + brows - 1u) / brows;
+    K->cblocks = (K->ctiles + bcols - 1u) / bcols;
+    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
+    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->L * 8u;
+    const uint64_t sums = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_BT_TARGET_GROUPS,
+                                    per_chunk, HRT_BT_PARTIAL_MAX, 65535u);
+    *off_los = align256(K->v.nchunks * per_chunk);
+    *bytes = sums - K->v.nchunks * per_chunk + *off_los + align256(links * K->npairs * 8u);
+    return HRT_OK;
+}
+
+int hrt_beam_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec,
+                                const hrt_array_spec *arrays, const hrt_beam_spec *beams, uint64_t *out)
+{
+    hrt_kbeam_taps K;
+    uint64_t bytes = 0, off_los = 0;
+    const int rc = bt_plan(p, s, spec, arrays, beams, &K, &bytes, &off_los);
+    return ps_scratch_out(rc, bytes, out, "hrt_beam_taps_scratch_bytes");
+}
+
+int hrt_beam_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+                  const hrt_array_spec *arrays, const hrt_beam_spec *beams, void *d_scratch, uint64_t scratch_bytes,
+                  float *d_out, int accumulate, void *stream)
+{
+    hrt_kbeam_taps K;
+    uint64_t need = 0, off_los = 0;
+    int rc = bt_plan(p, s, spec, arrays, beams, &K, &need, &off_los);
+    if (rc) return rc;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_beam_taps",
+                      "hrt_beam_taps_scratch_bytes", &K.partial)))
+        return rc;
+    K.los = (float *)((uint8_t *)K.partial + off_los);
+    K.rx_el = arrays->rx_elements;
+    K.tx_el = arrays->tx_elements;
+    K.rx_w = beams->rx_weights;
+    K.tx_w = beams->tx_weights;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_beam_taps(&K, stream), "beam taps kernels");
+    return HRT_OK;
+}
+
+static int bt_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    const hrt_beam_spec b = beam_job_beams(j);
+    return hrt_beam_taps_scratch_bytes(p, s, j->spec, &a, &b, out);
+}
+
+static int bt_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    const hrt_beam_spec b = beam_job_beams(j);
+    return hrt_beam_taps(p, s, d_ws, j->spec, &a, &b, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                          const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                          const hrt_taps_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt,
+                          double f_a, const float *rx_weights, size_t n_rx_beams, const float *tx_weights,
+                          size_t n_tx_beams, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = beam_counts_check(nr, nt, n_rx_beams, n_tx_beams, "hrt_beam_taps");
+    if (rc) return rc;
+    /* (the host pointers stand in for the device ones: bt_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    const hrt_beam_spec bm = {(uint32_t)n_rx_beams, (uint32_t)n_tx_beams, rx_weights, tx_weights};
+    if ((rc = bt_check(spec, &a, &bm))) return rc;
+    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, "hrt_beam_taps"))) return rc;
+    if ((rc = beam_weights_check(rx_weights, n_rx_beams, nr, "RX", "hrt_beam_taps"))) return rc;
+    if ((rc = beam_weights_check(tx_weights, n_tx_beams, nt, "TX", "hrt_beam_taps"))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out, "hrt_compute_beam_taps")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * n_rx_beams * n_tx_beams * 2u * spec->num_times * spec->num_taps * 8u;
+    job.scratch_bytes = bt_job_scratch;
+    job.run = bt_job_run;
+    return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                        rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);
 }

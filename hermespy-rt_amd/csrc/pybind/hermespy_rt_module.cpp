@@ -249,8 +249,8 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
-// What the seven path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
-// compute_power_profiles, compute_dominant_paths, compute_beam_channel) share.  The counts and the four position / velocity arguments, checked ...
+// What the eight path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
+// compute_power_profiles, compute_dominant_paths, compute_beam_channel, compute_beam_taps) share.  The counts and the four position / velocity arguments, checked ...
 struct endpoints {
     const Vec3 *rxp, *txp, *rxv, *txv;
     endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
@@ -492,6 +492,48 @@ py::array_t<std::complex<float>> compute_array_taps_py(
     return out;
 }
 
+// compute_beam_taps: the beamformed (codebook) sampled impulse response of the traced paths, formed on the device
+// (extension; see hrt_compute_beam_taps in hermespy_rt.h): complex64 (num_rx, num_tx, Br, Bt, 2, num_times, num_taps) =
+// sum_ij conj(rx_weights[a, i]) h[..., i, j, ...] tx_weights[b, j] of compute_array_taps's h, which is never formed.
+py::array_t<std::complex<float>> compute_beam_taps_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
+    py::array rx_weights, py::array tx_weights, long l_min, py::object center_frequency, double t0, double dt,
+    unsigned long num_times, bool los, bool scatter, py::object array_frequency)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_taps and num_times must fit 32 bits");
+    if (l_min < -(1L << 30) || l_min > (1L << 30))
+        throw py::value_error("hermespy_rt.compute_beam_taps: tap indices l_min outside +-2^24");
+    const array_elements a(rx_elements, tx_elements);
+    const carr wr = as_weights(rx_weights, a.nr, "rx_weights"), wt = as_weights(tx_weights, a.nt, "tx_weights");
+    const size_t br = (size_t)wr.shape(0), bt = (size_t)wt.shape(0);
+    const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_taps_spec spec{};
+    spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
+    spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
+    // beyond the limits would be refused, so only one within them is allocated.)
+    const unsigned long long tl = (unsigned long long)num_times * num_taps;
+    const bool fits = tl > 0 && tl <= (1ull << 20) && br <= 256 && bt <= 256 && br * bt * tl > 0 &&
+                      br * bt * tl <= (1ull << 24);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, br, bt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_taps}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const float *pwr = reinterpret_cast<const float *>(wr.data()), *pwt = reinterpret_cast<const float *>(wt.data());
+    run_pathsum("compute_beam_taps", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_beam_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                     num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, pwr, br, pwt, bt, dst, nullptr);
+    });
+    return out;
+}
+
 // compute_power_profiles: per-link power statistics of the traced paths, formed on the device (extension; see
 // hrt_compute_power_profiles in hermespy_rt.h): a dict of float64 views of one flat buffer -- moments
 // (num_rx, num_tx, 2, HRT_POWER_FIELDS), pdp (num_rx, num_tx, 2, Ld), arrival and departure (num_rx, num_tx, 2, Nth,
@@ -668,6 +710,18 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("l_min") = 0, py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("array_frequency") = py::none());
+    m.def("compute_beam_taps", &compute_beam_taps_py,
+          "Beamformed (codebook) sampled channel impulse response of the traced paths, formed on the device: complex64 "
+          "(num_rx, num_tx, Br, Bt, 2, num_times, num_taps); rx_weights (Br, Nr) is applied conjugated, tx_weights "
+          "(Bt, Nt) as it is",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("rx_weights"), py::arg("tx_weights"), py::arg("l_min") = 0,
+          py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
           py::arg("array_frequency") = py::none());
     m.def("compute_power_profiles", &compute_power_profiles_py,

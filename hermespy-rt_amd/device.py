@@ -400,7 +400,7 @@ class Tracer:
 
     def _pathsum(self, name, spec, shape, cache, out, accumulate, arrays=None, dtype=None, value_error=True):
         """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
-        hrt_power_profiles, hrt_dominant_paths or hrt_beam_channel): the scratch query, the buffers (scratch cache
+        hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel or hrt_beam_taps): the scratch query, the buffers (scratch cache
         `cache`) and the entry on the current stream.  `arrays`: what _elements prepared for the array families, the
         specs that follow `spec` and last the device tensor they point into.  A spec the library refuses raises
         ValueError, or HrtError where value_error is False."""
@@ -432,7 +432,8 @@ class Tracer:
         fa = self.f_ghz * 1e9 if array_frequency is None else float(array_frequency)
 
         def upload(weights=None):
-            """weights: (W_rx [Br, Nr], W_tx [Bt, Nt]) complex64, uploaded behind the offsets (beam_channel)"""
+            """weights: (W_rx [Br, Nr], W_tx [Bt, Nt]) complex64, uploaded behind the offsets (beam_channel,
+            beam_taps)"""
             parts = [re.reshape(-1), te.reshape(-1)]
             if weights is not None:
                 parts += [w.view(np.float32).reshape(-1) for w in weights]
@@ -543,6 +544,31 @@ class Tracer:
         self.counts()
         shape = (self.nrx, self.ntx, nr, nt, 2, int(num_times), int(num_taps))
         return self._pathsum("hrt_array_taps", spec, shape, "_at_scratch", out, accumulate, upload())
+
+    def beam_taps(self, rx_elements, tx_elements, rx_weights, tx_weights, fs, num_taps, l_min=0, fc=None, t0=0.0,
+                  dt=0.0, num_times=1, los=True, scatter=True, array_frequency=None, out=None, accumulate=False):
+        """Beamformed (codebook) sampled impulse response of the last trace, formed on the device (hrt_beam_taps): the
+        taps after the combiner w^H = conj(W_rx[a]) and the precoder f = W_tx[b],
+
+            h[rx, tx, a, b, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) g_rx[a](u_p^rx) g_tx[b](u_p^tx)
+                                               * sinc(l_k - f_s tau_p),      t_m = t0 + m dt,  l_k = l_min + k
+
+        with beam_channel()'s gains g_rx, g_tx: = sum_ij conj(W_rx[a, i]) h[rx, tx, i, j, pol, m, k] W_tx[b, j] with
+        array_taps()'s h for the same elements, without h being formed: the cost follows Br * Bt, not Nr * Nt, and
+        Nr * Nt is not limited (hermespy_rt_amd.beams.apply is the host form).  Elements and weights as in
+        beam_channel(); fs, num_taps, l_min and fc as in taps().  Returns a complex64 tensor
+        [nrx, ntx, Br, Bt, 2, num_times, num_taps] on the device, enqueued on the current stream; `out` is written in
+        place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        wr = abi.weights(rx_weights.cpu().numpy() if hasattr(rx_weights, "cpu") else rx_weights, nr, "rx_weights")
+        wt = abi.weights(tx_weights.cpu().numpy() if hasattr(tx_weights, "cpu") else tx_weights, nt, "tx_weights")
+        if not (np.isfinite(wr.view(np.float32)).all() and np.isfinite(wt.view(np.float32)).all()):
+            raise ValueError("beam weights must be finite")
+        fc = self.f_ghz * 1e9 if fc is None else float(fc)
+        spec = abi.taps_spec(fs, num_taps, l_min, fc, t0, dt, num_times, los, scatter)
+        self.counts()
+        shape = (self.nrx, self.ntx, wr.shape[0], wt.shape[0], 2, int(num_times), int(num_taps))
+        return self._pathsum("hrt_beam_taps", spec, shape, "_bt_scratch", out, accumulate, upload((wr, wt)))
 
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):

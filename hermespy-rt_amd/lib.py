@@ -35,6 +35,7 @@ EXPORTED = (
     "hrt_power_out_doubles", "hrt_power_profiles_scratch_bytes", "hrt_power_profiles", "hrt_compute_power_profiles",
     "hrt_dominant_out_bytes", "hrt_dominant_paths_scratch_bytes", "hrt_dominant_paths", "hrt_compute_dominant_paths",
     "hrt_beam_channel_scratch_bytes", "hrt_beam_channel", "hrt_compute_beam_channel",
+    "hrt_beam_taps_scratch_bytes", "hrt_beam_taps", "hrt_compute_beam_taps",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -281,6 +282,15 @@ def load():
                                            C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                            f32p, C.c_size_t, f32p, C.c_size_t, f32p, C.POINTER(Stats)]
     L.hrt_compute_beam_channel.restype = C.c_int
+    # beamformed impulse responses (hrt_taps_spec, hrt_array_spec and hrt_beam_spec)
+    L.hrt_beam_taps_scratch_bytes.argtypes = [vp, C.POINTER(Shard), tpp, app, bmp, C.POINTER(u64)]
+    L.hrt_beam_taps_scratch_bytes.restype = C.c_int
+    L.hrt_beam_taps.argtypes = [vp, C.POINTER(Shard), vp, tpp, app, bmp, vp, u64, vp, C.c_int, vp]
+    L.hrt_beam_taps.restype = C.c_int
+    L.hrt_compute_beam_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                        C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                        f32p, C.c_size_t, f32p, C.c_size_t, f32p, C.POINTER(Stats)]
+    L.hrt_compute_beam_taps.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

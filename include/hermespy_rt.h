@@ -300,6 +300,31 @@ int hrt_compute_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
                            size_t num_tx_elements, double array_frequency_hz,
                            float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Beamformed (codebook) sampled impulse responses of the traced paths, formed on the device (include/hrt_device.h:
+ * hrt_beam_taps): the taps after a combiner and a precoder from a codebook.  For every link, RX beam a < Br, TX beam
+ * b < Bt, polarisation, time sample m < num_times and tap l < num_taps:
+ *     h[rx][tx][a][b][pol][m][l] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) g_rx[a](u_p^rx) g_tx[b](u_p^tx)
+ *                                         * sinc(l_min + l - f_s tau_p)
+ *     g_rx[a](u) = sum_i conj(W_rx[a][i]) exp(j 2 pi f_a r_i . u / c)      (combiner  w^H)
+ *     g_tx[b](u) = sum_j      W_tx[b][j]  exp(j 2 pi f_a q_j . u / c)      (precoder  f)
+ * which is sum_ij conj(W_rx[a][i]) h[rx][tx][i][j][pol][m][l] W_tx[b][j] with hrt_compute_array_taps's h for the same
+ * elements and f_a: the paths, parts, u^rx, u^tx and the sinc rules are exactly its, the gains hrt_compute_beam_channel's.
+ * The weights are folded into each path's steering term, so h is never formed: the cost follows Br * Bt, not Nr * Nt,
+ * and Nr * Nt is not limited.  (An inverse FFT of hrt_compute_beam_channel aliases every delay beyond 1 / df; the
+ * weights cannot be applied to finished taps of single antennas, because the gain differs per path.)
+ * out: complex [num_rx][num_tx][Br][Bt][2][num_times][num_taps], re/im interleaved (numpy complex64).
+ * rx_elements / tx_elements: HOST arrays of Nr / Nt offsets; rx_weights / tx_weights: HOST arrays [Br][Nr][2] /
+ * [Bt][Nt][2] of (re, im) floats.  Traced and batched like hrt_compute_channel; only `out` is copied back.
+ * HRT_E_INVALID, before the device is touched: every hrt_taps_spec check; Nr or Nt outside 1..256; Br or Bt outside
+ * 1..256; Br * Bt * num_times * num_taps > 2^24; an offset, a weight or f_a not finite; f_a <= 0; a NULL pointer. */
+int hrt_compute_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                          const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                          size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
+                          const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                          size_t num_tx_elements, double array_frequency_hz, const float *rx_weights,
+                          size_t num_rx_beams, const float *tx_weights, size_t num_tx_beams,
+                          float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

@@ -377,6 +377,23 @@ int hrt_array_taps(const hrt_problem *p, const hrt_shard *s, const void *d_works
                    const hrt_array_spec *arrays, void *d_scratch, uint64_t scratch_bytes, float *d_out, int accumulate,
                    void *stream);
 
+/* ---- beamformed (codebook) impulse responses from the traced paths (csrc/host/channel.c, csrc/hrt_beam_taps.hip) ----
+ * h[rx][tx][a][b][pol][m][l] as hermespy_rt.h defines it (hrt_compute_beam_taps): hrt_array_taps' h contracted with
+ * the combiner conj(W_rx[a]) and the precoder W_tx[b], with the weights folded into every path's steering term on the
+ * device, so the element-domain taps are never formed and Nr * Nt is not limited.  Formed from the workspace of a
+ * finished hrt_trace, asynchronous on `stream`, with the guarantees of hrt_taps: accumulate = 0 overwrites d_out, 1
+ * adds to it; only shard rank 0 adds the LoS term; partial sums and the LoS gains go to the caller's scratch
+ * (hrt_beam_taps_scratch_bytes) and are reduced in a fixed order, no floating-point atomics, so two calls with the
+ * same inputs give the same bits.  The element offsets (hrt_array_spec) and the weights (hrt_beam_spec) are DEVICE
+ * pointers and are not read on the host, as in hrt_beam_channel.  HRT_E_INVALID, before the device is touched: every
+ * hrt_taps check; NULL arrays, beams, element or weight pointers; Nr or Nt outside 1..256; Br or Bt outside 1..256;
+ * Br * Bt * num_times * num_taps > 2^24; f_a not finite or <= 0; 2^39 outputs or more; scratch too small. */
+int hrt_beam_taps_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec,
+                                const hrt_array_spec *arrays, const hrt_beam_spec *beams, uint64_t *out);
+int hrt_beam_taps(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_taps_spec *spec,
+                  const hrt_array_spec *arrays, const hrt_beam_spec *beams, void *d_scratch, uint64_t scratch_bytes,
+                  float *d_out, int accumulate, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
