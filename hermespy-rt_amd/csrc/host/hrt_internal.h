@@ -38,7 +38,7 @@ typedef struct {
     int sort_rays, sort_fine, sort_dir_res;   /* sort_rays -1: by table size */
     uint64_t rxt_min_rays;       /* UINT64_MAX: by table size */
     uint32_t rxt_max_tri;
-    int no_rxt, no_txt, no_reorder, no_patch;
+    int no_rxt, no_txt, no_reorder, no_patch, patch_cone_only;
     double patch_size, accel_sparse;
     uint64_t accel_big, accel_fine_min;   /* accel_fine_min UINT64_MAX: HRT_FINE_MIN_TRI */
     int accel_fine;              /* -1: auto, 0: never */

@@ -386,7 +386,7 @@ static int patch_build(hrt_problem *p, const Vec3 *rx_pos, const Vec3 *tx_pos)
             (e = hrt_hip_h2d((uint8_t *)d_tmp + b_ptri, apex, (uint64_t)n_apex * 12))) { rc = hrt_fail_hip(e, "hipMemcpy(patch build)"); goto out; }
         if ((e = hrt_hip_patch_build(p->d_tri, T, (const float *)q, (const uint32_t *)d_tmp, (uint32_t)npatch,
                                      (const float *)((uint8_t *)d_tmp + b_ptri), n_rx, n_tx, hball, ro_rx, ro_img,
-                                     (unsigned long long *)(q + b_pdef), NULL))) { rc = hrt_fail_hip(e, "hrt_patch_build_kernel"); goto out; }
+                                     p->tune.patch_cone_only ? 1u : 0u, (unsigned long long *)(q + b_pdef), NULL))) { rc = hrt_fail_hip(e, "hrt_patch_build_kernel"); goto out; }
         {   /* TX cell masks: bins = [NB][4] axes then [NB][2] (cos, sin) */
             uint8_t *db = (uint8_t *)d_tmp + b_ptri + b_apex;
             if ((e = hrt_hip_h2d(db, bins, b_bins))) { rc = hrt_fail_hip(e, "hipMemcpy(patch build)"); goto out; }

@@ -75,6 +75,10 @@ int hrt_tune_load(hrt_tune *t)
         else if KEY("no_reorder") t->no_reorder = (int)v;
         else if KEY("no_patch") t->no_patch = (int)v;
         else if KEY("patch_size") t->patch_size = v;
+        else if KEY("patch_cone_only") {   /* 0 / 1: the patch masks from the cone test alone (A/B, tests) */
+            if (strcmp(val, "0") != 0 && strcmp(val, "1") != 0) rc = hrt_fail(HRT_E_INVALID, "HRT_TUNE: patch_cone_only must be 0 or 1, not '%s'", val);
+            else t->patch_cone_only = (int)u;
+        }
         else if KEY("accel_sparse") t->accel_sparse = v;
         else if KEY("accel_big") t->accel_big = u;
         else if KEY("accel_fine") t->accel_fine = (int)v;

@@ -3760,31 +3760,108 @@ __global__ __launch_bounds__(64) void hrt_txcell_build_kernel(const float *tri_f
     }
 }
 
-// Builder of the patch tables (hrt_kpatch): one thread per (patch, apex).  The patch is cell (iu, iv) of
-// the grid of triangle j, enlarged by HRT_PATCH_MARGIN of a cell on every side and by hball out of the
-// plane (the lanes are only served inside that), its packet { origins in the cell's ball, lines that meet
-// ball(apex, ro), directions within the cone the two balls span } goes through packet_culls against
-// every row of the table.  Apexes: the RXs (rays towards the apex), then per TX its image in the plane of
-// triangle j (rays leaving the apex).  A packet the test cannot serve (cone beyond 60 degrees: the apex
-// is next to the patch) keeps every triangle.  Output [apex][patch][HRT_PATCH_WORDS].
-__global__ __launch_bounds__(256) void hrt_patch_build_kernel(const float *tri_f, uint32_t num_tri, const float *pdef_f,
-                                                              const uint32_t *patch_tri, uint32_t num_patch,
-                                                              const float *apex_pos, uint32_t num_rx, float hball,
-                                                              float ro_rx, float ro_img, unsigned long long *masks)
+// ---- The pencil of a patch: a second filter on what the cone test kept (DESIGN_ACCEL.md A.5, items 4-6) ----
+// The rays a patch serves are the lines from a point p of its PRISM -- centre c0, half edges a = (0.5 + margin) / nu e1,
+// b = (0.5 + margin) / nv e2, c = hb n: the cell as patch_locate serves it -- to a point q of ball(apex, ro), with
+// d = sgn (q - p) |d| / |q - p| (sgn +1: towards an RX, -1: leaving an image; |d| = 1 within 2e-6).  Every quantity
+// packet_culls bounds is, before the division by |q - p|, affine in p and in q:
+//     (q - p).G  for the fixed G(apex) of the three edge tests and for N,   (p - v1).N,
+// so over the prism its extremes lie at the 8 corners: centre value +- (|a.G| + |b.G| + |c.G|), and the ball adds
+// +- ro |G|.  A negative upper bound of (q - p).G becomes an upper bound of d.G on division by the LARGEST |q - p| (lmax)
+// and a factor (1 - 1e-5) for |d|; like cone_bounds', the bounds are only used where they are negative.  All in double
+// (the table's floats are exact in it), every bound moved to the safe side by 1e-12 of the product of the lengths that
+// enter it -- thousands of times the rounding of its ~20 operations, a millionth of the tolerances it is compared with.
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 d3(F3 a) { return {(double)a.x, (double)a.y, (double)a.z}; }
+__device__ __forceinline__ D3 dsub3(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+// (bounds, not reference arithmetic: fused multiply-adds, like the culling test)
+__device__ __forceinline__ double ddot3(D3 a, D3 b) { return __builtin_fma(a.z, b.z, __builtin_fma(a.y, b.y, a.x * b.x)); }
+__device__ __forceinline__ D3 dcross3(D3 a, D3 b)
 {
-    const float4 *tri = reinterpret_cast<const float4 *>(tri_f);
-    const float4 *pdef = reinterpret_cast<const float4 *>(pdef_f);
-    const uint32_t pid = blockIdx.x * 256u + threadIdx.x, a = blockIdx.y;
-    if (pid >= num_patch) return;
-    const uint32_t j = patch_tri[pid];
-    const float4 q0 = tri[HRT_ROW * j], q1 = tri[HRT_ROW * j + 1], q2 = tri[HRT_ROW * j + 2];
-    const float4 p0 = pdef[2u * j], p1 = pdef[2u * j + 1u];
+    return {__builtin_fma(a.y, b.z, -(a.z * b.y)), __builtin_fma(a.z, b.x, -(a.x * b.z)), __builtin_fma(a.x, b.y, -(a.y * b.x))};
+}
+struct Pencil {
+    D3 w0;         // apex - c0
+    D3 a, b, c;    // half edges of the prism
+    double lmax;   // >= |q - p| (1 + 1e-9) for every p of the prism and q of the apex ball
+    double invl;   // (1 - 1e-5) / lmax
+    bool towards;  // rays towards the apex (RX) / leaving it (image)
+};
+// the reach of a linear form over the prism's corners about its centre value
+__device__ __forceinline__ double pencil_reach(const Pencil &Q, D3 G) { return fabs(ddot3(Q.a, G)) + fabs(ddot3(Q.b, G)) + fabs(ddot3(Q.c, G)); }
+// upper bounds of d.G (hp) and of -d.G (hm) over the pencil, valid wherever they are negative; gb >= |G|, sl: rounding
+__device__ __forceinline__ void pencil_bounds(const Pencil &Q, D3 G, double gb, double ro, double sl, double &hp, double &hm)
+{
+    const double m = ddot3(Q.w0, G), r = pencil_reach(Q, G) + (gb * ro + sl);
+    const double hi = m + r, lo = r - m;   // (q - p).G <= hi, -(q - p).G <= lo
+    hp = (Q.towards ? hi : lo) * Q.invl;
+    hm = (Q.towards ? lo : hi) * Q.invl;
+}
+// packet_culls on the pencil: the same acceptance conditions, tolerances (S from the patch's ball, the ro terms of the
+// line points), thresholds and one-sided / two-hypothesis rule; only the bounds of the numerators differ.
+__device__ __forceinline__ bool pencil_culls(const Packet &P, const Pencil &Q, float4 q0, float4 q1, float4 q2, float4 q3, float4 q4)
+{
+    const float4 C = make_float4(0.f, q3.x, q3.y, q3.z);
+    const float4 L = make_float4(q3.w, q4.x, q4.y, q4.z);
+    constexpr float kE = 16.f * kEps;
+    const F3 v1 = {q0.x, q0.y, q0.z};
+    const F3 nh = {q2.y, q2.z, q2.w};
+    const F3 sb = sub3(P.bc, v1);
+    const float S = (fabsf(sb.x) + fabsf(sb.y)) + (fabsf(sb.z) + P.br);
+    const float k2S = (2.f * kE) * S;
+    const double tol_u = (double)__builtin_fmaf(k2S, L.y, C.z);
+    const double tol_v = (double)__builtin_fmaf(k2S, L.x, C.z);
+    const double tol_w = (double)__builtin_fmaf(k2S, L.x + L.y, C.w);
+    const float h = fdot3(sb, nh);
+    const double thr = (double)__builtin_fmaf(-1e-4f * L.w, fabsf(h) + P.br, -(k2S * L.x) * L.y);   // <= -2 E_t
+    const double ro = (double)P.ro * 1.0001;
+    const D3 e1 = {(double)q0.w, (double)q1.x, (double)q1.y}, e2 = {(double)q1.z, (double)q1.w, (double)q2.x};
+    const D3 sc = dsub3(d3(P.oc), d3(v1));
+    const D3 N = dcross3(e1, e2);
+    const D3 Gu = dcross3(e2, sc), Gv = dcross3(sc, e1);
+    const D3 Gw = {Gu.x + Gv.x + N.x, Gu.y + Gv.y + N.y, Gu.z + Gv.z + N.z};   // (e2 - e1) x (sc - e1)
+    const double lsc = (fabs(sc.x) + fabs(sc.y)) + fabs(sc.z);   // >= |sc|: it only scales the ro |G| and rounding terms
+    const double lx = (double)L.x, ly = (double)L.y, lz = (double)L.z, lw = (double)L.w;   // (rounded up by the host)
+    // rounding: (q - p).G is a product of lengths below (|e1| + |e2| + |e2 - e1|) (|sc| + |e1| + |e2|) lmax, the two
+    // forms with N below |e1| |e2| (|sc| + lmax)
+    const double sl = 1e-12 * ((lx + ly + lz) * (lsc + lx + ly)) * Q.lmax;
+    const double slN = 1e-12 * (lx * ly) * (lsc + Q.lmax);
+    // behind: sigma (p - v1).N > -E_t is needed;  p - v1 = (sc - w0) +- a +- b +- c
+    const double rN = pencil_reach(Q, N);
+    const double hN = ddot3(dsub3(sc, Q.w0), N);
+    bool rej_p = (hN + rN) + slN < thr;
+    bool rej_m = (rN - hN) + slN < thr;
+    // the sign of det = -d.N is known when |d.N| > 3 E_d on the whole pencil
+    const double mN = ddot3(Q.w0, N);
+    const bool one_sided = (fabs(mN) - (rN + lw * ro + slN)) * Q.invl > (double)__builtin_fmaf(3.f, C.y, 1e-30f);
+    const bool dn_neg = (mN < 0.0) == Q.towards;
+    double hp, hm;
+    // acceptance needs sigma*Nu >= -tol_u, sigma*Nv >= -tol_v, sigma*(Nu+Nv-det) <= tol_w
+    pencil_bounds(Q, Gu, ly * lsc, ro, sl, hp, hm);
+    rej_p |= ly * ro + hp < -tol_u;
+    rej_m |= ly * ro + hm < -tol_u;
+    pencil_bounds(Q, Gv, lx * lsc, ro, sl, hp, hm);
+    rej_p |= lx * ro + hp < -tol_v;
+    rej_m |= lx * ro + hm < -tol_v;
+    pencil_bounds(Q, Gw, lz * (lsc + lx), ro, sl, hp, hm);
+    rej_p |= lz * ro + hm < -tol_w;
+    rej_m |= lz * ro + hp < -tol_w;
+    if (one_sided) return dn_neg ? rej_p : rej_m;
+    return rej_p & rej_m;
+}
+
+// the packet of (patch pid of triangle j's grid, apex a) -- both builder kernels form it with this sequence
+struct PatchCell { uint32_t iu, iv, nu, nv; bool image; };
+__device__ __forceinline__ PatchCell patch_packet(const float4 q0, const float4 q1, const float4 q2, const float4 p0, const float4 p1,
+                                                  uint32_t pid, uint32_t a, const float *apex_pos, uint32_t num_rx, float hball,
+                                                  float ro_rx, float ro_img, Packet &P)
+{
+    PatchCell X;
     const uint32_t base = __float_as_uint(p0.w), bits = __float_as_uint(p1.w), nu = bits & 0xffffu, nv = bits >> 16;
     const uint32_t c = pid - base, iv = c / nu, iu = c - iv * nu;
     const F3 v1 = {q0.x, q0.y, q0.z}, e1 = {q0.w, q1.x, q1.y}, e2 = {q1.z, q1.w, q2.x};
     const float fu = ((float)iu + 0.5f) / (float)nu, fv = ((float)iv + 0.5f) / (float)nv;
     const float hu = (0.5f + HRT_PATCH_MARGIN) / (float)nu, hv = (0.5f + HRT_PATCH_MARGIN) / (float)nv;
-    Packet P;
     P.bc = add3(v1, add3(mul3(e1, fu), mul3(e2, fv)));
     const F3 d1 = add3(mul3(e1, hu), mul3(e2, hv)), d2 = sub3(mul3(e1, hu), mul3(e2, hv));
     P.br = sqrtf(fmaxf(fdot3(d1, d1), fdot3(d2, d2))) * 1.001f + hball +
@@ -3802,6 +3879,31 @@ __global__ __launch_bounds__(256) void hrt_patch_build_kernel(const float *tri_f
     P.usable = sa < 0.86f;   // (NaN: not usable)
     P.sina = P.usable ? sa : 0.86f;
     P.cosa = sqrtf(fmaxf(0.f, 1.f - P.sina * P.sina)) * 0.9999f - 1e-6f;
+    X.iu = iu; X.iv = iv; X.nu = nu; X.nv = nv; X.image = image;
+    return X;
+}
+
+// Builder of the patch tables (hrt_kpatch): one thread per (patch, apex).  The patch is cell (iu, iv) of
+// the grid of triangle j, enlarged by HRT_PATCH_MARGIN of a cell on every side and by hball out of the
+// plane (the lanes are only served inside that), its packet { origins in the cell's ball, lines that meet
+// ball(apex, ro), directions within the cone the two balls span } goes through packet_culls against
+// every row of the table.  Apexes: the RXs (rays towards the apex), then per TX its image in the plane of
+// triangle j (rays leaving the apex).  A packet the test cannot serve (cone beyond 60 degrees: the apex
+// is next to the patch) keeps every triangle.  Output [apex][patch][HRT_PATCH_WORDS].  What the cone test keeps then goes
+// through pencil_culls in hrt_patch_pencil_kernel (unless HRT_TUNE patch_cone_only=1): the mask is the AND of the two tests.
+__global__ __launch_bounds__(256) void hrt_patch_build_kernel(const float *tri_f, uint32_t num_tri, const float *pdef_f,
+                                                              const uint32_t *patch_tri, uint32_t num_patch,
+                                                              const float *apex_pos, uint32_t num_rx, float hball,
+                                                              float ro_rx, float ro_img, unsigned long long *masks)
+{
+    const float4 *tri = reinterpret_cast<const float4 *>(tri_f);
+    const float4 *pdef = reinterpret_cast<const float4 *>(pdef_f);
+    const uint32_t pid = blockIdx.x * 256u + threadIdx.x, a = blockIdx.y;
+    if (pid >= num_patch) return;
+    const uint32_t j = patch_tri[pid];
+    Packet P;
+    patch_packet(tri[HRT_ROW * j], tri[HRT_ROW * j + 1], tri[HRT_ROW * j + 2], pdef[2u * j], pdef[2u * j + 1u], pid, a, apex_pos, num_rx,
+                 hball, ro_rx, ro_img, P);
     unsigned long long m[HRT_PATCH_WORDS];
 #pragma unroll
     for (uint32_t r = 0; r < HRT_PATCH_WORDS; ++r) m[r] = 0ull;
@@ -3815,6 +3917,61 @@ __global__ __launch_bounds__(256) void hrt_patch_build_kernel(const float *tri_f
     unsigned long long *out = masks + ((uint64_t)a * num_patch + pid) * HRT_PATCH_WORDS;
 #pragma unroll
     for (uint32_t r = 0; r < HRT_PATCH_WORDS; ++r) out[r] = m[r];
+}
+
+// The second pass over the patch tables: one thread per (patch, apex) takes the triangles the cone test kept -- the
+// bits of ITS OWN mask, a loop per lane: neighbouring patches keep different triangles -- through pencil_culls and
+// clears what that culls.  A pass of its own so that the cone pass keeps its registers and its wave-uniform loop.
+__global__ __launch_bounds__(256) void hrt_patch_pencil_kernel(const float *tri_f, uint32_t num_tri, const float *pdef_f,
+                                                               const uint32_t *patch_tri, uint32_t num_patch,
+                                                               const float *apex_pos, uint32_t num_rx, float hball,
+                                                               float ro_rx, float ro_img, unsigned long long *masks)
+{
+    const float4 *tri = reinterpret_cast<const float4 *>(tri_f);
+    const float4 *pdef = reinterpret_cast<const float4 *>(pdef_f);
+    const uint32_t pid = blockIdx.x * 256u + threadIdx.x, a = blockIdx.y;
+    if (pid >= num_patch) return;
+    const uint32_t j = patch_tri[pid];
+    const float4 q0 = tri[HRT_ROW * j], q1 = tri[HRT_ROW * j + 1], q2 = tri[HRT_ROW * j + 2];
+    Packet P;
+    const PatchCell X = patch_packet(q0, q1, q2, pdef[2u * j], pdef[2u * j + 1u], pid, a, apex_pos, num_rx, hball, ro_rx, ro_img, P);
+    if (!P.usable) return;
+    // the prism of the served origins p = v1 + u e1 + v e2 + w n (exact coordinates in the basis (e1, e2, n) of the
+    // table's floats): u nu in [iu - margin, iu + 1 + margin], v alike (patch_locate: accept + rounding < margin), and
+    // the exact (p - v1).n = u e1.n + v e2.n + w |n|^2 within hball -- n is a float cross product, not exactly normal
+    // to the edges, so |w| <= (hball + (1 + margin) (|e1.n| + |e2.n|)) / |n|^2
+    Pencil Q;
+    {
+        const D3 E1 = {(double)q0.w, (double)q1.x, (double)q1.y}, E2 = {(double)q1.z, (double)q1.w, (double)q2.x};
+        const D3 Nn = {(double)q2.y, (double)q2.z, (double)q2.w};
+        const double cu = ((double)X.iu + 0.5) / (double)X.nu, cv = ((double)X.iv + 0.5) / (double)X.nv;
+        const double su = (0.5 + (double)HRT_PATCH_MARGIN) / (double)X.nu, sv = (0.5 + (double)HRT_PATCH_MARGIN) / (double)X.nv;
+        const double hb = ((double)hball + (1.0 + (double)HRT_PATCH_MARGIN) * (fabs(ddot3(E1, Nn)) + fabs(ddot3(E2, Nn)))) /
+                          ddot3(Nn, Nn) * (1.0 + 1e-6);
+        const D3 c0 = {(double)q0.x + cu * E1.x + cv * E2.x, (double)q0.y + cu * E1.y + cv * E2.y, (double)q0.z + cu * E1.z + cv * E2.z};
+        Q.w0 = dsub3(d3(P.oc), c0);
+        Q.a = {su * E1.x, su * E1.y, su * E1.z};
+        Q.b = {sv * E2.x, sv * E2.y, sv * E2.z};
+        Q.c = {hb * Nn.x, hb * Nn.y, hb * Nn.z};
+        Q.lmax = (sqrt(ddot3(Q.w0, Q.w0)) + sqrt(ddot3(Q.a, Q.a)) + sqrt(ddot3(Q.b, Q.b)) + sqrt(ddot3(Q.c, Q.c)) + (double)P.ro * 1.0001) *
+                 (1.0 + 1e-6);
+        Q.invl = (1.0 - 1e-5) / Q.lmax;
+        Q.towards = !X.image;
+    }
+    if (!(Q.lmax < 1e30)) return;   // (NaN: the cone test alone)
+    unsigned long long *out = masks + ((uint64_t)a * num_patch + pid) * HRT_PATCH_WORDS;
+    for (uint32_t r = 0; r < HRT_PATCH_WORDS; ++r) {
+        const unsigned long long m0 = out[r];
+        unsigned long long m = m0, keep = m0;
+        while (m) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(m), t = r * 64u + b;
+            m &= m - 1ull;
+            if (t < num_tri && pencil_culls(P, Q, tri[HRT_ROW * t], tri[HRT_ROW * t + 1], tri[HRT_ROW * t + 2], tri[HRT_ROW * t + 3],
+                                            tri[HRT_ROW * t + 4]))
+                keep &= ~(1ull << b);
+        }
+        if (keep != m0) out[r] = keep;
+    }
 }
 
 // ===================================================================================
@@ -4725,12 +4882,16 @@ int hrt_hip_txcell_build(const float *d_tri, uint32_t num_tri, const float *d_tx
 
 int hrt_hip_patch_build(const float *d_tri, uint32_t num_tri, const float *d_pdef, const uint32_t *d_patch_tri,
                         uint32_t num_patch, const float *d_apex, uint32_t num_rx, uint32_t num_img, float hball,
-                        float ro_rx, float ro_img, unsigned long long *d_masks, void *stream)
+                        float ro_rx, float ro_img, uint32_t cone_only, unsigned long long *d_masks, void *stream)
 {
     if (num_patch == 0 || num_rx + num_img == 0 || num_rx + num_img > 65535u) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(hrt_patch_build_kernel, dim3((num_patch + 255u) / 256u, num_rx + num_img), dim3(256), 0,
                        (hipStream_t)stream, d_tri, num_tri, d_pdef, d_patch_tri, num_patch, d_apex, num_rx, hball,
                        ro_rx, ro_img, d_masks);
+    if (!cone_only)   // (same stream: the second pass reads the first one's masks)
+        hipLaunchKernelGGL(hrt_patch_pencil_kernel, dim3((num_patch + 255u) / 256u, num_rx + num_img), dim3(256), 0,
+                           (hipStream_t)stream, d_tri, num_tri, d_pdef, d_patch_tri, num_patch, d_apex, num_rx, hball,
+                           ro_rx, ro_img, d_masks);
     return (int)hipGetLastError();
 }
 

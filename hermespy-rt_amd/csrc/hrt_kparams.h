@@ -110,7 +110,8 @@ typedef struct {
  * Every ray of launch b >= 1 starts on the triangle it just hit.  Each triangle carries a (nu x nv) grid
  * of cells ("patches") in its (e1, e2) basis; per (apex, patch) ONE candidate mask of the whole table,
  * built once per problem on the device by the packet test itself (packet_culls) with the packet
- * { origins in the patch's ball, lines that meet ball(apex, ro) }:
+ * { origins in the patch's ball, lines that meet ball(apex, ro) }, then thinned by the same conditions on the pencil of
+ * lines from the cell's prism to the apex ball (pencil_culls; DESIGN_ACCEL.md A.5):
  *   apex k < num_rx            shadow rays towards RX k (they arrive at the apex);
  *   apex num_rx + tx           the bounce rays of launch 1: they left TX tx and were mirrored by the patch's
  *                              triangle, so they leave the IMAGE of the TX in that triangle's plane.
@@ -268,7 +269,7 @@ int hrt_hip_txcell_build(const float *d_tri, uint32_t num_tri, const float *d_tx
                          const float *d_bin_cs2, unsigned long long *d_masks, void *stream);
 int hrt_hip_patch_build(const float *d_tri, uint32_t num_tri, const float *d_pdef, const uint32_t *d_patch_tri,
                         uint32_t num_patch, const float *d_apex, uint32_t num_rx, uint32_t num_img, float hball,
-                        float ro_rx, float ro_img, unsigned long long *d_masks, void *stream);
+                        float ro_rx, float ro_img, uint32_t cone_only, unsigned long long *d_masks, void *stream);
 uint64_t hrt_hip_sort_temp_bytes(uint64_t cap);
 int hrt_hip_sort_hits(const hrt_kparams *P, uint32_t bounce, void *stream);
 int hrt_hip_export_copy(const void *d_ws, const void *d_segs, uint32_t num_segs, uint64_t max_words, void *d_out, void *stream);

@@ -428,3 +428,189 @@ void bounce_eval_split(const float *rows, int T, const float *o, const float *d,
     }
     out[0] = nw; out[1] = cost; out[2] = groups; out[3] = cands; out[4] = unus;
 }
+
+/* ---------------- the pencil of a patch (hrt_kernels.hip: Pencil, pencil_culls; DESIGN_ACCEL.md A.5 items 4-6) ----------------
+ * The product's builder restated: the patch packet as hrt_patch_build_kernel forms it (margin, hball), the cone test,
+ * and the second filter on the prism's corners in double.  mode 0: cone alone, 1: cone AND pencil. */
+#define PATCH_MARGIN 0.0625
+typedef struct { double w0[3], a[3], b[3], c[3], lmax, invl; int towards; } Pencil;
+static inline double ddot(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+static inline void dcross(const double *a, const double *b, double *o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+static inline double pencil_reach(const Pencil *Q, const double *G) { return fabs(ddot(Q->a, G)) + fabs(ddot(Q->b, G)) + fabs(ddot(Q->c, G)); }
+static inline void pencil_bounds(const Pencil *Q, const double *G, double gb, double ro, double sl, double *hp, double *hm)
+{
+    const double m = ddot(Q->w0, G), r = pencil_reach(Q, G) + (gb * ro + sl);
+    const double hi = m + r, lo = r - m;
+    *hp = (Q->towards ? hi : lo) * Q->invl;
+    *hm = (Q->towards ? lo : hi) * Q->invl;
+}
+static int pencil_culls(const Packet *P, const Pencil *Q, const float *r)
+{
+    const float Cy = r[12], Cz = r[13], Cw = r[14], Lx = r[15], Ly = r[16], Lz = r[17], Lw = r[18];
+    const float kE = 16.f * EPS;
+    const float *v1 = r, *nh = r + 9;
+    float sb[3] = {P->bc[0] - v1[0], P->bc[1] - v1[1], P->bc[2] - v1[2]};
+    const float S = (fabsf(sb[0]) + fabsf(sb[1])) + (fabsf(sb[2]) + P->br);
+    const float k2S = (2.f * kE) * S;
+    const double tol_u = fmaf(k2S, Ly, Cz), tol_v = fmaf(k2S, Lx, Cz), tol_w = fmaf(k2S, Lx + Ly, Cw);
+    const float h = fdot(sb, nh);
+    const double thr = fmaf(-1e-4f * Lw, fabsf(h) + P->br, -(k2S * Lx) * Ly);
+    const double ro = (double)P->ro * 1.0001;
+    const double e1[3] = {r[3], r[4], r[5]}, e2[3] = {r[6], r[7], r[8]};
+    const double sc[3] = {(double)P->oc[0] - v1[0], (double)P->oc[1] - v1[1], (double)P->oc[2] - v1[2]};
+    double N[3], Gu[3], Gv[3], Gw[3];
+    dcross(e1, e2, N); dcross(e2, sc, Gu); dcross(sc, e1, Gv);
+    for (int k = 0; k < 3; ++k) Gw[k] = Gu[k] + Gv[k] + N[k];
+    const double lsc = (fabs(sc[0]) + fabs(sc[1])) + fabs(sc[2]);
+    const double lx = Lx, ly = Ly, lz = Lz, lw = Lw;
+    const double sl = 1e-12 * ((lx + ly + lz) * (lsc + lx + ly)) * Q->lmax;
+    const double slN = 1e-12 * (lx * ly) * (lsc + Q->lmax);
+    const double rN = pencil_reach(Q, N);
+    const double sv[3] = {sc[0] - Q->w0[0], sc[1] - Q->w0[1], sc[2] - Q->w0[2]};
+    const double hN = ddot(sv, N);
+    int rej_p = (hN + rN) + slN < thr, rej_m = (rN - hN) + slN < thr;
+    const double mN = ddot(Q->w0, N);
+    const int one_sided = (fabs(mN) - (rN + lw * ro + slN)) * Q->invl > (double)fmaf(3.f, Cy, 1e-30f);
+    const int dn_neg = (mN < 0.0) == (Q->towards != 0);
+    double hp, hm;
+    pencil_bounds(Q, Gu, ly * lsc, ro, sl, &hp, &hm);
+    rej_p |= ly * ro + hp < -tol_u; rej_m |= ly * ro + hm < -tol_u;
+    pencil_bounds(Q, Gv, lx * lsc, ro, sl, &hp, &hm);
+    rej_p |= lx * ro + hp < -tol_v; rej_m |= lx * ro + hm < -tol_v;
+    pencil_bounds(Q, Gw, lz * (lsc + lx), ro, sl, &hp, &hm);
+    rej_p |= lz * ro + hm < -tol_w; rej_m |= lz * ro + hp < -tol_w;
+    if (one_sided) return dn_neg ? rej_p : rej_m;
+    return rej_p & rej_m;
+}
+/* packet and pencil of cell (iu, iv) of triangle row r, as the kernel forms them (the packet in float) */
+static void product_patch(const float *r, const PatchDef *pd, int iu, int iv, const float *apex, float ro_apex, int towards, float hball,
+                          Packet *P, Pencil *Q)
+{
+    const float nu = (float)pd->nu, nv = (float)pd->nv;
+    const float fu = ((float)iu + 0.5f) / nu, fv = ((float)iv + 0.5f) / nv;
+    const float hu = (0.5f + (float)PATCH_MARGIN) / nu, hv = (0.5f + (float)PATCH_MARGIN) / nv;
+    float d1[3], d2[3], w[3];
+    for (int k = 0; k < 3; ++k) {
+        P->bc[k] = r[k] + (r[3 + k] * fu + r[6 + k] * fv);
+        d1[k] = r[3 + k] * hu + r[6 + k] * hv;
+        d2[k] = r[3 + k] * hu - r[6 + k] * hv;
+        P->oc[k] = apex[k];
+    }
+    P->br = sqrtf(fmaxf(fdot(d1, d1), fdot(d2, d2))) * 1.001f + hball + 4e-6f * ((fabsf(P->bc[0]) + fabsf(P->bc[1])) + fabsf(P->bc[2]));
+    P->ro = ro_apex;
+    for (int k = 0; k < 3; ++k) w[k] = P->oc[k] - P->bc[k];
+    const float dist = sqrtf(fdot(w, w)), inv = (towards ? 1.f : -1.f) / fmaxf(dist, 1e-30f);
+    for (int k = 0; k < 3; ++k) P->ax[k] = w[k] * inv;
+    const float sa = (P->br + P->ro) / fmaxf(dist, 1e-30f) * 1.001f + 1e-5f;
+    P->usable = sa < 0.86f;
+    P->sina = P->usable ? sa : 0.86f;
+    P->cosa = sqrtf(fmaxf(0.f, 1.f - P->sina * P->sina)) * 0.9999f - 1e-6f;
+    const double E1[3] = {r[3], r[4], r[5]}, E2[3] = {r[6], r[7], r[8]}, Nn[3] = {r[9], r[10], r[11]};
+    const double cu = (iu + 0.5) / pd->nu, cv = (iv + 0.5) / pd->nv;
+    const double su = (0.5 + PATCH_MARGIN) / pd->nu, sv = (0.5 + PATCH_MARGIN) / pd->nv;
+    const double hb = ((double)hball + (1.0 + PATCH_MARGIN) * (fabs(ddot(E1, Nn)) + fabs(ddot(E2, Nn)))) / ddot(Nn, Nn) * (1.0 + 1e-6);
+    for (int k = 0; k < 3; ++k) {
+        Q->w0[k] = (double)apex[k] - ((double)r[k] + cu * E1[k] + cv * E2[k]);
+        Q->a[k] = su * E1[k]; Q->b[k] = sv * E2[k]; Q->c[k] = hb * Nn[k];
+    }
+    Q->lmax = (sqrt(ddot(Q->w0, Q->w0)) + sqrt(ddot(Q->a, Q->a)) + sqrt(ddot(Q->b, Q->b)) + sqrt(ddot(Q->c, Q->c)) + (double)ro_apex * 1.0001) * (1.0 + 1e-6);
+    Q->invl = (1.0 - 1e-5) / Q->lmax;
+    Q->towards = towards;
+}
+
+/* the product's patch masks: mode 0 = the cone test alone, 1 = cone AND pencil, k > 1 = cone AND the pencils of k x k
+ * sub-prisms (not built: it prices what ANY tighter description of the same prism could still remove);
+ * stride: every stride-th patch (others: zero) */
+void build_patch_table_product(const float *rows, int T, const PatchDef *pd, const float *apex, int apex_per_tri, float ro_apex, int towards,
+                               float hball, int mode, int stride, uint64_t *masks /* [npatch][W] */)
+{
+    const int W = (T + 63) / 64;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int a = 0; a < T; ++a)
+        for (int iv = 0; iv < pd[a].nv; ++iv)
+            for (int iu = 0; iu < pd[a].nu; ++iu) {
+                uint64_t *m = masks + (size_t)(pd[a].base + iv * pd[a].nu + iu) * W;
+                Packet P;
+                Pencil Q;
+                if ((pd[a].base + iv * pd[a].nu + iu) % stride) continue;   /* (the caller zeroed the masks) */
+                product_patch(rows + (size_t)a * ROWF, &pd[a], iu, iv, apex_per_tri ? apex + 3 * a : apex, ro_apex, towards, hball, &P, &Q);
+                for (int w = 0; w < W; ++w) m[w] = 0;
+                for (int j = 0; j < T; ++j) {
+                    int cand = !P.usable || !packet_culls(&P, rows + (size_t)j * ROWF);
+                    if (cand && P.usable && mode >= 1) {   /* mode x mode sub-prisms: culled when every one is */
+                        cand = 0;
+                        for (int sy = 0; sy < mode && !cand; ++sy)
+                            for (int sx = 0; sx < mode && !cand; ++sx) {
+                                Pencil S = Q;
+                                const double fx = (double)(2 * sx + 1 - mode) / mode, fy = (double)(2 * sy + 1 - mode) / mode;
+                                for (int k = 0; k < 3; ++k) {
+                                    S.w0[k] = Q.w0[k] - (fx * Q.a[k] + fy * Q.b[k]);
+                                    S.a[k] = Q.a[k] / mode; S.b[k] = Q.b[k] / mode;
+                                }
+                                cand = !pencil_culls(&P, &S, rows + (size_t)j * ROWF);
+                            }
+                    }
+                    if (cand) m[j >> 6] |= 1ull << (j & 63);
+                }
+            }
+}
+
+/* Sampled origins of every patch shot at (towards) or from (!towards) the apex, in double: the triangles whose
+ * LINE test a sample passes strictly (u, v > tol, u + v < 1 - tol) in front of the origin (t > tol), at any distance.
+ * ns x ns samples over the cell enlarged by `margin` cells on every side, heights cycling through -hb, 0, +hb (the four
+ * (u, v) corners at all three)
+ * (hb = 0: the cell's plane).  A floor for mask sizes (margin = hb = 0; unsound: samples, not all origins) and the
+ * necessary condition a sound mask meets (margin, hb of the prism).  stride: every stride-th patch (others: zero). */
+void sample_patch_table(const float *rows, int T, const PatchDef *pd, const float *apex, int apex_per_tri, int towards, int ns, double margin,
+                        double hb, double tol, int stride, uint64_t *masks /* [npatch][W] */)
+{
+    const int W = (T + 63) / 64;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int a = 0; a < T; ++a) {
+        const float *r = rows + (size_t)a * ROWF;
+        const float *ap = apex_per_tri ? apex + 3 * a : apex;
+        for (int iv = 0; iv < pd[a].nv; ++iv)
+            for (int iu = 0; iu < pd[a].nu; ++iu) {
+                const int pid = pd[a].base + iv * pd[a].nu + iu;
+                uint64_t *m = masks + (size_t)pid * W;
+                for (int w = 0; w < W; ++w) m[w] = 0;
+                if (pid % stride) continue;
+                for (int sy = 0; sy < ns; ++sy)
+                    for (int sx = 0; sx < ns; ++sx) {
+                        const double tu = ns > 1 ? (double)sx / (ns - 1) : 0.5, tv = ns > 1 ? (double)sy / (ns - 1) : 0.5;
+                        const double u = (iu - margin + tu * (1.0 + 2.0 * margin)) / pd[a].nu, v = (iv - margin + tv * (1.0 + 2.0 * margin)) / pd[a].nv;
+                        const int corner = (sx == 0 || sx == ns - 1) && (sy == 0 || sy == ns - 1);
+                        for (int hk = 0; hk < 3; ++hk) {   /* the four (u, v) corners at all three heights */
+                        if (!corner && hk != (sx + sy) % 3) continue;
+                        const double hh = hb * (double)(hk - 1);
+                        double o[3], d[3];
+                        for (int k = 0; k < 3; ++k) {
+                            o[k] = (double)r[k] + u * r[3 + k] + v * r[6 + k] + hh * r[9 + k];
+                            d[k] = (towards ? 1.0 : -1.0) * ((double)ap[k] - o[k]);
+                        }
+                        const double dl = sqrt(ddot(d, d));
+                        if (!(dl > 1e-9)) continue;
+                        for (int k = 0; k < 3; ++k) d[k] /= dl;
+                        for (int j = 0; j < T; ++j) {
+                            const float *q = rows + (size_t)j * ROWF;
+                            const double e1[3] = {q[3], q[4], q[5]}, e2[3] = {q[6], q[7], q[8]}, s[3] = {o[0] - q[0], o[1] - q[1], o[2] - q[2]};
+                            double pv[3], qv[3];
+                            dcross(d, e2, pv);
+                            const double det = ddot(e1, pv);
+                            if (fabs(det) < 1e-12) continue;
+                            const double uu = ddot(s, pv) / det;
+                            if (!(uu > tol && uu < 1.0 - tol)) continue;
+                            dcross(s, e1, qv);
+                            const double vv = ddot(d, qv) / det;
+                            if (!(vv > tol && uu + vv < 1.0 - tol)) continue;
+                            if (!(ddot(e2, qv) / det > tol)) continue;
+                            m[j >> 6] |= 1ull << (j & 63);
+                        }
+                        }
+                    }
+            }
+    }
+}

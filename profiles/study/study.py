@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Design study driver (CPU): candidate statistics of per-ray table lookups against today's packet
 culling, on the real waves of a workload (profiles/study/live_lists.py writes them).
-    python profiles/study/study.py /tmp/hrt_study/c3_4000000.npz [ratio] """
+    python profiles/study/study.py /tmp/hrt_study/c3_4000000.npz [ratio]
+    python profiles/study/study.py /tmp/hrt_study/c3_4000000.npz pencil     the patch masks' builders alone: cone / cone AND
+                                                                           pencil / sampled floor (profiles/study/pencil_c3_4M.txt) """
 import ctypes as C
 import os
 import subprocess
@@ -15,11 +17,22 @@ import hermespy_rt_amd  # noqa: E402,F401
 from hermespy_rt_amd.workloads import WORKLOADS  # noqa: E402
 from oracle import oracle  # noqa: E402
 
-os.makedirs("/tmp/hrt_study", exist_ok=True)
-so = "/tmp/hrt_study/libcand.so"
-subprocess.check_call(["gcc", "-O2", "-fopenmp", "-shared", "-fPIC", os.path.join(HERE, "cand.c"), "-o", so, "-lm"])
-L = C.CDLL(so)
+L = None
 f32p, u64p, i64p, f64p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+
+
+def load_lib(out_dir="/tmp/hrt_study"):
+    """compile cand.c into out_dir and load it (the module's L)"""
+    global L
+    os.makedirs(out_dir, exist_ok=True)
+    so = os.path.join(out_dir, "libcand.so")
+    subprocess.check_call(["gcc", "-O2", "-fopenmp", "-shared", "-fPIC", os.path.join(HERE, "cand.c"), "-o", so, "-lm"])
+    L = C.CDLL(so)
+    return L
+
+
+class PD(C.Structure):
+    _fields_ = [("nu", C.c_int), ("nv", C.c_int), ("base", C.c_int)]
 
 
 def P(a, t=f32p):
@@ -51,8 +64,94 @@ def rows_of(scene_path):
     return np.ascontiguousarray(rows), flat
 
 
+def product_consts(rows, rx, tx):
+    """hmax, hball, ro_rx, ro_img as csrc/host/problem.c patch_build forms them"""
+    v = np.concatenate([rows[:, 0:3], rows[:, 0:3].astype(np.float64) + rows[:, 3:6], rows[:, 0:3].astype(np.float64) + rows[:, 6:9]])
+    lo, hi = v.min(axis=0).astype(np.float32).astype(np.float64), v.max(axis=0).astype(np.float32).astype(np.float64)
+    ext1, cmax = float((hi - lo).sum()), float(np.maximum(np.abs(hi), np.abs(lo)).sum())
+    u = 2.0 ** -24
+    smax = ext1 + 1.0
+    hmax = np.float32(4e-4 + 4e-6 * cmax)
+    for a in np.concatenate([np.asarray(rx, np.float32).reshape(-1, 3), np.asarray(tx, np.float32).reshape(-1, 3)]):
+        cmax = max(cmax, float(np.abs(a.astype(np.float64)).sum()))
+    return dict(hmax=hmax, hball=np.float32(float(hmax) * 1.01 + 16.0 * u * (smax + cmax)),
+                ro_rx=np.float32(8.0 * u * (2.0 * cmax + ext1) * 1.001 + 2e-7), ro_img=np.float32(1e-3 + 1e-5 * (cmax + ext1)))
+
+
+def product_grid(rows, size):
+    """the (nu, nv, base) of every triangle at patch edge `size` (problem.c; every triangle served: no needle test)"""
+    T = len(rows)
+    pd = (PD * T)()
+    base = 0
+    for a in range(T):
+        nu = int(min(2048, max(1, np.ceil(float(np.linalg.norm(rows[a, 3:6].astype(np.float64))) / size))))
+        nv = int(min(2048, max(1, np.ceil(float(np.linalg.norm(rows[a, 6:9].astype(np.float64))) / size))))
+        pd[a].nu, pd[a].nv, pd[a].base = nu, nv, base
+        base += nu * nv
+    return pd, base
+
+
+def popc_rows(m):
+    return np.unpackbits(np.ascontiguousarray(m).view(np.uint8).reshape(m.shape[0], -1), axis=1).sum(axis=1)
+
+
+def pencil_study(D, rows, size=0.5):
+    """shadow rays of every launch against the product's patch masks: cone alone (today), cone AND pencil, and the
+    floor of 5 x 5 sampled origins per cell (unsound, for scale)"""
+    T = len(rows)
+    W = (T + 63) // 64
+    rx, tx = D["rx_pos"], D["tx_pos"]
+    k = product_consts(rows, rx, tx)
+    pd, npatch = product_grid(rows, size)
+    print("patch size %.2f m: %d patches; hball %.3g ro_rx %.3g" % (size, npatch, k["hball"], k["ro_rx"]))
+    slack = 2e-3   # patch_of: |h| <= 1e-3, well inside hball's prism
+    tabs = {}
+    for name in ("cone", "pencil", "pencil2", "pencil3", "floor"):
+        tabs[name] = []
+        for a in range(len(rx)):
+            m = np.zeros((npatch, W), np.uint64)
+            if name == "floor":
+                L.sample_patch_table(P(rows), T, pd, P(rx[a]), 0, 1, 5, C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), 1, P(m, u64p))
+            else:
+                L.build_patch_table_product(P(rows), T, pd, P(rx[a]), 0, C.c_float(k["ro_rx"]), 1, C.c_float(k["hball"]),
+                                            {"cone": 0, "pencil": 1, "pencil2": 2, "pencil3": 3}[name], 1, P(m, u64p))
+            tabs[name].append(m)
+        pc = np.concatenate([popc_rows(m) for m in tabs[name]])
+        print("%-6s table: mean population %.2f, max %d" % (name, pc.mean(), pc.max()))
+    for a in range(len(rx)):
+        assert not (tabs["pencil"][a] & ~tabs["cone"][a]).any()
+        lost = int((tabs["floor"][a] & ~tabs["pencil"][a]).any(axis=1).sum())
+        print("rx %d: patches whose sampled floor has a triangle the pencil mask lacks: %d" % (a, lost))
+    print("| launch | builder | candidates per lane | union per wave-trace | unserved lanes |")
+    print("|---|---|---|---|---|")
+    tot = {n: np.zeros(6) for n in tabs}
+    for b in (1, 2, 3, 4):
+        o = np.ascontiguousarray(D["o%d" % b], np.float32)
+        tri = np.ascontiguousarray(D["tri%d" % b], np.uint32)
+        n = len(o)
+        for name in tabs:
+            acc = np.zeros(6)
+            for a in range(len(rx)):
+                out = np.zeros(8)
+                hm, hu = np.zeros(257, np.int64), np.zeros(257, np.int64)
+                L.patch_eval(P(rows), T, pd, P(o), P(tri, C.POINTER(C.c_uint32)), n, P(tabs[name][a], u64p), C.c_float(slack), P(out, f64p),
+                             P(hm, i64p), P(hu, i64p))
+                acc += out[:6]
+            print("| %d | %s | %.2f | %.2f | %.5f |" % (b, name, acc[1] / (n * len(rx)), acc[3] / acc[0], acc[5] / (n * len(rx))))
+            tot[name] += acc
+    for name in tabs:
+        t = tot[name]
+        print("| all | %s | %.2f | %.2f | |" % (name, t[1] / (t[0] * 64), t[3] / t[0]))
+
+
 def main():
     path = sys.argv[1]
+    load_lib()
+    if len(sys.argv) > 2 and sys.argv[2] == "pencil":
+        D = np.load(path)
+        rows, _ = rows_of(WORKLOADS[os.path.basename(path).split("_")[0]]["scene_path"])
+        pencil_study(D, rows)
+        return
     ratio = float(sys.argv[2]) if len(sys.argv) > 2 else 1.5
     w = os.path.basename(path).split("_")[0]
     c = WORKLOADS[w]
@@ -105,8 +204,6 @@ def main():
     print("ALL shadow: per-lane mean %.2f | max-over-lanes %.2f | union %.2f | packet(today) %.2f" % (
         tot[1] / (nw * 64), tot[2] / nw, tot[3] / nw, tot[4] / nw))
     # ---- patch tables ----
-    class PD(C.Structure):
-        _fields_ = [("nu", C.c_int), ("nv", C.c_int), ("base", C.c_int)]
     for size in (float(x) for x in os.environ.get("PATCH_SIZES", "2,1,0.5").split(",")):
         slack = 2e-3
         pd = (PD * T)()
