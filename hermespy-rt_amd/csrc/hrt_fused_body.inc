@@ -31,7 +31,7 @@
     const float2 *g_tg = reinterpret_cast<const float2 *>(P.acc.tg);
     const float4 *g_leaf = reinterpret_cast<const float4 *>(P.acc.leaf);
     const uint32_t n_leaf = P.acc.num_leaf;
-    const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9)>(lds, T, n_leaf, P.num_rx, wave);
+    const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9), FIRST>(lds, T, n_leaf, P.num_rx, wave);
 #ifdef HRT_PHASE_STATS
     // (make EXTRA=-DHRT_PHASE_STATS) time stamps of a workgroup's life (thread 0, 100 MHz wall clock):
     // g_phase[chunk] = {start, loads + staging done, traces + publish done, records done, prefix
@@ -242,7 +242,7 @@
                     } else {
                         unblocked = true;
                         const float th_s = acos_f_ool(dot3(w, n));
-                        const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, th);
+                        const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, th, lds_addr(L.mat + kMatItems));
                         float o0 = a0[k] * S.x - a1[k] * S.y;
                         float o1 = a0[k] * S.y + a1[k] * S.x;
                         float o2 = a2[k] * S.z - a3[k] * S.w;

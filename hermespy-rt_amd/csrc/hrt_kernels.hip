@@ -1677,7 +1677,7 @@ __device__ __noinline__ float incidence_angle(F3 n, F3 d) { return incidence_ang
 // float libm calls of the shading code: bit-exact restatements of the host libm (hrt_libm.h)
 __device__ __forceinline__ float sin_f(float x) { return hrt_sinf(x); }
 __device__ __forceinline__ float cos_f(float x) { return hrt_cosf(x); }
-__device__ __forceinline__ float exp_f(float x) { return hrt_expf(x); }
+__device__ __forceinline__ float exp_f(float x, uint32_t tab) { return hrt_expf_lds(x, tab); }   // (tab: lds_addr of the kernel's copy of the 2^(i/32) table)
 __device__ __forceinline__ float acos_f(float x) { return hrt_acosf(x); }
 
 // src/compute_paths.c:152-164
@@ -1720,13 +1720,14 @@ __device__ __noinline__ float4 fresnel(float4 m0, float4 m1, float4 m2, float th
 // src/compute_paths.c:359-415; s = scattering coefficient, alpha = s1_alpha (small integer)
 // (kept out of line, like incidence_angle: inlined into the records kernel they spill -- C3 1.125 -> 1.39 ms with the
 // angle inlined, 1.78 with both, at 6 waves; 1.33 at 4)
-__device__ __noinline__ float4 scatter_pattern(float s, float alpha, float th_s, float th_i)
+__device__ __noinline__ float4 scatter_pattern(float s, float alpha, float th_s, float th_i, uint32_t exp_tab)
 {
+    // (the exponential first: the table's address and s are dead before the polynomials' double temporaries live)
+    const float dth = fabsf(th_s - th_i);
+    const float f = s * exp_f(-alpha * dth, exp_tab);
     const float cs = hrt_cosf_nb(th_s);
     float si, ci;
     hrt_sincosf(th_i, &si, &ci);
-    const float dth = fabsf(th_s - th_i);
-    const float f = s * exp_f(-alpha * dth);
     const float rough = 1.0f / (1.0f + alpha);
     const float spec = rough * cs;
     const float diff = (1.0f - rough) * cs;
@@ -1875,6 +1876,36 @@ __device__ __forceinline__ void copy16_commit(const float4 (&v)[N], float4 *l, c
 __device__ __forceinline__ float4 stage_pos(const float *pos, const uint32_t k)
 {
     return make_float4(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.f);
+}
+
+// The material table and, behind it, the 2^(i/32) table of hrt_expf_lds (hrt_libm.h: 32 words of 64 bits = kExpItems
+// items of 16 bytes) are the FIRST things in the LDS image of every kernel that shades, staged as one batch: the
+// materials are 68 items, one per thread, and 188 threads are idle, so the exp table rides on 16 of them as items
+// 68 .. 83 -- in the tables' one flight, with no register of its own.
+// (In LDS because as a constant array it is a global load, and a wait for all the wave has in flight, in every call
+// of scatter_pattern.  In the kernel's own image, reached through an address argument, because a module-scope
+// __shared__ array read by a function that is not inlined turns every uniform load of the calling kernels into a
+// vector load: a launch's count lands in a VGPR and is spilled.  First in the image because its address is then a
+// constant of the kernel -- behind tables whose sizes come with the problem it is a value that lives through the walk.)
+constexpr uint32_t kExpItems = HRT_EXP2_TAB_BYTES / 16u;
+constexpr uint32_t kMatItems = 4u * HRT_NUM_MATERIALS, kMatExpItems = kMatItems + kExpItems;
+static_assert(kMatExpItems <= HRT_BLOCK, "materials + exp table: one item per thread");
+// (the words of hrt_exp2_tab as an array with an address: an item of the batch is ONE load from a selected address)
+__device__ const uint64_t g_exp2_tab[32] __attribute__((aligned(16))) = {HRT_EXP2_TAB_WORDS};
+__device__ __forceinline__ void mat_exp_request(float4 (&v)[1], const float4 *g_mat, const uint32_t tid)
+{
+    stage_load(v, kMatExpItems, tid, [&](uint32_t k) {
+        return *(k < kMatItems ? g_mat + k : reinterpret_cast<const float4 *>(g_exp2_tab) + (k - kMatItems));
+    });
+}
+__device__ __forceinline__ void mat_exp_commit(const float4 (&v)[1], float4 *l_mat, const uint32_t tid)
+{
+    stage_store(l_mat, v, kMatExpItems, tid);
+}
+// the LDS address (byte offset) of a pointer into LDS
+__device__ __forceinline__ uint32_t lds_addr(const void *p)
+{
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
 
 // ---- workspace addressing (include/hrt_device.h) ----
@@ -2510,7 +2541,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void hrt_wide_finish_kernel(const hrt_kp
 //   (b < nb) the bounce itself: incidence angle, Fresnel, FSL, delay, reflect (:611-659), and
 //            the stable compaction: every survivor of the 256-entry chunk goes straight to
 //            (survivors of all earlier chunks) + (its rank in the chunk) of the next live list.
-// LDS: [17*4 float4 materials][num_rx float4 RX pos][4 u32 wave counts][4 u32 wave sums]
+// LDS: [17*4 float4 materials][16 float4: the exp table][num_rx float4 RX pos][4 u32 wave counts][4 u32 wave sums]
 // ===================================================================================
 #ifndef HRT_SHADE_WAVES
 #define HRT_SHADE_WAVES 6   /* at most 80 VGPRs: 6 waves/SIMD (5 is 7 % slower; 7 gains nothing, 8 spills and is
@@ -2540,7 +2571,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
     const Rsrc mesh_r = make_rsrc(reinterpret_cast<const uint8_t *>(P.mesh));
     const uint32_t cap4 = (uint32_t)P.cap * 4u;   // bytes per field array
     float4 *l_mat = lds;
-    float4 *l_rx = l_mat + 4u * HRT_NUM_MATERIALS;
+    float4 *l_rx = l_mat + kMatExpItems;
     uint32_t *l_wcnt = reinterpret_cast<uint32_t *>(l_rx + P.num_rx);
     float4 *l_trin = reinterpret_cast<float4 *>(l_wcnt + 8);   // [T]: n.xyz, mesh id (bits)
     float4 *l_mesh = l_trin + P.num_tri;                         // [M]: velocity, material (bits)
@@ -2558,7 +2589,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
             return make_float4(row[9], row[10], row[11], row[19]);
         };
         float4 s_mat[1], s_rx[1], s_trin[2], s_mesh[1];
-        copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        mat_exp_request(s_mat, g_mat, tid);
         stage_load(s_rx, P.num_rx, tid, ld_rx);
         stage_load(s_trin, n_trin, tid, ld_trin);
         copy16_request(s_mesh, g_mesh, n_mesh, tid);
@@ -2566,7 +2597,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
             ptri0 = ldu(res_blk(P, P.num_rx), 0u, ((uint32_t)base0 + tid) * 4u);
             pt0 = ldf(res_blk(P, P.num_rx), cap4, ((uint32_t)base0 + tid) * 4u);
         }
-        copy16_commit(s_mat, l_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        mat_exp_commit(s_mat, l_mat, tid);
         stage_store(l_rx, s_rx, P.num_rx, tid);
         stage_store(l_trin, s_trin, n_trin, tid);
         copy16_commit(s_mesh, l_mesh, g_mesh, n_mesh, tid);
@@ -2705,7 +2736,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
                         } else {
                             unblocked = true;
                             const float th_s = acos_f_ool(dot3(w, n));
-                            const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, theta);
+                            const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, theta, lds_addr(l_mat + kMatItems));
                             float o0 = a0 * S.x - a1 * S.y;
                             float o1 = a0 * S.y + a1 * S.x;
                             float o2 = a2 * S.z - a3 * S.w;
@@ -2913,7 +2944,7 @@ __global__ __launch_bounds__(HRT_BLOCK, 8) void hrt_image_kernel(const hrt_kpara
 #ifndef HRT_RECORDS_WAVES
 #define HRT_RECORDS_WAVES 6
 #endif
-// LDS: [T x 5 float4 rows][num_rx RX pos][17 x 4 float4 materials]
+// LDS: [17 x 4 float4 materials][16 float4: the exp table][T x 5 float4 rows][num_rx RX pos][T u32 reference-order indices]
 __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kernel(const hrt_kparams P, const uint32_t b)
 {
     extern __shared__ float4 lds[];
@@ -2926,12 +2957,12 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
     const uint32_t T = P.num_tri;
     const uint32_t cap4 = (uint32_t)P.cap * 4u;
     const Rsrc mesh_r = make_rsrc(reinterpret_cast<const uint8_t *>(P.mesh));
-    float4 *l_tri = lds;
-    float4 *l_rx = lds + HRT_ROW * T;
-    float4 *l_mat = l_rx + P.num_rx;
+    float4 *l_mat = lds;
+    float4 *l_tri = l_mat + kMatExpItems;
+    float4 *l_rx = l_tri + HRT_ROW * T;
     // (the reference-order index of every row, for the tie rule: in LDS, so that the exact stage of the walk has no
     // global load -- whose s_waitcnt vmcnt(0) would also wait for the masks requested ahead)
-    uint32_t *l_orig = reinterpret_cast<uint32_t *>(l_mat + 4u * HRT_NUM_MATERIALS);
+    uint32_t *l_orig = reinterpret_cast<uint32_t *>(l_rx + P.num_rx);
     const uint32_t pb = b - 1;
     // an entry's state (nothing of it depends on LDS): the first chunk's is requested with the tables
     F3 o, d;
@@ -2967,12 +2998,12 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
         uint32_t s_orig[1];
         copy16_request(s_tri, g_tri, HRT_ROW * T, tid);
         stage_load(s_rx, P.num_rx, tid, ld_rx);
-        copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        mat_exp_request(s_mat, g_mat, tid);
         stage_load(s_orig, T, tid, ld_orig);
         load_state(blockIdx.x);
         copy16_commit(s_tri, l_tri, g_tri, HRT_ROW * T, tid);
         stage_store(l_rx, s_rx, P.num_rx, tid);
-        copy16_commit(s_mat, l_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+        mat_exp_commit(s_mat, l_mat, tid);
         stage_store(l_orig, s_orig, T, tid);
         stage_rest<1, 2>(l_rx, P.num_rx, tid, ld_rx);
         stage_rest<1, 2>(l_orig, T, tid, ld_orig);
@@ -3009,6 +3040,10 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
         // (once per entry: the whole table for a wave with a valid lane that is not served.  Taking two register sets
         // in turn in a loop unrolled by two, to spare the copy below, costs 48 B of scratch)
         const bool whole = patch_whole(ref, valid);
+        // (consumed in front of the loop like every later set behind its walk, see below: a load still outstanding where
+        // the loop is entered puts the wait for it into the loop's head, where every iteration executes it)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(wnext[q]));
 #endif
         for (uint32_t rx = 0; rx < P.num_rx; ++rx) {
             const float4 rp = l_rx[rx];
@@ -3021,6 +3056,13 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
             for (int q = 0; q < 8; ++q) wcur[q] = wnext[q];
             if (rx + 1u < P.num_rx) patch_load(P.patch, ref, rx + 1u, valid, wnext);
             const Hit h = closest_hit_words(tri, l_orig, wcur, whole, T, o, w, valid, lane, 2);
+            // The masks of the next RX are consumed HERE, behind the walk they were requested in front of and in front
+            // of this RX's record stores: the wait for them then stands where only loads are outstanding.  Left to the
+            // loop's back edge (their first use, the copy into wcur) it is an s_waitcnt vmcnt(0) behind the five to
+            // ten stores of the record block, whose number differs by lane -- stores count in vmcnt, and the compiler
+            // cannot count past them -- so every iteration ended by draining its own stores.
+#pragma unroll
+            for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(wnext[q]));
 #else
             const Hit h = closest_hit_patch(tri, l_orig, P.patch, ref, rx, T, o, w, valid, lane, 2);
 #endif
@@ -3039,7 +3081,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
                 } else {
                     unblocked = true;
                     const float th_s = acos_f_ool(dot3(w, n));
-                    const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, theta);
+                    const float4 S = scatter_pattern(mat_s, mat_alpha, th_s, theta, lds_addr(l_mat + kMatItems));
                     float o0 = a0 * S.x - a1 * S.y;
                     float o1 = a0 * S.y + a1 * S.x;
                     float o2 = a2 * S.z - a3 * S.w;
@@ -3189,9 +3231,10 @@ __device__ __forceinline__ uint32_t lb_exclusive(const LbWords &W, uint32_t chun
 }
 
 // LDS image shared by the fused kernels (hrt_hip_launch_fused sizes it):
+// [17 x 4 float4 materials][16 float4: the exp table]                                    (launches >= 1)
 // [T x 5 float4 rows | T float2 guard pairs, padded to 16 B | 2 float4 per leaf] (only if staged)
 // [num_rx float4 RX pos][4 waves x 16 u64 masks][4 waves x 32 float4 per-wave scratch][64 u32]
-// [17 x 4 float4 materials][64 float4 TX pos]
+// [17 x 4 float4 materials][64 float4 TX pos]                                              (launch 0: no exp table)
 constexpr uint32_t kLdsTx = 64u;
 struct FusedLds {
     float4 *tri, *leaf, *rx, *wleaf, *mat, *tx;
@@ -3199,10 +3242,14 @@ struct FusedLds {
     unsigned long long *mask;
     uint32_t *wcnt;
 };
-template <bool TRI_IN_LDS, bool CAND_BUF>
+template <bool TRI_IN_LDS, bool CAND_BUF, bool FIRST>
 __device__ __forceinline__ FusedLds fused_lds(float4 *lds, uint32_t T, uint32_t n_leaf, uint32_t num_rx, uint32_t wave)
 {
     FusedLds L;
+    if constexpr (!FIRST) {
+        L.mat = lds;
+        lds += kMatExpItems;
+    }
     L.tri = lds;
     L.tg = reinterpret_cast<float2 *>(lds + HRT_ROW * T);
     L.leaf = lds + HRT_ROW * T + (T + 1u) / 2u;
@@ -3212,8 +3259,12 @@ __device__ __forceinline__ FusedLds fused_lds(float4 *lds, uint32_t T, uint32_t 
     float4 *w0 = reinterpret_cast<float4 *>(m0 + (HRT_BLOCK / 64u) * kMaskRounds);
     L.wleaf = w0 + wave * wave_scratch4(CAND_BUF);   // (per-wave scratch, + the candidate buffer of the fine walk)
     L.wcnt = reinterpret_cast<uint32_t *>(w0 + (HRT_BLOCK / 64u) * wave_scratch4(CAND_BUF));
-    L.mat = reinterpret_cast<float4 *>(L.wcnt + 64);
-    L.tx = L.mat + 4u * HRT_NUM_MATERIALS;   // the first kLdsTx TX positions (launch 0)
+    if constexpr (FIRST) {
+        L.mat = reinterpret_cast<float4 *>(L.wcnt + 64);
+        L.tx = L.mat + kMatItems;   // the first kLdsTx TX positions
+    } else {
+        L.tx = nullptr;
+    }
     return L;
 }
 // The tables of that image, in one flight (stage_load): triangle rows, guard pairs and leaf records (TREE: the tree
@@ -3238,12 +3289,13 @@ __device__ __forceinline__ void fused_stage(const hrt_kparams &P, const FusedLds
     stage_load(s_tg, n_tg, tid, ld_tg);
     copy16_request(s_leaf, g_leaf, n_leaf4, tid);
     stage_load(s_pos, n_pos, tid, ld_pos);
-    copy16_request(s_mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+    // (launch 0 writes no scatter records: the materials without the exp table)
+    if constexpr (FIRST) copy16_request(s_mat, g_mat, kMatItems, tid); else mat_exp_request(s_mat, g_mat, tid);
     copy16_commit(s_tri, L.tri, g_tri, n_tri4, tid);
     stage_store(L.tg, s_tg, n_tg, tid);
     copy16_commit(s_leaf, L.leaf, g_leaf, n_leaf4, tid);
     stage_store(l_pos, s_pos, n_pos, tid);
-    copy16_commit(s_mat, L.mat, g_mat, 4u * HRT_NUM_MATERIALS, tid);
+    if constexpr (FIRST) copy16_commit(s_mat, L.mat, g_mat, kMatItems, tid); else mat_exp_commit(s_mat, L.mat, tid);
     stage_rest<2, 2>(L.tg, n_tg, tid, ld_tg);
     stage_rest<1, 2>(l_pos, n_pos, tid, ld_pos);
 }
@@ -3423,7 +3475,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_FUSED_WAVESB) void hrt_chain_kernel(
     uint32_t *err_word = &counts[P.num_bounces + 1];
     if (*err_word & kErrVoid) return;
     const uint32_t G = gridDim.x;   // (<= kChainMaxGrid and <= lb_chunks: the shim)
-    const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9)>(lds, P.num_tri, P.acc.num_leaf, P.num_rx, tid >> 6);
+    const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9), false>(lds, P.num_tri, P.acc.num_leaf, P.num_rx, tid >> 6);
     {   // the tables, once
         const uint32_t T = P.num_tri, n_leaf = P.acc.num_leaf;
         fused_stage<TRI_IN_LDS, (VARIANT >= 4), false>(P, L, T, n_leaf, tid);
@@ -4232,7 +4284,7 @@ __global__ void hrt_fs0_kernel(const float *dirs, uint64_t n, float vx, float vy
 //    8  K = 8  wave_or256: the lane's eight mask words -> the wave's union (the same in every lane of the wave)
 //    9  K = 1  div_c
 //   10  K = 4  (s, alpha, th_s, th_i) -> scatter_pattern
-__device__ __forceinline__ void selftest_items(int fn, const float *in, float *out, uint64_t n, uint64_t i)
+__device__ __forceinline__ void selftest_items(int fn, const float *in, float *out, uint64_t n, uint64_t i, uint32_t exp_tab)
 {
     const uint64_t K = fn == 8 ? 8u : (fn == 9 ? 1u : 4u);
     const uint64_t items = n / K;
@@ -4252,7 +4304,7 @@ __device__ __forceinline__ void selftest_items(int fn, const float *in, float *o
     } else if (fn == 9) {
         y[0] = div_c(x[0]);
     } else if (live) {
-        const float4 S = scatter_pattern(x[0], x[1], x[2], x[3]);
+        const float4 S = scatter_pattern(x[0], x[1], x[2], x[3], exp_tab);
         y[0] = S.x; y[1] = S.y; y[2] = S.z; y[3] = S.w;
     }
     if (live) {
@@ -4267,8 +4319,11 @@ __device__ __forceinline__ void selftest_items(int fn, const float *in, float *o
 __global__ void hrt_selftest_math_kernel(int fn, const float *in, float *out, uint64_t n)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    __shared__ uint64_t l_exp[HRT_EXP2_TAB_BYTES / 8u];   // (hrt_expf_lds reads its table from LDS)
+    if (threadIdx.x < HRT_EXP2_TAB_BYTES / 8u) l_exp[threadIdx.x] = hrt_exp2_tab(threadIdx.x);
+    __syncthreads();
     if (fn >= 8) {   // the primitives of the patch-mask and record kernels: K floats in and K floats out per item
-        selftest_items(fn, in, out, n, i);
+        selftest_items(fn, in, out, n, i, lds_addr(l_exp));
         return;
     }
     if (i >= n) return;
@@ -4277,7 +4332,7 @@ __global__ void hrt_selftest_math_kernel(int fn, const float *in, float *out, ui
     switch (fn) {
     case 0: y = hrt_sinf(x); break;
     case 1: y = hrt_cosf(x); break;
-    case 2: y = hrt_expf(x); break;
+    case 2: y = hrt_expf_lds(x, lds_addr(l_exp)); break;
     case 3: y = hrt_acosf(x); break;
     case 5: { float c_; hrt_sincosf(x, &y, &c_); break; }
     case 6: { float s_; hrt_sincosf(x, &s_, &y); break; }
@@ -4694,7 +4749,7 @@ int hrt_hip_launch_records(const hrt_kparams *P, uint32_t bounce, void *stream)
     uint64_t rblocks = (P->cap + HRT_BLOCK - 1) / HRT_BLOCK;
     if (rblocks > 2u * max_grid) rblocks = 2u * max_grid;   // (1 024 .. 4 096 workgroups: 2-5 % slower)
     const size_t rlds = (size_t)T * HRT_TRI_FLOATS * 4u + (size_t)P->num_rx * 16u +
-                        (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u) + (size_t)T * 4u;
+                        (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + (size_t)T * 4u;
     if (rlds > 64u * 1024u) return (int)hipErrorInvalidValue;   // (cannot happen: T <= HRT_PATCH_MAX_TRI)
     hipLaunchKernelGGL(hrt_records_kernel, dim3((uint32_t)rblocks), dim3(HRT_BLOCK), rlds, (hipStream_t)stream, *P, bounce);
     return (int)hipGetLastError();
@@ -4713,7 +4768,7 @@ int hrt_hip_launch_shade(const hrt_kparams *P_in, uint32_t bounce, void *stream)
     const uint64_t max_grid = P->tune.shade_grid ? P->tune.shade_grid : HRT_SHADE_GRID;
     if (blocks > max_grid) blocks = max_grid;
     if (blocks == 0) blocks = 1;
-    const size_t lds0 = (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u) + (size_t)P->num_rx * 16u + 32u;
+    const size_t lds0 = (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + (size_t)P->num_rx * 16u + 32u;
     const uint64_t nlds_off = P->tune.shade_global_normals;
     if (!nlds_off && P->num_tri <= kShadeLdsTri && P->num_mesh <= kShadeLdsMesh)
         hipLaunchKernelGGL(hrt_shade_kernel<true>, dim3((uint32_t)blocks), dim3(HRT_BLOCK),
@@ -4746,7 +4801,7 @@ int hrt_hip_launch_fused(const hrt_kparams *P_in, uint32_t bounce, void *stream)
                           (variant == 7 || variant == 9);
     const size_t lds = (in_lds ? (size_t)tri_bytes : 0u) + (size_t)P->num_rx * 16u +
                        (HRT_BLOCK / 64u) * (kMaskRounds * 8u + wave_scratch4(fine_pre) * 16u) + 64u * 4u +
-                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u) + kLdsTx * 16u;
+                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + kLdsTx * 16u;
     hipStream_t st = (hipStream_t)stream;
     hipError_t err = hipSuccess;
     // the same choice of intersection loop as hrt_hip_launch_trace; on tables of a handful of
@@ -4798,7 +4853,7 @@ int hrt_hip_launch_chain(const hrt_kparams *P_in, uint32_t b0, void *stream)
     if (!in_lds || !one_block || walks_fine(P)) return -1;
     const size_t lds = (size_t)tri_bytes + (size_t)P->num_rx * 16u +
                        (HRT_BLOCK / 64u) * (kMaskRounds * 8u + wave_scratch4(false) * 16u) + 64u * 4u +
-                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u) + kLdsTx * 16u;
+                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + kLdsTx * 16u;
     const bool trees = P->acc.big && (variant >= 4) && variant != 9;
     const bool flat = variant == 2 || variant == 3 || (variant == 7 && !trees && one_block);
     const bool staged = variant == 1 || (variant == 7 && T <= P->tune.fuse_staged_max_tri);

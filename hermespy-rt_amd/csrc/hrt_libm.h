@@ -157,35 +157,40 @@ HRT_HD float hrt_cosf_nb(float y)
 
 /* bits of 2^(i/32) minus (i << 47): so that adding (k << 47) with k = 32*e + i yields the
  * bits of 2^(k/32) */
+#define HRT_EXP2_TAB_WORDS \
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, \
+    0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, \
+    0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull, \
+    0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull, \
+    0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull, \
+    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, \
+    0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull, \
+    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull
 HRT_HD uint64_t hrt_exp2_tab(uint32_t i)
 {
-    const uint64_t t[32] = {
-        0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
-        0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
-        0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
-        0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
-        0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
-        0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
-        0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
-        0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+    const uint64_t t[32] = {HRT_EXP2_TAB_WORDS};
     return t[i];
 }
 
-HRT_HD float hrt_expf(float xf)
+/* expf in two halves around its table lookup, so that the host reads the constants above and the
+ * device a copy of them in LDS (below) through the same operations:
+ * hrt_expf_reduce gives ki (k = 32 e + i in its low bits) and the reduced argument r,
+ * hrt_expf_scale the polynomial of r times 2^(k/32), from t = hrt_exp2_tab(ki & 31) + (ki << 47) */
+HRT_HD double hrt_expf_reduce(float xf, uint64_t *kip)
 {
-    const uint32_t at = hrt_abstop12(xf);
-    /* |x| >= 88, inf, NaN: glibc's special-case branch; not reachable from the tracer */
-    if (at >= hrt_abstop12(88.0f)) return (float)exp((double)xf);
     const double N = 32.0;
     const double inv_ln2_n = 0x1.71547652b82fep+0 * N, shift = 0x1.8p+52;
-    const double c0 = 0x1.c6af84b912394p-5 / N / N / N, c1 = 0x1.ebfce50fac4f3p-3 / N / N,
-                 c2 = 0x1.62e42ff0c52d6p-1 / N;
     const double xd = xf;
     double kd = fma(inv_ln2_n, xd, shift);
-    const uint64_t ki = hrt_d2u(kd);
+    *kip = hrt_d2u(kd);
     kd -= shift;
-    const double r = fma(inv_ln2_n, xd, -kd);
-    const uint64_t t = hrt_exp2_tab((uint32_t)(ki & 31u)) + (ki << 47);
+    return fma(inv_ln2_n, xd, -kd);
+}
+HRT_HD float hrt_expf_scale(double r, uint64_t t)
+{
+    const double N = 32.0;
+    const double c0 = 0x1.c6af84b912394p-5 / N / N / N, c1 = 0x1.ebfce50fac4f3p-3 / N / N,
+                 c2 = 0x1.62e42ff0c52d6p-1 / N;
     const double s = hrt_u2d(t);
     const double z = fma(c0, r, c1);
     const double r2 = r * r;
@@ -194,6 +199,38 @@ HRT_HD float hrt_expf(float xf)
     y = y * s;
     return (float)y;
 }
+
+/* HOST only: in device code the constant array is a global load -- and a wait for everything else
+ * the wave has in flight -- on the path of every call (hrt_expf_lds) */
+#if defined(__HIPCC__)
+__host__ __forceinline__
+#else
+static inline
+#endif
+float hrt_expf(float xf)
+{
+    /* |x| >= 88, inf, NaN: glibc's special-case branch; not reachable from the tracer */
+    if (hrt_abstop12(xf) >= hrt_abstop12(88.0f)) return (float)exp((double)xf);
+    uint64_t ki;
+    const double r = hrt_expf_reduce(xf, &ki);
+    return hrt_expf_scale(r, hrt_exp2_tab((uint32_t)(ki & 31u)) + (ki << 47));
+}
+
+#if defined(__HIPCC__)
+/* DEVICE: the table is read from LDS.  `tab` is the LDS address (a byte offset: 32 bits, one
+ * register where a function is called out of line) of 32 words filled with hrt_exp2_tab(0 .. 31)
+ * -- the one definition of the numbers -- by the kernel, with its other tables, in front of its
+ * first barrier. */
+#define HRT_EXP2_TAB_BYTES 256u
+__device__ __forceinline__ float hrt_expf_lds(float xf, uint32_t tab)
+{
+    if (hrt_abstop12(xf) >= hrt_abstop12(88.0f)) return (float)exp((double)xf);
+    uint64_t ki;
+    const double r = hrt_expf_reduce(xf, &ki);
+    const uint64_t e = *(const __attribute__((address_space(3))) uint64_t *)(uintptr_t)(tab + 8u * (uint32_t)(ki & 31u));
+    return hrt_expf_scale(r, e + (ki << 47));
+}
+#endif
 
 HRT_HD float hrt_acosf(float x)
 {
