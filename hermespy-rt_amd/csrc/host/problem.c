@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include "hrt_internal.h"
+#include "hrt_launch_plan.h"
 
 /* ------------------------------------------------------------------ errors */
 
@@ -1298,7 +1299,9 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
      * workgroups of that kernel (a launch less: it matters on launch sets of a few 10^4 rays) */
     /* (big tables with few pairs: the sliced LoS kernel, hrt_los_big_kernel, not one wave per pair as the tail of
      * launch 0 -- 0.8 ms per 100 k triangles) */
-    K.los_blocks = ((K.fuse & HRT_FUSE_LAUNCH0) &&
+    /* (whether launch 0 will run fused is the launch plan's answer, hrt_launch_plan.h: not on the fine walk) */
+    const hrt_launch_plan plan = hrt_plan(&K);
+    K.los_blocks = ((K.fuse & HRT_FUSE_LAUNCH0) && hrt_plan_fuses(&plan, 0u) &&
                     !(p->num_tri >= p->tune.k.los_big_min_tri && (uint64_t)p->num_rx * p->num_tx <= 32u)) ? 1u : 0u;
     if (ev) STEP(hrt_hip_event_record(ev[0], stream));
     if (!K.los_blocks) STEP(hrt_hip_launch_los(&K, stream));
@@ -1352,15 +1355,6 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
         const int fused = b == 0 ? (K.fuse & HRT_FUSE_LAUNCH0) != 0 : (K.fuse & HRT_FUSE_BOUNCES) != 0;
         int fused_rc = -1;
         if (fused && !hip) fused_rc = hrt_hip_launch_fused(&K, b, stream);   /* -1: this table / variant is not fusable */
-        if (fused_rc < 0 && b == 0 && K.los_blocks) {   /* launch 0 is not fused after all: the LoS pass as its own kernel */
-            K.los_blocks = 0u;
-            STEP(hrt_hip_launch_los(&K, stream));
-            if (ev) {   /* (the timer: LoS ends here, launch 0 begins here) */
-                STEP(hrt_hip_event_record(ev[1], stream));
-                STEP(hrt_hip_event_record(ev[2], stream));
-                STEP(hrt_hip_event_record(ev[4], stream));
-            }
-        }
         if (fused_rc >= 0) {
             STEP(fused_rc);
             if (ev) STEP(hrt_hip_event_record(ev[3 + 4 * b], stream));

@@ -54,6 +54,7 @@
 
 #include "hrt_kparams.h"
 #include "hrt_launch_dir.h"
+#include "hrt_launch_plan.h"
 #include "hrt_libm.h"
 
 #pragma clang fp contract(off)
@@ -665,7 +666,7 @@ __device__ __forceinline__ bool packet_culls(const Packet &P, float4 q0, float4 
 // its candidate mask parked in this wave's LDS slots, THEN the candidates are walked -- so the
 // packet description and the culling temporaries are dead while the intersection tests run
 // (and vice versa), which is what keeps the kernel's register allocation low.
-constexpr uint32_t kMaskRounds = 16;
+constexpr uint32_t kMaskRounds = HRT_MASK_ROUNDS;
 // Per-wave LDS scratch of the trace / fused kernels, in float4: 2 * kMaskRounds words-of-four for the
 // walks (leaf constants, stacks, queues) and -- for the fine-leaves walk (variant 9), whose table is
 // read from GLOBAL memory -- a buffer of kCandBuf candidate rows (3 float4 of the row + its index):
@@ -673,8 +674,8 @@ constexpr uint32_t kMaskRounds = 16;
 // here, so that the candidate walk reads LDS instead of paying a dependent L2 round trip per
 // candidate.  (The 64-row leaf walk gains nothing from it: it is bound by the instructions of its
 // ~350 culling rounds per trace, not by its candidates.)
-constexpr uint32_t kCandBuf = 64u;
-__host__ __device__ constexpr uint32_t wave_scratch4(bool cand_buf) { return 2u * kMaskRounds + (cand_buf ? 4u * kCandBuf : 0u); }
+constexpr uint32_t kCandBuf = HRT_CAND_BUF;
+__host__ __device__ constexpr uint32_t wave_scratch4(bool cand_buf) { return HRT_WAVE_SCRATCH4(cand_buf); }
 
 // cube-map cell of a direction (shared with the host builder, problem.c: rxt_cell_dir): face =
 // major axis + 3 * (major < 0), (u, v) = the two other components over the (signed) major one
@@ -2017,7 +2018,7 @@ __global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VA
     const float2 *g_tg = reinterpret_cast<const float2 *>(P.acc.tg);
     const float4 *g_leaf = reinterpret_cast<const float4 *>(P.acc.leaf);
     const uint32_t n_leaf = P.acc.num_leaf;
-    // LDS image (hrt_hip_launch_trace sizes it): [T x 5 float4 rows | T float2 guard pairs, padded to
+    // LDS image (hrt_launch_plan.h sizes it: lds_trace): [T x 5 float4 rows | T float2 guard pairs, padded to
     // 16 B | 2 float4 per leaf] (only if staged) [num_rx RX pos][4 waves x 16 u64 masks]
     // [4 waves x 16 float4 leaf constants][4 u32]
     float4 *l_tri = lds;
@@ -2548,11 +2549,10 @@ __global__ __launch_bounds__(HRT_BLOCK) void hrt_wide_finish_kernel(const hrt_kp
                              * 40 % slower) */
 #endif
 // NLDS: the per-triangle normals (+ mesh ids) and the mesh rows are staged in LDS (tables of up to
-// kShadeLdsTri triangles / kShadeLdsMesh meshes): the record loop then reads nothing from global
+// HRT_SHADE_LDS_TRI triangles / HRT_SHADE_LDS_MESH meshes): the record loop then reads nothing from global
 // memory between its stores except the shadow result words, which are requested four RXs at a time in
 // front of those RXs' records -- loads and stores share vmcnt in issue order, so a load behind a
 // record's nine stores waits for them to reach L2.
-constexpr uint32_t kShadeLdsTri = 2048u, kShadeLdsMesh = 256u;
 template <bool NLDS>
 __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(const hrt_kparams P,
                                                               const uint32_t b)
@@ -3230,12 +3230,12 @@ __device__ __forceinline__ uint32_t lb_exclusive(const LbWords &W, uint32_t chun
     }
 }
 
-// LDS image shared by the fused kernels (hrt_hip_launch_fused sizes it):
+// LDS image shared by the fused kernels (hrt_launch_plan.h sizes it: lds_fused):
 // [17 x 4 float4 materials][16 float4: the exp table]                                    (launches >= 1)
 // [T x 5 float4 rows | T float2 guard pairs, padded to 16 B | 2 float4 per leaf] (only if staged)
 // [num_rx float4 RX pos][4 waves x 16 u64 masks][4 waves x 32 float4 per-wave scratch][64 u32]
 // [17 x 4 float4 materials][64 float4 TX pos]                                              (launch 0: no exp table)
-constexpr uint32_t kLdsTx = 64u;
+constexpr uint32_t kLdsTx = HRT_LDS_TX;
 struct FusedLds {
     float4 *tri, *leaf, *rx, *wleaf, *mat, *tx;
     float2 *tg;
@@ -4631,40 +4631,17 @@ int hrt_hip_launch_los(const hrt_kparams *P, void *stream)
     return (int)hipGetLastError();
 }
 
-// does this problem walk the fine leaves (tables beyond LDS with fine spheres built, no big-table trees)?
-static bool walks_fine(const hrt_kparams *P)
-{
-    const int variant = P->tune.variant;
-    const uint64_t lds_max = P->tune.lds_tri_bytes_max;
-    const uint64_t T = P->num_tri;
-    const uint64_t tri_bytes = T * HRT_TRI_FLOATS * 4u + ((T + 1u) / 2u) * 16u +
-                               (uint64_t)P->acc.num_leaf * HRT_NODE_FLOATS * 4u;
-    const bool in_lds = T * HRT_TRI_FLOATS * 4u <= lds_max && tri_bytes <= 144u * 1024u;
-    const bool trees = P->acc.big && (variant >= 4) && variant != 9;
-    return !in_lds && !trees && P->acc.fine != nullptr && (variant == 7 || variant == 9);
-}
-
-// patch tables on a table that takes the small-table packet kernel: shadow traces + records of launch
-// `bounce` >= 1 are hrt_records_kernel's (launched by hrt_hip_launch_trace), the shade kernel skips them
-static bool records_in_own_kernel(const hrt_kparams *P, uint32_t bounce)
-{
-    const int variant = P->tune.variant;
-    const uint64_t lds_max = P->tune.lds_tri_bytes_max;
-    const uint64_t T = P->num_tri;
-    const uint64_t tri_bytes = T * HRT_TRI_FLOATS * 4u + ((T + 1u) / 2u) * 16u +
-                               (uint64_t)P->acc.num_leaf * HRT_NODE_FLOATS * 4u;
-    const bool in_lds = T * HRT_TRI_FLOATS * 4u <= lds_max && tri_bytes <= 144u * 1024u;
-    const bool one_block = P->num_tri <= kMaskRounds * 64u;
-    const bool trees = P->acc.big && (variant >= 4) && variant != 9;
-    const bool flat = variant == 2 || variant == 3 || (variant == 7 && !trees && one_block);
-    return bounce != 0 && P->patch.mask != nullptr && in_lds && flat && one_block && !walks_fine(P);
-}
+// The launch shims below launch what the launch plan says (hrt_launch_plan.h; DESIGN.md, "the launch plan"): which
+// kernel, for which walk, with how large an LDS image.  Theirs are the grids, hipFuncSetAttribute and the launch.
+// The cases of a dispatch are exactly the instantiations that exist (in the order that keeps the emitted code's).
+#define HRT_WALK(LDS, V) ((LDS) ? 16 + (V) : (V))
 
 // geometry of launch `bounce`: the trace kernel (all shadow + primary traces of the live list)
 int hrt_hip_launch_trace(const hrt_kparams *P_in, uint32_t bounce, void *stream)
 {
+    const hrt_launch_plan pl = hrt_plan(P_in);
     hrt_kparams Pc = *P_in;
-    Pc.cnt_per_wave = walks_fine(P_in) ? 1u : 0u;
+    Pc.cnt_per_wave = pl.cnt_per_wave;
     const hrt_kparams *P = &Pc;
     // Shapes are validated by the host (hrt_trace); here only the launch geometry.
     const uint64_t n_max = (bounce == 0) ? P->n0 : P->cap;
@@ -4673,67 +4650,31 @@ int hrt_hip_launch_trace(const hrt_kparams *P_in, uint32_t bounce, void *stream)
     const uint64_t max_grid = P->tune.trace_grid ? P->tune.trace_grid : HRT_TRACE_GRID;
     if (blocks > max_grid) blocks = max_grid;
     if (blocks == 0) blocks = 1;
-    // HRT_TRACE_VARIANT: unset = auto (see below).
-    // 6 = trees wherever built, else 4; 4 = packet culling behind the leaf spheres + guard; 2 = flat
-    // packet culling; 1 = staged tests over all triangles; 0 = the reference's plain sequence.  All
-    // give bit-identical results; the GPU tests run all of them.
-    const int variant = P->tune.variant;
-    const uint64_t T = P->num_tri;
-    // staged image: rows + guard pairs (padded to 16 B) + leaf records
-    const uint64_t tri_bytes = T * HRT_TRI_FLOATS * 4u + ((T + 1u) / 2u) * 16u +
-                               (uint64_t)P->acc.num_leaf * HRT_NODE_FLOATS * 4u;
-    const uint64_t lds_max = P->tune.lds_tri_bytes_max;
-    const bool in_lds = T * HRT_TRI_FLOATS * 4u <= lds_max && tri_bytes <= 144u * 1024u;
-    const bool one_block = P->num_tri <= kMaskRounds * 64u;   // packet culling: single-block build
-    const bool fine_pre = !in_lds && !(P->acc.big && variant >= 4 && variant != 9) && P->acc.fine != nullptr &&
-                          (variant == 7 || variant == 9);
-    const size_t lds = (in_lds ? (size_t)tri_bytes : 0u) + (size_t)P->num_rx * 16u +
-                       (HRT_BLOCK / 64u) * (kMaskRounds * 8u + wave_scratch4(fine_pre) * 16u) + 16u;
     hipStream_t st = (hipStream_t)stream;
     hipError_t err = hipSuccess;
-    const uint32_t nb = (uint32_t)blocks;
-    // auto (7): trees where the host built them; the leaf spheres + guard on tables of more than one
-    // block of 1024 triangles (where the live list is re-sorted between bounces, so that most leaves
-    // ARE far from a packet: city of 25 002 triangles 22.2 -> 17.9 ms, of 100 002 100 -> 87); the flat
-    // walk on small tables (C3: 1.67 vs 1.81 ms)
-    const bool trees = P->acc.big && (variant >= 4) && variant != 9;
-    const bool flat = variant == 2 || variant == 3 || (variant == 7 && !trees && one_block);
-    // fine leaves + plane tree where the host built them (beyond HRT_FINE_MIN_TRI triangles): auto, or variant 9
-    const bool fine = !in_lds && !trees && P->acc.fine != nullptr && (variant == 7 || variant == 9);
-    if (fine) {
-        launch_trace_t<false, 9>(P, bounce, nb, lds, st, &err);
-        if (err == hipSuccess && P->wide_cap != 0u) {   // the packets the walk queued as too wide to cull
-            const uint64_t wide_grid = P->tune.wide_grid ? P->tune.wide_grid : kWideGrid;
-            hipLaunchKernelGGL(hrt_wide_kernel, dim3((uint32_t)wide_grid), dim3(HRT_BLOCK), 0, st, *P, bounce);
-            hipLaunchKernelGGL(hrt_wide_finish_kernel, dim3(256), dim3(HRT_BLOCK), 0, st, *P, bounce);
+    if (hrt_plan_own_records(&pl, bounce)) {   // shadow traces + records are hrt_records_kernel's: the primary rays only
+        if (bounce >= P->num_bounces) return (int)hipGetLastError();
+        blocks = (n_max + HRT_BLOCK - 1) / HRT_BLOCK;
+        if (blocks > max_grid) blocks = max_grid;
+        if (hrt_plan_image(&pl, bounce)) {
+            hipLaunchKernelGGL(hrt_image_kernel, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_image, st, *P, bounce);
+            return (int)hipGetLastError();
         }
-    } else if (in_lds) {
-        if (variant == 0) launch_trace_t<true, 0>(P, bounce, nb, lds, st, &err);
-        else if (variant == 1) launch_trace_t<true, 1>(P, bounce, nb, lds, st, &err);
-        else if (flat) {
-            if (records_in_own_kernel(P, bounce)) {
-                // patch tables: shadow traces + records are hrt_records_kernel's (hrt_hip_launch_records), this
-                // kernel keeps the primary rays
-                if (bounce < P->num_bounces) {
-                    uint64_t pblocks = (n_max + HRT_BLOCK - 1) / HRT_BLOCK;
-                    if (pblocks > max_grid) pblocks = max_grid;
-                    if (bounce == 1 && P->patch.num_img != 0u)   // first-order images of the TXs: hrt_image_kernel
-                        hipLaunchKernelGGL(hrt_image_kernel, dim3((uint32_t)pblocks), dim3(HRT_BLOCK),
-                                           (size_t)T * HRT_TRI_FLOATS * 4u + 16u, st, *P, bounce);
-                    else
-                        launch_trace_t<true, 2>(P, bounce, (uint32_t)pblocks, lds, st, &err);
-                }
-            } else if (one_block) launch_trace_t<true, 2>(P, bounce, nb, lds, st, &err);
-            else launch_trace_t<true, 3>(P, bounce, nb, lds, st, &err);
-        } else if (trees) launch_trace_t<true, 6>(P, bounce, nb, lds, st, &err);
-        else if (one_block) launch_trace_t<true, 4>(P, bounce, nb, lds, st, &err);
-        else launch_trace_t<true, 5>(P, bounce, nb, lds, st, &err);
-    } else {
-        if (variant == 0) launch_trace_t<false, 0>(P, bounce, nb, lds, st, &err);
-        else if (variant == 1) launch_trace_t<false, 1>(P, bounce, nb, lds, st, &err);
-        else if (flat) launch_trace_t<false, 3>(P, bounce, nb, lds, st, &err);
-        else if (trees) launch_trace_t<false, 6>(P, bounce, nb, lds, st, &err);
-        else launch_trace_t<false, 5>(P, bounce, nb, lds, st, &err);   // tables beyond LDS are > 1 block
+    }
+    const uint32_t nb = (uint32_t)blocks;
+    const size_t lds = (size_t)pl.lds_trace;
+    switch (HRT_WALK(pl.in_lds, pl.trace_v)) {
+#define HRT_CASE(LDS, V) case HRT_WALK(LDS, V): launch_trace_t<LDS, V>(P, bounce, nb, lds, st, &err); break;
+        HRT_CASE(false, 9) HRT_CASE(true, 0) HRT_CASE(true, 1) HRT_CASE(true, 2) HRT_CASE(true, 3) HRT_CASE(true, 6)
+        HRT_CASE(true, 4) HRT_CASE(true, 5) HRT_CASE(false, 0) HRT_CASE(false, 1) HRT_CASE(false, 3) HRT_CASE(false, 6)
+        HRT_CASE(false, 5)
+#undef HRT_CASE
+        default: return (int)hipErrorInvalidValue;
+    }
+    if (pl.fine && err == hipSuccess && P->wide_cap != 0u) {   // the packets the walk queued as too wide to cull
+        const uint64_t wide_grid = P->tune.wide_grid ? P->tune.wide_grid : kWideGrid;
+        hipLaunchKernelGGL(hrt_wide_kernel, dim3((uint32_t)wide_grid), dim3(HRT_BLOCK), 0, st, *P, bounce);
+        hipLaunchKernelGGL(hrt_wide_finish_kernel, dim3(256), dim3(HRT_BLOCK), 0, st, *P, bounce);
     }
     if (err != hipSuccess) return (int)err;
     return (int)hipGetLastError();
@@ -4743,24 +4684,24 @@ int hrt_hip_launch_trace(const hrt_kparams *P_in, uint32_t bounce, void *stream)
 // problem / launch (then the trace and shade kernels do that work), nothing launched
 int hrt_hip_launch_records(const hrt_kparams *P, uint32_t bounce, void *stream)
 {
-    if (!records_in_own_kernel(P, bounce)) return -1;
+    const hrt_launch_plan pl = hrt_plan(P);
+    if (!hrt_plan_own_records(&pl, bounce)) return -1;
     const uint64_t max_grid = P->tune.trace_grid ? P->tune.trace_grid : HRT_TRACE_GRID;
-    const uint64_t T = P->num_tri;
     uint64_t rblocks = (P->cap + HRT_BLOCK - 1) / HRT_BLOCK;
     if (rblocks > 2u * max_grid) rblocks = 2u * max_grid;   // (1 024 .. 4 096 workgroups: 2-5 % slower)
-    const size_t rlds = (size_t)T * HRT_TRI_FLOATS * 4u + (size_t)P->num_rx * 16u +
-                        (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + (size_t)T * 4u;
-    if (rlds > 64u * 1024u) return (int)hipErrorInvalidValue;   // (cannot happen: T <= HRT_PATCH_MAX_TRI)
-    hipLaunchKernelGGL(hrt_records_kernel, dim3((uint32_t)rblocks), dim3(HRT_BLOCK), rlds, (hipStream_t)stream, *P, bounce);
+    if (pl.lds_records > 64u * 1024u) return (int)hipErrorInvalidValue;   // (cannot happen: T <= HRT_PATCH_MAX_TRI)
+    hipLaunchKernelGGL(hrt_records_kernel, dim3((uint32_t)rblocks), dim3(HRT_BLOCK), (size_t)pl.lds_records,
+                       (hipStream_t)stream, *P, bounce);
     return (int)hipGetLastError();
 }
 
 // shading of launch `bounce`: records of bounce-1, the bounce itself, compaction step 1
 int hrt_hip_launch_shade(const hrt_kparams *P_in, uint32_t bounce, void *stream)
 {
+    const hrt_launch_plan pl = hrt_plan(P_in);
     hrt_kparams Pc = *P_in;
-    Pc.cnt_per_wave = walks_fine(P_in) ? 1u : 0u;
-    Pc.records_done = records_in_own_kernel(P_in, bounce) ? 1u : 0u;
+    Pc.cnt_per_wave = pl.cnt_per_wave;
+    Pc.records_done = hrt_plan_own_records(&pl, bounce) ? 1u : 0u;
     if (Pc.records_done && bounce >= Pc.num_bounces) return 0;   // the last launch: records only, nothing left to shade
     const hrt_kparams *P = &Pc;
     const uint64_t n_max = (bounce == 0) ? P->n0 : P->cap;
@@ -4768,106 +4709,65 @@ int hrt_hip_launch_shade(const hrt_kparams *P_in, uint32_t bounce, void *stream)
     const uint64_t max_grid = P->tune.shade_grid ? P->tune.shade_grid : HRT_SHADE_GRID;
     if (blocks > max_grid) blocks = max_grid;
     if (blocks == 0) blocks = 1;
-    const size_t lds0 = (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + (size_t)P->num_rx * 16u + 32u;
-    const uint64_t nlds_off = P->tune.shade_global_normals;
-    if (!nlds_off && P->num_tri <= kShadeLdsTri && P->num_mesh <= kShadeLdsMesh)
-        hipLaunchKernelGGL(hrt_shade_kernel<true>, dim3((uint32_t)blocks), dim3(HRT_BLOCK),
-                           lds0 + ((size_t)P->num_tri + P->num_mesh) * 16u, (hipStream_t)stream, *P, bounce);
+    if (pl.shade_lds_normals)
+        hipLaunchKernelGGL(hrt_shade_kernel<true>, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_shade,
+                           (hipStream_t)stream, *P, bounce);
     else
-        hipLaunchKernelGGL(hrt_shade_kernel<false>, dim3((uint32_t)blocks), dim3(HRT_BLOCK), lds0,
+        hipLaunchKernelGGL(hrt_shade_kernel<false>, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_shade,
                            (hipStream_t)stream, *P, bounce);
     return (int)hipGetLastError();
 }
 
 int hrt_hip_launch_fused(const hrt_kparams *P_in, uint32_t bounce, void *stream)
 {
+    const hrt_launch_plan pl = hrt_plan(P_in);
     hrt_kparams Pc = *P_in;
 #ifdef HRT_PHASE_STATS
     Pc.phase_bounce = (uint32_t)env_u64("HRT_PHASE_BOUNCE", 0);
 #endif
-    Pc.records_done = records_in_own_kernel(P_in, bounce) ? 1u : 0u;
+    Pc.records_done = hrt_plan_own_records(&pl, bounce) ? 1u : 0u;
     if (bounce != 0) Pc.los_blocks = 0;
     else if (Pc.los_blocks) Pc.los_blocks = (Pc.num_rx * Pc.num_tx + HRT_BLOCK / 64u - 1u) / (HRT_BLOCK / 64u);
     const hrt_kparams *P = &Pc;
     if (P->cap / HRT_BLOCK + 1u > P->lb_chunks) return (int)hipErrorInvalidValue;   // (one word per chunk)
-    const int variant = P->tune.variant;
-    const uint64_t T = P->num_tri;
-    const uint64_t tri_bytes = T * HRT_TRI_FLOATS * 4u + ((T + 1u) / 2u) * 16u +
-                               (uint64_t)P->acc.num_leaf * HRT_NODE_FLOATS * 4u;
-    const uint64_t lds_max = P->tune.lds_tri_bytes_max;
-    const bool in_lds = T * HRT_TRI_FLOATS * 4u <= lds_max && tri_bytes <= 144u * 1024u;
-    const bool one_block = P->num_tri <= kMaskRounds * 64u;
-    const bool fine_pre = !in_lds && !(P->acc.big && variant >= 4 && variant != 9) && P->acc.fine != nullptr &&
-                          (variant == 7 || variant == 9);
-    const size_t lds = (in_lds ? (size_t)tri_bytes : 0u) + (size_t)P->num_rx * 16u +
-                       (HRT_BLOCK / 64u) * (kMaskRounds * 8u + wave_scratch4(fine_pre) * 16u) + 64u * 4u +
-                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + kLdsTx * 16u;
+    if (!hrt_plan_fuses(&pl, bounce)) return -1;   // not a HIP failure: this launch runs as two kernels
+    const size_t lds = (size_t)pl.lds_fused;
     hipStream_t st = (hipStream_t)stream;
     hipError_t err = hipSuccess;
-    // the same choice of intersection loop as hrt_hip_launch_trace; on tables of a handful of
-    // triangles (auto) the staged walk over all of them is cheaper than a culling round
-    const uint64_t staged_max = P->tune.fuse_staged_max_tri;
-    const bool trees = P->acc.big && (variant >= 4) && variant != 9;
-    const bool flat = variant == 2 || variant == 3 || (variant == 7 && !trees && one_block);
-    const bool staged = variant == 1 || (variant == 7 && T <= staged_max);
-    const bool fine = !in_lds && !trees && P->acc.fine != nullptr && (variant == 7 || variant == 9);
-    // (the fine walk wants the trace kernel's registers and its queue of wide packets: fused, launch 0 of
-    // the 100 002-triangle city took 6.4 ms against 2.1 + 0.1 for the two kernels)
-    if (fine) return -1;
-    else if (in_lds) {
-        if (variant == 0) launch_fused_t<true, 0>(P, bounce, lds, st, &err);
-        else if (staged) launch_fused_t<true, 1>(P, bounce, lds, st, &err);
-        else if (flat) {
-            if (one_block) launch_fused_t<true, 2>(P, bounce, lds, st, &err);
-            else launch_fused_t<true, 3>(P, bounce, lds, st, &err);
-        } else if (trees) launch_fused_t<true, 6>(P, bounce, lds, st, &err);
-        else if (one_block) launch_fused_t<true, 4>(P, bounce, lds, st, &err);
-        else launch_fused_t<true, 5>(P, bounce, lds, st, &err);
-    } else {
-        if (variant == 0) launch_fused_t<false, 0>(P, bounce, lds, st, &err);
-        else if (staged) launch_fused_t<false, 1>(P, bounce, lds, st, &err);
-        else if (flat) launch_fused_t<false, 3>(P, bounce, lds, st, &err);
-        else if (trees) launch_fused_t<false, 6>(P, bounce, lds, st, &err);
-        else launch_fused_t<false, 5>(P, bounce, lds, st, &err);
+    switch (HRT_WALK(pl.in_lds, pl.fused_v)) {
+#define HRT_CASE(LDS, V) case HRT_WALK(LDS, V): launch_fused_t<LDS, V>(P, bounce, lds, st, &err); break;
+        HRT_CASE(true, 0) HRT_CASE(true, 1) HRT_CASE(true, 2) HRT_CASE(true, 3) HRT_CASE(true, 6) HRT_CASE(true, 4)
+        HRT_CASE(true, 5) HRT_CASE(false, 0) HRT_CASE(false, 1) HRT_CASE(false, 3) HRT_CASE(false, 6) HRT_CASE(false, 5)
+#undef HRT_CASE
+        default: return (int)hipErrorInvalidValue;
     }
-    if (err == hipErrorNotSupported) return -1;   // not a HIP failure: this launch runs as two kernels
     if (err != hipSuccess) return (int)err;
     return (int)hipGetLastError();
 }
 
 int hrt_hip_launch_chain(const hrt_kparams *P_in, uint32_t b0, void *stream)
 {
-    if (b0 == 0 || b0 > P_in->num_bounces) return -1;
+    const hrt_launch_plan pl = hrt_plan(P_in);
+    if (b0 == 0 || b0 > P_in->num_bounces || hrt_plan_own_records(&pl, b0)) return -1;
     hrt_kparams Pc = *P_in;
     Pc.records_done = 0u;
     Pc.los_blocks = 0;
     const hrt_kparams *P = &Pc;
-    if (records_in_own_kernel(P_in, b0)) return -1;
     if (P->cap / HRT_BLOCK + 1u > P->lb_chunks) return (int)hipErrorInvalidValue;
-    const int variant = P->tune.variant;
-    const uint64_t T = P->num_tri;
-    const uint64_t tri_bytes = T * HRT_TRI_FLOATS * 4u + ((T + 1u) / 2u) * 16u +
-                               (uint64_t)P->acc.num_leaf * HRT_NODE_FLOATS * 4u;
-    const bool in_lds = T * HRT_TRI_FLOATS * 4u <= P->tune.lds_tri_bytes_max && tri_bytes <= 144u * 1024u;
-    const bool one_block = P->num_tri <= kMaskRounds * 64u;
-    if (!in_lds || !one_block || walks_fine(P)) return -1;
-    const size_t lds = (size_t)tri_bytes + (size_t)P->num_rx * 16u +
-                       (HRT_BLOCK / 64u) * (kMaskRounds * 8u + wave_scratch4(false) * 16u) + 64u * 4u +
-                       (size_t)(HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u + HRT_EXP2_TAB_BYTES) + kLdsTx * 16u;
-    const bool trees = P->acc.big && (variant >= 4) && variant != 9;
-    const bool flat = variant == 2 || variant == 3 || (variant == 7 && !trees && one_block);
-    const bool staged = variant == 1 || (variant == 7 && T <= P->tune.fuse_staged_max_tri);
+    const size_t lds = (size_t)pl.lds_chain;
     hipStream_t st = (hipStream_t)stream;
     hipError_t err = hipSuccess;
-    if (variant == 0) launch_chain_t<0>(P, b0, lds, st, &err);
-    else if (staged) launch_chain_t<1>(P, b0, lds, st, &err);
-    else if (flat) launch_chain_t<2>(P, b0, lds, st, &err);
-    else if (trees) return -1;
-    else launch_chain_t<4>(P, b0, lds, st, &err);
-    if (err == hipErrorNotSupported) return -1;
+    switch (pl.chain_v) {
+#define HRT_CASE(V) case V: launch_chain_t<V>(P, b0, lds, st, &err); break;
+        HRT_CASE(0) HRT_CASE(1) HRT_CASE(2) HRT_CASE(4)
+#undef HRT_CASE
+        default: return -1;   // no chain on this table / walk
+    }
+    if (err == hipErrorNotSupported) return -1;   // (the occupancy query: nothing resident)
     if (err != hipSuccess) return (int)err;
     return (int)hipGetLastError();
 }
+#undef HRT_WALK
 
 int hrt_hip_launch_dirs(uint64_t num_paths, uint32_t rank, uint32_t count, uint32_t chunk,
                         uint64_t num_local, float *d_dirs, uint32_t *d_fix_count,

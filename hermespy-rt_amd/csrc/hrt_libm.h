@@ -157,6 +157,7 @@ HRT_HD float hrt_cosf_nb(float y)
 
 /* bits of 2^(i/32) minus (i << 47): so that adding (k << 47) with k = 32*e + i yields the
  * bits of 2^(k/32) */
+#define HRT_EXP2_TAB_BYTES 256u   /* the 32 words of the table (the launch plan sizes LDS images with it) */
 #define HRT_EXP2_TAB_WORDS \
     0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, \
     0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, \
@@ -221,7 +222,6 @@ float hrt_expf(float xf)
  * register where a function is called out of line) of 32 words filled with hrt_exp2_tab(0 .. 31)
  * -- the one definition of the numbers -- by the kernel, with its other tables, in front of its
  * first barrier. */
-#define HRT_EXP2_TAB_BYTES 256u
 __device__ __forceinline__ float hrt_expf_lds(float xf, uint32_t tab)
 {
     if (hrt_abstop12(xf) >= hrt_abstop12(88.0f)) return (float)exp((double)xf);

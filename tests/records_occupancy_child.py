@@ -25,8 +25,9 @@ def dense(c, ref):
     return st
 
 
-def timer_pass(c, ref):
-    """the device-resident entry with HIP events around every kernel (hrt_trace_flags with a timer)"""
+def timer_pass(c, ref, records_kernel=True):
+    """the device-resident entry with HIP events around every kernel (hrt_trace_flags with a timer); records_kernel:
+    hrt_records_kernel runs on this problem, so its phase takes time"""
     from hermespy_rt_amd.abi import written
     from hermespy_rt_amd.device import Tracer
     tr = Tracer(c["scene_path"], c["rx_pos"], c["tx_pos"], c["rx_vel"], c["tx_vel"], c["f_ghz"], c["num_paths"],
@@ -34,7 +35,7 @@ def timer_pass(c, ref):
     t = tr.new_timer()
     tr.trace_with_timer(t)
     times = tr.read_timer(t)
-    assert len(times["records_ms"]) == c["num_bounces"] + 1 and max(times["records_ms"]) > 0.0, times
+    assert len(times["records_ms"]) == c["num_bounces"] + 1 and (max(times["records_ms"]) > 0.0 or not records_kernel), times
     d = tr.to_dense()
     ex, s = ref["extras"], ref["scat"]
     assert list(d["counts"][:c["num_bounces"] + 1]) == [int(x) for x in ex["live"]]
