@@ -233,6 +233,114 @@ def plant(tr, keyed=False, seed=0):
     return concat(T, *los)
 
 
+def link_hash(link):
+    """the default `where` of plant_single"""
+    return mix(link, 0x51C)
+
+
+def plant_single(tr, tau32_by_link, where=link_hash, nu_by_link=None, only_live_bit=False):
+    """One live record per link (tests/test_gpu_sinc_weights.py): after a trace, every link (rx, tx) that has an
+    unblocked scatter record gets exactly one with a_te = 1 + 0j, a_tm = 0.5 + 0j, FS0 = 0, DFS = -nu (default 0) and
+    tau = tau32_by_link[rx * ntx + tx]: record number where(link) mod N of its N unblocked records, counted block by
+    block in index order.  Every other unblocked record keeps its traced tau and has its four amplitude fields zeroed.
+    Every LoS entry is forced clear with a = 1, the link's tau and nu; its direction stays as traced (entries that
+    were not clear get the coincident convention's).  only_live_bit=True also clears the mask bit of every other
+    record, so that the live one is a batch of its own.
+
+    With fc = 0 or t = 0 and nu = 0 the phase of the live record is exactly 0 and its term is a * w: the output tap is
+    the kernel's sinc weight bit for bit (TM: half of it; through the LoS route TE = TM = w).
+
+    Returns S: covered [nlinks] bool (links with a live scatter record), block / index [nlinks] (-1: none), ordinal
+    (the live record's number among the link's unblocked records) and count (N); retau_single(tr, S, ...) replants
+    the delays and Doppler shifts alone."""
+    torch = tr.torch
+    torch.cuda.synchronize(tr.device)
+    counts = tr.counts()
+    nl = tr.nrx * tr.ntx
+    blocks = []
+    per = np.zeros((tr.nrx, tr.ntx), np.int64)
+    for b in range(tr.nb):
+        n = int(counts[b + 1])
+        if n == 0:
+            continue
+        ray = tr.hit_block(b)[HIT_RAY, :n].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        tx, _ = tr.global_path(ray)
+        ub = _mask_bits(tr, b, n)
+        blocks.append((b, n, tx, ub, per.copy()))
+        for rx in range(tr.nrx):
+            per[rx] += np.bincount(tx[ub[rx]], minlength=tr.ntx)
+    count = per.reshape(-1)
+    links = np.arange(nl)
+    pick = np.where(count > 0, np.asarray(where(links), np.uint64) % np.maximum(count, 1).astype(np.uint64), 0)
+    pick = pick.astype(np.int64).reshape(tr.nrx, tr.ntx)
+    S = dict(covered=count > 0, count=count.copy(), ordinal=np.where(count > 0, pick.reshape(-1), -1),
+             block=np.full(nl, -1, np.int64), index=np.full(nl, -1, np.int64))
+    for b, n, tx, ub, before in blocks:
+        recs = tr.rec_block(b)[:, :, :n].cpu().numpy().view(np.float32).copy()
+        keep = np.zeros_like(ub)
+        for rx in range(tr.nrx):
+            i = np.nonzero(ub[rx])[0]
+            recs[rx, REC_A_TE_RE:REC_A_TM_IM + 1, i] = 0.0
+            for t in range(tr.ntx):
+                it = i[tx[i] == t]
+                k = pick[rx, t] - before[rx, t]
+                if per[rx, t] and 0 <= k < it.size:
+                    lk = rx * tr.ntx + t
+                    S["block"][lk], S["index"][lk] = b, it[k]
+                    recs[rx, REC_A_TE_RE, it[k]] = 1.0
+                    recs[rx, REC_A_TM_RE, it[k]] = 0.5
+                    keep[rx, it[k]] = True
+        tr.rec_block(b)[:, :, :n] = torch.from_numpy(recs.view(np.int32)).to(tr.device)
+        tr.hit_block(b)[HIT_FS0, :n] = 0   # (float 0: the bits 0)
+        if only_live_bit:
+            _write_mask_bits(tr, b, n, keep)
+    assert ((S["block"] >= 0) == S["covered"]).all()
+
+    L = los_view(tr)
+    Lh = L.cpu().numpy().copy()
+    status = Lh[:, :, LOS_STATUS].view(np.uint32)
+    d = Lh[:, :, LOS_DIRX:LOS_DIRZ + 1]
+    d[(status != 2) | ~np.isfinite(d).all(axis=-1)] = (-1.0, 0.0, 0.0)
+    status[:] = 2
+    Lh[:, :, LOS_A] = 1.0
+    L.copy_(torch.from_numpy(Lh).to(tr.device))
+    retau_single(tr, S, tau32_by_link, nu_by_link)
+    return S
+
+
+def retau_single(tr, S, tau32_by_link, nu_by_link=None):
+    """the delays (and Doppler shifts, default 0) of plant_single's live records and LoS entries, replanted"""
+    torch = tr.torch
+    nl = tr.nrx * tr.ntx
+    tau = np.asarray(tau32_by_link, np.float32).reshape(nl)
+    nu = np.zeros(nl, np.float32) if nu_by_link is None else np.asarray(nu_by_link, np.float32).reshape(nl)
+    bits = lambda a: torch.from_numpy(a.view(np.int32).copy()).to(tr.device)   # noqa: E731
+    rx = np.arange(nl) // tr.ntx
+    for b in np.unique(S["block"][S["covered"]]):
+        s = S["block"] == b
+        r, i = torch.from_numpy(rx[s]).to(tr.device), torch.from_numpy(S["index"][s]).to(tr.device)
+        blk = tr.rec_block(int(b))
+        blk[r, REC_TAU, i] = bits(tau[s])
+        blk[r, REC_DFS, i] = bits(-nu[s])
+    L = los_view(tr)
+    L[:, :, LOS_TAU] = torch.from_numpy(tau.reshape(tr.nrx, tr.ntx)).to(tr.device)
+    L[:, :, LOS_FS] = torch.from_numpy(nu.reshape(tr.nrx, tr.ntx)).to(tr.device)
+    torch.cuda.synchronize(tr.device)
+
+
+def _write_mask_bits(tr, b, n, keep):
+    """the unblocked bits below n of hit block b := keep [nrx, n]; the bits at and beyond n stay as they are"""
+    torch = tr.torch
+    pad = (-n) % 64
+    bits = np.pad(keep, ((0, 0), (0, pad))).reshape(tr.nrx, -1, 64).astype(np.uint64)
+    words = (bits << np.arange(64, dtype=np.uint64)).sum(axis=-1, dtype=np.uint64)   # [nrx, ceil(n / 64)]
+    m = tr.mask_block(b).view(torch.int64)   # [nrx, cap / 64]
+    if n % 64:
+        old = m[:, words.shape[1] - 1].cpu().numpy().view(np.uint64)
+        words[:, -1] |= old & ~np.uint64((1 << (n % 64)) - 1)
+    m[:, :words.shape[1]] = torch.from_numpy(words.view(np.int64)).to(tr.device)
+
+
 def poison(tr, counts, value):
     """Write `value` (a float) into every slot a path-sum kernel must not read: all record fields where the mask bit
     is 0, every hit and record slot from the block's count up to cap (HRT_HIT_RAY there = 0), every mask bit at and
