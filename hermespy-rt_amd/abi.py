@@ -313,9 +313,10 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                  out_shape, extra, stats, dtype=np.complex64):
-    """One of the eight path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
-    _power_profiles, _dominant_paths, _beam_channel or _beam_taps) through ctypes, into a numpy array of `dtype` and shape (nrx, ntx) + out_shape
-    (a flat buffer of out_shape doubles for float64 or bytes for uint8; out_shape None: a placeholder the library
+    """One of the nine path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
+    _power_profiles, _dominant_paths, _beam_channel, _beam_taps or _array_covariance) through ctypes, into a numpy array
+    of `dtype` and shape (nrx, ntx) + out_shape (a flat buffer of out_shape doubles for float64, floats for float32 or
+    bytes for uint8; out_shape None: a placeholder the library
     refuses to write); `extra` are the arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
     rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
     tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
@@ -528,6 +529,63 @@ def run_compute_power_profiles(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, 
                        num_bounces, spec, (n,) if n <= 2 * (POWER_FIELDS * 65535 + (1 << 26)) else None, (), stats,
                        np.float64)
     return power_views(out, nrx, ntx, spec)
+
+
+COV_RX, COV_TX = 1, 2       # hrt_covariance_spec.sides
+COV_MAX_ELEMENTS = 256      # per side; and num_rx * num_tx * 2 * (Nr^2 + Nt^2) <= 2^26
+
+
+class CovarianceSpec(C.Structure):
+    """include/hermespy_rt.h hrt_covariance_spec"""
+    _fields_ = [("parts", C.c_uint32), ("sides", C.c_uint32)]
+
+
+def covariance_spec(rx=True, tx=True, los=True, scatter=True, parts=None, sides=None):
+    if parts is None:
+        parts = (CHANNEL_LOS if los else 0) | (CHANNEL_SCATTER if scatter else 0)
+    if sides is None:
+        sides = (COV_RX if rx else 0) | (COV_TX if tx else 0)
+    return CovarianceSpec(int(parts), int(sides))
+
+
+def covariance_out_floats(nrx, ntx, arrays, spec):
+    """the floats of a covariance output (hrt_covariance_out_floats): arrays an ArraySpec, or (Nr, Nt)"""
+    nr, nt = (arrays.num_rx_elements, arrays.num_tx_elements) if isinstance(arrays, ArraySpec) else arrays
+    nr = int(nr) if int(spec.sides) & COV_RX else 0
+    nt = int(nt) if int(spec.sides) & COV_TX else 0
+    return nrx * ntx * 2 * (nr * nr + nt * nt) * 2
+
+
+def covariance_views(buf, nrx, ntx, nr, nt):
+    """the regions of a flat complex64 covariance buffer (numpy array or torch tensor) as views: rx [nrx, ntx, 2, Nr,
+    Nr], tx [nrx, ntx, 2, Nt, Nt] (nr / nt 0: the side is absent, a zero-sized view), buffer"""
+    o1 = nrx * ntx * 2 * nr * nr
+    o2 = o1 + nrx * ntx * 2 * nt * nt
+    return {"rx": buf[:o1].reshape(nrx, ntx, 2, nr, nr), "tx": buf[o1:o2].reshape(nrx, ntx, 2, nt, nt), "buffer": buf}
+
+
+def run_compute_array_covariance(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                                 rx_elements=None, tx_elements=None, array_frequency=None, stats=None):
+    """hrt_compute_array_covariance through ctypes -> covariance_views of a complex64 numpy buffer (elements None: no
+    elements for that side; array_frequency defaults to the carrier).  Raises
+    RuntimeError("hrt_compute_array_covariance failed (<rc>): ...") on an error code."""
+    none = np.zeros((0, 3), np.float32)
+    nr, nt, extra = _array_args(none if rx_elements is None else rx_elements,
+                                none if tx_elements is None else tx_elements, f_ghz, array_frequency)
+    if rx_elements is None:
+        extra = (None,) + extra[1:]
+    if tx_elements is None:
+        extra = extra[:2] + (None,) + extra[3:]
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    n = covariance_out_floats(nrx, ntx, (nr, nt), spec)
+    fits = nr <= COV_MAX_ELEMENTS and nt <= COV_MAX_ELEMENTS and 0 < n <= 1 << 27 and nrx * ntx <= 65535
+    out = _run_pathsum(lib, "hrt_compute_array_covariance", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (n,) if fits else None, extra, stats, np.float32)
+    if not fits:
+        raise RuntimeError("hrt_compute_array_covariance accepted a call beyond its limits")
+    return covariance_views(out.view(np.complex64), nrx, ntx, nr if int(spec.sides) & COV_RX else 0,
+                            nt if int(spec.sides) & COV_TX else 0)
 
 
 DOMINANT_MAX_PATHS = 1024   # hrt_dominant_spec.max_paths; and num_rx * num_tx * max_paths <= 2^22

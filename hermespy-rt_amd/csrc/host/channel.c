@@ -1,6 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps; include/hermespy_rt.h: hrt_compute_channel,
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance; include/hermespy_rt.h:
+ * hrt_compute_array_covariance, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
  *
@@ -10,7 +11,7 @@
  * from compute_paths()'s per-path arrays, formed where the records already are: of C3's 2.3 GB of dense host
  * arrays only nrx * ntx * 2 * T * K complex values leave the device.  The kernels are in csrc/hrt_channel.hip,
  * csrc/hrt_array_channel.hip, csrc/hrt_taps.hip, csrc/hrt_array_taps.hip, csrc/hrt_power.hip,
- * csrc/hrt_dominant.hip, csrc/hrt_beam_channel.hip and csrc/hrt_beam_taps.hip, over the workspace view of
+ * csrc/hrt_dominant.hip, csrc/hrt_beam_channel.hip, csrc/hrt_beam_taps.hip and csrc/hrt_covariance.hip, over the workspace view of
  * csrc/hrt_pathsum.h.  The two pair
  * families (hrt_array_channel: element pairs, hrt_beam_channel: beam pairs) share one grid (hrt_kgrid, pair_grid) as
  * their kernels share one GEMM body (csrc/hrt_pair_gemm.inc), and the array and beam drop-ins one packing of the
@@ -27,6 +28,7 @@
 #include "../hrt_beam_channel.h"
 #include "../hrt_beam_taps.h"
 #include "../hrt_channel.h"
+#include "../hrt_covariance.h"
 #include "../hrt_dominant.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_power.h"
@@ -188,13 +190,14 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-/* One drop-in call: what the eight hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
+/* One drop-in call: what the nine hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
 struct ch_job {
     const void *spec;   /* hrt_channel_spec (hrt_compute_channel, hrt_compute_array_channel), hrt_taps_spec
-                           (hrt_compute_taps, hrt_compute_array_taps), hrt_power_spec or hrt_dominant_spec */
+                           (hrt_compute_taps, hrt_compute_array_taps), hrt_power_spec, hrt_dominant_spec or
+                           hrt_covariance_spec */
     uint64_t out_bytes;
     const void *h_const;
     uint64_t const_bytes;
@@ -883,6 +886,153 @@ int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
     job.scratch_bytes = pw_job_scratch;
     job.run = pw_job_run;
     return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ spatial covariance matrices (hrt_array_covariance) */
+
+#define HRT_CV_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
+#define HRT_CV_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this (the pair families' cap) */
+
+/* the checks of a covariance call that need no problem (device pointers are not read); n[0], n[1]: the elements of the
+ * RX and the TX side, 0 for a side that is not asked for */
+static int cov_check(const hrt_covariance_spec *spec, const hrt_array_spec *a, uint32_t n[2])
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: NULL spec");
+    if (!a) return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: NULL arrays");
+    int rc = parts_check(spec->parts, "hrt_array_covariance");
+    if (rc) return rc;
+    if (spec->sides == 0 || (spec->sides & ~(uint32_t)(HRT_COV_RX | HRT_COV_TX)))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: sides 0x%x (HRT_COV_RX | HRT_COV_TX)", spec->sides);
+    n[0] = (spec->sides & HRT_COV_RX) ? a->num_rx_elements : 0u;
+    n[1] = (spec->sides & HRT_COV_TX) ? a->num_tx_elements : 0u;
+    if ((spec->sides & HRT_COV_RX) && (n[0] < 1 || n[0] > HRT_CV_MAX_ELEMENTS))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_rx_elements = %u (1 .. %u)", n[0], HRT_CV_MAX_ELEMENTS);
+    if ((spec->sides & HRT_COV_TX) && (n[1] < 1 || n[1] > HRT_CV_MAX_ELEMENTS))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_tx_elements = %u (1 .. %u)", n[1], HRT_CV_MAX_ELEMENTS);
+    if (!isfinite(a->array_frequency_hz) || !(a->array_frequency_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: the array frequency must be finite and > 0");
+    if ((spec->sides & HRT_COV_RX) && !a->rx_elements)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: NULL rx_elements");
+    if ((spec->sides & HRT_COV_TX) && !a->tx_elements)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: NULL tx_elements");
+    return HRT_OK;
+}
+
+/* the checks that need the link count */
+static int cov_links_check(uint64_t nrx, uint64_t ntx, const uint32_t n[2])
+{
+    if (nrx > 65535u || ntx > 65535u || nrx * ntx > 65535u)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_rx * num_tx = %llu > 65535",
+                        (unsigned long long)(nrx * ntx));
+    const uint64_t outs = nrx * ntx * 2u * ((uint64_t)n[0] * n[0] + (uint64_t)n[1] * n[1]);
+    if (outs > HRT_CV_MAX_OUTPUTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_rx * num_tx * 2 * (Nr^2 + Nt^2) = %llu > 2^26",
+                        (unsigned long long)outs);
+    return HRT_OK;
+}
+
+uint64_t hrt_covariance_out_floats(size_t num_rx, size_t num_tx, const hrt_array_spec *arrays,
+                                   const hrt_covariance_spec *spec)
+{
+    if (!arrays || !spec) return 0;
+    const uint64_t nr = (spec->sides & HRT_COV_RX) ? arrays->num_rx_elements : 0u;
+    const uint64_t nt = (spec->sides & HRT_COV_TX) ? arrays->num_tx_elements : 0u;
+    return (uint64_t)num_rx * num_tx * 2u * (nr * nr + nt * nt) * 2u;
+}
+
+/* the tiling of one covariance call: a pure function of the problem, the shard, the spec and the array sizes */
+static int cov_plan(const hrt_problem *p, const hrt_shard *s, const hrt_covariance_spec *spec, const hrt_array_spec *a,
+                    hrt_kcov *K, uint64_t *bytes)
+{
+    uint32_t n[2];
+    int rc = cov_check(spec, a, n);
+    if (rc) return rc;
+    memset(K, 0, sizeof *K);
+    if ((rc = ps_view(p, s, spec->parts, "hrt_array_covariance", &K->v))) return rc;
+    if ((rc = cov_links_check(K->v.nrx, K->v.ntx, n))) return rc;
+    ps_shard(s, &K->sh);
+    K->sides = spec->sides;
+    for (int q = 0; q < 2; ++q) {
+        const uint32_t nb = (n[q] + HRT_CV_BLOCK - 1u) / HRT_CV_BLOCK;
+        K->n[q] = n[q];
+        K->nblk[q] = nb * (nb + 1u) / 2u;
+    }
+    K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
+    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx, blocks = K->nblk[0] + K->nblk[1];
+    const uint64_t per_chunk = links * 2u * blocks * HRT_CV_BLOCK * HRT_CV_BLOCK * 8u;
+    *bytes = ps_chunks(&K->v, spec->parts, links * blocks, HRT_CV_TARGET_GROUPS, per_chunk, HRT_CV_PARTIAL_MAX, 65535u);
+    return HRT_OK;
+}
+
+int hrt_array_covariance_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_covariance_spec *spec,
+                                       const hrt_array_spec *arrays, uint64_t *out)
+{
+    hrt_kcov K;
+    uint64_t bytes = 0;
+    const int rc = cov_plan(p, s, spec, arrays, &K, &bytes);
+    return ps_scratch_out(rc, bytes, out, "hrt_array_covariance_scratch_bytes");
+}
+
+int hrt_array_covariance(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                         const hrt_covariance_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
+                         uint64_t scratch_bytes, float *d_out, int accumulate, void *stream)
+{
+    hrt_kcov K;
+    uint64_t need = 0;
+    int rc = cov_plan(p, s, spec, arrays, &K, &need);
+    if (rc) return rc;
+    if ((rc = ps_bind(&K.v, need, d_workspace, d_scratch, scratch_bytes, d_out, accumulate, "hrt_array_covariance",
+                      "hrt_array_covariance_scratch_bytes", &K.partial)))
+        return rc;
+    K.el[0] = K.n[0] ? arrays->rx_elements : NULL;
+    K.el[1] = K.n[1] ? arrays->tx_elements : NULL;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_covariance(&K, stream), "covariance kernels");
+    return HRT_OK;
+}
+
+static int cv_job_scratch(const ch_job *j, const hrt_problem *p, const hrt_shard *s, uint64_t *out)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_covariance_scratch_bytes(p, s, j->spec, &a, out);
+}
+
+static int cv_job_run(const ch_job *j, const hrt_problem *p, const hrt_shard *s, const void *d_ws, void *d_scratch,
+                      uint64_t scratch_bytes, void *d_out, int accumulate)
+{
+    const hrt_array_spec a = ac_job_arrays(j);
+    return hrt_array_covariance(p, s, d_ws, j->spec, &a, d_scratch, scratch_bytes, d_out, accumulate, NULL);
+}
+
+int hrt_compute_array_covariance(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                 const hrt_covariance_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                                 size_t nt, double f_a, float *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: NULL spec");
+    /* a side that is not asked for needs no elements: its count and pointer are not looked at */
+    if (!(spec->sides & HRT_COV_RX)) { nr = 0; rx_el = NULL; }
+    if (!(spec->sides & HRT_COV_TX)) { nt = 0; tx_el = NULL; }
+    if (nr > HRT_CV_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_rx_elements = %zu (1 .. %u)", nr, HRT_CV_MAX_ELEMENTS);
+    if (nt > HRT_CV_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "hrt_array_covariance: num_tx_elements = %zu (1 .. %u)", nt, HRT_CV_MAX_ELEMENTS);
+    /* (the element pointers stand in for the device ones: cov_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    uint32_t n[2];
+    int rc = cov_check(spec, &a, n);
+    if (rc) return rc;
+    if ((rc = cov_links_check(nrx, ntx, n))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = hrt_covariance_out_floats(nrx, ntx, &a, spec) * 4u;
+    job.scratch_bytes = cv_job_scratch;
+    job.run = cv_job_run;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_covariance", "hrt_compute_array_covariance");
 }
 
 /* ------------------------------------------------------------------ the K strongest paths per link (hrt_dominant_paths) */

@@ -1,7 +1,8 @@
 /* hrt_pathsum.h -- what the path-sum families (hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps) share: the view of the workspace of a finished
- * hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray, hrt_ktaps, hrt_karray_taps,
- * hrt_kpower, hrt_kdominant, hrt_kbeam and hrt_kbeam_taps; filled by csrc/host/channel.c), the grid of the two pair families (hrt_kgrid), and, for
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance) share: the view of the
+ * workspace of a finished hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray,
+ * hrt_ktaps, hrt_karray_taps, hrt_kpower, hrt_kdominant, hrt_kbeam, hrt_kbeam_taps and hrt_kcov; filled by
+ * csrc/host/channel.c), the grid of the two pair families (hrt_kgrid), and, for
  * the .hip files, the device helpers that read them: the field accessors, the chunk ranges and the batch fill, the
  * staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the array
  * families, the LoS entry, the two halves the complex reduce kernels share, and the reduce walk and the launch of the
@@ -30,7 +31,7 @@ typedef struct {
 } hrt_kview;
 
 /* The shard of the trace, for the families that need a record's departure direction: the member right after v in
- * hrt_karray, hrt_karray_taps, hrt_kpower, hrt_kdominant, hrt_kbeam and hrt_kbeam_taps.  20 bytes, 4-aligned (not padded to 24): the fields that follow it
+ * hrt_karray, hrt_karray_taps, hrt_kpower, hrt_kdominant, hrt_kbeam, hrt_kbeam_taps and hrt_kcov.  20 bytes, 4-aligned (not padded to 24): the fields that follow it
  * in those structs keep the kernel-argument offsets they had when these four were written out there (new offsets
  * alone moved hrt_array_partial_kernel's SGPR spills and its time: profiles/HISTORY.md). */
 typedef struct {

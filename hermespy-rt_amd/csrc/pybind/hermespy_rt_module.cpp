@@ -249,8 +249,8 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
     return d;
 }
 
-// What the eight path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
-// compute_power_profiles, compute_dominant_paths, compute_beam_channel, compute_beam_taps) share.  The counts and the four position / velocity arguments, checked ...
+// What the nine path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
+// compute_power_profiles, compute_dominant_paths, compute_beam_channel, compute_beam_taps, compute_array_covariance) share.  The counts and the four position / velocity arguments, checked ...
 struct endpoints {
     const Vec3 *rxp, *txp, *rxv, *txv;
     endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
@@ -587,6 +587,55 @@ py::dict compute_power_profiles_py(
     return d;
 }
 
+// compute_array_covariance: per-link spatial covariance matrices of an antenna array, formed on the device (extension;
+// see hrt_compute_array_covariance in hermespy_rt.h): a dict of complex64 views of one flat buffer -- rx (num_rx, num_tx,
+// 2, Nr, Nr), tx (num_rx, num_tx, 2, Nt, Nt) -- and the buffer itself.  A side whose elements are None is not asked for
+// (its view has N = 0).
+py::dict compute_array_covariance_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, py::object rx_elements, py::object tx_elements, bool los, bool scatter,
+    py::object array_frequency)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    const farr none(std::vector<size_t>{0, 3});
+    const farr re = rx_elements.is_none() ? none : rx_elements.cast<farr>();
+    const farr te = tx_elements.is_none() ? none : tx_elements.cast<farr>();
+    const array_elements a(re, te);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_covariance_spec spec{};
+    spec.parts = parts_word(los, scatter);
+    spec.sides = (rx_elements.is_none() ? 0u : HRT_COV_RX) | (tx_elements.is_none() ? 0u : HRT_COV_TX);
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t links = (size_t)num_rx * num_tx, nr = a.nr, nt = a.nt;
+    const bool fits = links <= 65535u && nr <= 256u && nt <= 256u && links * 2u * (nr * nr + nt * nt) <= (1ull << 26);
+    const size_t n_rx = links * 2u * nr * nr, n_tx = links * 2u * nt * nt;
+    py::array_t<std::complex<float>> buf(fits ? n_rx + n_tx : (size_t)1);
+    std::complex<float> *dst = buf.mutable_data();
+    run_pathsum("compute_array_covariance", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_array_covariance(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                            num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa,
+                                            reinterpret_cast<float *>(dst), nullptr);
+    });
+    auto view = [&](size_t n, size_t off) {
+        const std::vector<size_t> shape{(size_t)num_rx, (size_t)num_tx, 2, n, n};
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(std::complex<float>);
+        for (size_t k = shape.size(); k-- > 0;) {
+            strides[k] = st;
+            st *= (py::ssize_t)shape[k];
+        }
+        return py::array_t<std::complex<float>>(shape, strides, dst + off, buf);
+    };
+    py::dict d;
+    d["rx"] = view(nr, 0);
+    d["tx"] = view(nt, n_rx);
+    d["buffer"] = buf;
+    return d;
+}
+
 // compute_dominant_paths: the max_paths strongest paths of every link, selected on the device (extension; see
 // hrt_compute_dominant_paths in hermespy_rt.h): a dict of views of one buffer -- kept, eligible (num_rx, num_tx);
 // power, path, bounce, tri, tau, freq_shift (num_rx, num_tx, K); a_te, a_tm complex64 (num_rx, num_tx, K); u_rx, u_tx
@@ -732,6 +781,15 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("tau0"), py::arg("dtau"), py::arg("num_delay_bins"), py::arg("num_zenith_bins") = 0,
           py::arg("num_azimuth_bins") = 0, py::arg("los") = true, py::arg("scatter") = true);
+    m.def("compute_array_covariance", &compute_array_covariance_py,
+          "Per-link spatial covariance matrices of an antenna array, formed on the device: a dict of complex64 arrays "
+          "(rx (num_rx, num_tx, 2, Nr, Nr), tx (num_rx, num_tx, 2, Nt, Nt), buffer); a side whose elements are None is "
+          "not formed",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("rx_elements") = py::none(), py::arg("tx_elements") = py::none(), py::arg("los") = true,
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none());
     m.def("compute_dominant_paths", &compute_dominant_paths_py,
           "The max_paths strongest paths of every link, selected on the device: a dict of arrays (kept, eligible, "
           "power, path, bounce, tri, a_te, a_tm, tau, freq_shift, u_rx, u_tx, buffer)",

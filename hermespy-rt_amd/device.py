@@ -400,7 +400,8 @@ class Tracer:
 
     def _pathsum(self, name, spec, shape, cache, out, accumulate, arrays=None, dtype=None, value_error=True):
         """One call of a path-sum family (`name`: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
-        hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel or hrt_beam_taps): the scratch query, the buffers (scratch cache
+        hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps or hrt_array_covariance): the scratch
+        query, the buffers (scratch cache
         `cache`) and the entry on the current stream.  `arrays`: what _elements prepared for the array families, the
         specs that follow `spec` and last the device tensor they point into.  A spec the library refuses raises
         ValueError, or HrtError where value_error is False."""
@@ -589,6 +590,30 @@ class Tracer:
         out = self._pathsum("hrt_power_profiles", spec, shape, "_pw_scratch", out, accumulate,
                             dtype=self.torch.float64)
         return abi.power_views(out, self.nrx, self.ntx, spec)
+
+    def array_covariance(self, rx_elements=None, tx_elements=None, los=True, scatter=True, array_frequency=None,
+                         out=None, accumulate=False):
+        """Per-link spatial covariance matrices of an antenna array of the last trace, formed on the device
+        (hrt_array_covariance; include/hermespy_rt.h hrt_compute_array_covariance):
+
+            rx  [nrx, ntx, 2, Nr, Nr]   R_rx[i, i'] = sum_p |a_p^pol|^2 s_i(u_p^rx) conj(s_i'(u_p^rx))
+            tx  [nrx, ntx, 2, Nt, Nt]   R_tx[j, j'] = sum_p |a_p^pol|^2 t_j(u_p^tx) conj(t_j'(u_p^tx))
+            s_i(u) = exp(j 2 pi f_a r_i . u / c),  t_j(u) = exp(j 2 pi f_a q_j . u / c)
+
+        over the terms of power_profiles() with the elements, f_a and steering of array_channel(): with independent
+        uniform path phases R_rx = E[H H^H] / Nt and R_tx[j, j'] = E[sum_i H[i, j] conj(H[i, j'])] / Nr.  A side whose
+        elements are None is not formed (its view has N = 0).  Exactly Hermitian, with a real diagonal.  Returns a
+        dict of complex64 views of one flat device tensor, itself under "buffer", enqueued on the current stream; `out`
+        (such a flat tensor) is written in place, or added to with accumulate=True.  hermespy_rt_amd.covariance has the
+        host-side reference and what is built on the matrices.  Invalid arguments raise ValueError."""
+        none = np.zeros((0, 3), np.float32)
+        nr, nt, upload = self._elements(none if rx_elements is None else rx_elements,
+                                        none if tx_elements is None else tx_elements, array_frequency)
+        spec = abi.covariance_spec(rx_elements is not None, tx_elements is not None, los, scatter)
+        self.counts()
+        shape = (abi.covariance_out_floats(self.nrx, self.ntx, (nr, nt), spec) // 2,)
+        out = self._pathsum("hrt_array_covariance", spec, shape, "_cv_scratch", out, accumulate, upload())
+        return abi.covariance_views(out, self.nrx, self.ntx, nr, nt)
 
     def dominant_paths(self, max_paths, los=True, scatter=True, out=None, accumulate=False):
         """The max_paths strongest paths of every link of the last trace, selected on the device (hrt_dominant_paths;

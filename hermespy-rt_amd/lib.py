@@ -36,6 +36,8 @@ EXPORTED = (
     "hrt_dominant_out_bytes", "hrt_dominant_paths_scratch_bytes", "hrt_dominant_paths", "hrt_compute_dominant_paths",
     "hrt_beam_channel_scratch_bytes", "hrt_beam_channel", "hrt_compute_beam_channel",
     "hrt_beam_taps_scratch_bytes", "hrt_beam_taps", "hrt_compute_beam_taps",
+    "hrt_covariance_out_floats", "hrt_array_covariance_scratch_bytes", "hrt_array_covariance",
+    "hrt_compute_array_covariance",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -261,6 +263,18 @@ def load():
                                              C.c_size_t, C.c_size_t, C.c_size_t, pwp, C.POINTER(C.c_double),
                                              C.POINTER(Stats)]
     L.hrt_compute_power_profiles.restype = C.c_int
+    # spatial covariance matrices of an antenna array (hrt_covariance_spec: abi.CovarianceSpec, and hrt_array_spec)
+    cvp = C.POINTER(abi.CovarianceSpec)
+    L.hrt_covariance_out_floats.argtypes = [C.c_size_t, C.c_size_t, app, cvp]
+    L.hrt_covariance_out_floats.restype = u64
+    L.hrt_array_covariance_scratch_bytes.argtypes = [vp, C.POINTER(Shard), cvp, app, C.POINTER(u64)]
+    L.hrt_array_covariance_scratch_bytes.restype = C.c_int
+    L.hrt_array_covariance.argtypes = [vp, C.POINTER(Shard), vp, cvp, app, vp, u64, vp, C.c_int, vp]
+    L.hrt_array_covariance.restype = C.c_int
+    L.hrt_compute_array_covariance.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                               C.c_size_t, C.c_size_t, cvp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                               f32p, C.POINTER(Stats)]
+    L.hrt_compute_array_covariance.restype = C.c_int
     # the K strongest paths per link (hrt_dominant_spec: abi.DominantSpec)
     dmp = C.POINTER(abi.DominantSpec)
     L.hrt_dominant_out_bytes.argtypes = [C.c_size_t, C.c_size_t, dmp]

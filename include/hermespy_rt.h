@@ -366,6 +366,46 @@ int hrt_compute_power_profiles(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
                                size_t num_rays, size_t num_bounces, const hrt_power_spec *spec,
                                double *out /* hrt_power_out_doubles, layout above */, hrt_stats *stats);
 
+/* Per-link spatial covariance matrices of an antenna array, formed on the device (include/hrt_device.h:
+ * hrt_array_covariance): the second-order statistics of hrt_compute_array_channel's H under independent uniform path
+ * phases.  For every link, polarisation pol (0 = TE, 1 = TM) and element pair of ONE side:
+ *     R_rx[rx][tx][pol][i][i'] = sum_p |a_p^pol|^2 s_i(u_p^rx) conj(s_i'(u_p^rx)),   s_i(u) = exp(j 2 pi f_a r_i . u / c)
+ *     R_tx[rx][tx][pol][j][j'] = sum_p |a_p^pol|^2 t_j(u_p^tx) conj(t_j'(u_p^tx)),   t_j(u) = exp(j 2 pi f_a q_j . u / c)
+ * so that R_rx = E[H H^H] / Nt and R_tx[j][j'] = E[sum_i H[i][j] conj(H[i][j'])] / Nr.
+ *   Terms: those of hrt_compute_power_profiles (the same `parts`): the LoS entry, added by shard rank 0 only where
+ *     the LoS is not blocked (coincident a = 1, u_rx = (1, 0, 0), u_tx = (-1, 0, 0); clear a = HRT_LOS_A,
+ *     u_tx = HRT_LOS_DIR, u_rx = -u_tx), and every unblocked scatter record of every bounce; blocked records add nothing.
+ *   Directions: u_rx = directions_rx of the record, u_tx = the launch direction of the record's global path (as
+ *     hrt_compute_array_channel).
+ *   Weight: p = |a^pol|^2, the exact FP64 value of the float amplitudes rounded once to float.
+ *   Steering: exactly the array families' rule: the phase in revolutions is (f_a / c) (r . u) in FP64 from float
+ *     operands, reduced to its fraction and evaluated in float (sincospi), once per (term, element) and never per
+ *     element pair; the products and sums are float (one f32 MFMA per record, tile and polarisation).
+ *   Hermitian to the bit: only the upper triangle (i' >= i) is summed; R[i'][i] is written as its conjugate and the
+ *     diagonal with imaginary part exactly 0.
+ *   Additive: shards and batches add up to the whole; record chunks are added in a fixed order without atomics, so two
+ *     calls with the same inputs give the same bits.
+ * Elements and f_a are hrt_compute_array_channel's; `sides` selects R_rx (HRT_COV_RX), R_tx (HRT_COV_TX) or both.  A
+ * side that is not asked for needs no elements (its count and pointer are ignored) and writes nothing.
+ * out: one flat complex buffer, re/im interleaved floats (numpy complex64): R_rx [num_rx][num_tx][2][Nr][Nr], then
+ * R_tx [num_rx][num_tx][2][Nt][Nt]; an absent side has size 0.  hrt_covariance_out_floats (include/hrt_device.h, beside
+ * hrt_array_spec) gives its size in floats.  hrt_compute_array_covariance traces and batches like hrt_compute_channel
+ * (one device, one download at the end).  HRT_E_INVALID, before the device is touched: NULL spec; parts 0 or with
+ * unknown bits; sides 0 or with unknown bits; a requested side with 0 or more than 256 elements or a NULL element
+ * pointer; an offset or f_a not finite; f_a <= 0; num_rx * num_tx > 65535; num_rx * num_tx * 2 * (Nr^2 + Nt^2) > 2^26. */
+#define HRT_COV_RX 1u
+#define HRT_COV_TX 2u
+typedef struct {
+    uint32_t parts;                             /* HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER */
+    uint32_t sides;                             /* HRT_COV_RX | HRT_COV_TX */
+} hrt_covariance_spec;
+int hrt_compute_array_covariance(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                 size_t num_rays, size_t num_bounces, const hrt_covariance_spec *spec,
+                                 const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                                 size_t num_tx_elements, double array_frequency_hz,
+                                 float *out /* complex interleaved, layout above */, hrt_stats *stats);
+
 /* The K strongest paths of every link, selected on the device (include/hrt_device.h: hrt_dominant_paths): the short
  * list of (gain, delay, Doppler, arrival and departure direction) a link-level simulator builds a sparse channel
  * from, instead of the full path list.  The ELIGIBLE terms of a link are exactly the terms hrt_channel sums (the same

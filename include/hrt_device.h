@@ -409,6 +409,27 @@ int hrt_power_profiles_scratch_bytes(const hrt_problem *p, const hrt_shard *s, c
 int hrt_power_profiles(const hrt_problem *p, const hrt_shard *s, const void *d_workspace, const hrt_power_spec *spec,
                        void *d_scratch, uint64_t scratch_bytes, double *d_out, int accumulate, void *stream);
 
+/* ---- spatial covariance matrices of an antenna array (csrc/host/channel.c, csrc/hrt_covariance.hip) ----
+ * R_rx and R_tx as hermespy_rt.h defines them (hrt_covariance_spec, hrt_compute_array_covariance),
+ * hrt_covariance_out_floats floats at d_out (0 for a NULL argument; the element counts of the sides asked for are
+ * read from `arrays`), formed from the workspace of a finished hrt_trace (its counts read on the device: no host
+ * synchronisation), asynchronous on `stream`, with the guarantees of hrt_power_profiles: accumulate = 0 overwrites
+ * d_out, 1 adds to it; only shard rank 0 adds the LoS term, so the outputs of the shards of one launch set sum to the
+ * whole result; partial sums go to the caller's scratch (hrt_array_covariance_scratch_bytes) and are reduced in a
+ * fixed order, no floating-point atomics, so two calls with the same inputs give the same bits; the output is
+ * undefined if the trace's error word is set.  The element offsets are DEVICE pointers, as in hrt_array_channel (their
+ * finiteness is the caller's to ensure; the host entries check it); those of a side that is not asked for are not read
+ * and may be NULL.  HRT_E_INVALID, before the device is touched: NULL spec or arrays; parts or sides 0 or with unknown
+ * bits; a requested side with 0 or more than 256 elements or a NULL element pointer; f_a not finite or <= 0;
+ * num_rx * num_tx > 65535; num_rx * num_tx * 2 * (Nr^2 + Nt^2) > 2^26; scratch too small. */
+uint64_t hrt_covariance_out_floats(size_t num_rx, size_t num_tx, const hrt_array_spec *arrays,
+                                   const hrt_covariance_spec *spec);
+int hrt_array_covariance_scratch_bytes(const hrt_problem *p, const hrt_shard *s, const hrt_covariance_spec *spec,
+                                       const hrt_array_spec *arrays, uint64_t *out);
+int hrt_array_covariance(const hrt_problem *p, const hrt_shard *s, const void *d_workspace,
+                         const hrt_covariance_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
+                         uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
+
 /* ---- the K strongest paths per link from the traced paths (csrc/host/channel.c, csrc/hrt_dominant.hip) ----
  * header and records as hermespy_rt.h defines them (hrt_dominant_spec, hrt_dominant_path,
  * hrt_compute_dominant_paths), hrt_dominant_out_bytes bytes at d_out, selected from the workspace of a finished
