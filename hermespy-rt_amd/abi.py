@@ -314,7 +314,8 @@ def channel_spec(f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True, scatt
 def _run_pathsum(lib, name, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
                  out_shape, extra, stats, dtype=np.complex64):
     """One of the nine path-sum drop-in entries (`name`: hrt_compute_channel, _array_channel, _taps, _array_taps,
-    _power_profiles, _dominant_paths, _beam_channel, _beam_taps or _array_covariance) through ctypes, into a numpy array
+    _power_profiles, _dominant_paths, _beam_channel, _beam_taps or _array_covariance) or hrt_compute_received_signal
+    through ctypes, into a numpy array
     of `dtype` and shape (nrx, ntx) + out_shape (a flat buffer of out_shape doubles for float64, floats for float32 or
     bytes for uint8; out_shape None: a placeholder the library
     refuses to write); `extra` are the arguments that follow the spec.  Raises RuntimeError("<name> failed (<rc>): ...") on an error code."""
@@ -475,6 +476,55 @@ def run_compute_beam_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz
     fits = 0 < br * bt * ntm * nl <= (1 << 24) and ntm * nl <= (1 << 20)
     return _run_pathsum(lib, "hrt_compute_beam_taps", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
                         num_bounces, spec, (br, bt, 2, ntm, nl) if fits else None, extra, stats)
+
+
+class PropagateSpec(C.Structure):
+    """include/hermespy_rt.h hrt_propagate_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_taps", C.c_uint32), ("l_min", C.c_int32),
+                ("samples_per_block", C.c_uint32), ("num_samples", C.c_uint64), ("num_out", C.c_uint64)]
+
+
+def propagate_spec(num_rx, num_tx, nr, nt, num_times, num_taps, l_min, samples_per_block, num_samples, num_out):
+    return PropagateSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_taps), int(l_min),
+                         int(samples_per_block), int(num_samples), int(num_out))
+
+
+def run_propagate(lib, device, spec, d_taps, d_signal, d_out, accumulate=0, stream=None):
+    """hrt_propagate through ctypes on device pointers (integers or None).  Raises RuntimeError("hrt_propagate failed
+    (<rc>): ...") on an error code."""
+    rc = lib.hrt_propagate(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_taps),
+                           C.c_void_p(d_signal), C.c_void_p(d_out), int(accumulate), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_propagate failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_received_signal(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                                rx_elements, tx_elements, signal, samples_per_block=None, num_out=None,
+                                array_frequency=None, stats=None):
+    """hrt_compute_received_signal through ctypes -> complex64 [nrx, Nr, 2, num_out]: `signal` complex [ntx, Nt, N]
+    (or [ntx, N] with Nt = 1; None: a NULL pointer), samples_per_block None: one block of num_out samples; num_out
+    defaults to N + L - 1 + max(l_min, 0); array_frequency to the carrier.  Raises
+    RuntimeError("hrt_compute_received_signal failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx = np.asarray(rx_pos).size // 3
+    x, n = None, 0
+    if signal is not None:
+        x = np.ascontiguousarray(signal, np.complex64)
+        n = x.shape[-1] if x.ndim else 0
+    if num_out is None:
+        num_out = n + int(spec.num_taps) - 1 + max(int(spec.l_min), 0)
+    s = max(int(num_out), 1) if samples_per_block is None else int(samples_per_block)
+    extra += (C.c_uint32(s), x.ctypes.data_as(c_float_p) if x is not None else None, C.c_uint64(n),
+              C.c_uint64(int(num_out)))
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    fits = 0 < nr <= 1024 and 0 < int(num_out) <= 1 << 31
+    out = _run_pathsum(lib, "hrt_compute_received_signal", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (nrx * nr * 2 * int(num_out) * 2,) if fits else None, extra,
+                       stats, np.float32)
+    if not fits:
+        raise RuntimeError("hrt_compute_received_signal accepted a call beyond its limits")
+    return out.view(np.complex64).reshape(nrx, nr, 2, int(num_out))
 
 
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)

@@ -1,7 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance; include/hermespy_rt.h:
- * hrt_compute_array_covariance, hrt_compute_channel,
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate;
+ * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
  *
@@ -32,6 +32,7 @@
 #include "../hrt_dominant.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_power.h"
+#include "../hrt_propagate.h"
 #include "../hrt_taps.h"
 
 /* ------------------------------------------------------------------ what the path-sum families share (hrt_pathsum.h) */
@@ -190,7 +191,7 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
-/* One drop-in call: what the nine hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
+/* One drop-in call: what the ten hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
 typedef struct ch_job ch_job;
@@ -211,6 +212,10 @@ struct ch_job {
     uint32_t nbr, nbt; /* the beam calls' beam counts (hrt_compute_beam_channel, hrt_compute_beam_taps) */
     /* optional: runs on the downloaded output while the problem still exists (NULL: nothing to do) */
     int (*finish)(const ch_job *j, const hrt_problem *p, void *out);
+    /* optional: replaces the download of the accumulated output at d_out (out_bytes) after the last batch: what
+     * reaches the host `out` is its business (hrt_compute_received_signal: the propagated signal, not the taps) */
+    int (*deliver)(const ch_job *j, int device, const void *d_out, void *out);
+    const void *aux;   /* what `deliver` needs (hrt_compute_received_signal: its pr_job) */
 };
 
 static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel, const Vec3 *tx_vel,
@@ -267,7 +272,9 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
     }
     {
         const double t0 = hrt_now_s();
-        if ((rc = hrt_device_download(device, out, d_out, out_bytes))) goto done;
+        if (job->deliver) {
+            if ((rc = job->deliver(job, device, d_out, out))) goto done;
+        } else if ((rc = hrt_device_download(device, out, d_out, out_bytes))) goto done;
         if (job->finish && (rc = job->finish(job, prob, out))) goto done;
         st.t_readback_s = hrt_now_s() - t0;
     }
@@ -749,6 +756,129 @@ int hrt_compute_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos,
     job.run = at_job_run;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_array_taps", "hrt_compute_array_taps");
+}
+
+/* ------------------------------------------------------------------ received signals (hrt_propagate) */
+
+/* the checks of a propagation call (`who`); device pointers are not read */
+static int propagate_check(const hrt_propagate_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->nr == 0 || sp->nt == 0 || sp->num_times == 0 || sp->num_taps == 0 ||
+        sp->samples_per_block == 0 || sp->num_samples == 0 || sp->num_out == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, nr, nt, num_times, num_taps, samples_per_block, num_samples "
+                        "and num_out must be > 0", who);
+    if (sp->nr > HRT_PG_MAX_ELEMENTS || sp->nt > HRT_PG_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u and nt = %u (1 .. %u each)", who, sp->nr, sp->nt,
+                        HRT_PG_MAX_ELEMENTS);
+    const uint64_t pts = (uint64_t)sp->nr * sp->nt * sp->num_times;   /* <= 2^52 */
+    if (pts > HRT_PG_MAX_POINTS || pts * sp->num_taps > HRT_PG_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr * nt * num_times * num_taps > 2^24", who);
+    const int64_t lo = sp->l_min, hi = (int64_t)sp->l_min + sp->num_taps;
+    if (lo < -HRT_PG_MAX_TAP || lo > HRT_PG_MAX_TAP || hi < -HRT_PG_MAX_TAP || hi > HRT_PG_MAX_TAP)
+        return hrt_fail(HRT_E_INVALID, "%s: tap indices l_min = %lld .. %lld outside +-2^24", who, (long long)lo,
+                        (long long)hi);
+    if (sp->num_samples > HRT_PG_MAX_SAMPLES || sp->num_out > HRT_PG_MAX_SAMPLES)
+        return hrt_fail(HRT_E_INVALID, "%s: num_samples = %llu and num_out = %llu (at most 2^31 each)", who,
+                        (unsigned long long)sp->num_samples, (unsigned long long)sp->num_out);
+    return HRT_OK;
+}
+
+uint64_t hrt_propagate_out_floats(const hrt_propagate_spec *spec)
+{
+    if (!spec) return 0;
+    return (uint64_t)spec->num_rx * spec->nr * 2u * spec->num_out * 2u;
+}
+
+int hrt_propagate(int device, const hrt_propagate_spec *spec, const void *d_taps, const void *d_signal, void *d_out,
+                  int accumulate, void *stream)
+{
+    int rc = propagate_check(spec, "hrt_propagate");
+    if (rc) return rc;
+    if (!d_taps || !d_signal || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_propagate: NULL device pointer");
+    if (accumulate != 0 && accumulate != 1)
+        return hrt_fail(HRT_E_INVALID, "hrt_propagate: accumulate = %d (0 or 1)", accumulate);
+    if ((uint64_t)spec->num_rx * spec->nr * 2u > UINT32_MAX || (uint64_t)spec->num_tx * spec->nt > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_propagate: more than 2^32 rows or TX ports");
+    hrt_kpropagate K;
+    memset(&K, 0, sizeof K);
+    K.R = spec->num_rx * spec->nr * 2u;
+    K.P = spec->num_tx * spec->nt;
+    K.ntx = spec->num_tx; K.nr = spec->nr; K.nt = spec->nt;
+    K.M = spec->num_times; K.L = spec->num_taps; K.S = spec->samples_per_block;
+    K.l_min = spec->l_min;
+    K.accumulate = (uint32_t)accumulate;
+    K.N = spec->num_samples; K.N_out = spec->num_out;
+    K.h = (const float *)d_taps; K.x = (const float *)d_signal; K.out = (float *)d_out;
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_propagate(&K, hrt_propagate_form(K.M, K.S), stream), "propagation kernel");
+    return HRT_OK;
+}
+
+/* what hrt_compute_received_signal's `deliver` needs */
+typedef struct {
+    hrt_propagate_spec spec;
+    const float *x;
+} pr_job;
+
+/* after the last batch: the taps stay at d_taps; x goes up, the propagation runs once, only y comes down */
+static int pr_job_deliver(const ch_job *j, int device, const void *d_taps, void *out)
+{
+    const pr_job *pj = (const pr_job *)j->aux;
+    const uint64_t x_bytes = (uint64_t)pj->spec.num_tx * pj->spec.nt * pj->spec.num_samples * 8u;
+    const uint64_t y_bytes = hrt_propagate_out_floats(&pj->spec) * 4u;
+    void *d_x = NULL, *d_y = NULL;
+    int rc = hrt_device_malloc(device, &d_x, x_bytes);
+    if (!rc) rc = hrt_device_malloc(device, &d_y, y_bytes);
+    if (!rc) rc = hrt_device_upload(device, d_x, pj->x, x_bytes);
+    if (!rc) rc = hrt_propagate(device, &pj->spec, d_taps, d_x, d_y, 0, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_y, y_bytes);
+    if (d_y) hrt_device_free(device, d_y);
+    if (d_x) hrt_device_free(device, d_x);
+    return rc;
+}
+
+int hrt_compute_received_signal(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                const hrt_taps_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt,
+                                double f_a, uint32_t samples_per_block, const float *x, uint64_t num_samples,
+                                uint64_t num_out, float *y, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_taps");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: at_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = at_check(spec, &a))) return rc;
+    if (!x || !y) return hrt_fail(HRT_E_INVALID, "hrt_compute_received_signal: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_received_signal: num_rx or num_tx > 2^32");
+    pr_job pj;
+    memset(&pj, 0, sizeof pj);
+    pj.spec.num_rx = (uint32_t)nrx; pj.spec.num_tx = (uint32_t)ntx;
+    pj.spec.nr = (uint32_t)nr; pj.spec.nt = (uint32_t)nt;
+    pj.spec.num_times = spec->num_times; pj.spec.num_taps = spec->num_taps;
+    pj.spec.l_min = spec->l_min;
+    pj.spec.samples_per_block = samples_per_block;
+    pj.spec.num_samples = num_samples; pj.spec.num_out = num_out;
+    pj.x = x;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_taps) */
+    if (nrx && ntx && (rc = propagate_check(&pj.spec, "hrt_compute_received_signal"))) return rc;
+    if (nrx && ntx && (uint64_t)spec->num_times != (num_out + samples_per_block - 1u) / samples_per_block)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_received_signal: num_times = %u, but ceil(num_out / "
+                        "samples_per_block) = %llu", spec->num_times,
+                        (unsigned long long)((num_out + samples_per_block - 1u) / samples_per_block));
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_taps * 8u;
+    job.scratch_bytes = at_job_scratch;
+    job.run = at_job_run;
+    job.deliver = pr_job_deliver;
+    job.aux = &pj;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      y, stats, t_begin, "hrt_array_taps", "hrt_compute_received_signal");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

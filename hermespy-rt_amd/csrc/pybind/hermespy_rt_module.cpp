@@ -250,7 +250,7 @@ py::dict compute_paths_list_py(const std::string &mesh_filepath, farr rx_positio
 }
 
 // What the nine path-sum entries (compute_channel, compute_array_channel, compute_taps, compute_array_taps,
-// compute_power_profiles, compute_dominant_paths, compute_beam_channel, compute_beam_taps, compute_array_covariance) share.  The counts and the four position / velocity arguments, checked ...
+// compute_power_profiles, compute_dominant_paths, compute_beam_channel, compute_beam_taps, compute_array_covariance) and compute_received_signal share.  The counts and the four position / velocity arguments, checked ...
 struct endpoints {
     const Vec3 *rxp, *txp, *rxv, *txv;
     endpoints(const farr &rx_positions, const farr &tx_positions, const farr &rx_velocities,
@@ -488,6 +488,67 @@ py::array_t<std::complex<float>> compute_array_taps_py(
     run_pathsum("compute_array_taps", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_array_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                       num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
+    });
+    return out;
+}
+
+// compute_received_signal: the samples the receivers see when the transmitters send `signal` through the traced
+// channel (extension; see hrt_compute_received_signal in hermespy_rt.h): complex64 (num_rx, Nr, 2, num_out).  signal is
+// complex (num_tx, Nt, N), or (num_tx, N) with Nt = 1.  The channel is block-wise time-variant: M = ceil(num_out /
+// samples_per_block) blocks formed at their centres, t0 = t_start + (S - 1) / (2 f_s), dt = S / f_s;
+// samples_per_block None is the time-invariant channel at t_start.  num_out defaults to N + num_taps - 1 + max(l_min, 0).
+// The taps stay on the device; only the signal comes back.
+py::array_t<std::complex<float>> compute_received_signal_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
+    py::array_t<std::complex<float>, py::array::c_style | py::array::forcecast> signal, long l_min,
+    py::object samples_per_block, double t_start, py::object center_frequency, py::object num_out, bool los,
+    bool scatter, py::object array_frequency)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_taps > 0xffffffffUL) throw std::invalid_argument("num_taps must fit 32 bits");
+    if (l_min < -(1L << 30) || l_min > (1L << 30))
+        throw py::value_error("hermespy_rt.compute_received_signal: tap indices l_min outside +-2^24");
+    const array_elements a(rx_elements, tx_elements);
+    if (signal.ndim() != 2 && signal.ndim() != 3)
+        throw std::invalid_argument("signal must have shape (num_tx, Nt, N) or (num_tx, N)");
+    const size_t n = (size_t)signal.shape(signal.ndim() - 1);
+    const size_t ports = signal.ndim() == 3 ? (size_t)signal.shape(0) * (size_t)signal.shape(1) : (size_t)signal.shape(0);
+    if (ports != (size_t)num_tx * a.nt || (signal.ndim() == 3 && (size_t)signal.shape(0) != num_tx))
+        throw std::invalid_argument("signal must have num_tx x Nt TX ports");
+    const uint64_t n_out = num_out.is_none() ? (uint64_t)n + num_taps - 1u + (uint64_t)(l_min > 0 ? l_min : 0)
+                                             : num_out.cast<uint64_t>();
+    uint64_t s = n_out ? n_out : 1u, m = 1;
+    double t0 = t_start, dt = 0.0;
+    if (!samples_per_block.is_none()) {
+        s = samples_per_block.cast<uint64_t>();
+        if (s > 0xffffffffULL) throw std::invalid_argument("samples_per_block must fit 32 bits");
+        m = s ? (n_out + s - 1u) / s : 1u;
+        if (m < 1) m = 1;
+        t0 = t_start + ((double)s - 1.0) / (2.0 * sampling_rate);
+        dt = (double)s / sampling_rate;
+    }
+    if (s > 0xffffffffULL) s = 0xffffffffULL;   // (one block of more than 2^32 samples: num_out is refused)
+    if (m > 0xffffffffULL) throw py::value_error("hermespy_rt.compute_received_signal: more than 2^32 blocks");
+    const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_taps_spec spec{};
+    spec.fs_hz = sampling_rate; spec.fc_hz = fc; spec.t0_s = t0; spec.dt_s = dt;
+    spec.l_min = (int32_t)l_min; spec.num_taps = (uint32_t)num_taps; spec.num_times = (uint32_t)m;
+    spec.parts = parts_word(los, scatter);
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  An output
+    // beyond the limits would be refused, so only one within them is allocated.)
+    const bool fits = a.nr >= 1 && a.nr <= 1024 && n_out >= 1 && n_out <= (1ull << 31);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, a.nr, (size_t)2, (size_t)n_out}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const float *x = reinterpret_cast<const float *>(signal.data());
+    run_pathsum("compute_received_signal", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_received_signal(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                           num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, (uint32_t)s, x,
+                                           (uint64_t)n, n_out, dst, nullptr);
     });
     return out;
 }
@@ -761,6 +822,16 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("l_min") = 0, py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
           py::arg("array_frequency") = py::none());
+    m.def("compute_received_signal", &compute_received_signal_py,
+          "The samples the receivers see when the transmitters send `signal` (num_tx, Nt, N) through the traced "
+          "channel, formed on the device: complex64 (num_rx, Nr, 2, num_out)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("signal"), py::arg("l_min") = 0, py::arg("samples_per_block") = py::none(),
+          py::arg("t_start") = 0.0, py::arg("center_frequency") = py::none(), py::arg("num_out") = py::none(),
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none());
     m.def("compute_beam_taps", &compute_beam_taps_py,
           "Beamformed (codebook) sampled channel impulse response of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_taps); rx_weights (Br, Nr) is applied conjugated, tx_weights "

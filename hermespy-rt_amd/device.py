@@ -571,6 +571,108 @@ class Tracer:
         shape = (self.nrx, self.ntx, wr.shape[0], wt.shape[0], 2, int(num_times), int(num_taps))
         return self._pathsum("hrt_beam_taps", spec, shape, "_bt_scratch", out, accumulate, upload((wr, wt)))
 
+    def apply_taps(self, taps, signal, l_min=0, samples_per_block=None, num_out=None, out=None, accumulate=False):
+        """Received signals: taps applied to baseband waveforms on the device (hrt_propagate; include/hermespy_rt.h
+        hrt_propagate_spec):
+
+            y[rx, i, pol, n] = sum_tx sum_j sum_l taps[rx, tx, i, j, pol, m(n), l] signal[tx, j, n - l_min - l]
+            m(n) = min(n // samples_per_block, M - 1),   signal[.., k] = 0 outside 0 <= k < N
+
+        taps: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, M, L] (array_taps(), or beam_taps() with beams for
+        elements) or [nrx, ntx, 2, M, L] (taps()); signal: complex64 [ntx, Nt, N] or [ntx, N] on the same device.
+        l_min is the l_min the taps were formed with.  samples_per_block=None requires M = 1 (time-invariant);
+        num_out defaults to N + L - 1 + max(l_min, 0).  It reads only the two tensors (no trace is needed).  Returns
+        a complex64 tensor [nrx, Nr, 2, num_out], enqueued on the current stream; `out` is written in place, or added
+        to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        for name, t in (("taps", taps), ("signal", signal)):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.device == self.device and t.dtype == torch.complex64):
+                raise ValueError("%s must be a complex64 tensor on %s" % (name, self.device))
+        if taps.dim() == 5:
+            taps = taps[:, :, None, None]
+        if signal.dim() == 2:
+            signal = signal[:, None]
+        if taps.dim() != 7 or signal.dim() != 3 or taps.shape[4] != 2:
+            raise ValueError("taps [nrx, ntx, Nr, Nt, 2, M, L] (or [nrx, ntx, 2, M, L]) and signal [ntx, Nt, N] (or "
+                             "[ntx, N]) expected, got %s and %s" % (tuple(taps.shape), tuple(signal.shape)))
+        nrx, ntx, nr, nt, _, m, num_taps = (int(v) for v in taps.shape)
+        if (int(signal.shape[0]), int(signal.shape[1])) != (ntx, nt):
+            raise ValueError("signal has %d x %d TX ports, the taps %d x %d"
+                             % (int(signal.shape[0]), int(signal.shape[1]), ntx, nt))
+        n = int(signal.shape[2])
+        if samples_per_block is None:
+            if m != 1:
+                raise ValueError("samples_per_block=None requires taps of one time sample, got %d" % m)
+            s = 1
+        else:
+            s = int(samples_per_block)
+        if num_out is None:
+            num_out = n + num_taps - 1 + max(int(l_min), 0)
+        num_out = int(num_out)
+        if not (0 <= s < 1 << 32 and 0 <= num_out < 1 << 62 and -(1 << 31) <= int(l_min) < 1 << 31):
+            raise ValueError("samples_per_block, num_out or l_min out of range")
+        spec = abi.propagate_spec(nrx, ntx, nr, nt, m, num_taps, l_min, s, n, num_out)
+        shape = (nrx, nr, 2, num_out)
+        taps, signal = taps.contiguous(), signal.contiguous()
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                # (an empty output is refused by the library, below: a placeholder it does not write)
+                out = torch.empty(shape if nrx * nr * num_out > 0 and num_out <= 1 << 31 else (1,),
+                                  dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_propagate(self.device.index, C.byref(spec), C.c_void_p(taps.data_ptr()),
+                                  C.c_void_p(signal.data_ptr()), C.c_void_p(out.data_ptr()), 1 if accumulate else 0,
+                                  C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_propagate: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_propagate")
+        taps.record_stream(stream)     # (the kernel reads them after this call returns)
+        signal.record_stream(stream)
+        return out
+
+    def propagate(self, signal, fs, num_taps, l_min=0, samples_per_block=None, t_start=0.0, rx_elements=None,
+                  tx_elements=None, rx_weights=None, tx_weights=None, fc=None, array_frequency=None, num_out=None,
+                  los=True, scatter=True, out=None, accumulate=False):
+        """The samples the receivers see when the transmitters send `signal` (complex64 [ntx, Nt, N] or [ntx, N] on the
+        device, at the rate fs) through the channel of the last trace: what a link-level simulator's
+        Channel.propagate(signal) returns, without leaving the device.  It is, bit for bit, apply_taps() of
+
+            beam_taps()   where rx_weights and tx_weights are given (with rx_elements, tx_elements),
+            array_taps()  where rx_elements and tx_elements are given,
+            taps()        otherwise,
+
+        with num_times = M = ceil(num_out / samples_per_block) blocks formed at their centres, t0 = t_start + (S - 1) /
+        (2 fs), dt = S / fs (hermespy_rt_amd.propagate.num_blocks, block_times); samples_per_block=None is the
+        time-invariant channel at t_start (M = 1).  num_out defaults to N + num_taps - 1 + max(l_min, 0).  Returns a
+        complex64 tensor [nrx, Nr, 2, num_out] (Nr = 1 without elements, Br with weights); `out` is written in place, or
+        added to with accumulate=True (the shards of one launch set add up to the whole signal).  Invalid arguments
+        raise ValueError."""
+        from . import propagate as _pg
+        if not hasattr(signal, "dim") or signal.dim() not in (2, 3):
+            raise ValueError("signal must be a complex64 tensor [ntx, Nt, N] or [ntx, N] on %s" % (self.device,))
+        if num_out is None:
+            num_out = _pg.default_num_out(int(signal.shape[-1]), num_taps, l_min)
+        m = _pg.num_blocks(num_out, samples_per_block)
+        t0, dt = _pg.block_times(fs, samples_per_block, t_start)
+        if (rx_weights is None) != (tx_weights is None) or (rx_elements is None) != (tx_elements is None):
+            raise ValueError("elements and weights are given for both sides or for neither")
+        if rx_weights is not None and rx_elements is None:
+            raise ValueError("weights need the elements they apply to")
+        kw = dict(l_min=l_min, fc=fc, t0=t0, dt=dt, num_times=m, los=los, scatter=scatter)
+        if rx_weights is not None:
+            h = self.beam_taps(rx_elements, tx_elements, rx_weights, tx_weights, fs, num_taps,
+                               array_frequency=array_frequency, **kw)
+        elif rx_elements is not None:
+            h = self.array_taps(rx_elements, tx_elements, fs, num_taps, array_frequency=array_frequency, **kw)
+        else:
+            h = self.taps(fs, num_taps, **kw)
+        return self.apply_taps(h, signal, l_min, samples_per_block, num_out, out, accumulate)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

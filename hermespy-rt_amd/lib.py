@@ -38,6 +38,7 @@ EXPORTED = (
     "hrt_beam_taps_scratch_bytes", "hrt_beam_taps", "hrt_compute_beam_taps",
     "hrt_covariance_out_floats", "hrt_array_covariance_scratch_bytes", "hrt_array_covariance",
     "hrt_compute_array_covariance",
+    "hrt_propagate_out_floats", "hrt_propagate", "hrt_compute_received_signal",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -305,6 +306,16 @@ def load():
                                         C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                         f32p, C.c_size_t, f32p, C.c_size_t, f32p, C.POINTER(Stats)]
     L.hrt_compute_beam_taps.restype = C.c_int
+    # received signals: taps applied to waveforms (hrt_propagate_spec: abi.PropagateSpec)
+    prp = C.POINTER(abi.PropagateSpec)
+    L.hrt_propagate_out_floats.argtypes = [prp]
+    L.hrt_propagate_out_floats.restype = u64
+    L.hrt_propagate.argtypes = [C.c_int, prp, vp, vp, vp, C.c_int, vp]
+    L.hrt_propagate.restype = C.c_int
+    L.hrt_compute_received_signal.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                              C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                              u32, f32p, u64, u64, f32p, C.POINTER(Stats)]
+    L.hrt_compute_received_signal.restype = C.c_int
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

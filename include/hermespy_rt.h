@@ -325,6 +325,43 @@ int hrt_compute_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, 
                           size_t num_rx_beams, const float *tx_weights, size_t num_tx_beams,
                           float *out /* complex interleaved, layout above */, hrt_stats *stats);
 
+/* Received signals: the traced taps applied to baseband waveforms on the device (include/hrt_device.h: hrt_propagate),
+ * what a link-level simulator's Channel.propagate(signal) returns.  With h the output of hrt_compute_array_taps
+ * (hrt_compute_taps: Nr = Nt = 1; hrt_compute_beam_taps: beams in place of elements) and x the samples of every TX
+ * port at the rate f_s, for every rx, RX element i, polarisation pol and output sample n < num_out:
+ *     y[rx][i][pol][n] = sum_tx sum_j sum_{l < num_taps} h[rx][tx][i][j][pol][m(n)][l] x[tx][j][n - l_min - l]
+ *     m(n) = min(n / samples_per_block, num_times - 1)     (integer division)
+ * with x[..][k] = 0 for k < 0 or k >= num_samples; the index n - l_min - l is formed in 64-bit signed arithmetic.  The
+ * sum over TX is part of the definition: a receiver hears all transmitters.  The channel varies block-wise in the
+ * observation time: the taps of block m are meant to be formed at the centre of the block, t0 = t_start + (S - 1) /
+ * (2 f_s), dt = S / f_s.  S = 1 with num_times = num_out is the per-sample time-variant channel, num_times = 1 the
+ * time-invariant one; blocks past the last sample are not read.
+ * x: complex [num_tx][Nt][num_samples]; y: complex [num_rx][Nr][2][num_out]; both re/im interleaved (numpy complex64).
+ * The products and sums are float (f32 MFMA where num_times = 1 or samples_per_block is a multiple of 16, an fmaf
+ * chain otherwise), every output summed in one fixed order: two calls give the same bits.  Non-finite taps or samples
+ * give an undefined result.
+ * hrt_compute_received_signal traces and batches exactly as hrt_compute_array_taps does, keeps the accumulated taps on
+ * the device, uploads x (HOST) and runs the propagation once after the last batch; only y is copied back.
+ * HRT_E_INVALID, before the device is touched: every refusal of hrt_compute_array_taps; a NULL x or y; every refusal
+ * of hrt_propagate (include/hrt_device.h); spec->num_times != ceil(num_out / samples_per_block). */
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* RX / TX elements (or beams) per link */
+    uint32_t num_times, num_taps;               /* M blocks, L taps */
+    int32_t l_min;                              /* tap l has the delay (l_min + l) / f_s */
+    uint32_t samples_per_block;                 /* S */
+    uint64_t num_samples, num_out;              /* N samples of x per port, N_out samples of y per row */
+} hrt_propagate_spec;
+uint64_t hrt_propagate_out_floats(const hrt_propagate_spec *spec);   /* num_rx nr 2 num_out 2; 0 for NULL */
+int hrt_compute_received_signal(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                size_t num_rays, size_t num_bounces, const hrt_taps_spec *spec,
+                                const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                                size_t num_tx_elements, double array_frequency_hz, uint32_t samples_per_block,
+                                const float *x /* host, complex [num_tx][Nt][num_samples] */, uint64_t num_samples,
+                                uint64_t num_out, float *y /* host, complex [num_rx][Nr][2][num_out] */,
+                                hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

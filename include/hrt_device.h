@@ -394,6 +394,19 @@ int hrt_beam_taps(const hrt_problem *p, const hrt_shard *s, const void *d_worksp
                   const hrt_array_spec *arrays, const hrt_beam_spec *beams, void *d_scratch, uint64_t scratch_bytes,
                   float *d_out, int accumulate, void *stream);
 
+/* ---- received signals: taps applied to waveforms (csrc/host/channel.c, csrc/hrt_propagate.hip) ----
+ * y as hermespy_rt.h defines it (hrt_propagate_spec, hrt_compute_received_signal), hrt_propagate_out_floats floats at
+ * d_out, from d_taps (complex [num_rx][num_tx][nr][nt][2][num_times][num_taps]: the output of hrt_array_taps, of
+ * hrt_taps with nr = nt = 1, or of hrt_beam_taps with its beam counts) and d_signal (complex [num_tx][nt]
+ * [num_samples]), all DEVICE pointers, asynchronous on `stream` of `device`.  It needs no problem: it reads only the
+ * two tensors.  accumulate = 0 overwrites d_out, 1 adds to it; every element of d_out is written exactly once, also
+ * where the sum is empty; no scratch, no partial sums and no floating-point atomics, so two calls with the same inputs
+ * give the same bits.  HRT_E_INVALID, before the device is touched: a NULL pointer; any of num_rx, num_tx, nr, nt,
+ * num_times, num_taps, samples_per_block, num_samples, num_out equal to 0; nr or nt > 1024; nr * nt * num_times *
+ * num_taps > 2^24; |l_min| or |l_min + num_taps| > 2^24; num_samples or num_out > 2^31; accumulate not 0 or 1. */
+int hrt_propagate(int device, const hrt_propagate_spec *spec, const void *d_taps, const void *d_signal, void *d_out,
+                  int accumulate, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
