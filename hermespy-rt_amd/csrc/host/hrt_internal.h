@@ -30,6 +30,9 @@ typedef struct {
 } hrt_eta;
 void hrt_material_eta(uint32_t material_index, float f_ghz, hrt_eta *out);
 
+/* records streams a problem may hold: with the caller's stream within the 4 hardware queues a process opens */
+#define HRT_AUX_STREAMS_MAX 3
+
 /* developer / test switches (tune.c: HRT_TUNE="key=value,..."), read once per problem */
 typedef struct {
     hrt_ktune k;                 /* the part the launch shims see (hrt_kparams.tune) */
@@ -45,6 +48,8 @@ typedef struct {
     int no_bounce_prefetch, no_scatter;
     int no_chain;                  /* launches 1 .. nb one by one instead of hrt_chain_kernel */
     int chain_from;                /* first launch of the chain kernel (default 1) */
+    int aux_streams;               /* records streams of a trace, 1 .. HRT_AUX_STREAMS_MAX (default 2) */
+    int aux_prio;                  /* 1: the records streams at the lowest priority (default), 0: the default priority */
 } hrt_tune;
 void hrt_tune_defaults(hrt_tune *t);
 int hrt_tune_load(hrt_tune *t);
@@ -94,8 +99,12 @@ struct hrt_problem {
     hrt_krxt krxt;
     uint64_t rxt_entries;        /* total list entries over all (rx, cell) */
     uint32_t *h_fuse_flag, *d_fuse_flag;   /* pinned words a fused launch / the chain kernel sets when it gives up (hrt_kparams.host_flag) */
-    void *aux_stream;            /* second stream of a trace: the records kernels run beside the bounce kernels */
-    void *aux_ev[2];             /* fork (live list complete) / join (records done): ordering-only events */
+    /* records streams of a trace: launch b >= 1 runs its records kernel on stream (b - 1) mod A, beside the bounce
+     * kernels and beside the records kernels of its neighbours (problem.c: trace_impl) */
+    void *aux_stream[HRT_AUX_STREAMS_MAX];
+    int aux_low[HRT_AUX_STREAMS_MAX];       /* the stream was created at the lowest priority */
+    void *aux_fork[HRT_AUX_STREAMS_MAX];    /* live list complete (recorded on the caller's stream): ordering-only events */
+    void *aux_join[HRT_AUX_STREAMS_MAX];    /* the stream's last records kernel done */
     void *d_patch;               /* patch tables (device blob), or NULL */
     hrt_kpatch kpatch;
     int sort_rays;               /* re-sort the live list between bounces (hrt_ksort) */

@@ -74,8 +74,11 @@ void hrt_problem_destroy(hrt_problem *p)
         if (p->d_rxt) hrt_hip_free(p->d_rxt);
         if (p->d_patch) hrt_hip_free(p->d_patch);
         if (p->h_fuse_flag) hrt_hip_host_free(p->h_fuse_flag);
-        if (p->aux_stream) hrt_hip_stream_destroy(p->aux_stream);
-        for (int k = 0; k < 2; ++k) if (p->aux_ev[k]) hrt_hip_event_destroy(p->aux_ev[k]);
+        for (int k = 0; k < HRT_AUX_STREAMS_MAX; ++k) {
+            if (p->aux_stream[k]) hrt_hip_stream_destroy(p->aux_stream[k]);
+            if (p->aux_fork[k]) hrt_hip_event_destroy(p->aux_fork[k]);
+            if (p->aux_join[k]) hrt_hip_event_destroy(p->aux_join[k]);
+        }
     }
     free(p->h_tri); free(p->h_mesh); free(p->h_mat); free(p->h_tri_mesh); free(p->h_tri_face);
     hrt_accel_free(&p->accel);
@@ -1271,19 +1274,37 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
 
     HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
     const uint32_t nb = s->num_bounces;
-    /* the second stream (created with the first trace that can use it; HRT_OVERLAP=0: one stream) */
+    /* the records streams (created with the first trace that can use them).  HRT_OVERLAP=0: none, everything on the
+     * caller's stream; HRT_OVERLAP=1: ONE stream at the default priority (the schedule before there were several);
+     * unset: HRT_TUNE aux_streams (1 .. 3) streams, at the lowest priority unless aux_prio=0.  A stream whose
+     * priority is not the one asked for now (the variable changed between two traces) is made again. */
     hrt_problem *pp = (hrt_problem *)p;
-    int aux = 0, forked = 0;
-    if (p->kpatch.mask) {
+    int aux = 0;                                 /* A: how many records streams this trace deals its launches to */
+    int used[HRT_AUX_STREAMS_MAX] = {0};         /* a records kernel of this trace went to stream k */
+    if (p->kpatch.mask && !timer) {
         const char *ov = getenv("HRT_OVERLAP");
+        const int legacy = ov && *ov == '1';
         if (!(ov && *ov == '0')) {
-            if (!pp->aux_stream) {
-                int e2;
-                if ((e2 = hrt_hip_stream_create(&pp->aux_stream)) || (e2 = hrt_hip_event_create_sync(&pp->aux_ev[0])) ||
-                    (e2 = hrt_hip_event_create_sync(&pp->aux_ev[1])))
-                    return hrt_fail_hip(e2, "hipStreamCreate(records stream)");
+            aux = legacy ? 1 : p->tune.aux_streams;
+            if (aux < 1) aux = 1;
+            if (aux > HRT_AUX_STREAMS_MAX) aux = HRT_AUX_STREAMS_MAX;
+            if ((uint32_t)aux > nb) aux = (int)nb;   /* launches 1 .. nb have records */
+            const int low = !legacy && p->tune.aux_prio != 0;
+            for (int k = 0; k < aux; ++k) {
+                int e2 = 0;
+                if (pp->aux_stream[k] && pp->aux_low[k] != low) {
+                    if ((e2 = hrt_hip_stream_destroy(pp->aux_stream[k]))) return hrt_fail_hip(e2, "hipStreamDestroy(records stream)");
+                    pp->aux_stream[k] = NULL;
+                }
+                if (!pp->aux_stream[k]) {
+                    e2 = low ? hrt_hip_stream_create_prio(&pp->aux_stream[k], 1) : hrt_hip_stream_create(&pp->aux_stream[k]);
+                    if (e2) { pp->aux_stream[k] = NULL; return hrt_fail_hip(e2, "hipStreamCreate(records stream)"); }
+                    pp->aux_low[k] = low;
+                }
+                if ((!pp->aux_fork[k] && (e2 = hrt_hip_event_create_sync(&pp->aux_fork[k]))) ||
+                    (!pp->aux_join[k] && (e2 = hrt_hip_event_create_sync(&pp->aux_join[k]))))
+                    return hrt_fail_hip(e2, "hipEventCreate(records stream)");
             }
-            aux = 1;
         }
     }
     /* events (only with a timer): [0,1] around LoS; per launch b: [2] start, [4] end of the records kernel (patch
@@ -1309,10 +1330,11 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
     for (uint32_t b = 0; b <= nb; ++b) {
         if (ev) STEP(hrt_hip_event_record(ev[2 + 4 * b], stream));
         /* Patch tables: the records of bounce b-1 (shadow traces + records, hrt_records_kernel) need only the
-         * live list of this launch, and nothing of this launch needs them: they run on the problem's second
-         * stream, beside the bounce's own kernels (a VALU-bound kernel beside latency-bound ones), forked and
-         * joined by events.  With a timer everything stays on one stream, so that the per-kernel times mean
-         * what they say. */
+         * live list of this launch, and nothing of this launch needs them: they run on one of the problem's
+         * records streams, beside the bounce's own kernels (a VALU-bound kernel beside latency-bound ones), forked
+         * and joined by events.  Each launch has its own hit block, record blocks and mask words, so the records
+         * kernels of successive launches, on different streams, may run beside each other too.  With a timer
+         * everything stays on one stream, so that the per-kernel times mean what they say. */
         /* Tables on which whole bounces are fused: the TAIL -- launches 2 .. nb -- as ONE persistent kernel
          * (hrt_chain_kernel: a grid barrier instead of a launch per bounce, and it ends with the first empty
          * list).  Measured on C4 (profiles/HISTORY.md r4): an empty launch costs 3 us + the dispatch of a grid
@@ -1332,15 +1354,16 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
         int own_records = 0;
         if (b >= 1 && !hip) {
             void *rs = stream;
-            if (aux && !ev) {
-                STEP(hrt_hip_event_record(pp->aux_ev[0], stream));
-                STEP(hrt_hip_stream_wait_event(pp->aux_stream, pp->aux_ev[0]));
-                rs = pp->aux_stream;
+            const int k = aux ? (int)((b - 1u) % (uint32_t)aux) : 0;
+            if (aux) {   /* fork: the live list of launch b is complete where the caller's stream stands now */
+                STEP(hrt_hip_event_record(pp->aux_fork[k], stream));
+                STEP(hrt_hip_stream_wait_event(pp->aux_stream[k], pp->aux_fork[k]));
+                rs = pp->aux_stream[k];
             }
             const int rr = hip ? 0 : hrt_hip_launch_records(&K, b, rs);   /* -1: not this problem */
             if (rr > 0) hip = rr;
             if (rr == 0) own_records = 1;
-            if (rr == 0 && rs != stream) forked = 1;
+            if (rr == 0 && rs != stream) used[k] = 1;
         }
         if (ev) STEP(hrt_hip_event_record(ev[4 + 4 * b], stream));   /* end of the records kernel (or: nothing ran) */
         if (own_records && b == nb) {   /* the last launch: records only */
@@ -1368,10 +1391,13 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
         if (p->sort_rays && b < nb) STEP(hrt_hip_sort_hits(&K, b, stream));   /* part of the "shade" time */
         if (ev) STEP(hrt_hip_event_record(ev[5 + 4 * b], stream));
     }
-    if (forked) {   /* join: the caller's stream continues behind the last records kernel */
-        STEP(hrt_hip_event_record(pp->aux_ev[1], pp->aux_stream));
-        STEP(hrt_hip_stream_wait_event(stream, pp->aux_ev[1]));
-    }
+    /* join: the caller's stream continues behind the last records kernel of EVERY stream this trace used -- so the next
+     * trace's memset and launch 0, on the caller's stream, come after all records kernels of this one */
+    for (int k = 0; k < aux; ++k)
+        if (used[k]) {
+            STEP(hrt_hip_event_record(pp->aux_join[k], pp->aux_stream[k]));
+            STEP(hrt_hip_stream_wait_event(stream, pp->aux_join[k]));
+        }
 #undef STEP
     if (timer) timer->recorded = !hip;
     if (hip) return hrt_fail_hip(hip, "hrt_trace");

@@ -36,6 +36,8 @@ void hrt_tune_defaults(hrt_tune *t)
     t->accel_big = HRT_ACCEL_BIG;
     t->accel_fine = -1;
     t->accel_fine_min = UINT64_MAX;
+    t->aux_streams = 2;             /* records streams of a trace (problem.c: trace_impl; profiles/streams/ holds the measurements) */
+    t->aux_prio = 1;                /* ... created at the lowest priority */
 }
 
 int hrt_tune_load(hrt_tune *t)
@@ -87,6 +89,14 @@ int hrt_tune_load(hrt_tune *t)
         else if KEY("no_scatter") t->no_scatter = (int)v;
         else if KEY("no_chain") t->no_chain = (int)v;
         else if KEY("chain_from") t->chain_from = (int)v;
+        else if KEY("aux_streams") {   /* 1 .. 3: records streams of a trace; launch b's records run on stream (b - 1) mod A */
+            if (strlen(val) != 1 || u < 1u || u > HRT_AUX_STREAMS_MAX) rc = hrt_fail(HRT_E_INVALID, "HRT_TUNE: aux_streams must be 1 .. %d, not '%s'", HRT_AUX_STREAMS_MAX, val);
+            else t->aux_streams = (int)u;
+        }
+        else if KEY("aux_prio") {   /* 1: the records streams at the lowest priority, behind the bounce kernels; 0: the default */
+            if (strcmp(val, "0") != 0 && strcmp(val, "1") != 0) rc = hrt_fail(HRT_E_INVALID, "HRT_TUNE: aux_prio must be 0 or 1, not '%s'", val);
+            else t->aux_prio = (int)u;
+        }
         else rc = hrt_fail(HRT_E_INVALID, "HRT_TUNE: unknown key '%s'", tok);
 #undef KEY
     }

@@ -2553,7 +2553,10 @@ __global__ __launch_bounds__(HRT_BLOCK) void hrt_wide_finish_kernel(const hrt_kp
 // memory between its stores except the shadow result words, which are requested four RXs at a time in
 // front of those RXs' records -- loads and stores share vmcnt in issue order, so a load behind a
 // record's nine stores waits for them to reach L2.
-template <bool NLDS>
+// RECORDS: the kernel writes the scatter records of bounce b-1 itself.  false where hrt_records_kernel owns them (patch
+// tables): the bounce alone, compiled without the record loop -- 72 registers and no scratch instead of 80 and 16 B, a
+// seventh wave per SIMD (C3, one stream: 81 / 46 / 24 -> 65 / 38 / 21 us by launch; profiles/HISTORY.md).
+template <bool NLDS, bool RECORDS>
 __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(const hrt_kparams P,
                                                               const uint32_t b)
 {
@@ -2644,7 +2647,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
             ptri = ldu(res_blk(P, P.num_rx), 0u, i4);
             pt = ldf(res_blk(P, P.num_rx), cap4, i4);
         }
-        const bool need_state = valid && !(P.records_done && ptri == HRT_NO_HIT);
+        const bool need_state = valid && !(!RECORDS && ptri == HRT_NO_HIT);
         if (need_state) {
             if (first) {
                 // src/compute_paths.c:452-466 + the launch Doppler term :494-500
@@ -2671,7 +2674,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_SHADE_WAVES) void hrt_shade_kernel(c
         }
 
         // ---- scatter records of bounce b-1 (unless hrt_records_kernel wrote them) ----
-        if (!first && !P.records_done) {
+        if constexpr (RECORDS) if (!first) {
             const uint32_t pb = b - 1;
             F3 n = {0.f, 0.f, 1.f}, mvel = {0.f, 0.f, 0.f};
             float mat_s = 0.f, mat_alpha = 1.f;
@@ -4602,6 +4605,19 @@ int hrt_hip_stream_create(void **stream)
     *stream = (void *)s;
     return rc;
 }
+// a non-blocking stream at the device's lowest (`lowest` != 0) or its default priority
+int hrt_hip_stream_create_prio(void **stream, int lowest)
+{
+    hipStream_t s = nullptr;
+    *stream = nullptr;
+    if (!lowest) return hrt_hip_stream_create(stream);
+    int least = 0, greatest = 0;   // (numerically: least >= greatest)
+    int rc = (int)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (rc) return rc;
+    rc = (int)hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
+    *stream = (void *)s;
+    return rc;
+}
 int hrt_hip_stream_destroy(void *stream) { return (int)hipStreamDestroy((hipStream_t)stream); }
 int hrt_hip_mem_info(uint64_t *free_b, uint64_t *total_b)
 {
@@ -4709,12 +4725,16 @@ int hrt_hip_launch_shade(const hrt_kparams *P_in, uint32_t bounce, void *stream)
     const uint64_t max_grid = P->tune.shade_grid ? P->tune.shade_grid : HRT_SHADE_GRID;
     if (blocks > max_grid) blocks = max_grid;
     if (blocks == 0) blocks = 1;
-    if (pl.shade_lds_normals)
-        hipLaunchKernelGGL(hrt_shade_kernel<true>, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_shade,
-                           (hipStream_t)stream, *P, bounce);
-    else
-        hipLaunchKernelGGL(hrt_shade_kernel<false>, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_shade,
-                           (hipStream_t)stream, *P, bounce);
+    const dim3 grid((uint32_t)blocks), block(HRT_BLOCK);
+    const size_t lds = (size_t)pl.lds_shade;
+    hipStream_t st = (hipStream_t)stream;
+    if (Pc.records_done) {   // the bounce alone
+        if (pl.shade_lds_normals) hipLaunchKernelGGL((hrt_shade_kernel<true, false>), grid, block, lds, st, *P, bounce);
+        else hipLaunchKernelGGL((hrt_shade_kernel<false, false>), grid, block, lds, st, *P, bounce);
+    } else {
+        if (pl.shade_lds_normals) hipLaunchKernelGGL((hrt_shade_kernel<true, true>), grid, block, lds, st, *P, bounce);
+        else hipLaunchKernelGGL((hrt_shade_kernel<false, true>), grid, block, lds, st, *P, bounce);
+    }
     return (int)hipGetLastError();
 }
 

@@ -248,6 +248,7 @@ int hrt_hip_memset_async(void *dst, int value, uint64_t bytes, void *stream);
 int hrt_hip_stream_sync(void *stream);
 int hrt_hip_d2h_async(void *dst, const void *src, uint64_t bytes, void *stream);
 int hrt_hip_stream_create(void **stream);
+int hrt_hip_stream_create_prio(void **stream, int lowest);   /* non-blocking too; lowest != 0: at the device's lowest priority */
 int hrt_hip_stream_destroy(void *stream);
 int hrt_hip_mem_info(uint64_t *free_b, uint64_t *total_b);
 int hrt_hip_launch_los(const hrt_kparams *P, void *stream);
