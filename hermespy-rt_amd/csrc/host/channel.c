@@ -552,6 +552,7 @@ int hrt_compute_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_p
 
 /* ------------------------------------------------------------------ impulse responses (hrt_taps) */
 
+/* (of the three taps families) */
 #define HRT_TP_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
 #define HRT_TP_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
 
@@ -575,7 +576,32 @@ static int taps_spec_check(const hrt_taps_spec *spec, const char *who)
     return parts_check(spec->parts, who);
 }
 
-/* the tiling of one taps call: a pure function of the problem, the shard and the spec */
+/* The grid of one call of a taps family (hrt_ktgrid, csrc/hrt_pathsum.h) with npairs * num_times rows, and the record
+ * chunks of its scatter part (v->nchunks): returns the scratch of seg and the partial sums, *per_chunk the bytes of
+ * one chunk's.  Where the grid has four row tiles (rows >= 13) a wave holds 4 row tiles (U read once per MFMA, V formed
+ * once per four) and the `wr` waves of a block that stand along the rows make it 4 wr x 4 tiles: wr = 1 in hrt_taps
+ * (4 x 1 tiles a wave), 4 in the array and beam families (4 x 4 tiles a wave: a block of 64 rows, so a staged record
+ * serves 64 MFMAs).  Otherwise 1 x 4 tiles a wave, the waves along the columns: a block of 1 x 16 tiles (the rows past
+ * 4 rows of the tile are padding). */
+static uint64_t taps_grid(hrt_kview *v, const hrt_taps_spec *spec, uint32_t npairs, uint32_t wr, hrt_ktgrid *g,
+                          uint64_t *per_chunk)
+{
+    g->L = spec->num_taps; g->T = spec->num_times; g->l_min = spec->l_min;
+    g->rows = npairs * g->T;
+    g->rtiles = (4u * g->rows + 15u) / 16u;
+    g->ctiles = (g->L + 15u) / 16u;
+    g->rt = g->rtiles >= 4u ? 4u : 1u;
+    const uint32_t brows = g->rt == 4u ? 4u * wr : 1u, bcols = g->rt == 4u ? 4u : 16u;   /* tiles of a block */
+    g->rblocks = (g->rtiles + brows - 1u) / brows;
+    g->cblocks = (g->ctiles + bcols - 1u) / bcols;
+    g->fs = spec->fs_hz; g->fc = spec->fc_hz; g->t0 = spec->t0_s; g->dt = spec->dt_s;
+    const uint64_t links = (uint64_t)v->nrx * v->ntx;
+    *per_chunk = links * 2u * npairs * g->T * g->L * 8u;
+    return ps_chunks(v, spec->parts, links * g->rblocks * g->cblocks, HRT_TP_TARGET_GROUPS, *per_chunk,
+                     HRT_TP_PARTIAL_MAX, 65535u);
+}
+
+/* the plan of one taps call: a pure function of the problem, the shard and the spec */
 static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, hrt_ktaps *K,
                      uint64_t *bytes)
 {
@@ -583,20 +609,12 @@ static int taps_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_sp
     if (rc) return rc;
     memset(K, 0, sizeof *K);
     if ((rc = ps_view(p, s, spec->parts, "hrt_taps", &K->v))) return rc;
-    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
-    K->rtiles = (4u * K->T + 15u) / 16u;
-    K->ctiles = (K->L + 15u) / 16u;
-    /* four row tiles per wave (U read once per MFMA, V formed once per four) where the grid has them; one row tile
-     * and four column tiles otherwise (T < 4: the rows past 4 T of the tile are padding) */
-    K->rt = K->rtiles >= 4u ? 4u : 1u;
-    const uint32_t ct = HRT_TP_WTILES / K->rt;
-    K->rblocks = (K->rtiles + K->rt - 1u) / K->rt;
-    K->cblocks = (K->ctiles + 4u * ct - 1u) / (4u * ct);
-    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    const uint64_t links = (uint64_t)K->v.nrx * K->v.ntx;
-    const uint64_t per_chunk = links * 2u * K->T * K->L * 8u;
-    *bytes = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_TP_TARGET_GROUPS, per_chunk,
-                       HRT_TP_PARTIAL_MAX, 65535u);
+    hrt_ktgrid g;   /* hrt_ktaps holds these fields written out (csrc/hrt_taps.h) */
+    uint64_t per_chunk;
+    *bytes = taps_grid(&K->v, spec, 1u, 1u, &g, &per_chunk);
+    K->L = g.L; K->T = g.T; K->l_min = g.l_min;
+    K->rtiles = g.rtiles; K->ctiles = g.ctiles; K->rt = g.rt; K->rblocks = g.rblocks; K->cblocks = g.cblocks;
+    K->fs = g.fs; K->fc = g.fc; K->t0 = g.t0; K->dt = g.dt;
     return HRT_OK;
 }
 
@@ -655,9 +673,6 @@ int hrt_compute_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const
 
 /* ------------------------------------------------------------------ antenna-array impulse responses (hrt_array_taps) */
 
-#define HRT_AT_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
-#define HRT_AT_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
-
 /* the checks of an array taps call that need no problem (device pointers are not read) */
 static int at_check(const hrt_taps_spec *spec, const hrt_array_spec *a)
 {
@@ -666,7 +681,7 @@ static int at_check(const hrt_taps_spec *spec, const hrt_array_spec *a)
     return arrays_check(a, (uint64_t)spec->num_times * spec->num_taps, "num_times * num_taps", "hrt_array_taps");
 }
 
-/* the tiling of one array taps call: a pure function of the problem, the shard, the spec and the array sizes */
+/* the plan of one array taps call: a pure function of the problem, the shard, the spec and the array sizes */
 static int at_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, const hrt_array_spec *a,
                    hrt_karray_taps *K, uint64_t *bytes)
 {
@@ -679,20 +694,8 @@ static int at_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec
                         &K->npairs, &K->fa_c)))
         return rc;
     ps_shard(s, &K->sh);
-    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
-    K->rows = K->npairs * K->T;
-    K->rtiles = (4u * K->rows + 15u) / 16u;
-    K->ctiles = (K->L + 15u) / 16u;
-    /* where the grid has four row tiles (Nr Nt T >= 13), 4 x 4 tiles per wave and the waves along the rows: a block
-     * of 16 x 4 tiles; otherwise hrt_taps' RT = 1 form: 1 x 4 tiles per wave, the waves along the columns */
-    K->rt = K->rtiles >= 4u ? 4u : 1u;
-    const uint32_t brows = K->rt == 4u ? 16u : 1u, bcols = K->rt == 4u ? 4u : 16u;   /* tiles of a block */
-    K->rblocks = (K->rtiles + brows - 1u) / brows;
-    K->cblocks = (K->ctiles + bcols - 1u) / bcols;
-    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->L * 8u;
-    *bytes = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_AT_TARGET_GROUPS, per_chunk,
-                       HRT_AT_PARTIAL_MAX, 65535u);
+    uint64_t per_chunk;
+    *bytes = taps_grid(&K->v, spec, K->npairs, 4u, &K->g, &per_chunk);
     return HRT_OK;
 }
 
@@ -1498,9 +1501,6 @@ int hrt_compute_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_po
 
 /* ------------------------------------------------------------------ beamformed impulse responses (hrt_beam_taps) */
 
-#define HRT_BT_TARGET_GROUPS 2048u          /* workgroups of the partial kernel worth launching (8 per CU) */
-#define HRT_BT_PARTIAL_MAX (512ull << 20)   /* partial sums beyond one chunk: at most this */
-
 /* the checks of a beam taps call that need no problem (device pointers are not read).  There is no limit on Nr * Nt:
  * the element-domain taps are never formed */
 static int bt_check(const hrt_taps_spec *spec, const hrt_array_spec *a, const hrt_beam_spec *bm)
@@ -1529,9 +1529,9 @@ static int bt_check(const hrt_taps_spec *spec, const hrt_array_spec *a, const hr
     return HRT_OK;
 }
 
-/* the tiling of one beam taps call: a pure function of the problem, the shard, the spec and the array and codebook
- * sizes (hrt_array_taps' rule with Br Bt for Nr Nt).  The scratch is seg, the partial sums (*off_los bytes of them)
- * and the LoS gains of every (link, pair) */
+/* the plan of one beam taps call: a pure function of the problem, the shard, the spec and the array and codebook
+ * sizes (taps_grid with Br Bt pairs: a block of 64 rows covers up to 64 beam pairs).  The scratch is seg, the partial
+ * sums (*off_los bytes of them) and the LoS gains of every (link, pair) */
 static int bt_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec *spec, const hrt_array_spec *a,
                    const hrt_beam_spec *bm, hrt_kbeam_taps *K, uint64_t *bytes, uint64_t *off_los)
 {
@@ -1546,20 +1546,8 @@ static int bt_plan(const hrt_problem *p, const hrt_shard *s, const hrt_taps_spec
     K->nr = a->num_rx_elements; K->nt = a->num_tx_elements;
     K->br = bm->num_rx_beams; K->bt = bm->num_tx_beams; K->npairs = K->br * K->bt;
     K->fa_c = a->array_frequency_hz / HRT_SPEED_OF_LIGHT;
-    K->L = spec->num_taps; K->T = spec->num_times; K->l_min = spec->l_min;
-    K->rows = K->npairs * K->T;
-    K->rtiles = (4u * K->rows + 15u) / 16u;
-    K->ctiles = (K->L + 15u) / 16u;
-    /* where the grid has four row tiles (Br Bt T >= 13), 4 x 4 tiles per wave and the waves along the rows: a block
-     * of 16 x 4 tiles (64 rows: up to 64 beam pairs); otherwise 1 x 4 tiles per wave, the waves along the columns */
-    K->rt = K->rtiles >= 4u ? 4u : 1u;
-    const uint32_t brows = K->rt == 4u ? 16u : 1u, bcols = K->rt == 4u ? 4u : 16u;   /* tiles of a block */
-    K->rblocks = (K->rtiles + brows - 1u) / brows;
-    K->cblocks = (K->ctiles + bcols - 1u) / bcols;
-    K->fs = spec->fs_hz; K->fc = spec->fc_hz; K->t0 = spec->t0_s; K->dt = spec->dt_s;
-    const uint64_t per_chunk = links * 2u * K->npairs * K->T * K->L * 8u;
-    const uint64_t sums = ps_chunks(&K->v, spec->parts, links * K->rblocks * K->cblocks, HRT_BT_TARGET_GROUPS,
-                                    per_chunk, HRT_BT_PARTIAL_MAX, 65535u);
+    uint64_t per_chunk;
+    const uint64_t sums = taps_grid(&K->v, spec, K->npairs, 4u, &K->g, &per_chunk);
     *off_los = align256(K->v.nchunks * per_chunk);
     *bytes = sums - K->v.nchunks * per_chunk + *off_los + align256(links * K->npairs * 8u);
     return HRT_OK;

@@ -9,7 +9,8 @@
  * on v_mfma_f32_16x16x4_f32: a row tile is 16 rows g (4 (pair, time) rows), a column tile 16 taps, one MFMA takes 4
  * records.  The steering folds into U (the sinc is real), so a record costs 8 FLOP per (pair, time, tap), as in
  * hrt_taps.  A workgroup (4 waves) writes one chunk of the link's records to the partial sums of the scratch; the
- * reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h).  Two forms:
+ * reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h).  The GEMM's tile setup, MFMA loop and write-back
+ * are csrc/hrt_taps_gemm.inc, the grid hrt_ktgrid (csrc/hrt_pathsum.h), both shared with hrt_beam_taps.  Two forms:
  *   rt = 4 (the grid has at least 4 row tiles: Nr Nt T >= 13): a wave holds RT = 4 row tiles x CT = 4 column tiles,
  *          the 4 waves stand along the rows: a block of 16 row tiles (64 (pair, time) rows) x 4 column tiles, so a
  *          staged record (its loads, u_tx, sinc parameters) serves 64 MFMAs;
@@ -17,6 +18,7 @@
 #ifndef HRT_ARRAY_TAPS_H
 #define HRT_ARRAY_TAPS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "hrt_pathsum.h"
@@ -30,18 +32,16 @@ typedef struct {
     hrt_kview v;
     hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t nr, nt, npairs;        /* elements; npairs = nr * nt */
-    uint32_t L, T;                  /* taps, time samples */
-    int32_t l_min;
-    uint32_t rows;                  /* (pair, time) rows: npairs * T */
-    uint32_t rtiles, ctiles;        /* ceil(4 rows / 16), ceil(L / 16) */
-    uint32_t rt;                    /* the form: row tiles per wave, 4 or 1 */
-    uint32_t rblocks, cblocks;      /* rt 4: ceil(rtiles / 16), ceil(ctiles / 4); rt 1: rtiles, ceil(ctiles / 16) */
-    double fs, fc, t0, dt;
+    hrt_ktgrid g;                   /* L .. dt (csrc/hrt_pathsum.h): rows = npairs * T; rt 4: rblocks = ceil(rtiles / 16),
+                                       cblocks = ceil(ctiles / 4); rt 1: rblocks = rtiles, cblocks = ceil(ctiles / 16) */
     double fa_c;                    /* f_a / c: revolutions per metre of path difference */
     const float *rx_el, *tx_el;     /* device [nr][3], [nt][3] element offsets (m) */
     float *partial;                 /* scratch: complex [link][chunk][pair][pol][T][L] */
     float *out;                     /* complex [nrx][ntx][nr][nt][2][T][L] */
 } hrt_karray_taps;
+
+_Static_assert(offsetof(hrt_karray_taps, g) == 144 && offsetof(hrt_karray_taps, g.fs) == 184 &&
+               offsetof(hrt_karray_taps, rx_el) == 224, "hrt_karray_taps: the argument offsets");
 
 int hrt_hip_launch_array_taps(const hrt_karray_taps *P, void *stream);
 

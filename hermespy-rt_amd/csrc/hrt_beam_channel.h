@@ -53,4 +53,18 @@ int hrt_hip_launch_beam_channel(const hrt_kbeam *P, void *stream);
 #ifdef __cplusplus
 }
 #endif
+
+#ifdef __HIPCC__
+/* what the kernels of the two beam families (csrc/hrt_beam_channel.hip, csrc/hrt_beam_taps.hip) share besides the
+ * kernel text of csrc/hrt_beam_gains.inc */
+namespace {
+
+// weight e of beam `beam` of a codebook [beams][n][2]; the combiner (RX side) takes the conjugate
+__device__ __forceinline__ float2 beam_weight(const float *w, uint32_t n, uint32_t beam, uint32_t e, bool conj)
+{
+    const float *p = w + ((uint64_t)beam * n + e) * 2u;
+    return make_float2(p[0], conj ? -p[1] : p[1]);
+}
+}  // namespace
+#endif /* __HIPCC__ */
 #endif /* HRT_BEAM_CHANNEL_H */

@@ -8,11 +8,12 @@
 // combiner w^H and the precoder f, without H ever being formed (csrc/hrt_beam_channel.h).  Paths, parts, u_rx and
 // u_tx are those of csrc/hrt_array_channel.hip; the workspace view and its readers are csrc/hrt_pathsum.h.
 //   hrt_beam_partial_kernel  one workgroup (4 waves) per (pair block x column block, record chunk, link): the GEMM of
-//                            hrt_array_partial_kernel with beam pairs for rows.  Only the S stage differs: per batch
-//                            of staged records, the element phase factors (FP64 reduction, f32 sincospi) tile by tile
-//                            in LDS, the gains of the beams the block's pairs touch (FP32 within a tile, FP64 across
-//                            the tiles), and G = g_rx g_tx as the A operand of each lane.
-//   hrt_beam_los_kernel      per (link, pair): G at the LoS directions (u_tx = HRT_LOS_DIR, u_rx = -u_tx), FP64 sums.
+//                            csrc/hrt_pair_gemm.inc with beam pairs for rows.  Its S stage: per batch of staged
+//                            records, the gain stage of csrc/hrt_beam_gains.inc (the element phase factors tile by
+//                            tile in LDS, the gains of the beams the block's pairs touch, FP32 within a tile, FP64
+//                            across the tiles), and G = g_rx g_tx as the A operand of each lane.
+//   hrt_beam_los_kernel      per (link, pair): G at the LoS directions (u_tx = HRT_LOS_DIR, u_rx = -u_tx), FP64 sums
+//                            (part 2 of csrc/hrt_beam_gains.inc).
 //   hrt_beam_reduce_kernel   per output: the chunks in a fixed order, plus the LoS term, into out.
 // No floating-point atomics anywhere: two calls with the same inputs give the same bits.
 #include <hip/hip_runtime.h>
@@ -26,17 +27,6 @@
 #define HRT_BM_SLOTS (HRT_AC_BATCH * HRT_AC_PAIRS / HRT_AC_THREADS)   // (record, beam) gains per thread and side
 
 static_assert(HRT_AC_BATCH == 32u && HRT_AC_PAIRS == 32u && HRT_BM_ETILE == 32u, "the index arithmetic of the S stage");
-
-namespace {
-
-// weight e of beam `beam` of a codebook [beams][n][2]; the combiner (RX side) takes the conjugate
-__device__ __forceinline__ float2 beam_weight(const float *w, uint32_t n, uint32_t beam, uint32_t e, bool conj)
-{
-    const float *p = w + ((uint64_t)beam * n + e) * 2u;
-    return make_float2(p[0], conj ? -p[1] : p[1]);
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_beam_partial_kernel(const hrt_kbeam P)
 {
@@ -76,57 +66,16 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_beam_partial_kernel(const 
         __syncthreads();
 #define HRT_PG_PART 2
 #include "hrt_pair_gemm.inc"
-        // S: the gains of the touched beams at every staged record, side 0 = RX (u_rx, conj W_rx), 1 = TX
-#pragma unroll 1
-        for (uint32_t side = 0; side < 2u; ++side) {
-            const uint32_t N = side ? P.nt : P.nr, ns = side ? nb : na;
-            const float *el = side ? P.tx_el : P.rx_el, *wt = side ? P.tx_w : P.rx_w;
-            double gre[HRT_BM_SLOTS], gim[HRT_BM_SLOTS];
-#pragma unroll
-            for (uint32_t s = 0; s < HRT_BM_SLOTS; ++s) gre[s] = gim[s] = 0.0;
-#pragma unroll 1
-            for (uint32_t e0 = 0; e0 < N; e0 += HRT_BM_ETILE) {
-                const uint32_t ne = min(HRT_BM_ETILE, N - e0);
-                __syncthreads();   // the readers of the tile before are done
-#pragma unroll 1
-                for (uint32_t x = tid; x < ne * HRT_AC_BATCH; x += HRT_AC_THREADS) {   // phase factors
-                    const uint32_t j = x & 31u, e = x >> 5;
-                    if (j < n) {
-                        float sn, cs;
-                        sincospif(half_revs(P.g.fa_c * dot3(el + 3u * (e0 + e), sRec[j] + 6u + 3u * side)), &sn, &cs);
-                        sE[e][j] = make_float2(cs, sn);
-                    }
-                }
-#pragma unroll 1
-                for (uint32_t x = tid; x < ns * HRT_BM_ETILE; x += HRT_AC_THREADS) {   // weights
-                    const uint32_t e = x & 31u, s = x >> 5;
-                    const uint32_t beam = side == 0u ? a0 + s : (tx_all ? s : (p0 + s) % P.bt);
-                    if (e < ne) sW[s][e] = beam_weight(wt, N, beam, e0 + e, side == 0u);
-                }
-                __syncthreads();
-#pragma unroll
-                for (uint32_t s = 0; s < HRT_BM_SLOTS; ++s) {
-                    const uint32_t x = tid + s * HRT_AC_THREADS, j = x & 31u, slot = x >> 5;
-                    if (j < n && slot < ns) {
-                        float re = 0.f, im = 0.f;
-                        for (uint32_t e = 0; e < ne; ++e) {
-                            const float2 wv = sW[slot][e], ph = sE[e][j];
-                            re = fmaf(wv.x, ph.x, re);
-                            re = fmaf(-wv.y, ph.y, re);
-                            im = fmaf(wv.x, ph.y, im);
-                            im = fmaf(wv.y, ph.x, im);
-                        }
-                        gre[s] += (double)re;
-                        gim[s] += (double)im;
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t s = 0; s < HRT_BM_SLOTS; ++s) {
-                const uint32_t x = tid + s * HRT_AC_THREADS, j = x & 31u, slot = x >> 5;
-                if (j < n && slot < ns) sG[side][slot][j] = make_float2((float)gre[s], (float)gim[s]);
-            }
-        }
+        // S: the gains of the touched beams at every staged record
+#define HRT_BG_BATCH HRT_AC_BATCH
+#define HRT_BG_THREADS HRT_AC_THREADS
+#define HRT_BG_SLOTS HRT_BM_SLOTS
+#define HRT_BG_E(e, j) sE[e][j]
+#define HRT_BG_W(s, e) sW[s][e]
+#define HRT_BG_P0 p0
+#define HRT_BG_FA_C P.g.fa_c
+#define HRT_BG_PART 1
+#include "hrt_beam_gains.inc"
         __syncthreads();
 #pragma unroll 1
         for (uint32_t e = tid; e < n * HRT_AC_PAIRS; e += HRT_AC_THREADS) {   // G, as the A operand of each lane
@@ -155,32 +104,12 @@ __global__ void __launch_bounds__(HRT_AC_THREADS) hrt_beam_partial_kernel(const 
 #include "hrt_pair_gemm.inc"
 }
 
-// one thread per (link, pair): G = g_rx[a](-u) g_tx[b](u) at the LoS entry's u = directions_tx (the coincident
-// convention of los_entry; a blocked entry's gains are not read)
+// one thread per (link, pair): G at the LoS directions (part 2 of csrc/hrt_beam_gains.inc)
 __global__ void hrt_beam_los_kernel(const hrt_kbeam P)
 {
-    const hrt_kview &V = P.v;
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (uint64_t)P.npairs * V.nrx * V.ntx) return;
-    const uint32_t link = (uint32_t)(gid / P.npairs), pair = (uint32_t)(gid - (uint64_t)link * P.npairs);
-    const uint32_t a = pair / P.bt, b = pair - a * P.bt;
-    hrt_los_entry L;
-    (void)los_entry(V, link, L);
-    const float u_tx[3] = {L.ux, L.uy, L.uz}, u_rx[3] = {-L.ux, -L.uy, -L.uz};
-    double g[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    for (uint32_t side = 0; side < 2u; ++side) {
-        const uint32_t N = side ? P.nt : P.nr, beam = side ? b : a;
-        const float *el = side ? P.tx_el : P.rx_el, *wt = side ? P.tx_w : P.rx_w, *u = side ? u_tx : u_rx;
-        for (uint32_t e = 0; e < N; ++e) {
-            const float2 wv = beam_weight(wt, N, beam, e, side == 0u);
-            float sn, cs;
-            sincospif(half_revs(P.g.fa_c * dot3(el + 3u * e, u)), &sn, &cs);
-            g[side][0] += (double)wv.x * cs - (double)wv.y * sn;
-            g[side][1] += (double)wv.x * sn + (double)wv.y * cs;
-        }
-    }
-    reinterpret_cast<float2 *>(P.los)[gid] = make_float2((float)(g[0][0] * g[1][0] - g[0][1] * g[1][1]),
-                                                         (float)(g[0][0] * g[1][1] + g[0][1] * g[1][0]));
+#define HRT_BG_FA_C P.g.fa_c
+#define HRT_BG_PART 2
+#include "hrt_beam_gains.inc"
 }
 
 // one thread per output (link, pair, pol, m, k): the chunks in order, + LoS, -> out

@@ -10,7 +10,7 @@
  * their tiles are hrt_array_taps': rt = 4 (Br Bt T >= 13) with blocks of 64 (pair, time) rows x 4 column tiles, rt = 1
  * with blocks of 4 rows x 16 column tiles.
  *
- * The gain stage is hrt_beam_partial_kernel's (element tiles of HRT_BM_ETILE in LDS, FP32 within a tile, FP64 across
+ * The gain stage is csrc/hrt_beam_gains.inc (element tiles of HRT_BM_ETILE in LDS, FP32 within a tile, FP64 across
  * the tiles) for the beams the block's rows touch.  A block of `cap` rows (64 or 4) that starts at row0 covers the
  * pairs pf = row0 / T .. pl = (min(row0 + cap, rows) - 1) / T: at most cap of them, and it may begin and end inside
  * a pair.  Its RX slot s is beam pf / Bt + s, up to beam pl / Bt; its TX slot s is beam s where every TX beam fits
@@ -35,13 +35,7 @@ typedef struct {
     hrt_kview v;
     hrt_kshard sh;                  /* (20 bytes: the fields below follow it directly) */
     uint32_t nr, nt, br, bt, npairs;   /* elements, beams; npairs = br * bt */
-    uint32_t L, T;                  /* taps, time samples */
-    int32_t l_min;
-    uint32_t rows;                  /* (pair, time) rows: npairs * T */
-    uint32_t rtiles, ctiles;        /* ceil(4 rows / 16), ceil(L / 16) */
-    uint32_t rt;                    /* the form: row tiles per wave, 4 or 1 */
-    uint32_t rblocks, cblocks;      /* rt 4: ceil(rtiles / 16), ceil(ctiles / 4); rt 1: rtiles, ceil(ctiles / 16) */
-    double fs, fc, t0, dt;
+    hrt_ktgrid g;                   /* L .. dt (csrc/hrt_pathsum.h): hrt_karray_taps' with npairs = br * bt */
     double fa_c;                    /* f_a / c: revolutions per metre of path difference */
     const float *rx_el, *tx_el;     /* device [nr][3], [nt][3] element offsets (m) */
     const float *rx_w, *tx_w;       /* device [br][nr][2], [bt][nt][2] weights (re, im) */
@@ -50,7 +44,8 @@ typedef struct {
     float *out;                     /* complex [nrx][ntx][br][bt][2][T][L] */
 } hrt_kbeam_taps;
 
-_Static_assert(offsetof(hrt_kbeam_taps, nr) == 132 && offsetof(hrt_kbeam_taps, fs) == 192,
+_Static_assert(offsetof(hrt_kbeam_taps, nr) == 132 && offsetof(hrt_kbeam_taps, g.fs) == 192 &&
+               offsetof(hrt_kbeam_taps, g) == 152 && offsetof(hrt_kbeam_taps, rx_el) == 232,
                "hrt_kbeam_taps: the argument offsets");
 
 int hrt_hip_launch_beam_taps(const hrt_kbeam_taps *P, void *stream);

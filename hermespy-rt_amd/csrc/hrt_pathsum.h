@@ -2,11 +2,11 @@
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance) share: the view of the
  * workspace of a finished hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray,
  * hrt_ktaps, hrt_karray_taps, hrt_kpower, hrt_kdominant, hrt_kbeam, hrt_kbeam_taps and hrt_kcov; filled by
- * csrc/host/channel.c), the grid of the two pair families (hrt_kgrid), and, for
- * the .hip files, the device helpers that read them: the field accessors, the chunk ranges and the batch fill, the
+ * csrc/host/channel.c), the grid of the two pair families (hrt_kgrid) and of the three taps families (hrt_ktgrid), and,
+ * for the .hip files, the device helpers that read them: the field accessors, the chunk ranges and the batch fill, the
  * staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the array
  * families, the LoS entry, the two halves the complex reduce kernels share, and the reduce walk and the launch of the
- * pair families.
+ * pair families and of the taps families.
  *
  * Every family sums, per link (rx, tx), the LoS entry (shard rank 0 only) and the scatter records of the link's TX
  * segment in every hit block.  The records of a segment are cut into nchunks chunks; a partial kernel writes one
@@ -49,6 +49,25 @@ typedef struct {
     double fa_c;                    /* f_a / c: revolutions per metre of path difference */
 } hrt_kgrid;
 
+/* The grid of the taps families (hrt_taps: rows = T; hrt_array_taps, hrt_beam_taps: rows = pairs * T), filled by
+ * taps_grid() of csrc/host/channel.c.  A member of hrt_karray_taps and hrt_kbeam_taps at the offsets these fields had
+ * when they were written out there (8-aligned in both; asserted in the two headers).  hrt_ktaps keeps these fields
+ * (without rows, which is its T) written out where they always were: taps_plan() copies them from one of these, and
+ * the device code below takes either as its grid G (profiles/HISTORY.md: the struct's layout in hrt_ktaps alone
+ * regrouped the kernel-argument loads of hrt_taps_partial_kernel).  csrc/hrt_taps_gemm.inc, taps_output and
+ * launch_taps_family read it as G.  A row tile is 16 rows g = 4 row + q (4 rows), a column tile 16 taps; a workgroup
+ * holds 16 x 4 tiles (rt = 4: 4 x 4 a wave, the 4 waves along the rows; hrt_taps: 4 x 4 tiles, 4 x 1 a wave, the waves
+ * along the columns) or 1 x 16 tiles (rt = 1: 1 x 4 a wave, the waves along the columns). */
+typedef struct {
+    uint32_t L, T;                  /* taps, time samples */
+    int32_t l_min;
+    uint32_t rows;                  /* (pair, time) rows */
+    uint32_t rtiles, ctiles;        /* ceil(4 rows / 16), ceil(L / 16) */
+    uint32_t rt;                    /* the form: row tiles per wave, 4 (rtiles >= 4) or 1 */
+    uint32_t rblocks, cblocks;      /* workgroups along the rows and the columns */
+    double fs, fc, t0, dt;
+} hrt_ktgrid;
+
 /* hrt_channel_segments_kernel: V->seg[b][t] for every bounce b and t <= ntx */
 int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
 
@@ -61,6 +80,7 @@ int hrt_hip_launch_segments(const hrt_kview *V, void *stream);
 
 #include "hrt_device.h"
 #include "hrt_launch_dir.h"
+#include "hrt_sinc.h"
 
 static_assert(sizeof(hrt_kshard) == 20 && sizeof(hrt_kview) % 8 == 0, "hrt_kshard: the offsets after it");
 
@@ -226,6 +246,47 @@ __device__ __forceinline__ bool los_entry(const hrt_kview &V, uint32_t link, hrt
     return status == 0u || status == 2u;
 }
 
+// What the reduce kernels of the taps families share (one thread per output gid = ((link * npairs + pair) * 2 + pol)
+// * T L + m L + tap; partial sums in the same order per chunk; hrt_taps: npairs = 1; G: the hrt_ktgrid, or the
+// hrt_ktaps, which has its fields): the output's link, pair, time sample and tap and the sum s of its chunks (false
+// past the last output); of a LoS entry at an output, the phase nu t_m - f_c tau in revolutions (the array family adds
+// its steering) and the weight a sinc(l - f_s tau).
+struct hrt_taps_output {
+    uint32_t link, pair, m, tap;
+    float2 s;
+};
+
+template <typename TG>
+__device__ __forceinline__ bool taps_output(const hrt_kview &V, const TG &G, uint32_t npairs, const float *partial,
+                                            uint64_t gid, hrt_taps_output &o)
+{
+    const uint64_t tl = (uint64_t)G.T * G.L;
+    const uint64_t per_link = (uint64_t)npairs * 2u * tl;
+    if (gid >= per_link * V.nrx * V.ntx) return false;
+    o.link = (uint32_t)(gid / per_link);
+    const uint64_t e = gid - (uint64_t)o.link * per_link;   // = (pair * 2 + pol) * tl + m * L + tap
+    o.pair = (uint32_t)(e / (2u * tl));
+    const uint64_t mi = e % tl;
+    o.m = (uint32_t)(mi / G.L);
+    o.tap = (uint32_t)(mi % G.L);
+    const float2 *src = reinterpret_cast<const float2 *>(partial) + (uint64_t)o.link * V.nchunks * per_link + e;
+    o.s = sum_chunks(src, V.nchunks, per_link);
+    return true;
+}
+
+template <typename TG>
+__device__ __forceinline__ double taps_los_phase(const TG &G, uint32_t m, const hrt_los_entry &L)
+{
+    const double t = G.t0 + (double)m * G.dt;
+    return (double)L.nu * t - G.fc * (double)L.tau;
+}
+
+template <typename TG>
+__device__ __forceinline__ float taps_los_weight(const TG &G, uint32_t tap, const hrt_los_entry &L)
+{
+    return L.a * sinc_tap(G.l_min + (int32_t)tap, sinc_prep(G.fs, L.tau));
+}
+
 // Fill sB / sI (bounce, hit) with the next at most BATCH unblocked records of chunk c of link (rx, tx), compacted by
 // mask ballots; (b, cur, end) is where the walk stands (start it with b = 0 and chunk_range of block 0).  Every wave
 // takes the same decisions; wave 0 writes the list.  Returns the number of records staged: 0 once the chunk is done.
@@ -282,6 +343,29 @@ int launch_pair_family(const KP *P, uint32_t threads, void (*partial)(const KP),
         hipLaunchKernelGGL(los, dim3((unsigned)((g + 255u) / 256u)), dim3(256), 0, st, *P);
     }
     const uint64_t n = (uint64_t)links * P->npairs * 2u * P->g.T * P->g.K;
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
+    return (int)hipGetLastError();
+}
+
+// The launch of a taps family (P: hrt_ktaps, hrt_karray_taps or hrt_kbeam_taps, G its grid; npairs 1 for hrt_ktaps): as
+// launch_pair_family, with the partial kernel in the form of G.rt (`partial4`: rt = 4, `partial1`: rt = 1).
+template <typename KP, typename TG>
+int launch_taps_family(const KP *P, const TG &G, uint32_t npairs, uint32_t threads, void (*partial4)(const KP),
+                       void (*partial1)(const KP), void (*los)(const KP), void (*reduce)(const KP), void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t links = P->v.nrx * P->v.ntx;
+    if (P->v.nchunks) {
+        const int e = hrt_hip_launch_segments(&P->v, stream);
+        if (e) return e;
+        hipLaunchKernelGGL(G.rt == 4u ? partial4 : partial1, dim3(G.rblocks * G.cblocks, P->v.nchunks, links),
+                           dim3(threads), 0, st, *P);
+    }
+    if (los && P->v.los) {
+        const uint64_t g = (uint64_t)links * npairs;
+        hipLaunchKernelGGL(los, dim3((unsigned)((g + 255u) / 256u)), dim3(256), 0, st, *P);
+    }
+    const uint64_t n = (uint64_t)links * npairs * 2u * G.T * G.L;
     hipLaunchKernelGGL(reduce, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
     return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// hrt_sinc.h -- the sinc weights of the sampled impulse responses, shared by the taps kernels (csrc/hrt_taps.hip) and
-// the array taps kernels (csrc/hrt_array_taps.hip).  HIP device code only.
+// hrt_sinc.h -- the sinc weights of the sampled impulse responses, for the kernels of the three taps families
+// (csrc/hrt_taps_gemm.inc, the reduce helpers of csrc/hrt_pathsum.h, which includes this file).  HIP device code only.
 //
 // Every delay is reduced in FP64 to x = f_s tau.  With n = rint(x), f = x - n, sinc(l - x) = -(-1)^(l - n) sin(pi f) /
 // (pi (l - n - f)): one f32 sinpi per record and, per tap, an exact integer difference, one v_rcp_f32 and a sign.

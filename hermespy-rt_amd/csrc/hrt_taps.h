@@ -8,7 +8,13 @@
  * records.  A workgroup (4 waves) forms HRT_TP_WTILES accumulator tiles per wave: RT row tiles x CT column tiles with
  * RT * CT = 4 (RT = 4 when the grid has at least 4 row tiles, else RT = 1); wave w takes column tiles
  * (cb * 4 + w) * CT .. + CT - 1 and row tiles rb * RT .. + RT - 1.  It writes one chunk of the link's records to
- * the partial sums of the scratch; the reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h). */
+ * the partial sums of the scratch; the reduce kernel adds the chunks in a fixed order (csrc/hrt_pathsum.h).  The tile
+ * setup and the MFMA loop are csrc/hrt_taps_gemm.inc, shared with the array and beam taps kernels.
+ *
+ * hrt_ktaps holds the fields of the taps grid (hrt_ktgrid of csrc/hrt_pathsum.h, without rows: here rows = T) written
+ * out, where they always were: taps_plan() of csrc/host/channel.c fills them from a hrt_ktgrid, and the shared device
+ * code takes the hrt_ktaps itself as its grid.  As a hrt_ktgrid member the fields move by 4 and 8 bytes and the
+ * kernel-argument loads of hrt_taps_partial_kernel regroup (profiles/HISTORY.md). */
 #ifndef HRT_TAPS_H
 #define HRT_TAPS_H
 

@@ -5,7 +5,8 @@
 //
 // over the LoS entry (hrt_taps_reduce_kernel) and every unblocked scatter record (hrt_taps_partial_kernel) of the
 // link.  The TX segments of the hit blocks come from hrt_channel_segments_kernel (csrc/hrt_channel.hip); the workspace
-// view, its readers and the batch fill are csrc/hrt_pathsum.h; the sinc weights csrc/hrt_sinc.h.
+// view, its readers, the batch fill, the reduce walk and the launch are csrc/hrt_pathsum.h; the sinc weights
+// csrc/hrt_sinc.h; the tile setup and the MFMA loop csrc/hrt_taps_gemm.inc.
 //   hrt_taps_partial_kernel  one workgroup (4 waves) per (row block x column block, record chunk, link): the real
 //                            GEMM of csrc/hrt_taps.h on v_mfma_f32_16x16x4_f32, partial sums to the scratch.  The
 //                            unblocked records of the chunk are compacted by mask ballots and staged HRT_TP_BATCH at a
@@ -23,22 +24,21 @@
 #include <stdint.h>
 
 #include "hrt_pathsum.h"
-#include "hrt_sinc.h"
 #include "hrt_taps.h"
 
-typedef float hrt_f32x4 __attribute__((ext_vector_type(4)));
-
-// RT row tiles x (HRT_TP_WTILES / RT) column tiles per wave (csrc/hrt_taps.h)
+// RT row tiles x (HRT_TP_WTILES / RT) column tiles per wave, the 4 waves along the columns (csrc/hrt_taps.h)
 template <uint32_t RT>
 __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const hrt_ktaps P)
 {
-    constexpr uint32_t CT = HRT_TP_WTILES / RT;
+    constexpr uint32_t CT = HRT_TP_WTILES / RT, WT = HRT_TP_WTILES, WR = 1u, WC = 4u;
     constexpr uint32_t BT = RT * 4u;   // time samples of the block
     const hrt_kview &V = P.v;
+    const hrt_ktaps &G = P;   // the grid of csrc/hrt_taps_gemm.inc: its fields, written out (csrc/hrt_taps.h)
     const uint32_t blk = blockIdx.x, c = blockIdx.y, link = blockIdx.z;
     const uint32_t rb = blk % P.rblocks, cb = blk / P.rblocks;
     const uint32_t rx = link / V.ntx, tx = link % V.ntx;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    const uint32_t wr = 0, wc = w;                     // the wave's place in the block
     const uint32_t kq = lane >> 4, col = lane & 15u;   // A / B operand: record 4 g + kq; row / tap `col` of a tile
 
     __shared__ float sU[HRT_TP_BATCH][BT * 4u];   // U of the block's rows g = 4 mm + q
@@ -46,16 +46,9 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
     __shared__ sinc_rec sS[HRT_TP_BATCH];
     __shared__ uint32_t sB[HRT_TP_BATCH], sI[HRT_TP_BATCH];   // (bounce, hit) of the staged records
 
-    const uint32_t r0 = rb * RT, c0 = (cb * 4u + w) * CT;   // this wave's first row tile and column tile
-    bool live[HRT_TP_WTILES];
-    int32_t tap[CT];
-#pragma unroll
-    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) live[t] = r0 + t / CT < P.rtiles && c0 + t % CT < P.ctiles;
-#pragma unroll
-    for (uint32_t t = 0; t < CT; ++t) tap[t] = P.l_min + (int32_t)((c0 + t) * 16u + col);
-    hrt_f32x4 acc[HRT_TP_WTILES];
-#pragma unroll
-    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) acc[t] = hrt_f32x4{0.f, 0.f, 0.f, 0.f};
+#define HRT_TG_U(j, x) sU[j][x]
+#define HRT_TG_PART 1
+#include "hrt_taps_gemm.inc"
 
     uint32_t b = 0, cur = 0, end = 0;
     chunk_range(V, 0, tx, c, cur, end);
@@ -99,29 +92,18 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
             U[0] = u0; U[1] = u1; U[2] = u2; U[3] = u3;
         }
         __syncthreads();
-        for (uint32_t g = 0; 4u * g < n; ++g) {
-            const uint32_t j = 4u * g + kq;
-            const sinc_rec q = sS[j];
-            float v[CT];
-#pragma unroll
-            for (uint32_t t = 0; t < CT; ++t) v[t] = sinc_tap(tap[t], q);
-#pragma unroll
-            for (uint32_t rt = 0; rt < RT; ++rt) {
-                const float a = sU[j][rt * 16u + col];
-#pragma unroll
-                for (uint32_t t = 0; t < CT; ++t)
-                    if (live[rt * CT + t])
-                        acc[rt * CT + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, v[t], acc[rt * CT + t], 0, 0, 0);
-            }
-        }
+#define HRT_TG_PART 2
+#include "hrt_taps_gemm.inc"
         __syncthreads();
     }
+#undef HRT_TG_U
 
-    // D: lane = (row group kq, column col), register q: row 4 kq + q of the tile = (time 4 R + kq, part q)
+    // D: lane = (row group kq, column col), register q: row 4 kq + q of the tile = (time 4 R + kq, part q).  Part 3 of
+    // the shared text splits a row into (pair, time); here a row is a time sample
     const uint64_t tl = (uint64_t)P.T * P.L;
     float2 *dst = reinterpret_cast<float2 *>(P.partial) + ((uint64_t)link * V.nchunks + c) * 2u * tl;
 #pragma unroll
-    for (uint32_t t = 0; t < HRT_TP_WTILES; ++t) {
+    for (uint32_t t = 0; t < WT; ++t) {
         const uint32_t m = (r0 + t / CT) * 4u + kq, i = (c0 + t % CT) * 16u + col;
         if (live[t] && m < P.T && i < P.L) {
             float2 *d = dst + (uint64_t)m * P.L + i;
@@ -135,23 +117,15 @@ __global__ void __launch_bounds__(HRT_TP_THREADS) hrt_taps_partial_kernel(const 
 __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
 {
     const hrt_kview &V = P.v;
-    const uint64_t tl = (uint64_t)P.T * P.L;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t per_link = 2u * tl;
-    if (gid >= per_link * V.nrx * V.ntx) return;
-    const uint32_t link = (uint32_t)(gid / per_link);
-    const uint64_t e = gid - (uint64_t)link * per_link;   // = pol * tl + m * L + i
-
-    const float2 *src = reinterpret_cast<const float2 *>(P.partial) + (uint64_t)link * V.nchunks * per_link + e;
-    float2 s = sum_chunks(src, V.nchunks, per_link);
+    hrt_taps_output o;
+    if (!taps_output(V, P, 1u, P.partial, gid, o)) return;
+    float2 s = o.s;
     hrt_los_entry L;
-    if (V.los && los_entry(V, link, L)) {   // a real: TE = TM
-        const uint64_t mi = e % tl;
-        const uint32_t m = (uint32_t)(mi / P.L), i = (uint32_t)(mi % P.L);
-        const double t = P.t0 + (double)m * P.dt;
+    if (V.los && los_entry(V, o.link, L)) {   // a real: TE = TM
         float sn, cs;
-        sincospif(half_revs((double)L.nu * t - P.fc * (double)L.tau), &sn, &cs);
-        const float v = L.a * sinc_tap(P.l_min + (int32_t)i, sinc_prep(P.fs, L.tau));
+        sincospif(half_revs(taps_los_phase(P, o.m, L)), &sn, &cs);
+        const float v = taps_los_weight(P, o.tap, L);
         s.x += v * cs;
         s.y += v * sn;
     }
@@ -160,18 +134,6 @@ __global__ void hrt_taps_reduce_kernel(const hrt_ktaps P)
 
 extern "C" int hrt_hip_launch_taps(const hrt_ktaps *P, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t links = P->v.nrx * P->v.ntx;
-    if (P->v.nchunks) {
-        const int e = hrt_hip_launch_segments(&P->v, stream);
-        if (e) return e;
-        const dim3 grid(P->rblocks * P->cblocks, P->v.nchunks, links);
-        if (P->rt == 4u)
-            hipLaunchKernelGGL(hrt_taps_partial_kernel<4u>, grid, dim3(HRT_TP_THREADS), 0, st, *P);
-        else
-            hipLaunchKernelGGL(hrt_taps_partial_kernel<1u>, grid, dim3(HRT_TP_THREADS), 0, st, *P);
-    }
-    const uint64_t n = (uint64_t)links * 2u * P->T * P->L;
-    hipLaunchKernelGGL(hrt_taps_reduce_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, *P);
-    return (int)hipGetLastError();
+    return launch_taps_family<hrt_ktaps>(P, *P, 1u, HRT_TP_THREADS, hrt_taps_partial_kernel<4u>,
+                                         hrt_taps_partial_kernel<1u>, NULL, hrt_taps_reduce_kernel, stream);
 }
