@@ -638,6 +638,63 @@ def run_compute_array_covariance(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel
                             nt if int(spec.sides) & COV_TX else 0)
 
 
+class Pattern(C.Structure):
+    """include/hermespy_rt.h hrt_pattern (d_table: a device pointer in PatternSpec, a host pointer in PatternsHost)"""
+    _fields_ = [("kind", C.c_uint32), ("num_zenith", C.c_uint32), ("num_azimuth", C.c_uint32),
+                ("gain_db", C.c_float), ("d_table", C.c_void_p)]
+
+
+class PatternSpec(C.Structure):
+    """include/hrt_device.h hrt_pattern_spec (device pointers)"""
+    _fields_ = [("rx", Pattern), ("tx", Pattern), ("d_rx_rot", C.c_void_p), ("d_tx_rot", C.c_void_p)]
+
+
+class PatternsHost(C.Structure):
+    """include/hermespy_rt.h hrt_patterns_host (host pointers)"""
+    _fields_ = [("rx", Pattern), ("tx", Pattern), ("rx_rot", C.c_void_p), ("tx_rot", C.c_void_p),
+                ("num_rx", C.c_size_t), ("num_tx", C.c_size_t)]
+
+
+def pattern_struct(p, table_ptr=None):
+    """the hrt_pattern of a pattern dict (hermespy_rt_amd.patterns) whose table is at table_ptr"""
+    t = None if p.get("table") is None else np.asarray(p["table"])
+    nz, na = (int(t.shape[0]), int(t.shape[1])) if t is not None and t.ndim == 2 else (0, 0)
+    return Pattern(int(p["kind"]), nz, na, float(p["gain_db"]), table_ptr)
+
+
+class compute_patterns:
+    """with abi.compute_patterns(lib, rx=..., tx=..., rx_orientation=..., tx_orientation=...): the path-sum drop-in
+    calls (run_compute_channel, ...) of this thread inside the block apply the patterns (hrt_compute_set_patterns).
+    The patterns are pattern dicts (None: isotropic), the orientations float32 [n, 3, 3] arrays (None: identity); what
+    the library refuses is refused by the call inside the block."""
+
+    def __init__(self, lib, rx=None, tx=None, rx_orientation=None, tx_orientation=None):
+        from . import patterns as _pt
+        self.lib = lib
+        rx, tx = _pt.isotropic() if rx is None else rx, _pt.isotropic() if tx is None else tx
+        self.keep = []
+
+        def ptr(a):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+            self.keep.append(a)
+            return a.ctypes.data, a.shape[0]
+
+        rr, nrx = ptr(rx_orientation)
+        tr, ntx = ptr(tx_orientation)
+        self.host = PatternsHost(pattern_struct(rx, ptr(rx.get("table"))[0]), pattern_struct(tx, ptr(tx.get("table"))[0]),
+                                 rr, tr, nrx, ntx)
+
+    def __enter__(self):
+        self.lib.hrt_compute_set_patterns(C.byref(self.host))
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.hrt_compute_set_patterns(None)
+        return False
+
+
 DOMINANT_MAX_PATHS = 1024   # hrt_dominant_spec.max_paths; and num_rx * num_tx * max_paths <= 2^22
 
 

@@ -31,6 +31,7 @@
 #include "../hrt_covariance.h"
 #include "../hrt_dominant.h"
 #include "../hrt_pathsum.h"
+#include "../hrt_patterns.h"
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
 #include "../hrt_taps.h"
@@ -191,6 +192,124 @@ int hrt_channel(const hrt_problem *p, const hrt_shard *s, const void *d_workspac
     return HRT_OK;
 }
 
+/* ------------------------------------------------------------------ antenna patterns (hrt_apply_patterns) */
+
+/* the checks of one side's pattern (`side`: "rx" or "tx") of a call (`who`); the table pointer is tested for NULL only */
+static int pattern_check(const hrt_pattern *f, const char *side, const char *who)
+{
+    if (f->kind > HRT_PATTERN_TABLE)
+        return hrt_fail(HRT_E_INVALID, "%s: %s kind = %u (HRT_PATTERN_ISOTROPIC .. HRT_PATTERN_TABLE)", who, side, f->kind);
+    if (f->kind == HRT_PATTERN_TABLE) {
+        if (!f->d_table) return hrt_fail(HRT_E_INVALID, "%s: NULL %s table", who, side);
+        if (f->num_zenith < 2 || f->num_zenith > HRT_PT_MAX_ZENITH)
+            return hrt_fail(HRT_E_INVALID, "%s: %s num_zenith = %u (2 .. %u)", who, side, f->num_zenith, HRT_PT_MAX_ZENITH);
+        if (f->num_azimuth < 1 || f->num_azimuth > HRT_PT_MAX_AZIMUTH)
+            return hrt_fail(HRT_E_INVALID, "%s: %s num_azimuth = %u (1 .. %u)", who, side, f->num_azimuth,
+                            HRT_PT_MAX_AZIMUTH);
+    }
+    if (!isfinite(f->gain_db) || fabsf(f->gain_db) > HRT_PT_MAX_GAIN_DB)
+        return hrt_fail(HRT_E_INVALID, "%s: %s gain_db must be finite and within +-200 dB", who, side);
+    return HRT_OK;
+}
+
+static void pattern_fields(const hrt_pattern *f, uint32_t side, hrt_kpatterns *K)
+{
+    K->kind[side] = f->kind;
+    K->g[side] = (float)pow(10.0, (double)f->gain_db / 20.0);
+    if (f->kind == HRT_PATTERN_TABLE) {
+        K->nz[side] = f->num_zenith; K->na[side] = f->num_azimuth;
+        K->table[side] = f->d_table;
+    }
+}
+
+int hrt_apply_patterns(const hrt_problem *p, const hrt_shard *s, void *d_workspace, uint64_t workspace_bytes,
+                       const hrt_pattern_spec *spec, void *stream)
+{
+    if (!spec) return hrt_fail(HRT_E_INVALID, "hrt_apply_patterns: NULL spec");
+    int rc = pattern_check(&spec->rx, "rx", "hrt_apply_patterns");
+    if (rc) return rc;
+    if ((rc = pattern_check(&spec->tx, "tx", "hrt_apply_patterns"))) return rc;
+    if (!p || !s || !d_workspace) return hrt_fail(HRT_E_INVALID, "hrt_apply_patterns: NULL argument");
+    hrt_kpatterns K;
+    memset(&K, 0, sizeof K);
+    if ((rc = ps_view(p, s, HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER, "hrt_apply_patterns", &K.v))) return rc;
+    hrt_layout L;
+    if ((rc = hrt_layout_query(p, s, &L))) return rc;
+    if (workspace_bytes < L.total_bytes)
+        return hrt_fail(HRT_E_INVALID, "hrt_apply_patterns: workspace of %llu bytes, %llu needed (hrt_layout_query)",
+                        (unsigned long long)workspace_bytes, (unsigned long long)L.total_bytes);
+    ps_shard(s, &K.sh);
+    pattern_fields(&spec->rx, 0u, &K);
+    pattern_fields(&spec->tx, 1u, &K);
+    K.rot[0] = spec->d_rx_rot; K.rot[1] = spec->d_tx_rot;
+    K.v.ws = (const uint8_t *)d_workspace;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_patterns(&K, stream), "pattern kernels");
+    return HRT_OK;
+}
+
+/* the patterns the path-sum drop-ins of this thread apply (hermespy_rt.h: hrt_compute_set_patterns); NULL: none */
+static __thread const hrt_patterns_host *g_patterns;
+
+void hrt_compute_set_patterns(const hrt_patterns_host *patterns)
+{
+    g_patterns = patterns;
+}
+
+static uint64_t pattern_table_floats(const hrt_pattern *f)
+{
+    return f->kind == HRT_PATTERN_TABLE ? (uint64_t)f->num_zenith * f->num_azimuth : 0u;
+}
+
+/* the checks of the patterns of a drop-in call with nrx x ntx links: host arrays, so their contents too */
+static int patterns_host_check(const hrt_patterns_host *h, size_t nrx, size_t ntx)
+{
+    const char *who = "hrt_compute_set_patterns";
+    int rc = pattern_check(&h->rx, "rx", who);
+    if (rc) return rc;
+    if ((rc = pattern_check(&h->tx, "tx", who))) return rc;
+    for (int side = 0; side < 2; ++side) {
+        const hrt_pattern *f = side ? &h->tx : &h->rx;
+        for (uint64_t i = 0, n = pattern_table_floats(f); i < n; ++i)
+            if (!isfinite(f->d_table[i]) || f->d_table[i] < 0.f)
+                return hrt_fail(HRT_E_INVALID, "%s: %s table value %llu is not finite and >= 0", who, side ? "tx" : "rx",
+                                (unsigned long long)i);
+    }
+    if (h->rx_rot && h->num_rx != nrx)
+        return hrt_fail(HRT_E_INVALID, "%s: %zu rx rotations, but the call has num_rx = %zu", who, h->num_rx, nrx);
+    if (h->tx_rot && h->num_tx != ntx)
+        return hrt_fail(HRT_E_INVALID, "%s: %zu tx rotations, but the call has num_tx = %zu", who, h->num_tx, ntx);
+    for (size_t i = 0; h->rx_rot && i < 9u * nrx; ++i)
+        if (!isfinite(h->rx_rot[i])) return hrt_fail(HRT_E_INVALID, "%s: rx rotation %zu is not finite", who, i / 9u);
+    for (size_t i = 0; h->tx_rot && i < 9u * ntx; ++i)
+        if (!isfinite(h->tx_rot[i])) return hrt_fail(HRT_E_INVALID, "%s: tx rotation %zu is not finite", who, i / 9u);
+    return HRT_OK;
+}
+
+/* the patterns of a drop-in call on its device: tables and rotations uploaded to one buffer (*d_buf, the caller's to
+ * free), rx table, tx table, rx rotations, tx rotations */
+static int patterns_upload(const hrt_patterns_host *h, int device, size_t nrx, size_t ntx, void **d_buf,
+                           hrt_pattern_spec *spec)
+{
+    const uint64_t n[4] = {pattern_table_floats(&h->rx), pattern_table_floats(&h->tx), h->rx_rot ? 9u * nrx : 0u,
+                           h->tx_rot ? 9u * ntx : 0u};
+    const float *src[4] = {h->rx.d_table, h->tx.d_table, h->rx_rot, h->tx_rot};
+    const float *dst[4] = {NULL, NULL, NULL, NULL};
+    int rc = hrt_device_malloc(device, d_buf, (n[0] + n[1] + n[2] + n[3] + 1u) * 4u);
+    if (rc) return rc;
+    float *at = (float *)*d_buf;
+    for (int k = 0; k < 4; ++k) {
+        if (!n[k]) continue;
+        if ((rc = hrt_device_upload(device, at, src[k], n[k] * 4u))) return rc;
+        dst[k] = at;
+        at += n[k];
+    }
+    spec->rx = h->rx; spec->tx = h->tx;
+    spec->rx.d_table = dst[0]; spec->tx.d_table = dst[1];
+    spec->d_rx_rot = dst[2]; spec->d_tx_rot = dst[3];
+    return HRT_OK;
+}
+
 /* One drop-in call: what the ten hrt_compute_* entries of this file share.  `scratch_bytes` and `run` are
  * the device entry of the call; h_const (const_bytes, may be 0) is uploaded to the device once before the first
  * batch, and `run` finds it at d_const. */
@@ -222,6 +341,14 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
                       float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb, ch_job *job, void *out,
                       hrt_stats *stats, double t_begin)
 {
+    /* the thread's patterns, read once: what the call applies after each batch's trace (NULL: nothing) */
+    const hrt_patterns_host *const pat = g_patterns;
+    if (pat) {
+        const int prc = patterns_host_check(pat, nrx, ntx);
+        if (prc) return prc;
+    }
+    hrt_pattern_spec pat_spec;
+    void *d_pat = NULL;
     hrt_stats st;
     memset(&st, 0, sizeof st);
     st.num_devices = 1;
@@ -242,6 +369,7 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
         if ((rc = hrt_device_malloc(device, &job->d_const, job->const_bytes))) goto done;
         if ((rc = hrt_device_upload(device, job->d_const, job->h_const, job->const_bytes))) goto done;
     }
+    if (pat && (rc = patterns_upload(pat, device, nrx, ntx, &d_pat, &pat_spec))) goto done;
     /* scratch: the largest any batch needs (batch 0 has the most local rays) */
     for (uint32_t g = 0; g < G; ++g) {
         hrt_shard s = {np, g, G, 0, (uint32_t)nb};
@@ -263,6 +391,7 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
         t_dirs += hrt_now_s() - t0;
         t0 = hrt_now_s();
         if ((rc = hrt_trace_batch(prob, &s, &L, w, &st))) goto done;   /* (batch.c) */
+        if (pat && (rc = hrt_apply_patterns(prob, &s, w->d_ws, L.total_bytes, &pat_spec, NULL))) goto done;
         /* batch 0 is rank 0 of the launch set: it adds the LoS term; the others add their records */
         if ((rc = job->run(job, prob, &s, w->d_ws, d_scratch, scratch_bytes, d_out, first ? 0 : 1)))
             goto done;
@@ -292,6 +421,7 @@ static int ch_compute(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, cons
 done:
     if (d_scratch) hrt_device_free(st.device, d_scratch);
     if (d_out) hrt_device_free(st.device, d_out);
+    if (d_pat) hrt_device_free(st.device, d_pat);
     if (job->d_const) hrt_device_free(st.device, job->d_const);
     job->d_const = NULL;
     hrt_solo_end(&so, rc);

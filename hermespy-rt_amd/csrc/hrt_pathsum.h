@@ -2,7 +2,8 @@
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance) share: the view of the
  * workspace of a finished hrt_trace that their kernels read (plain C, the first member of hrt_kchannel, hrt_karray,
  * hrt_ktaps, hrt_karray_taps, hrt_kpower, hrt_kdominant, hrt_kbeam, hrt_kbeam_taps and hrt_kcov; filled by
- * csrc/host/channel.c), the grid of the two pair families (hrt_kgrid) and of the three taps families (hrt_ktgrid), and,
+ * csrc/host/channel.c; also of hrt_kpatterns, csrc/hrt_patterns.h, whose kernels WRITE the amplitudes this view reads,
+ * before any family runs), the grid of the two pair families (hrt_kgrid) and of the three taps families (hrt_ktgrid), and,
  * for the .hip files, the device helpers that read them: the field accessors, the chunk ranges and the batch fill, the
  * staged record with its departure direction (hrt_kshard), the element offsets and the steering products of the array
  * families, the LoS entry, the two halves the complex reduce kernels share, and the reduce walk and the launch of the

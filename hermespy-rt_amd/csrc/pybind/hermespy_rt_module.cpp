@@ -291,6 +291,79 @@ uint32_t parts_word(bool los, bool scatter)
     return (los ? HRT_CHANNEL_LOS : 0u) | (scatter ? HRT_CHANNEL_SCATTER : 0u);
 }
 
+// ... the `patterns` keyword: None, or a dict with rx and tx (pattern dicts of hermespy_rt_amd.patterns: kind, gain_db,
+// table; None: isotropic) and rx_orientation and tx_orientation ((n, 3, 3) world -> local rotations, or one (3, 3) for
+// all endpoints of the side; None: identity).  A scope guard: the patterns are set for this thread's path-sum call while
+// it lives and cleared when it goes (hrt_compute_set_patterns); the library checks the contents when the call starts ...
+struct pattern_scope {
+    hrt_patterns_host host{};
+    farr tables[2];
+    std::vector<float> rot[2];
+    bool set = false;
+
+    static void pattern(const py::object &o, const char *side, hrt_pattern &f, farr &keep)
+    {
+        if (o.is_none()) return;   // isotropic, 0 dB
+        if (!py::isinstance<py::dict>(o))
+            throw py::value_error(std::string("patterns['") + side + "'] must be a pattern dict (kind, gain_db, table)");
+        const py::dict d = o.cast<py::dict>();
+        if (!d.contains("kind") || !d.contains("gain_db"))
+            throw py::value_error(std::string("patterns['") + side + "'] needs kind and gain_db");
+        const long long kind = d["kind"].cast<long long>();
+        if (kind < 0 || kind > 0xffffffffLL)
+            throw py::value_error(std::string("patterns['") + side + "']: kind must fit 32 bits");
+        f.kind = (uint32_t)kind;
+        f.gain_db = d["gain_db"].cast<float>();
+        if (d.contains("table") && !d["table"].is_none()) {
+            keep = d["table"].cast<farr>();
+            if (keep.ndim() != 2)
+                throw py::value_error(std::string("patterns['") + side + "']: the table must have shape (num_zenith, num_azimuth)");
+            f.num_zenith = (uint32_t)keep.shape(0);
+            f.num_azimuth = (uint32_t)keep.shape(1);
+            f.d_table = keep.data();
+        }
+    }
+
+    static const float *rotations(const py::object &o, const char *name, size_t n, std::vector<float> &keep, size_t &count)
+    {
+        if (o.is_none()) return nullptr;
+        const farr a = o.cast<farr>();
+        const bool one = a.ndim() == 2 && a.shape(0) == 3 && a.shape(1) == 3;
+        if (!one && !(a.ndim() == 3 && a.shape(1) == 3 && a.shape(2) == 3))
+            throw py::value_error(std::string("patterns['") + name + "'] must have shape (3, 3) or (n, 3, 3)");
+        count = one ? n : (size_t)a.shape(0);
+        keep.resize(9u * count);
+        for (size_t i = 0; i < keep.size(); ++i) keep[i] = a.data()[one ? i % 9u : i];
+        return keep.data();
+    }
+
+    pattern_scope(const py::object &patterns, size_t num_rx, size_t num_tx)
+    {
+        if (patterns.is_none()) return;
+        if (!py::isinstance<py::dict>(patterns))
+            throw py::value_error("patterns must be None or a dict (rx, tx, rx_orientation, tx_orientation)");
+        const py::dict d = patterns.cast<py::dict>();
+        for (auto kv : d) {
+            const std::string k = py::str(kv.first);
+            if (k != "rx" && k != "tx" && k != "rx_orientation" && k != "tx_orientation")
+                throw py::value_error("patterns: unknown key '" + k + "' (rx, tx, rx_orientation, tx_orientation)");
+        }
+        auto get = [&](const char *k) { return d.contains(k) ? py::object(d[k]) : py::object(py::none()); };
+        pattern(get("rx"), "rx", host.rx, tables[0]);
+        pattern(get("tx"), "tx", host.tx, tables[1]);
+        host.rx_rot = rotations(get("rx_orientation"), "rx_orientation", num_rx, rot[0], host.num_rx);
+        host.tx_rot = rotations(get("tx_orientation"), "tx_orientation", num_tx, rot[1], host.num_tx);
+        hrt_compute_set_patterns(&host);
+        set = true;
+    }
+    ~pattern_scope()
+    {
+        if (set) hrt_compute_set_patterns(nullptr);
+    }
+    pattern_scope(const pattern_scope &) = delete;
+    pattern_scope &operator=(const pattern_scope &) = delete;
+};
+
 // ... and the call of the entry (`name`): the scene loaded and freed around `call` without the GIL; a refused argument raises ValueError, any other error RuntimeError
 template <typename F>
 void run_pathsum(const char *name, const std::string &mesh_filepath, F call)
@@ -316,7 +389,8 @@ py::array_t<std::complex<float>> compute_channel_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double f0, double df, unsigned long num_freqs, double t0, double dt,
-    unsigned long num_times, bool los, bool scatter)
+    unsigned long num_times, bool los, bool scatter,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -330,6 +404,7 @@ py::array_t<std::complex<float>> compute_channel_py(
     py::array_t<std::complex<float>> out({(size_t)num_rx, (size_t)num_tx, (size_t)2, (size_t)num_times,
                                           (size_t)num_freqs});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_channel", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                    num_bounces, &spec, dst, nullptr);
@@ -344,7 +419,8 @@ py::array_t<std::complex<float>> compute_array_channel_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
-    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency)
+    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -363,6 +439,7 @@ py::array_t<std::complex<float>> compute_array_channel_py(
                                                                     (size_t)num_times, (size_t)num_freqs}
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_array_channel", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_array_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                          num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
@@ -388,7 +465,8 @@ py::array_t<std::complex<float>> compute_beam_channel_py(
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
     py::array rx_weights, py::array tx_weights, double t0, double dt, unsigned long num_times, bool los, bool scatter,
-    py::object array_frequency)
+    py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -411,6 +489,7 @@ py::array_t<std::complex<float>> compute_beam_channel_py(
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
     const float *pwr = reinterpret_cast<const float *>(wr.data()), *pwt = reinterpret_cast<const float *>(wt.data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_beam_channel", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_beam_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                         num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, pwr, br, pwt, bt, dst,
@@ -427,7 +506,8 @@ py::array_t<std::complex<float>> compute_taps_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double sampling_rate, unsigned long num_taps, long l_min, py::object center_frequency,
-    double t0, double dt, unsigned long num_times, bool los, bool scatter)
+    double t0, double dt, unsigned long num_times, bool los, bool scatter,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -447,6 +527,7 @@ py::array_t<std::complex<float>> compute_taps_py(
                                                                      (size_t)num_times, (size_t)num_taps}
                                               : std::vector<size_t>{(size_t)1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_taps", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths, num_bounces,
                                 &spec, dst, nullptr);
@@ -463,7 +544,8 @@ py::array_t<std::complex<float>> compute_array_taps_py(
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
     long l_min, py::object center_frequency, double t0, double dt, unsigned long num_times, bool los, bool scatter,
-    py::object array_frequency)
+    py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -485,6 +567,7 @@ py::array_t<std::complex<float>> compute_array_taps_py(
                                                                     (size_t)num_times, (size_t)num_taps}
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_array_taps", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_array_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                       num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, dst, nullptr);
@@ -504,7 +587,8 @@ py::array_t<std::complex<float>> compute_received_signal_py(
     unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
     py::array_t<std::complex<float>, py::array::c_style | py::array::forcecast> signal, long l_min,
     py::object samples_per_block, double t_start, py::object center_frequency, py::object num_out, bool los,
-    bool scatter, py::object array_frequency)
+    bool scatter, py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL) throw std::invalid_argument("num_taps must fit 32 bits");
@@ -545,6 +629,7 @@ py::array_t<std::complex<float>> compute_received_signal_py(
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
     const float *x = reinterpret_cast<const float *>(signal.data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_received_signal", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_received_signal(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
                                            num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, (uint32_t)s, x,
@@ -561,7 +646,8 @@ py::array_t<std::complex<float>> compute_beam_taps_py(
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
     py::array rx_weights, py::array tx_weights, long l_min, py::object center_frequency, double t0, double dt,
-    unsigned long num_times, bool los, bool scatter, py::object array_frequency)
+    unsigned long num_times, bool los, bool scatter, py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
@@ -588,6 +674,7 @@ py::array_t<std::complex<float>> compute_beam_taps_py(
                                               : std::vector<size_t>{1});
     float *dst = reinterpret_cast<float *>(out.mutable_data());
     const float *pwr = reinterpret_cast<const float *>(wr.data()), *pwt = reinterpret_cast<const float *>(wt.data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_beam_taps", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_beam_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                      num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, pwr, br, pwt, bt, dst, nullptr);
@@ -603,7 +690,8 @@ py::dict compute_power_profiles_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, double tau0, double dtau, unsigned long num_delay_bins, unsigned long num_zenith_bins,
-    unsigned long num_azimuth_bins, bool los, bool scatter)
+    unsigned long num_azimuth_bins, bool los, bool scatter,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (num_delay_bins > 0xffffffffUL || num_zenith_bins > 0xffffffffUL || num_azimuth_bins > 0xffffffffUL)
@@ -624,6 +712,7 @@ py::dict compute_power_profiles_py(
                       Nth * Nph <= (1u << 14) && links * (Ld + 2u * Nth * Nph) <= (1ull << 26);
     py::array_t<double> buf(fits ? (size_t)n : (size_t)1);
     double *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_power_profiles", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_power_profiles(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
                                           num_bounces, &spec, dst, nullptr);
@@ -656,7 +745,8 @@ py::dict compute_array_covariance_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
     unsigned long num_bounces, py::object rx_elements, py::object tx_elements, bool los, bool scatter,
-    py::object array_frequency)
+    py::object array_frequency,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     const farr none(std::vector<size_t>{0, 3});
@@ -675,6 +765,7 @@ py::dict compute_array_covariance_py(
     const size_t n_rx = links * 2u * nr * nr, n_tx = links * 2u * nt * nt;
     py::array_t<std::complex<float>> buf(fits ? n_rx + n_tx : (size_t)1);
     std::complex<float> *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_array_covariance", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_array_covariance(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
                                             num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa,
@@ -704,7 +795,8 @@ py::dict compute_array_covariance_py(
 py::dict compute_dominant_paths_py(
     const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
     float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
-    unsigned long num_bounces, unsigned long max_paths, bool los, bool scatter)
+    unsigned long num_bounces, unsigned long max_paths, bool los, bool scatter,
+    py::object patterns)
 {
     const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
     if (max_paths > 0xffffffffUL)
@@ -717,6 +809,7 @@ py::dict compute_dominant_paths_py(
     const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &spec);
     py::array_t<uint64_t> buf((size_t)(n ? n / 8u : 1u));   // (8-byte aligned words; 72 and 16 are multiples of 8)
     uint8_t *dst = reinterpret_cast<uint8_t *>(buf.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
     run_pathsum("compute_dominant_paths", mesh_filepath, [&](Scene *scene) {
         return hrt_compute_dominant_paths(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
                                           num_paths, num_bounces, &spec, dst, nullptr);
@@ -782,7 +875,8 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
-          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("patterns") = py::none());
     m.def("compute_array_channel", &compute_array_channel_py,
           "Antenna-array channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Nr, Nt, 2, num_times, num_freqs)",
@@ -791,7 +885,7 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
-          py::arg("scatter") = true, py::arg("array_frequency") = py::none());
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "
@@ -802,7 +896,7 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("rx_weights"), py::arg("tx_weights"), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
-          py::arg("array_frequency") = py::none());
+          py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_taps", &compute_taps_py,
           "Sampled channel impulse response of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, 2, num_times, num_taps)",
@@ -811,7 +905,8 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("l_min") = 0,
           py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
-          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true);
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("patterns") = py::none());
     m.def("compute_array_taps", &compute_array_taps_py,
           "Antenna-array sampled channel impulse response of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Nr, Nt, 2, num_times, num_taps)",
@@ -821,7 +916,7 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("l_min") = 0, py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
-          py::arg("array_frequency") = py::none());
+          py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_received_signal", &compute_received_signal_py,
           "The samples the receivers see when the transmitters send `signal` (num_tx, Nt, N) through the traced "
           "channel, formed on the device: complex64 (num_rx, Nr, 2, num_out)",
@@ -831,7 +926,7 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("signal"), py::arg("l_min") = 0, py::arg("samples_per_block") = py::none(),
           py::arg("t_start") = 0.0, py::arg("center_frequency") = py::none(), py::arg("num_out") = py::none(),
-          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none());
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_beam_taps", &compute_beam_taps_py,
           "Beamformed (codebook) sampled channel impulse response of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_taps); rx_weights (Br, Nr) is applied conjugated, tx_weights "
@@ -843,7 +938,7 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("rx_weights"), py::arg("tx_weights"), py::arg("l_min") = 0,
           py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
-          py::arg("array_frequency") = py::none());
+          py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_power_profiles", &compute_power_profiles_py,
           "Per-link power statistics of the traced paths, formed on the device: a dict of float64 arrays "
           "(moments, pdp, arrival, departure, buffer)",
@@ -851,7 +946,8 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("tau0"), py::arg("dtau"), py::arg("num_delay_bins"), py::arg("num_zenith_bins") = 0,
-          py::arg("num_azimuth_bins") = 0, py::arg("los") = true, py::arg("scatter") = true);
+          py::arg("num_azimuth_bins") = 0, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("patterns") = py::none());
     m.def("compute_array_covariance", &compute_array_covariance_py,
           "Per-link spatial covariance matrices of an antenna array, formed on the device: a dict of complex64 arrays "
           "(rx (num_rx, num_tx, 2, Nr, Nr), tx (num_rx, num_tx, 2, Nt, Nt), buffer); a side whose elements are None is "
@@ -860,14 +956,15 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("rx_elements") = py::none(), py::arg("tx_elements") = py::none(), py::arg("los") = true,
-          py::arg("scatter") = true, py::arg("array_frequency") = py::none());
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
     m.def("compute_dominant_paths", &compute_dominant_paths_py,
           "The max_paths strongest paths of every link, selected on the device: a dict of arrays (kept, eligible, "
           "power, path, bounce, tri, a_te, a_tm, tau, freq_shift, u_rx, u_tx, buffer)",
           py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
           py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
-          py::arg("max_paths"), py::arg("los") = true, py::arg("scatter") = true);
+          py::arg("max_paths"), py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("patterns") = py::none());
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

@@ -115,6 +115,8 @@ class Tracer:
             self.ws = torch.empty(int(self.layout.total_bytes), dtype=torch.uint8, device=self.device)
         assert self.ws.data_ptr() % 256 == 0
         self.last_times = None
+        self._patterns = None      # (abi.PatternSpec, the device tensor it points into) while patterns are set
+        self.patterned = False     # the workspace's amplitudes are weighted by the patterns (since the last trace)
 
     def close(self):
         if getattr(self, "problem", None):
@@ -146,6 +148,7 @@ class Tracer:
                 C.c_void_p(self.order.data_ptr()) if self.order is not None else None,
                 C.c_void_p(self.ws.data_ptr()), C.c_uint64(self.ws.numel()), C.c_void_p(stream),
                 None, C.c_uint32(self.flags)), "hrt_trace_flags")
+            self._after_trace()
         if timed:
             n = int(times.num_bounce_launches)
             self.last_times = (float(times.los_ms), [float(times.trace_ms[i]) for i in range(n)])
@@ -186,6 +189,62 @@ class Tracer:
             C.c_void_p(self.order.data_ptr()) if self.order is not None else None,
             C.c_void_p(self.ws.data_ptr()), C.c_uint64(self.ws.numel()), C.c_void_p(stream), timer,
             C.c_uint32(self.flags)), "hrt_trace_flags")
+        self._after_trace()
+
+    # ------------------------------------------------------------------ antenna patterns
+    def set_patterns(self, rx=None, tx=None, rx_orientation=None, tx_orientation=None):
+        """Antenna radiation patterns and orientations of the endpoints (hermespy_rt_amd.patterns; include/hermespy_rt.h
+        hrt_pattern): rx / tx a pattern (isotropic(), dipole(), tr38901(), table(values); None: isotropic), one per
+        side; rx_orientation / tx_orientation the world -> local rotations, (3, 3) for all endpoints of the side or
+        (nrx, 3, 3) / (ntx, 3, 3) (rotation(), look_at(); None: identity).  While patterns are set, trace() and
+        trace_with_timer() weight the amplitudes of every unblocked record and every clear LoS entry right after the
+        trace, on the same stream (hrt_apply_patterns), so every path-sum member (channel(), taps(), ...) sums the
+        weighted paths; paths(), records() and los() show the weighted amplitudes too.  A coincident LoS entry has
+        amplitude 1 by definition and is not weighted.  The workspace is not touched here: the patterns hold from the
+        next trace() on (or apply_patterns()).  set_patterns() with no arguments removes them.  Invalid arguments
+        raise ValueError."""
+        from . import patterns as _pt
+        if rx is None and tx is None and rx_orientation is None and tx_orientation is None:
+            self._patterns = None
+            return
+        rx, tx = _pt.check(rx), _pt.check(tx)
+        rr = _pt.orientations(rx_orientation, self.nrx, "rx_orientation")
+        tr = _pt.orientations(tx_orientation, self.ntx, "tx_orientation")
+        parts = [a.reshape(-1) for a in (rx["table"], tx["table"], rr, tr) if a is not None]
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            d = torch.from_numpy(np.concatenate(parts + [np.zeros(1, np.float32)])).to(self.device)
+        at, ptr = d.data_ptr(), []
+        for a in (rx["table"], tx["table"], rr, tr):
+            ptr.append(at if a is not None else None)
+            at += 0 if a is None else 4 * a.size
+        spec = abi.PatternSpec(abi.pattern_struct(rx, ptr[0]), abi.pattern_struct(tx, ptr[1]), ptr[2], ptr[3])
+        self._patterns = (spec, d)
+
+    def apply_patterns(self):
+        """Weight the current workspace by the stored patterns, on the current stream: for a workspace the caller wrote
+        itself after the trace (trace() has applied them already to its own).  RuntimeError if no patterns are set, or
+        if the workspace is already weighted since the last trace (applying twice would weight twice)."""
+        if self._patterns is None:
+            raise RuntimeError("apply_patterns: no patterns are set (set_patterns)")
+        if self.patterned:
+            raise RuntimeError("apply_patterns: the workspace is already weighted since the last trace")
+        self._apply_patterns()
+
+    def _apply_patterns(self):
+        spec, d = self._patterns
+        stream = self.torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_apply_patterns(self.problem, C.byref(self.shard), C.c_void_p(self.ws.data_ptr()),
+                                       C.c_uint64(self.ws.numel()), C.byref(spec), C.c_void_p(stream.cuda_stream))
+        _lib.check(rc, "hrt_apply_patterns")
+        d.record_stream(stream)   # (the kernels read the tables after this call returns)
+        self.patterned = True
+
+    def _after_trace(self):
+        """what follows every trace on its stream: the patterns, while some are set"""
+        self.patterned = False
+        if self._patterns is not None:
+            self._apply_patterns()
 
     def _dirs_ptr(self):
         return (self.dirs_launch if self.flags & _lib.DIRS_IN_LAUNCH_ORDER else self.dirs).data_ptr()

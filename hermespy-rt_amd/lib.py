@@ -39,6 +39,7 @@ EXPORTED = (
     "hrt_covariance_out_floats", "hrt_array_covariance_scratch_bytes", "hrt_array_covariance",
     "hrt_compute_array_covariance",
     "hrt_propagate_out_floats", "hrt_propagate", "hrt_compute_received_signal",
+    "hrt_apply_patterns", "hrt_compute_set_patterns",
 )
 
 HIT_FIELDS = ("ray", "tri", "theta", "fs0", "ox", "oy", "oz", "dx", "dy", "dz",
@@ -316,6 +317,11 @@ def load():
                                               C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                               u32, f32p, u64, u64, f32p, C.POINTER(Stats)]
     L.hrt_compute_received_signal.restype = C.c_int
+    # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
+    L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
+    L.hrt_apply_patterns.restype = C.c_int
+    L.hrt_compute_set_patterns.argtypes = [C.POINTER(abi.PatternsHost)]
+    L.hrt_compute_set_patterns.restype = None
     L.hrt_layout_size.restype = u64
     # the library writes hrt_stats / hrt_layout in full: a mirror of another size would be overrun
     if int(L.hrt_stats_size()) != C.sizeof(Stats) or int(L.hrt_layout_size()) != C.sizeof(Layout):

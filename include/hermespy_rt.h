@@ -485,6 +485,54 @@ int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
                                size_t num_rays, size_t num_bounces, const hrt_dominant_spec *spec,
                                void *out /* hrt_dominant_out_bytes, layout above */, hrt_stats *stats);
 
+/* Antenna radiation patterns and orientations (include/hrt_device.h: hrt_apply_patterns; csrc/hrt_patterns.hip).  A
+ * pattern is a real factor per (path, RX, TX): for every unblocked scatter record p of link (rx, tx), and for every
+ * clear LoS entry,
+ *     w_p = fl32( F_rx(R_rx[rx] u_p^rx) F_tx(R_tx[tx] u_p^tx) ),     a_te, a_tm <- fl32(field * w_p)
+ * for each of the four float amplitude fields (LoS: HRT_LOS_A).  u_p^rx and u_p^tx are the directions the steering
+ * terms of the array families use, both outward look directions from their endpoint: u^rx = directions_rx of the
+ * record, u^tx = the launch direction of the record's global path; LoS: u^tx = HRT_LOS_DIR, u^rx = -u^tx.  R is the
+ * 3 x 3 row-major world -> local rotation of the endpoint (NULL: identity).  In the local frame the boresight is +x,
+ * the zenith theta = atan2(hypot(x, y), z) is measured from +z and the azimuth is phi = atan2(y, x); R u is not
+ * re-normalised (both angles are scale-invariant).  F >= 0 is a linear FIELD amplitude (sqrt of the gain), one
+ * pattern per side shared by all endpoints of that side, g = 10^(gain_db / 20) (formed in double, passed as float):
+ *   HRT_PATTERN_ISOTROPIC  F = g
+ *   HRT_PATTERN_DIPOLE     a half-wave dipole along local z: F = g sqrt(1.64) cos((pi / 2) cos theta) / sin theta;
+ *                          where sin theta < 2^-12 its limit F = g sqrt(1.64) (pi / 4) sin theta
+ *   HRT_PATTERN_TR38901    TR 38.901 table 7.3-1: A_v = -min(12 ((theta_deg - 90) / 65)^2, 30),
+ *                          A_h = -min(12 (phi_deg / 65)^2, 30), A = -min(-(A_v + A_h), 30), F = g 10^((8 + A) / 20)
+ *   HRT_PATTERN_TABLE      float amplitudes [num_zenith][num_azimuth] at theta_i = pi i / (num_zenith - 1)
+ *                          (2 <= num_zenith <= 181) and phi_k = -pi + 2 pi k / num_azimuth, periodic
+ *                          (1 <= num_azimuth <= 360), bilinear; every one-dimensional interpolation is
+ *                          v0 + s (v1 - v0), so a constant table returns its constant exactly
+ * Untouched, bit for bit: blocked records (their direction fields are not read), the slots from a block's count up to
+ * cap, mask words, hit blocks, the tau, DFS and direction fields, blocked LoS entries, and COINCIDENT LoS entries
+ * (status 0): their amplitude is 1 by definition, never read from the workspace, so a coincident link is not weighted.
+ *
+ * hrt_compute_set_patterns sets the patterns the path-sum drop-ins of the calling thread apply (hrt_compute_channel,
+ * _array_channel, _taps, _array_taps, _beam_channel, _beam_taps, _power_profiles, _dominant_paths, _array_covariance,
+ * _received_signal): after each batch's trace and before its sums.  The pointer is kept, not the contents: what it
+ * points to must stay valid until it is cleared (NULL), and is read once at the entry of each call.  compute_paths,
+ * hrt_compute_paths_ex / _interleaved / _list and the export path never see it.  Tables and rotations are HOST arrays
+ * here; rx_rot [num_rx][9] / tx_rot [num_tx][9] may be NULL (identity).  A drop-in call refuses (HRT_E_INVALID) what
+ * hrt_apply_patterns refuses, a table value that is not finite or < 0, and a rotation count that is not the call's
+ * num_rx / num_tx. */
+#define HRT_PATTERN_ISOTROPIC 0u
+#define HRT_PATTERN_DIPOLE 1u
+#define HRT_PATTERN_TR38901 2u
+#define HRT_PATTERN_TABLE 3u
+typedef struct {
+    uint32_t kind, num_zenith, num_azimuth;     /* HRT_PATTERN_*; the table's nodes (HRT_PATTERN_TABLE only) */
+    float gain_db;
+    const float *d_table;                       /* [num_zenith][num_azimuth] (HRT_PATTERN_TABLE only) */
+} hrt_pattern;
+typedef struct {
+    hrt_pattern rx, tx;                         /* d_table: HOST memory here */
+    const float *rx_rot, *tx_rot;               /* host [num_rx][9], [num_tx][9]; NULL: identity */
+    size_t num_rx, num_tx;                      /* the rotation counts (of a non-NULL rotation array) */
+} hrt_patterns_host;
+void hrt_compute_set_patterns(const hrt_patterns_host *patterns);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *hrt_last_error(void);
 

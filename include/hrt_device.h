@@ -443,6 +443,22 @@ int hrt_array_covariance(const hrt_problem *p, const hrt_shard *s, const void *d
                          const hrt_covariance_spec *spec, const hrt_array_spec *arrays, void *d_scratch,
                          uint64_t scratch_bytes, float *d_out, int accumulate, void *stream);
 
+/* ---- antenna radiation patterns and orientations (csrc/host/channel.c, csrc/hrt_patterns.hip) ----
+ * The weights hermespy_rt.h defines (hrt_pattern), applied IN PLACE to the workspace of a finished hrt_trace (its
+ * counts read on the device: no host synchronisation), asynchronous on `stream`: afterwards every path-sum family
+ * above sums the weighted paths.  It applies whenever it is called: applying twice weights twice (a trace writes the
+ * amplitudes anew).  Tables and rotations are DEVICE pointers (d_rx_rot [num_rx][9], d_tx_rot [num_tx][9]; NULL:
+ * identity); their contents are the caller's to ensure (the host entries check them).  No atomics: two runs on equal
+ * inputs give equal bits.  HRT_E_INVALID, before the device is touched: a NULL problem, shard, workspace or spec;
+ * kind > 3; a table with a NULL pointer, num_zenith outside 2 .. 181 or num_azimuth outside 1 .. 360; gain_db not
+ * finite or |gain_db| > 200; a workspace smaller than the layout. */
+typedef struct {
+    hrt_pattern rx, tx;
+    const float *d_rx_rot, *d_tx_rot;
+} hrt_pattern_spec;
+int hrt_apply_patterns(const hrt_problem *p, const hrt_shard *s, void *d_workspace, uint64_t workspace_bytes,
+                       const hrt_pattern_spec *spec, void *stream);
+
 /* ---- the K strongest paths per link from the traced paths (csrc/host/channel.c, csrc/hrt_dominant.hip) ----
  * header and records as hermespy_rt.h defines them (hrt_dominant_spec, hrt_dominant_path,
  * hrt_compute_dominant_paths), hrt_dominant_out_bytes bytes at d_out, selected from the workspace of a finished
