@@ -527,6 +527,84 @@ def run_compute_received_signal(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel,
     return out.view(np.complex64).reshape(nrx, nr, 2, int(num_out))
 
 
+SVD_U, SVD_V = 1, 2              # hrt_svd_spec.want
+SVD_NOT_CONVERGED = 0xFFFFFFFF    # a point's `sweeps` at the cap
+SVD_MAX_SHORT, SVD_MAX_LONG = 16, 64
+
+
+class SvdSpec(C.Structure):
+    """include/hermespy_rt.h hrt_svd_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("want", C.c_uint32)]
+
+
+def svd_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, vectors=True, want=None):
+    if want is None:
+        want = (SVD_U | SVD_V) if vectors else 0
+    return SvdSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs), int(want))
+
+
+def svd_regions(spec):
+    """the byte offsets of sigma, u, v, sweeps and the end of an SVD output (hrt_svd_out_bytes is the last)"""
+    pts = int(spec.num_rx) * int(spec.num_tx) * 2 * int(spec.num_times) * int(spec.num_freqs)
+    nr, nt = int(spec.nr), int(spec.nt)
+    n = min(nr, nt)
+    o1 = pts * n * 4
+    o2 = o1 + (pts * nr * n * 8 if int(spec.want) & SVD_U else 0)
+    o3 = o2 + (pts * nt * n * 8 if int(spec.want) & SVD_V else 0)
+    return 0, o1, o2, o3, o3 + pts * 4
+
+
+def svd_views(buf, spec):
+    """the regions of a flat uint8 SVD buffer (numpy array or torch tensor) as views: sigma float32 [nrx, ntx, n, 2, T,
+    K], u complex64 [nrx, ntx, Nr, n, 2, T, K], v complex64 [nrx, ntx, Nt, n, 2, T, K] (None where not asked for),
+    sweeps [nrx, ntx, 2, T, K] (uint32 in numpy; int32 in torch, where SVD_NOT_CONVERGED reads -1), buffer"""
+    o = svd_regions(spec)
+    nrx, ntx, nr, nt = int(spec.num_rx), int(spec.num_tx), int(spec.nr), int(spec.nt)
+    T, K, n = int(spec.num_times), int(spec.num_freqs), min(nr, nt)
+    if isinstance(buf, np.ndarray):
+        f32, c64, u32 = np.float32, np.complex64, np.uint32
+    else:
+        import torch
+        f32, c64, u32 = torch.float32, torch.complex64, torch.int32
+    out = {"sigma": buf[o[0]:o[1]].view(f32).reshape(nrx, ntx, n, 2, T, K), "u": None, "v": None,
+           "sweeps": buf[o[3]:o[4]].view(u32).reshape(nrx, ntx, 2, T, K), "buffer": buf}
+    if int(spec.want) & SVD_U:
+        out["u"] = buf[o[1]:o[2]].view(c64).reshape(nrx, ntx, nr, n, 2, T, K)
+    if int(spec.want) & SVD_V:
+        out["v"] = buf[o[2]:o[3]].view(c64).reshape(nrx, ntx, nt, n, 2, T, K)
+    return out
+
+
+def run_channel_svd(lib, device, spec, d_H, d_out, stream=None):
+    """hrt_channel_svd through ctypes on device pointers (integers or None).  Raises RuntimeError("hrt_channel_svd
+    failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_channel_svd(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                             C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_channel_svd failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_channel_svd(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                            rx_elements, tx_elements, vectors=True, want=None, array_frequency=None, stats=None):
+    """hrt_compute_channel_svd through ctypes -> svd_views of a uint8 numpy buffer (spec: a ChannelSpec, as for
+    run_compute_array_channel; array_frequency defaults to the carrier).  Raises
+    RuntimeError("hrt_compute_channel_svd failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    sv = svd_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), vectors, want)
+    extra += (C.c_uint32(int(sv.want)),)
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    fits = (0 < min(nr, nt) <= SVD_MAX_SHORT and max(nr, nt) <= SVD_MAX_LONG and 0 < nr * nt * grid <= 1 << 24
+            and 0 < nrx * ntx * 2 * grid < 1 << 31 and not int(sv.want) & ~(SVD_U | SVD_V))
+    out = _run_pathsum(lib, "hrt_compute_channel_svd", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths,
+                       num_bounces, spec, (svd_regions(sv)[4],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_channel_svd accepted a call beyond its limits")
+    return svd_views(out, sv)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

@@ -1,6 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
- * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate;
+ * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
+ * hrt_channel_svd;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
@@ -34,6 +35,7 @@
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
+#include "../hrt_svd.h"
 #include "../hrt_taps.h"
 
 /* ------------------------------------------------------------------ what the path-sum families share (hrt_pathsum.h) */
@@ -1012,6 +1014,122 @@ int hrt_compute_received_signal(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx
     job.aux = &pj;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       y, stats, t_begin, "hrt_array_taps", "hrt_compute_received_signal");
+}
+
+/* ------------------------------------------------------------------ per-point SVD (hrt_channel_svd) */
+
+/* the checks of an SVD call (`who`); device pointers are not read */
+static int svd_check(const hrt_svd_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->num_times == 0 || sp->num_freqs == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, num_times and num_freqs must be > 0", who);
+    const uint32_t m = sp->nr > sp->nt ? sp->nr : sp->nt, n = sp->nr > sp->nt ? sp->nt : sp->nr;
+    if (n < 1 || n > HRT_SVD_MAX_SHORT || m > HRT_SVD_MAX_LONG)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u and nt = %u (the smaller 1 .. %u, the larger 1 .. %u)", who, sp->nr,
+                        sp->nt, HRT_SVD_MAX_SHORT, HRT_SVD_MAX_LONG);
+    const uint64_t grid = (uint64_t)sp->num_times * sp->num_freqs;   /* < 2^64 */
+    if (grid > HRT_SVD_MAX_POINTS || (uint64_t)sp->nr * sp->nt * grid > HRT_SVD_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr * nt * num_times * num_freqs > 2^24", who);
+    if (sp->want & ~(HRT_SVD_U | HRT_SVD_V))
+        return hrt_fail(HRT_E_INVALID, "%s: want = 0x%x has unknown bits", who, sp->want);
+    if ((uint64_t)sp->num_rx * sp->num_tx >= (1ull << 31) / (2u * grid))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 points or more", who);
+    return HRT_OK;
+}
+
+/* the regions of the output: byte offsets of sigma, u, v, sweeps and the end (hermespy_rt.h) */
+static void svd_regions(const hrt_svd_spec *sp, uint64_t off[5])
+{
+    const uint64_t points = (uint64_t)sp->num_rx * sp->num_tx * 2u * sp->num_times * sp->num_freqs;
+    const uint64_t n = sp->nr > sp->nt ? sp->nt : sp->nr;
+    off[0] = 0;
+    off[1] = off[0] + points * n * 4u;
+    off[2] = off[1] + ((sp->want & HRT_SVD_U) ? points * sp->nr * n * 8u : 0u);
+    off[3] = off[2] + ((sp->want & HRT_SVD_V) ? points * sp->nt * n * 8u : 0u);
+    off[4] = off[3] + points * 4u;
+}
+
+uint64_t hrt_svd_out_bytes(const hrt_svd_spec *spec)
+{
+    if (!spec) return 0;
+    uint64_t off[5];
+    svd_regions(spec, off);
+    return off[4];
+}
+
+int hrt_channel_svd(int device, const hrt_svd_spec *spec, const void *d_H, void *d_out, void *stream)
+{
+    int rc = svd_check(spec, "hrt_channel_svd");
+    if (rc) return rc;
+    if (!d_H || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_channel_svd: NULL device pointer");
+    uint64_t off[5];
+    svd_regions(spec, off);
+    hrt_ksvd K;
+    memset(&K, 0, sizeof K);
+    K.nr = spec->nr; K.nt = spec->nt;
+    K.tall = spec->nr >= spec->nt;
+    K.m = K.tall ? K.nr : K.nt; K.n = K.tall ? K.nt : K.nr;
+    const uint32_t g = hrt_svd_form(K.nr, K.nt);
+    K.mk = (K.m + g - 1u) / g; K.nk = (K.n + g - 1u) / g;
+    K.pts = 2ull * spec->num_times * spec->num_freqs;
+    K.points = (uint64_t)spec->num_rx * spec->num_tx * K.pts;
+    K.H = (const float *)d_H;
+    K.sigma = (float *)((char *)d_out + off[0]);
+    K.u = (spec->want & HRT_SVD_U) ? (float *)((char *)d_out + off[1]) : NULL;
+    K.v = (spec->want & HRT_SVD_V) ? (float *)((char *)d_out + off[2]) : NULL;
+    K.sweeps = (uint32_t *)((char *)d_out + off[3]);
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_svd(&K, g, stream), "SVD kernel");
+    return HRT_OK;
+}
+
+/* after the last batch: H stays at d_H; the decomposition runs once, only its result comes down */
+static int svd_job_deliver(const ch_job *j, int device, const void *d_H, void *out)
+{
+    const hrt_svd_spec *sp = (const hrt_svd_spec *)j->aux;
+    const uint64_t bytes = hrt_svd_out_bytes(sp);
+    void *d_svd = NULL;
+    int rc = hrt_device_malloc(device, &d_svd, bytes);
+    if (!rc) rc = hrt_channel_svd(device, sp, d_H, d_svd, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_svd, bytes);
+    if (d_svd) hrt_device_free(device, d_svd);
+    return rc;
+}
+
+int hrt_compute_channel_svd(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                            const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                            const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el, size_t nt,
+                            double f_a, uint32_t want, void *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = array_check(spec, &a))) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_svd: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_svd: num_rx or num_tx > 2^32");
+    hrt_svd_spec sv;
+    memset(&sv, 0, sizeof sv);
+    sv.num_rx = (uint32_t)nrx; sv.num_tx = (uint32_t)ntx;
+    sv.nr = (uint32_t)nr; sv.nt = (uint32_t)nt;
+    sv.num_times = spec->num_times; sv.num_freqs = spec->num_freqs;
+    sv.want = want;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_channel) */
+    if (nrx && ntx && (rc = svd_check(&sv, "hrt_compute_channel_svd"))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.deliver = svd_job_deliver;
+    job.aux = &sv;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_svd");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

@@ -447,6 +447,74 @@ py::array_t<std::complex<float>> compute_array_channel_py(
     return out;
 }
 
+// compute_channel_svd: the per-point MIMO SVD of compute_array_channel's H, formed on the device (extension; see
+// hrt_compute_channel_svd in hermespy_rt.h): a dict of views of one buffer -- sigma float32 (num_rx, num_tx, n, 2,
+// num_times, num_freqs) with n = min(Nr, Nt); u complex64 (num_rx, num_tx, Nr, n, 2, num_times, num_freqs) and v
+// (num_rx, num_tx, Nt, n, ...), both None with vectors=False; sweeps uint32 (num_rx, num_tx, 2, num_times, num_freqs)
+// -- and the buffer itself (uint8).
+py::dict compute_channel_svd_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency, bool vectors,
+    py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL || num_rx > 0xffffffffUL || num_tx > 0xffffffffUL)
+        throw std::invalid_argument("num_rx, num_tx, num_freqs and num_times must fit 32 bits");
+    const array_elements a(rx_elements, tx_elements);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    const uint32_t want = vectors ? (HRT_SVD_U | HRT_SVD_V) : 0u;
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t nr = a.nr, nt = a.nt, n = nr < nt ? nr : nt, big = nr < nt ? nt : nr;
+    const size_t pts = (size_t)num_rx * num_tx * 2u * num_times * num_freqs;
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs) && n <= 16u && big <= 64u && pts < (1ull << 31);
+    hrt_svd_spec sv{};
+    sv.num_rx = (uint32_t)num_rx; sv.num_tx = (uint32_t)num_tx; sv.nr = (uint32_t)nr; sv.nt = (uint32_t)nt;
+    sv.num_times = (uint32_t)num_times; sv.num_freqs = (uint32_t)num_freqs; sv.want = want;
+    py::array_t<uint8_t> buf(fits ? (size_t)hrt_svd_out_bytes(&sv) : (size_t)1);
+    uint8_t *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_channel_svd", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_channel_svd(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx, num_paths,
+                                       num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, want, dst, nullptr);
+    });
+    size_t off = 0;
+    auto view = [&](auto zero, std::vector<size_t> shape) {
+        using T = decltype(zero);
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(T);
+        size_t count = 1;
+        for (size_t k = shape.size(); k-- > 0;) {
+            strides[k] = st;
+            st *= (py::ssize_t)shape[k];
+            count *= shape[k];
+        }
+        py::array_t<T> v(shape, strides, reinterpret_cast<T *>(dst + off), buf);
+        off += count * sizeof(T);
+        return v;
+    };
+    const size_t R = num_rx, X = num_tx, T_ = num_times, K_ = num_freqs;
+    py::dict d;
+    d["sigma"] = view(0.0f, {R, X, n, 2, T_, K_});
+    if (vectors) {
+        d["u"] = view(std::complex<float>(), {R, X, nr, n, 2, T_, K_});
+        d["v"] = view(std::complex<float>(), {R, X, nt, n, 2, T_, K_});
+    } else {
+        d["u"] = py::none();
+        d["v"] = py::none();
+    }
+    d["sweeps"] = view((uint32_t)0, {R, X, 2, T_, K_});
+    d["buffer"] = buf;
+    return d;
+}
+
 // a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
 using carr = py::array_t<std::complex<float>, py::array::c_style>;
 carr as_weights(const py::array &w, size_t n_elements, const char *name)
@@ -886,6 +954,16 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
           py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
           py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none());
+    m.def("compute_channel_svd", &compute_channel_svd_py,
+          "Per-point MIMO SVD of the antenna-array channel, formed on the device: a dict of views of one buffer -- "
+          "sigma (num_rx, num_tx, n, 2, num_times, num_freqs), u (.., Nr, n, ..), v (.., Nt, n, ..), sweeps, buffer",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("vectors") = true,
+          py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "

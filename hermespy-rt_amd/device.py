@@ -732,6 +732,61 @@ class Tracer:
             h = self.taps(fs, num_taps, **kw)
         return self.apply_taps(h, signal, l_min, samples_per_block, num_out, out, accumulate)
 
+    def svd(self, H, vectors=True, out=None):
+        """Per-point MIMO SVD of an array channel on the device (hrt_channel_svd; include/hermespy_rt.h
+        hrt_compute_channel_svd): for every link, polarisation, time sample and frequency,
+
+            H[rx, tx, :, :, pol, m, k] = u diag(sigma) v^H,   sigma descending, >= 0,   n = min(Nr, Nt)
+
+            sigma   float32   [nrx, ntx, n, 2, T, K]
+            u       complex64 [nrx, ntx, Nr, n, 2, T, K]      (None with vectors=False)
+            v       complex64 [nrx, ntx, Nt, n, 2, T, K]      (None with vectors=False)
+            sweeps  int32     [nrx, ntx, 2, T, K]             Jacobi sweeps that rotated; -1 (abi.SVD_NOT_CONVERGED as a
+                                                              signed word) where the cap was reached
+
+        H: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, T, K] (array_channel(), or any tensor of that layout; no
+        trace is needed); min(Nr, Nt) <= 16, max(Nr, Nt) <= 64.  One-sided Jacobi in float32: a null column (sigma_i <=
+        max(Nr, Nt) 2^-23 sigma_0) has an exactly zero vector on the long side; no gauge beyond sigma >= 0 is fixed.
+        The SVD is not additive: the SVD of one shard's partial H is not the channel's, so a sharded caller sums H over
+        the shards first and then calls svd().  Returns a dict of views of one flat uint8 device tensor, itself under
+        "buffer", enqueued on the current stream; `out` (such a flat tensor) is written in place.
+        hermespy_rt_amd.mimo has the host-side reference and what is read from the decomposition.  Invalid arguments
+        raise ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        spec = abi.svd_spec(nrx, ntx, nr, nt, T, K, vectors)
+        H = H.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and 0 < min(nr, nt) <= abi.SVD_MAX_SHORT and max(nr, nt) <= abi.SVD_MAX_LONG
+        need = abi.svd_regions(spec)[4] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_channel_svd(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_channel_svd: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_channel_svd")
+        H.record_stream(stream)     # (the kernel reads it after this call returns)
+        return abi.svd_views(out, spec)
+
+    def channel_svd(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                    scatter=True, array_frequency=None, vectors=True):
+        """The per-point MIMO SVD of the last trace's array channel, without leaving the device: bit for bit
+        svd(array_channel(...), vectors) with array_channel()'s arguments.  On a sharded trace this is the SVD of the
+        shard's partial channel, which is not the channel's: sum array_channel() over the shards and call svd()."""
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.svd(H, vectors)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

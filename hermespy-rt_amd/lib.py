@@ -39,6 +39,7 @@ EXPORTED = (
     "hrt_covariance_out_floats", "hrt_array_covariance_scratch_bytes", "hrt_array_covariance",
     "hrt_compute_array_covariance",
     "hrt_propagate_out_floats", "hrt_propagate", "hrt_compute_received_signal",
+    "hrt_svd_out_bytes", "hrt_channel_svd", "hrt_compute_channel_svd",
     "hrt_apply_patterns", "hrt_compute_set_patterns",
 )
 
@@ -317,6 +318,16 @@ def load():
                                               C.c_size_t, C.c_size_t, tpp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                               u32, f32p, u64, u64, f32p, C.POINTER(Stats)]
     L.hrt_compute_received_signal.restype = C.c_int
+    # per-point SVD of an array channel (hrt_svd_spec: abi.SvdSpec)
+    svp = C.POINTER(abi.SvdSpec)
+    L.hrt_svd_out_bytes.argtypes = [svp]
+    L.hrt_svd_out_bytes.restype = u64
+    L.hrt_channel_svd.argtypes = [C.c_int, svp, vp, vp, vp]
+    L.hrt_channel_svd.restype = C.c_int
+    L.hrt_compute_channel_svd.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t, C.c_size_t,
+                                          C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
+                                          u32, vp, C.POINTER(Stats)]
+    L.hrt_compute_channel_svd.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

@@ -362,6 +362,51 @@ int hrt_compute_received_signal(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx
                                 uint64_t num_out, float *y /* host, complex [num_rx][Nr][2][num_out] */,
                                 hrt_stats *stats);
 
+/* Per-point MIMO SVD of the array channel, formed on the device (include/hrt_device.h: hrt_channel_svd).  For every
+ * link, polarisation, time sample and frequency, one "point" is the SVD of the Nr x Nt matrix
+ * H[rx][tx][:][:][pol][m][k] of hrt_compute_array_channel's layout.  With n = min(Nr, Nt) the outputs keep that axis
+ * order (the point axes innermost), in one flat buffer of hrt_svd_out_bytes bytes, the regions in this order (a region
+ * not asked for in `want` is absent, size 0):
+ *   sigma   float  [num_rx][num_tx][n][2][T][K]        descending in the n axis, >= 0
+ *   u       complex [num_rx][num_tx][Nr][n][2][T][K]   left vectors   (HRT_SVD_U)
+ *   v       complex [num_rx][num_tx][Nt][n][2][T][K]   right vectors  (HRT_SVD_V)
+ *   sweeps  uint32 [num_rx][num_tx][2][T][K]           Jacobi sweeps that rotated; HRT_SVD_NOT_CONVERGED at the cap
+ *   H = u diag(sigma) v^H
+ * Algorithm (a definition: the tests emulate it): one-sided (Hestenes) complex Jacobi in float on A = H where
+ * Nr >= Nt, else H^H (m x n, m = max(Nr, Nt)); never through the Gram matrix.  Column pairs (p, q), p < q, are rotated
+ * in cyclic order and the rotations accumulated in an n x n unitary, so the short side's vectors are always a full
+ * unitary matrix and the long side's the normalised columns of the rotated A.  With eps = max(m, n) 2^-23, a pair is
+ * skipped where |a_p^H a_q| <= (eps / 2) |a_p| |a_q|, or where either column's squared norm is at or below eps^2 times
+ * the largest column's squared norm at the start of the sweep (a rank-deficient channel, such as a LoS-only link, is
+ * not rotated noise against noise).  A point is finished by the first sweep that rotates nothing; at most
+ * HRT_SVD_MAX_SWEEPS (csrc/hrt_svd.h) sweeps are made, and a point that has rotated in all of them, or whose column
+ * norms are not finite (NaN, Inf, or squares beyond float), reports HRT_SVD_NOT_CONVERGED and writes finite or NaN
+ * values.  Order: sigma descending, equal values by their original column index, the vectors with them.  Column i is
+ * null iff sigma_i <= eps sigma_0: its long-side vector is exact zeros (sigma_i is written as computed, the short side
+ * stays unitary); H = 0 gives sigma = 0, the identity on the short side and zeros on the long side.  No gauge beyond
+ * sigma real and >= 0 is fixed.  A point's bits depend on its own matrix only (not on its neighbours, the batch or
+ * the launch); two calls give the same bytes.
+ * hrt_compute_channel_svd traces and batches exactly as hrt_compute_array_channel does, keeps the accumulated H on the
+ * device and decomposes once after the last batch (the SVD is not additive over batches); only the result is copied
+ * back.  HRT_E_INVALID, before the device is touched: every refusal of hrt_compute_array_channel; a NULL out; every
+ * refusal of hrt_channel_svd (include/hrt_device.h). */
+#define HRT_SVD_U 1u
+#define HRT_SVD_V 2u
+#define HRT_SVD_NOT_CONVERGED 0xffffffffu
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t want;                              /* HRT_SVD_U | HRT_SVD_V (0: singular values only) */
+} hrt_svd_spec;
+uint64_t hrt_svd_out_bytes(const hrt_svd_spec *spec);   /* 0 for NULL */
+int hrt_compute_channel_svd(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                            const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                            size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                            const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                            size_t num_tx_elements, double array_frequency_hz, uint32_t want,
+                            void *out /* host, hrt_svd_out_bytes bytes, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

@@ -407,6 +407,17 @@ int hrt_beam_taps(const hrt_problem *p, const hrt_shard *s, const void *d_worksp
 int hrt_propagate(int device, const hrt_propagate_spec *spec, const void *d_taps, const void *d_signal, void *d_out,
                   int accumulate, void *stream);
 
+/* ---- per-point MIMO SVD of an array channel (csrc/host/channel.c, csrc/hrt_svd.hip) ----
+ * sigma, u, v and sweeps as hermespy_rt.h defines them (hrt_svd_spec, hrt_compute_channel_svd), hrt_svd_out_bytes
+ * bytes at d_out, from d_H (complex [num_rx][num_tx][nr][nt][2][num_times][num_freqs]: the output of
+ * hrt_array_channel, or any tensor of that layout), both DEVICE pointers, asynchronous on `stream` of `device`.  It
+ * needs no problem: it reads only the tensor, and does not write it.  Every byte of d_out is written exactly once; no
+ * scratch and no atomics, so two calls with the same input give the same bytes.  The SVD of one shard's partial H is
+ * not the channel's SVD: a sharded caller sums H first.  HRT_E_INVALID, before the device is touched: a NULL pointer;
+ * num_rx, num_tx, num_times or num_freqs equal to 0; min(nr, nt) outside 1..16; max(nr, nt) outside 1..64;
+ * nr * nt * num_times * num_freqs > 2^24; `want` with bits other than HRT_SVD_U | HRT_SVD_V; 2^31 points or more. */
+int hrt_channel_svd(int device, const hrt_svd_spec *spec, const void *d_H, void *d_out, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
