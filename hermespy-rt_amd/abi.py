@@ -605,6 +605,97 @@ def run_compute_channel_svd(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_g
     return svd_views(out, sv)
 
 
+EQ_ZF, EQ_LMMSE = 0, 1                 # hrt_equalizer_spec.kind
+EQ_W = 1                               # hrt_equalizer_spec.flags
+EQ_SINGULAR, EQ_NONFINITE = 1, 2       # a point's `status`
+EQ_MAX_NT, EQ_MAX_NR = 16, 64
+EQ_KINDS = {"zf": EQ_ZF, "lmmse": EQ_LMMSE}
+
+
+class EqualizerSpec(C.Structure):
+    """include/hermespy_rt.h hrt_equalizer_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32),
+                ("noise", C.c_float)]
+
+
+def equalizer_kind(kind):
+    """"zf" / "lmmse" (any case) or the constant itself -> hrt_equalizer_spec.kind; an unknown name raises ValueError,
+    an unknown number is passed on for the library to refuse"""
+    if isinstance(kind, str):
+        if kind.lower() not in EQ_KINDS:
+            raise ValueError("kind must be 'zf' or 'lmmse', got %r" % (kind,))
+        return EQ_KINDS[kind.lower()]
+    return int(kind)
+
+
+def equalizer_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, noise, kind=EQ_LMMSE, weights=True, flags=None):
+    if flags is None:
+        flags = EQ_W if weights else 0
+    return EqualizerSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs),
+                         equalizer_kind(kind), int(flags), float(noise))
+
+
+def equalizer_regions(spec):
+    """the byte offsets of W, sinr, status and the end of an equalizer output (hrt_equalizer_out_bytes is the last)"""
+    pts = int(spec.num_rx) * int(spec.num_tx) * 2 * int(spec.num_times) * int(spec.num_freqs)
+    nr, nt = int(spec.nr), int(spec.nt)
+    o1 = pts * nt * nr * 8 if int(spec.flags) & EQ_W else 0
+    o2 = o1 + pts * nt * 4
+    return 0, o1, o2, o2 + pts * 4
+
+
+def equalizer_views(buf, spec):
+    """the regions of a flat uint8 equalizer buffer (numpy array or torch tensor) as views: W complex64 [nrx, ntx, Nt,
+    Nr, 2, T, K] (None where not asked for), sinr float32 [nrx, ntx, Nt, 2, T, K], status [nrx, ntx, 2, T, K] (uint32
+    in numpy, int32 in torch), buffer"""
+    o = equalizer_regions(spec)
+    nrx, ntx, nr, nt = int(spec.num_rx), int(spec.num_tx), int(spec.nr), int(spec.nt)
+    T, K = int(spec.num_times), int(spec.num_freqs)
+    if isinstance(buf, np.ndarray):
+        f32, c64, u32 = np.float32, np.complex64, np.uint32
+    else:
+        import torch
+        f32, c64, u32 = torch.float32, torch.complex64, torch.int32
+    out = {"W": None, "sinr": buf[o[1]:o[2]].view(f32).reshape(nrx, ntx, nt, 2, T, K),
+           "status": buf[o[2]:o[3]].view(u32).reshape(nrx, ntx, 2, T, K), "buffer": buf}
+    if int(spec.flags) & EQ_W:
+        out["W"] = buf[o[0]:o[1]].view(c64).reshape(nrx, ntx, nt, nr, 2, T, K)
+    return out
+
+
+def run_channel_equalizer(lib, device, spec, d_H, d_out, stream=None):
+    """hrt_channel_equalizer through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_channel_equalizer failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_channel_equalizer(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                                   C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_channel_equalizer failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_channel_equalizer(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                                  rx_elements, tx_elements, noise, kind=EQ_LMMSE, weights=True, flags=None,
+                                  array_frequency=None, stats=None):
+    """hrt_compute_channel_equalizer through ctypes -> equalizer_views of a uint8 numpy buffer (spec: a ChannelSpec, as
+    for run_compute_array_channel; array_frequency defaults to the carrier).  The equalizer is formed once, of the H
+    accumulated over all batches: it is not additive.  Raises RuntimeError("hrt_compute_channel_equalizer failed
+    (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    eq = equalizer_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), noise, kind, weights, flags)
+    extra += (C.c_uint32(int(eq.kind)), C.c_uint32(int(eq.flags)), C.c_float(float(noise)))
+    # (an output too large for the host is refused by the library's limits first: allocate only what passes them)
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    fits = (0 < nt <= EQ_MAX_NT and 0 < nr <= EQ_MAX_NR and 0 < nr * nt * grid <= 1 << 24
+            and 0 < nrx * ntx * 2 * grid < 1 << 31 and not int(eq.flags) & ~EQ_W and int(eq.kind) in (EQ_ZF, EQ_LMMSE)
+            and (int(eq.kind) == EQ_LMMSE or nr >= nt) and 0.0 < float(eq.noise) < float("inf"))
+    out = _run_pathsum(lib, "hrt_compute_channel_equalizer", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (equalizer_regions(eq)[3],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_channel_equalizer accepted a call beyond its limits")
+    return equalizer_views(out, eq)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

@@ -1,7 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd;
+ * hrt_channel_svd, hrt_channel_equalizer;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
@@ -31,6 +31,7 @@
 #include "../hrt_channel.h"
 #include "../hrt_covariance.h"
 #include "../hrt_dominant.h"
+#include "../hrt_equalizer.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
@@ -1130,6 +1131,125 @@ int hrt_compute_channel_svd(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos
     job.aux = &sv;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_svd");
+}
+
+/* ------------------------------------------------------------------ per-point equalizers (hrt_channel_equalizer) */
+
+/* the checks of an equalizer call (`who`); device pointers are not read */
+static int eq_check(const hrt_equalizer_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->num_times == 0 || sp->num_freqs == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, num_times and num_freqs must be > 0", who);
+    if (sp->nt < 1 || sp->nt > HRT_EQ_MAX_NT || sp->nr < 1 || sp->nr > HRT_EQ_MAX_NR)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u and nt = %u (nr 1 .. %u, nt 1 .. %u)", who, sp->nr, sp->nt,
+                        HRT_EQ_MAX_NR, HRT_EQ_MAX_NT);
+    if (sp->kind != HRT_EQ_ZF && sp->kind != HRT_EQ_LMMSE)
+        return hrt_fail(HRT_E_INVALID, "%s: kind = %u is neither HRT_EQ_ZF nor HRT_EQ_LMMSE", who, sp->kind);
+    if (sp->kind == HRT_EQ_ZF && sp->nr < sp->nt)
+        return hrt_fail(HRT_E_INVALID, "%s: zero-forcing needs nr >= nt (nr = %u, nt = %u)", who, sp->nr, sp->nt);
+    if (sp->flags & ~HRT_EQ_W)
+        return hrt_fail(HRT_E_INVALID, "%s: flags = 0x%x has unknown bits", who, sp->flags);
+    if (!(sp->noise > 0.f) || !(sp->noise <= 3.402823466e+38f))
+        return hrt_fail(HRT_E_INVALID, "%s: noise = %g must be finite and > 0", who, (double)sp->noise);
+    const uint64_t grid = (uint64_t)sp->num_times * sp->num_freqs;   /* < 2^64 */
+    if (grid > HRT_EQ_MAX_POINTS || (uint64_t)sp->nr * sp->nt * grid > HRT_EQ_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr * nt * num_times * num_freqs > 2^24", who);
+    if ((uint64_t)sp->num_rx * sp->num_tx >= (1ull << 31) / (2u * grid))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 points or more", who);
+    return HRT_OK;
+}
+
+/* the regions of the output: byte offsets of W, sinr, status and the end (hermespy_rt.h) */
+static void eq_regions(const hrt_equalizer_spec *sp, uint64_t off[4])
+{
+    const uint64_t points = (uint64_t)sp->num_rx * sp->num_tx * 2u * sp->num_times * sp->num_freqs;
+    off[0] = 0;
+    off[1] = off[0] + ((sp->flags & HRT_EQ_W) ? points * sp->nt * sp->nr * 8u : 0u);
+    off[2] = off[1] + points * sp->nt * 4u;
+    off[3] = off[2] + points * 4u;
+}
+
+uint64_t hrt_equalizer_out_bytes(const hrt_equalizer_spec *spec)
+{
+    if (!spec) return 0;
+    uint64_t off[4];
+    eq_regions(spec, off);
+    return off[3];
+}
+
+int hrt_channel_equalizer(int device, const hrt_equalizer_spec *spec, const void *d_H, void *d_out, void *stream)
+{
+    int rc = eq_check(spec, "hrt_channel_equalizer");
+    if (rc) return rc;
+    if (!d_H || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_channel_equalizer: NULL device pointer");
+    uint64_t off[4];
+    eq_regions(spec, off);
+    hrt_kequalizer K;
+    memset(&K, 0, sizeof K);
+    K.nr = spec->nr; K.nt = spec->nt;
+    const uint32_t g = hrt_equalizer_form(K.nr, K.nt);
+    K.mk = (K.nr + g - 1u) / g; K.nk = (K.nt + g - 1u) / g;
+    K.lmmse = spec->kind == HRT_EQ_LMMSE;
+    K.n0 = spec->noise;
+    K.pts = 2ull * spec->num_times * spec->num_freqs;
+    K.points = (uint64_t)spec->num_rx * spec->num_tx * K.pts;
+    K.H = (const float *)d_H;
+    K.W = (spec->flags & HRT_EQ_W) ? (float *)((char *)d_out + off[0]) : NULL;
+    K.sinr = (float *)((char *)d_out + off[1]);
+    K.status = (uint32_t *)((char *)d_out + off[2]);
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_equalizer(&K, g, stream), "equalizer kernel");
+    return HRT_OK;
+}
+
+/* after the last batch: H stays at d_H; the equalizer is formed once, only its result comes down */
+static int eq_job_deliver(const ch_job *j, int device, const void *d_H, void *out)
+{
+    const hrt_equalizer_spec *sp = (const hrt_equalizer_spec *)j->aux;
+    const uint64_t bytes = hrt_equalizer_out_bytes(sp);
+    void *d_eq = NULL;
+    int rc = hrt_device_malloc(device, &d_eq, bytes);
+    if (!rc) rc = hrt_channel_equalizer(device, sp, d_H, d_eq, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_eq, bytes);
+    if (d_eq) hrt_device_free(device, d_eq);
+    return rc;
+}
+
+int hrt_compute_channel_equalizer(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                  const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                  const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                                  size_t nt, double f_a, uint32_t kind, uint32_t flags, float noise, void *out,
+                                  hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = array_check(spec, &a))) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_equalizer: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_equalizer: num_rx or num_tx > 2^32");
+    hrt_equalizer_spec eq;
+    memset(&eq, 0, sizeof eq);
+    eq.num_rx = (uint32_t)nrx; eq.num_tx = (uint32_t)ntx;
+    eq.nr = (uint32_t)nr; eq.nt = (uint32_t)nt;
+    eq.num_times = spec->num_times; eq.num_freqs = spec->num_freqs;
+    eq.kind = kind; eq.flags = flags; eq.noise = noise;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_channel) */
+    if (nrx && ntx && (rc = eq_check(&eq, "hrt_compute_channel_equalizer"))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.deliver = eq_job_deliver;
+    job.aux = &eq;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_equalizer");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

@@ -515,6 +515,72 @@ py::dict compute_channel_svd_py(
     return d;
 }
 
+// compute_channel_equalizer: the per-point linear MIMO equalizer (kind "zf" or "lmmse") of compute_array_channel's H and
+// its post-equalisation SINR, formed on the device (extension; see hrt_compute_channel_equalizer in hermespy_rt.h): a
+// dict of views of one buffer -- W complex64 (num_rx, num_tx, Nt, Nr, 2, num_times, num_freqs), None with
+// weights=False; sinr float32 (num_rx, num_tx, Nt, 2, num_times, num_freqs); status uint32 (num_rx, num_tx, 2,
+// num_times, num_freqs) -- and the buffer itself (uint8).  The equalizer is formed once, of the H of all batches.
+py::dict compute_channel_equalizer_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    float noise, const std::string &kind, double t0, double dt, unsigned long num_times, bool los, bool scatter,
+    py::object array_frequency, bool weights, py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL || num_rx > 0xffffffffUL || num_tx > 0xffffffffUL)
+        throw std::invalid_argument("num_rx, num_tx, num_freqs and num_times must fit 32 bits");
+    if (kind != "zf" && kind != "lmmse") throw std::invalid_argument("kind must be 'zf' or 'lmmse'");
+    const array_elements a(rx_elements, tx_elements);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    const uint32_t k = kind == "zf" ? HRT_EQ_ZF : HRT_EQ_LMMSE, flags = weights ? HRT_EQ_W : 0u;
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t nr = a.nr, nt = a.nt;
+    const size_t pts = (size_t)num_rx * num_tx * 2u * num_times * num_freqs;
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs) && nt <= 16u && nr <= 64u && pts < (1ull << 31);
+    hrt_equalizer_spec eq{};
+    eq.num_rx = (uint32_t)num_rx; eq.num_tx = (uint32_t)num_tx; eq.nr = (uint32_t)nr; eq.nt = (uint32_t)nt;
+    eq.num_times = (uint32_t)num_times; eq.num_freqs = (uint32_t)num_freqs; eq.kind = k; eq.flags = flags;
+    eq.noise = noise;
+    py::array_t<uint8_t> buf(fits ? (size_t)hrt_equalizer_out_bytes(&eq) : (size_t)1);
+    uint8_t *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_channel_equalizer", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_channel_equalizer(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                             num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, k, flags,
+                                             noise, dst, nullptr);
+    });
+    size_t off = 0;
+    auto view = [&](auto zero, std::vector<size_t> shape) {
+        using T = decltype(zero);
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(T);
+        size_t count = 1;
+        for (size_t i = shape.size(); i-- > 0;) {
+            strides[i] = st;
+            st *= (py::ssize_t)shape[i];
+            count *= shape[i];
+        }
+        py::array_t<T> v(shape, strides, reinterpret_cast<T *>(dst + off), buf);
+        off += count * sizeof(T);
+        return v;
+    };
+    const size_t R = num_rx, X = num_tx, T_ = num_times, K_ = num_freqs;
+    py::dict d;
+    if (weights) d["W"] = view(std::complex<float>(), {R, X, nt, nr, 2, T_, K_});
+    else d["W"] = py::none();
+    d["sinr"] = view(0.0f, {R, X, nt, 2, T_, K_});
+    d["status"] = view((uint32_t)0, {R, X, 2, T_, K_});
+    d["buffer"] = buf;
+    return d;
+}
+
 // a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
 using carr = py::array_t<std::complex<float>, py::array::c_style>;
 carr as_weights(const py::array &w, size_t n_elements, const char *name)
@@ -964,6 +1030,17 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
           py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("vectors") = true,
           py::arg("patterns") = py::none());
+    m.def("compute_channel_equalizer", &compute_channel_equalizer_py,
+          "Per-point linear MIMO equalizer (kind 'zf' or 'lmmse') of the antenna-array channel and its SINR, formed on "
+          "the device: a dict of views of one buffer -- W (num_rx, num_tx, Nt, Nr, 2, num_times, num_freqs), "
+          "sinr (.., Nt, 2, ..), status, buffer",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("noise"), py::arg("kind") = "lmmse", py::arg("t0") = 0.0, py::arg("dt") = 0.0,
+          py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
+          py::arg("array_frequency") = py::none(), py::arg("weights") = true, py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "

@@ -787,6 +787,61 @@ class Tracer:
                                array_frequency)
         return self.svd(H, vectors)
 
+    def equalizer(self, H, noise, kind="lmmse", weights=True, out=None):
+        """Per-point linear MIMO equalizer of an array channel and its post-equalisation SINR on the device
+        (hrt_channel_equalizer; include/hermespy_rt.h hrt_compute_channel_equalizer).  For every link, polarisation,
+        time sample and frequency the model is y = H x + n, E[x x^H] = I, E[n n^H] = noise I, H = H[rx, tx, :, :, pol,
+        m, k]; with lambda = noise for kind "lmmse", 0 for "zf", and G = (H^H H + lambda I)^-1:
+
+            W       complex64 [nrx, ntx, Nt, Nr, 2, T, K]     G H^H: x_hat = W y           (None with weights=False)
+            sinr    float32   [nrx, ntx, Nt, 2, T, K]         1 / (noise G_ii) - [lmmse]   per stream
+            status  int32     [nrx, ntx, 2, T, K]             0, abi.EQ_SINGULAR, abi.EQ_NONFINITE
+
+        H: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, T, K] (array_channel(), or any tensor of that layout, such
+        as equalize.stack_users() of several links for a multi-user detector; no trace is needed); Nt <= 16, Nr <= 64,
+        "zf" needs Nr >= Nt.  `noise`: one finite float > 0.  Modified Gram-Schmidt in float32 on [H; sqrt(lambda) I],
+        never through the Gram matrix; a singular or non-finite point writes exact zeros and its status.  The equalizer
+        is not additive: the equalizer of one shard's partial H is not the channel's, so a sharded caller sums H over
+        the shards first and then calls equalizer().  Returns a dict of views of one flat uint8 device tensor, itself
+        under "buffer", enqueued on the current stream; `out` (such a flat tensor) is written in place.
+        hermespy_rt_amd.equalize has the host-side reference and what is read from the SINR.  Invalid arguments raise
+        ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        spec = abi.equalizer_spec(nrx, ntx, nr, nt, T, K, noise, kind, weights)
+        H = H.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and 0 < nt <= abi.EQ_MAX_NT and 0 < nr <= abi.EQ_MAX_NR
+        need = abi.equalizer_regions(spec)[3] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_channel_equalizer(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_channel_equalizer: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_channel_equalizer")
+        H.record_stream(stream)     # (the kernel reads it after this call returns)
+        return abi.equalizer_views(out, spec)
+
+    def channel_equalizer(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                          scatter=True, array_frequency=None, noise=1.0, kind="lmmse", weights=True):
+        """The per-point equalizer of the last trace's array channel, without leaving the device: bit for bit
+        equalizer(array_channel(...), noise, kind, weights) with array_channel()'s arguments.  On a sharded trace this
+        is the equalizer of the shard's partial channel, which is not the channel's: sum array_channel() over the
+        shards and call equalizer()."""
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.equalizer(H, noise, kind, weights)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

@@ -40,6 +40,7 @@ EXPORTED = (
     "hrt_compute_array_covariance",
     "hrt_propagate_out_floats", "hrt_propagate", "hrt_compute_received_signal",
     "hrt_svd_out_bytes", "hrt_channel_svd", "hrt_compute_channel_svd",
+    "hrt_equalizer_out_bytes", "hrt_channel_equalizer", "hrt_compute_channel_equalizer",
     "hrt_apply_patterns", "hrt_compute_set_patterns",
 )
 
@@ -328,6 +329,16 @@ def load():
                                           C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3, C.c_size_t, C.c_double,
                                           u32, vp, C.POINTER(Stats)]
     L.hrt_compute_channel_svd.restype = C.c_int
+    # per-point equalizers of an array channel (hrt_equalizer_spec: abi.EqualizerSpec)
+    eqp = C.POINTER(abi.EqualizerSpec)
+    L.hrt_equalizer_out_bytes.argtypes = [eqp]
+    L.hrt_equalizer_out_bytes.restype = u64
+    L.hrt_channel_equalizer.argtypes = [C.c_int, eqp, vp, vp, vp]
+    L.hrt_channel_equalizer.restype = C.c_int
+    L.hrt_compute_channel_equalizer.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                                C.c_size_t, C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3,
+                                                C.c_size_t, C.c_double, u32, u32, C.c_float, vp, C.POINTER(Stats)]
+    L.hrt_compute_channel_equalizer.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

@@ -407,6 +407,57 @@ int hrt_compute_channel_svd(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos
                             size_t num_tx_elements, double array_frequency_hz, uint32_t want,
                             void *out /* host, hrt_svd_out_bytes bytes, layout above */, hrt_stats *stats);
 
+/* Per-point linear MIMO equalizers (zero-forcing, LMMSE) of the array channel and their post-equalisation SINR, formed
+ * on the device (include/hrt_device.h: hrt_channel_equalizer).  The model of a point -- one (rx, tx, pol, time,
+ * frequency), H = H[rx][tx][:][:][pol][m][k] of hrt_compute_array_channel's layout, Nr x Nt -- is y = H x + n with
+ * E[x x^H] = I and E[n n^H] = N0 I.  With lambda = N0 for HRT_EQ_LMMSE, lambda = 0 for HRT_EQ_ZF and
+ * G = (H^H H + lambda I)^-1 (Nt x Nt), the outputs lie in one flat buffer of hrt_equalizer_out_bytes bytes, the point
+ * axes innermost, the regions in this order (W is absent, size 0, without HRT_EQ_W in `flags`):
+ *   W       complex [num_rx][num_tx][Nt][Nr][2][T][K]   W = G H^H: x_hat = W y                      (HRT_EQ_W)
+ *   sinr    float   [num_rx][num_tx][Nt][2][T][K]       1 / (N0 G_ii) - [kind == HRT_EQ_LMMSE]: the noise enhancement
+ *                                                       of ZF, the unbiased SINR of LMMSE, per stream i
+ *   status  uint32  [num_rx][num_tx][2][T][K]           0, HRT_EQ_SINGULAR or HRT_EQ_NONFINITE
+ * `noise` (N0) is one float per call, finite and > 0, for ZF too, where it only scales the SINR.  1 <= Nt <= 16,
+ * 1 <= Nr <= 64; ZF requires Nr >= Nt, LMMSE accepts Nr < Nt.
+ * Algorithm (a definition: the tests emulate it): modified Gram-Schmidt in float, column by column, on the augmented
+ * matrix A = [H; sqrt(lambda) I] = Q R ((Nr + Nt) x Nt; just H for ZF), never through the Gram matrix.  The column
+ * operations are carried on an Nt x Nt block T that starts as I and ends as R^-1; the bottom block of A is
+ * sqrt(lambda) T throughout, so an inner product is the sum over H's rows plus lambda times the sum over T's.
+ * G_ii is the squared norm of row i of T, and W^H = Q1 T^H with Q1 the top Nr rows of Q.  With u = (Nr + Nt) 2^-24, a
+ * point is singular (HRT_EQ_SINGULAR) when a diagonal entry of R is at or below 2 u times the largest column norm of A
+ * at the start; a point whose squared column norms do not sum to a finite float (NaN, Inf, or squares beyond float) is
+ * HRT_EQ_NONFINITE, which takes precedence.  Either writes exact zeros to W and sinr, plus its status.  H = 0 under
+ * LMMSE is regular (W = 0, sinr = 0, status 0); under ZF it is singular.  A point's bits depend on its own matrix only
+ * (not on its neighbours, the batch or the launch); two calls give the same bytes.
+ * Multi-user use: the transmitters of an uplink stacked along Nt, or the users of a downlink along Nr, in any tensor
+ * of this layout, give the multi-user detector and the per-user SINR (hermespy_rt_amd.equalize.stack_users).
+ * hrt_compute_channel_equalizer traces and batches exactly as hrt_compute_array_channel does, keeps the accumulated H
+ * on the device and equalises once after the last batch: the equalizer is NOT additive over batches or shards (the
+ * equalizer of a partial H is not the channel's), only the result is copied back.  HRT_E_INVALID, before the device is
+ * touched: every refusal of hrt_compute_array_channel; a NULL out; every refusal of hrt_channel_equalizer
+ * (include/hrt_device.h). */
+#define HRT_EQ_ZF 0u
+#define HRT_EQ_LMMSE 1u
+#define HRT_EQ_W 1u
+#define HRT_EQ_SINGULAR 1u
+#define HRT_EQ_NONFINITE 2u
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t kind;                              /* HRT_EQ_ZF or HRT_EQ_LMMSE */
+    uint32_t flags;                             /* HRT_EQ_W (0: sinr and status only) */
+    float noise;                                /* N0, finite and > 0 */
+} hrt_equalizer_spec;
+uint64_t hrt_equalizer_out_bytes(const hrt_equalizer_spec *spec);   /* 0 for NULL */
+int hrt_compute_channel_equalizer(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                  const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                  size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                                  const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                                  size_t num_tx_elements, double array_frequency_hz, uint32_t kind, uint32_t flags,
+                                  float noise,
+                                  void *out /* host, hrt_equalizer_out_bytes bytes, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);
