@@ -1,10 +1,10 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer;
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
- * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps).
+ * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps, hrt_compute_sparse_array_channel).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -36,6 +36,7 @@
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
+#include "../hrt_sparse_channel.h"
 #include "../hrt_svd.h"
 #include "../hrt_taps.h"
 
@@ -1673,6 +1674,145 @@ int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
     job.run = dm_job_run;
     job.finish = dm_job_finish;
     return ch_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ array channels of path lists (hrt_sparse_array_channel) */
+
+/* the checks of a sparse spec (`who`) */
+static int sparse_check(const hrt_sparse_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    const uint64_t links = (uint64_t)sp->num_rx * sp->num_tx;
+    if (links == 0 || links > HRT_SP_MAX_LINKS)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx * num_tx = %llu (1 .. 65535)", who, (unsigned long long)links);
+    if (sp->max_paths == 0 || sp->max_paths > HRT_DM_MAX_PATHS)
+        return hrt_fail(HRT_E_INVALID, "%s: max_paths = %u (1 .. %u)", who, sp->max_paths, HRT_DM_MAX_PATHS);
+    if (links * sp->max_paths > HRT_DM_MAX_LINK_PATHS)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx * num_tx * max_paths = %llu > 2^22", who,
+                        (unsigned long long)(links * sp->max_paths));
+    const hrt_channel_spec grid = {sp->f0_hz, sp->df_hz, sp->num_freqs, sp->t0_s, sp->dt_s, sp->num_times,
+                                   HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER};
+    return spec_check(&grid);
+}
+
+uint64_t hrt_sparse_paths_bytes(const hrt_sparse_spec *spec)
+{
+    if (sparse_check(spec, "hrt_sparse_paths_bytes")) return 0;
+    return (uint64_t)spec->num_rx * spec->num_tx * (16u + (uint64_t)spec->max_paths * sizeof(hrt_dominant_path));
+}
+
+uint64_t hrt_sparse_out_bytes(const hrt_sparse_spec *spec, uint32_t nr, uint32_t nt)
+{
+    if (sparse_check(spec, "hrt_sparse_out_bytes")) return 0;
+    return (uint64_t)spec->num_rx * spec->num_tx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+}
+
+int hrt_sparse_array_channel(int device, const hrt_sparse_spec *spec, const float *d_rx_el, uint32_t nr,
+                             const float *d_tx_el, uint32_t nt, double fa_hz, const void *d_paths, float *d_out,
+                             int accumulate, void *stream)
+{
+    _Static_assert(sizeof(hrt_dominant_path) == HRT_SP_SLOT_BYTES &&
+                   offsetof(hrt_dominant_path, a_te_re) == HRT_SP_SLOT_FIRST, "hrt_dominant_path: the staged floats");
+    int rc = sparse_check(spec, "hrt_sparse_array_channel");
+    if (rc) return rc;
+    if (!d_paths || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_sparse_array_channel: NULL device pointer");
+    const uint64_t grid = (uint64_t)spec->num_times * spec->num_freqs;
+    const hrt_array_spec a = {nr, nt, d_rx_el, d_tx_el, fa_hz};
+    if ((rc = arrays_check(&a, grid, "num_times * num_freqs", "hrt_sparse_array_channel"))) return rc;
+    if ((uintptr_t)d_paths % 8u) return hrt_fail(HRT_E_INVALID, "hrt_sparse_array_channel: d_paths is not 8-byte aligned");
+    if (accumulate != 0 && accumulate != 1)
+        return hrt_fail(HRT_E_INVALID, "hrt_sparse_array_channel: accumulate must be 0 or 1");
+    hrt_ksparse K;
+    memset(&K, 0, sizeof K);
+    K.links = spec->num_rx * spec->num_tx;
+    K.max_paths = spec->max_paths;
+    if ((rc = ac_fields(&a, K.links, grid, "hrt_sparse_array_channel", &K.nr, &K.nt, &K.npairs, &K.g.fa_c))) return rc;
+    K.g.K = spec->num_freqs; K.g.T = spec->num_times;
+    K.g.K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
+    K.g.rows = K.g.K1 * K.g.T;
+    K.g.pblocks = (K.npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
+    K.g.cblocks = (K.g.rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
+    K.g.f0 = spec->f0_hz; K.g.df = spec->df_hz; K.g.t0 = spec->t0_s; K.g.dt = spec->dt_s;
+    K.accumulate = (uint32_t)accumulate;
+    K.rx_el = d_rx_el; K.tx_el = d_tx_el;
+    K.paths = (const uint8_t *)d_paths;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_sparse_channel(&K, stream), "sparse channel kernel");
+    return HRT_OK;
+}
+
+/* what the deliver and finish hooks of hrt_compute_sparse_array_channel need */
+typedef struct {
+    hrt_sparse_spec sp;
+    void *paths_out;     /* host, hrt_dominant_out_bytes; may be NULL */
+} sp_job;
+
+/* after the last batch: the merged lists stay at d_paths; the channel is evaluated once, and only it (and the lists, if
+ * asked for) comes down.  The offsets are ch_compute's upload (ac_job_arrays). */
+static int sp_job_deliver(const ch_job *j, int device, const void *d_paths, void *out)
+{
+    const sp_job *sj = (const sp_job *)j->aux;
+    const hrt_array_spec a = ac_job_arrays(j);
+    const uint64_t bytes = hrt_sparse_out_bytes(&sj->sp, j->nr, j->nt);
+    void *d_H = NULL;
+    int rc = hrt_device_malloc(device, &d_H, bytes);
+    if (!rc)
+        rc = hrt_sparse_array_channel(device, &sj->sp, a.rx_elements, j->nr, a.tx_elements, j->nt, j->fa, d_paths,
+                                      (float *)d_H, 0, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_H, bytes);
+    if (!rc && sj->paths_out) rc = hrt_device_download(device, sj->paths_out, d_paths, j->out_bytes);
+    if (d_H) hrt_device_free(device, d_H);
+    return rc;
+}
+
+static int sp_job_finish(const ch_job *j, const hrt_problem *p, void *out)
+{
+    (void)out;
+    const sp_job *sj = (const sp_job *)j->aux;
+    return sj->paths_out ? dm_job_finish(j, p, sj->paths_out) : HRT_OK;
+}
+
+int hrt_compute_sparse_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                     const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                     const hrt_dominant_spec *dspec, const hrt_channel_spec *grid, const Vec3 *rx_el,
+                                     size_t nr, const Vec3 *tx_el, size_t nt, double f_a, float *out, void *paths_out,
+                                     hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = dominant_check(dspec);
+    if (rc) return rc;
+    if ((rc = dominant_links_check(nrx, ntx, dspec))) return rc;
+    if (!grid) return hrt_fail(HRT_E_INVALID, "hrt_compute_sparse_array_channel: NULL grid");
+    if ((rc = ac_counts_check(nr, nt, "hrt_sparse_array_channel"))) return rc;
+    sp_job sj;
+    memset(&sj, 0, sizeof sj);
+    sj.sp.f0_hz = grid->f0_hz; sj.sp.df_hz = grid->df_hz; sj.sp.num_freqs = grid->num_freqs;
+    sj.sp.t0_s = grid->t0_s; sj.sp.dt_s = grid->dt_s; sj.sp.num_times = grid->num_times;
+    sj.sp.num_rx = (uint32_t)nrx; sj.sp.num_tx = (uint32_t)ntx;
+    sj.sp.max_paths = dspec->max_paths;
+    sj.paths_out = paths_out;
+    {   /* the grid and the arrays (the element pointers stand in for the device ones: tested for NULL only) */
+        const hrt_channel_spec g = {grid->f0_hz, grid->df_hz, grid->num_freqs, grid->t0_s, grid->dt_s,
+                                    grid->num_times, dspec->parts};
+        if ((rc = spec_check(&g))) return rc;
+        const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+        if ((rc = arrays_check(&a, (uint64_t)g.num_times * g.num_freqs, "num_times * num_freqs",
+                               "hrt_sparse_array_channel")))
+            return rc;
+    }
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = dspec;
+    job.out_bytes = (uint64_t)nrx * ntx * (16u + (uint64_t)dspec->max_paths * sizeof(hrt_dominant_path));
+    job.scratch_bytes = dm_job_scratch;
+    job.run = dm_job_run;
+    job.deliver = sp_job_deliver;
+    job.finish = sp_job_finish;
+    job.aux = &sj;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel");
 }
 
 /* ------------------------------------------------------------------ beamformed channel responses (hrt_beam_channel) */

@@ -3,7 +3,8 @@
 // beam pairs) x HRT_AC_GROWS * 16 padded columns.  Kernel text, pulled in part by part inside the kernel body
 // (#define HRT_PG_PART n, then #include) like csrc/hrt_fused_body.inc: as helper functions the same lines cost
 // hrt_array_partial_kernel 16 AGPRs or another schedule (profiles/HISTORY.md).  Each kernel keeps its __shared__
-// declarations, its batch fill and its S stage (the A operand of each lane, in sA).
+// declarations, its batch fill and its S stage (the A operand of each lane, in sA).  hrt_sparse_channel_kernel
+// (csrc/hrt_sparse_channel.hip) pulls in parts 1 .. 3 over the slots of a path list and writes acc out itself.
 //
 // In scope everywhere: P (the kernel's parameters: P.g the hrt_kgrid, P.npairs, P.partial), V = P.v, and
 //     cb, link, c          column block, link and record chunk of the workgroup

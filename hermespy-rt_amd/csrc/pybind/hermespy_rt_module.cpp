@@ -922,32 +922,11 @@ py::dict compute_array_covariance_py(
     return d;
 }
 
-// compute_dominant_paths: the max_paths strongest paths of every link, selected on the device (extension; see
-// hrt_compute_dominant_paths in hermespy_rt.h): a dict of views of one buffer -- kept, eligible (num_rx, num_tx);
-// power, path, bounce, tri, tau, freq_shift (num_rx, num_tx, K); a_te, a_tm complex64 (num_rx, num_tx, K); u_rx, u_tx
-// (num_rx, num_tx, K, 3) -- and the buffer itself (uint8).
-py::dict compute_dominant_paths_py(
-    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
-    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
-    unsigned long num_bounces, unsigned long max_paths, bool los, bool scatter,
-    py::object patterns)
+// the views of a dominant paths buffer (hrt_dominant_out_bytes = n bytes at dst, kept alive by `buf`) as a dict:
+// compute_dominant_paths' result, and compute_sparse_array_channel's lists
+py::dict dominant_dict(py::array_t<uint64_t> &buf, uint8_t *dst, uint64_t n, unsigned long num_rx, unsigned long num_tx,
+                       unsigned long max_paths)
 {
-    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
-    if (max_paths > 0xffffffffUL)
-        throw py::value_error("hermespy_rt.compute_dominant_paths: max_paths must fit 32 bits");
-    check_scene_file(mesh_filepath);
-    hrt_dominant_spec spec{};
-    spec.max_paths = (uint32_t)max_paths;
-    spec.parts = parts_word(los, scatter);
-    // (the library validates the spec before it traces anything: a refused one raises ValueError and has no output)
-    const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &spec);
-    py::array_t<uint64_t> buf((size_t)(n ? n / 8u : 1u));   // (8-byte aligned words; 72 and 16 are multiples of 8)
-    uint8_t *dst = reinterpret_cast<uint8_t *>(buf.mutable_data());
-    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
-    run_pathsum("compute_dominant_paths", mesh_filepath, [&](Scene *scene) {
-        return hrt_compute_dominant_paths(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
-                                          num_paths, num_bounces, &spec, dst, nullptr);
-    });
     const py::ssize_t R = (py::ssize_t)num_rx, T = (py::ssize_t)num_tx, K = (py::ssize_t)max_paths;
     const py::ssize_t rec = (py::ssize_t)sizeof(hrt_dominant_path);
     uint8_t *recs = dst + 16 * R * T;
@@ -977,6 +956,80 @@ py::dict compute_dominant_paths_py(
     d["u_tx"] = vec3(offsetof(hrt_dominant_path, u_tx));
     d["buffer"] = py::array_t<uint8_t>({(py::ssize_t)n}, {(py::ssize_t)1}, dst, buf);
     return d;
+}
+
+// compute_dominant_paths: the max_paths strongest paths of every link, selected on the device (extension; see
+// hrt_compute_dominant_paths in hermespy_rt.h): a dict of views of one buffer -- kept, eligible (num_rx, num_tx);
+// power, path, bounce, tri, tau, freq_shift (num_rx, num_tx, K); a_te, a_tm complex64 (num_rx, num_tx, K); u_rx, u_tx
+// (num_rx, num_tx, K, 3) -- and the buffer itself (uint8).
+py::dict compute_dominant_paths_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, unsigned long max_paths, bool los, bool scatter,
+    py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (max_paths > 0xffffffffUL)
+        throw py::value_error("hermespy_rt.compute_dominant_paths: max_paths must fit 32 bits");
+    check_scene_file(mesh_filepath);
+    hrt_dominant_spec spec{};
+    spec.max_paths = (uint32_t)max_paths;
+    spec.parts = parts_word(los, scatter);
+    // (the library validates the spec before it traces anything: a refused one raises ValueError and has no output)
+    const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &spec);
+    py::array_t<uint64_t> buf((size_t)(n ? n / 8u : 1u));   // (8-byte aligned words; 72 and 16 are multiples of 8)
+    uint8_t *dst = reinterpret_cast<uint8_t *>(buf.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_dominant_paths", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_dominant_paths(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                          num_paths, num_bounces, &spec, dst, nullptr);
+    });
+    return dominant_dict(buf, dst, n, num_rx, num_tx, max_paths);
+}
+
+// compute_sparse_array_channel: the antenna-array channel of the max_paths strongest paths of every link, selected and
+// evaluated on the device (extension; see hrt_compute_sparse_array_channel in hermespy_rt.h): complex64 (num_rx, num_tx,
+// Nr, Nt, 2, num_times, num_freqs), or with return_paths the tuple (H, compute_dominant_paths' dict of the lists).
+py::object compute_sparse_array_channel_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    unsigned long max_paths, double t0, double dt, unsigned long num_times, bool los, bool scatter,
+    py::object array_frequency, py::object patterns, bool return_paths)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_freqs and num_times must fit 32 bits");
+    if (max_paths > 0xffffffffUL)
+        throw py::value_error("hermespy_rt.compute_sparse_array_channel: max_paths must fit 32 bits");
+    const array_elements a(rx_elements, tx_elements);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_dominant_spec dm{};
+    dm.max_paths = (uint32_t)max_paths;
+    dm.parts = parts_word(los, scatter);
+    hrt_channel_spec grid{};
+    grid.f0_hz = f0; grid.df_hz = df; grid.num_freqs = (uint32_t)num_freqs;
+    grid.t0_s = t0; grid.dt_s = dt; grid.num_times = (uint32_t)num_times;
+    grid.parts = dm.parts;
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  Outputs beyond
+    // the limits would be refused, so only ones within them are allocated.)
+    const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &dm);
+    const bool fits = n && a.fits((unsigned long long)num_times * num_freqs);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, a.nr, a.nt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_freqs}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    py::array_t<uint64_t> buf((size_t)(return_paths && n ? n / 8u : 1u));
+    uint8_t *lists = reinterpret_cast<uint8_t *>(buf.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_sparse_array_channel", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_sparse_array_channel(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                                num_paths, num_bounces, &dm, &grid, a.rxe, a.nr, a.txe, a.nt, fa, dst,
+                                                return_paths ? (void *)lists : nullptr, nullptr);
+    });
+    if (!return_paths) return out;
+    return py::make_tuple(out, dominant_dict(buf, lists, n, num_rx, num_tx, max_paths));
 }
 
 }  // namespace
@@ -1120,6 +1173,17 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
           py::arg("max_paths"), py::arg("los") = true, py::arg("scatter") = true,
           py::arg("patterns") = py::none());
+    m.def("compute_sparse_array_channel", &compute_sparse_array_channel_py,
+          "Antenna-array channel of the max_paths strongest paths of every link, selected and evaluated on the device: "
+          "complex64 (num_rx, num_tx, Nr, Nt, 2, num_times, num_freqs); with return_paths=True the tuple (H, the lists as "
+          "compute_dominant_paths returns them)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("max_paths"), py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1,
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(),
+          py::arg("patterns") = py::none(), py::arg("return_paths") = false);
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

@@ -908,6 +908,90 @@ class Tracer:
                             dtype=self.torch.uint8)
         return abi.dominant_views(out, self.nrx, self.ntx, spec.max_paths)
 
+    def _path_lists(self, paths):
+        """The lists of a sparse call -> (flat uint8 device tensor, nrx, ntx, K): `paths` is a result dict
+        (abi.dominant_views: dominant_paths(), dominant.merge, dominant.from_terms), whose "buffer" is read and whose
+        views give (nrx, ntx, K), or a flat uint8 buffer of this tracer's (nrx, ntx).  A numpy buffer is uploaded."""
+        torch = self.torch
+        if isinstance(paths, dict):
+            buf = paths["buffer"]
+            nrx, ntx, K = (int(v) for v in paths["power"].shape)
+        else:
+            buf, nrx, ntx = paths, self.nrx, self.ntx
+            K = (int(np.prod(buf.shape)) // max(nrx * ntx, 1) - 16) // 72 if hasattr(buf, "shape") else 0
+        if isinstance(buf, np.ndarray):
+            if buf.dtype != np.uint8:
+                raise ValueError("paths: a uint8 buffer expected, got %s" % (buf.dtype,))
+        elif not (hasattr(buf, "is_cuda") and buf.dtype == torch.uint8):
+            raise ValueError("paths: a uint8 buffer (numpy array or tensor on %s) expected" % (self.device,))
+        elif not buf.is_cuda or buf.device != self.device:
+            raise ValueError("paths: the buffer must be on %s, got %s" % (self.device, buf.device))
+        need = nrx * ntx * (16 + 72 * K)
+        if K < 1 or len(buf.shape) != 1 or int(buf.shape[0]) != need:
+            raise ValueError("paths: a flat buffer of %d bytes expected for (nrx, ntx, K) = (%d, %d, %d), got %s"
+                             % (need, nrx, ntx, K, tuple(buf.shape)))
+        if isinstance(buf, np.ndarray):
+            with torch.cuda.device(self.device):
+                buf = torch.from_numpy(np.ascontiguousarray(buf)).to(self.device)
+        elif not buf.is_contiguous():
+            raise ValueError("paths: the buffer must be contiguous")
+        return buf, nrx, ntx, K
+
+    def sparse_array_channel(self, paths, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1,
+                             array_frequency=None, out=None, accumulate=False):
+        """The antenna-array channel of dominant-path lists, formed on the device (hrt_sparse_array_channel;
+        include/hermespy_rt.h hrt_compute_sparse_array_channel): with n = min(kept, K) of the link,
+
+            H[rx, tx, i, j, pol, m, k] = sum_{p < n} a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
+                                                    * exp(j 2 pi f_a (r_i . u_rx_p + q_j . u_tx_p) / c)
+
+        paths: the dict dominant_paths() returns (its "buffer" is read where it is), or a numpy result of
+        dominant.merge / dominant.from_terms (uploaded).  The grid, the elements and f_a are array_channel()'s.  No
+        trace is needed: only the lists are read, so a traced channel can be evaluated again for another grid, array or
+        time axis, and merged or synthetic lists run through the same kernel.  Slots at or beyond n are never read.
+        Returns a complex64 tensor [nrx, ntx, Nr, Nt, 2, num_times, num_freqs] on the device, enqueued on the current
+        stream; `out` is written in place, or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        buf, nrx, ntx, K = self._path_lists(paths)
+        spec = abi.sparse_spec(nrx, ntx, K, f0, df, num_freqs, t0, dt, num_times)
+        # (a call the library refuses may have no sensible size: a placeholder it does not write)
+        fits = (abi.sparse_out_bytes(spec, nr, nt) > 0 and 0 < nr <= 1024 and 0 < nt <= 1024
+                and nr * nt * int(num_times) * int(num_freqs) <= 1 << 24)
+        shape = (nrx, ntx, nr, nt, 2, int(num_times), int(num_freqs)) if fits else (1,)
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        arrays, d_el = upload()
+        rc = self.L.hrt_sparse_array_channel(self.device.index, C.byref(spec), C.c_void_p(arrays.rx_elements), nr,
+                                             C.c_void_p(arrays.tx_elements), nt, float(arrays.array_frequency_hz),
+                                             C.c_void_p(buf.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             1 if accumulate else 0, C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_sparse_array_channel: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_sparse_array_channel")
+        d_el.record_stream(stream)   # (the kernel reads the offsets and the lists after this call returns)
+        buf.record_stream(stream)
+        return out
+
+    def sparse_channel(self, paths, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, out=None, accumulate=False):
+        """The SISO channel of dominant-path lists: sparse_array_channel() at one zero-offset element per side, bit for
+        bit, as a complex64 tensor [nrx, ntx, 2, num_times, num_freqs] (channel()'s layout)."""
+        z = np.zeros((1, 3), np.float32)
+        o7 = None
+        if out is not None:
+            if out.dim() != 5 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous complex64 tensor [nrx, ntx, 2, num_times, num_freqs]")
+            o7 = out.view(tuple(out.shape[:2]) + (1, 1) + tuple(out.shape[2:]))
+        H = self.sparse_array_channel(paths, z, z, f0, df, num_freqs, t0, dt, num_times, 1.0, o7, accumulate)
+        return H.view(tuple(H.shape[:2]) + tuple(H.shape[4:])) if out is None else out
+
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):
         """Assemble the reference's dense [rx][tx][b][p] scatter arrays on the host from the

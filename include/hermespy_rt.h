@@ -581,6 +581,46 @@ int hrt_compute_dominant_paths(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
                                size_t num_rays, size_t num_bounces, const hrt_dominant_spec *spec,
                                void *out /* hrt_dominant_out_bytes, layout above */, hrt_stats *stats);
 
+/* The antenna-array channel of dominant-path lists, formed on the device (include/hrt_device.h:
+ * hrt_sparse_array_channel): the second half of the sentence above, the sparse channel built from the short lists and
+ * evaluated again for any grid, array or time axis, without the workspace.  The input is a buffer in exactly the layout
+ * hrt_dominant_paths writes: a header uint64_t [L][2] = {kept, eligible}, then hrt_dominant_path [L][K], L = num_rx *
+ * num_tx, K = max_paths.  For every link, element pair (i, j), polarisation (0 = TE, 1 = TM), time sample m and
+ * frequency k:
+ *     n = min(kept[link], K)
+ *     H[rx][tx][i][j][pol][m][k] = sum over slots p < n of
+ *           a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) exp(j 2 pi f_a (r_i . u_rx_p + q_j . u_tx_p) / c)
+ * a^TE = (a_te_re, a_te_im), a^TM = (a_tm_re, a_tm_im); tau, nu = freq_shift, u_rx and u_tx are the slot's floats; f_k,
+ * t_m, f_a, c, the element offsets and the output layout are hrt_compute_array_channel's:
+ * out: complex [num_rx][num_tx][Nr][Nt][2][num_times][num_freqs], re/im interleaved (numpy complex64).
+ * The LoS entry is an ordinary slot (bounce -1) without a rule of its own.  power, path, bounce and tri are not read.
+ * Slots at or beyond n are never read: whatever they hold does not reach the output.  A link with n = 0 writes zeros
+ * (or leaves `out` unchanged when accumulating).  With Nr = Nt = 1 and zero offsets this is the SISO channel of the
+ * list.  Where kept = eligible for a link the result is hrt_compute_array_channel's for the same parts, up to the
+ * order of the float32 sums; where kept < eligible it is the channel of the strongest K terms.
+ * Every byte of `out` is written exactly once (added to once when accumulating); no atomics and no scratch buffer; two
+ * calls with the same input give the same bytes; a link's bytes depend only on its own slots, the grid and the
+ * elements; a non-finite field in one link's list stays within that link's outputs.
+ * hrt_compute_sparse_array_channel runs hrt_compute_dominant_paths' batch loop (the lists merged on the device) and
+ * evaluates the merged lists once after the last batch; only `out`, and the lists if paths_out is not NULL
+ * (hrt_dominant_out_bytes, `tri` as hrt_compute_dominant_paths reports it), is copied back.  HRT_E_INVALID, before the
+ * device is touched: every hrt_compute_dominant_paths check; every grid check of hrt_channel_spec (the spec's parts
+ * are not read: the parts are the dominant spec's); Nr or Nt outside 1..1024; Nr * Nt * num_times * num_freqs > 2^24;
+ * an offset or f_a not finite; f_a <= 0. */
+typedef struct {
+    double f0_hz, df_hz;  uint32_t num_freqs;   /* f_k = f0 + k*df */
+    double t0_s, dt_s;    uint32_t num_times;   /* t_m = t0 + m*dt */
+    uint32_t num_rx, num_tx;                    /* L = num_rx * num_tx links */
+    uint32_t max_paths;                         /* K: slots per link */
+} hrt_sparse_spec;
+int hrt_compute_sparse_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                     const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                     size_t num_rays, size_t num_bounces, const hrt_dominant_spec *dominant_spec,
+                                     const hrt_channel_spec *grid, const Vec3 *rx_elements, size_t num_rx_elements,
+                                     const Vec3 *tx_elements, size_t num_tx_elements, double array_frequency_hz,
+                                     float *out /* complex interleaved, layout above */,
+                                     void *paths_out /* hrt_dominant_out_bytes, or NULL */, hrt_stats *stats);
+
 /* Antenna radiation patterns and orientations (include/hrt_device.h: hrt_apply_patterns; csrc/hrt_patterns.hip).  A
  * pattern is a real factor per (path, RX, TX): for every unblocked scatter record p of link (rx, tx), and for every
  * clear LoS entry,

@@ -502,6 +502,25 @@ int hrt_dominant_paths(const hrt_problem *p, const hrt_shard *s, const void *d_w
                        const hrt_dominant_spec *spec, void *d_scratch, uint64_t scratch_bytes, void *d_out,
                        int accumulate, void *stream);
 
+/* ---- the array channel of dominant-path lists (csrc/host/channel.c, csrc/hrt_sparse_channel.hip) ----
+ * H as hermespy_rt.h defines it (hrt_sparse_spec, hrt_compute_sparse_array_channel), hrt_sparse_out_bytes bytes at
+ * d_out, from the lists at d_paths (hrt_sparse_paths_bytes bytes in hrt_dominant_paths' layout: its output, a merged or
+ * a synthetic list; 8-byte aligned), the element offsets d_rx_el [nr][3] and d_tx_el [nt][3] -- all DEVICE pointers --
+ * asynchronous on `stream` of `device`.  It takes no problem handle and reads only the buffer, and does not write it.
+ * accumulate = 0 overwrites d_out, 1 adds to it.  One workgroup sums all live slots of a link in index order: every
+ * byte of d_out is written exactly once (added to once), no atomics and no scratch, so two calls with the same input
+ * give the same bytes; a link's bytes depend only on its own slots; slots at or beyond min(kept, max_paths) are never
+ * read.  The finiteness of the offsets is the caller's to ensure (the host entries check it).  The two size functions
+ * return 0 for a NULL or refused spec.  HRT_E_INVALID, before the device is touched: a NULL pointer; num_rx * num_tx
+ * of 0 or above 65 535; max_paths of 0 or above 1 024; num_rx * num_tx * max_paths above 2^22; num_freqs or num_times
+ * 0; num_freqs * num_times above 2^20; f0, df, t0 or dt not finite; nr or nt outside 1..1024; nr * nt * num_times *
+ * num_freqs above 2^24; f_a not finite or <= 0; d_paths not 8-byte aligned; accumulate not 0 or 1. */
+uint64_t hrt_sparse_paths_bytes(const hrt_sparse_spec *spec);
+uint64_t hrt_sparse_out_bytes(const hrt_sparse_spec *spec, uint32_t nr, uint32_t nt);
+int hrt_sparse_array_channel(int device, const hrt_sparse_spec *spec, const float *d_rx_el, uint32_t nr,
+                             const float *d_tx_el, uint32_t nt, double fa_hz, const void *d_paths, float *d_out,
+                             int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
