@@ -1025,6 +1025,85 @@ def run_compute_sparse_array_channel(lib, scene_path, rx_pos, tx_pos, rx_vel, tx
     return (out, dominant_views(paths, nrx, ntx, dominant.max_paths)) if return_paths else out
 
 
+# ---- the array taps of dominant-path lists (include/hermespy_rt.h: hrt_sparse_taps_spec) ----
+class SparseTapsSpec(C.Structure):
+    """include/hermespy_rt.h hrt_sparse_taps_spec"""
+    _fields_ = [("fs_hz", C.c_double), ("fc_hz", C.c_double), ("t0_s", C.c_double), ("dt_s", C.c_double),
+                ("l_min", C.c_int32), ("num_taps", C.c_uint32), ("num_times", C.c_uint32),
+                ("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("max_paths", C.c_uint32)]
+
+
+assert C.sizeof(SparseTapsSpec) == 56
+
+
+def sparse_taps_spec(num_rx, num_tx, max_paths, fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0, num_times=1):
+    return SparseTapsSpec(float(fs), float(fc), float(t0), float(dt), int(l_min), int(num_taps), int(num_times),
+                          int(num_rx), int(num_tx), int(max_paths))
+
+
+def sparse_taps_out_bytes(spec, nr, nt):
+    """the bytes of the array taps of a list (hrt_sparse_taps_out_bytes; 0 for a spec the library refuses)"""
+    links, k = int(spec.num_rx) * int(spec.num_tx), int(spec.max_paths)
+    L, T, lo = int(spec.num_taps), int(spec.num_times), int(spec.l_min)
+    if not 0 < links <= 65535 or not 0 < k <= DOMINANT_MAX_PATHS or links * k > (1 << 22):
+        return 0
+    if L == 0 or T == 0 or L * T > (1 << 20) or abs(lo) > (1 << 24) or lo + L > (1 << 24):
+        return 0
+    if not all(np.isfinite([spec.fs_hz, spec.fc_hz, spec.t0_s, spec.dt_s])) or not spec.fs_hz > 0.0:
+        return 0
+    return links * int(nr) * int(nt) * 2 * T * L * 8
+
+
+def run_sparse_array_taps(lib, device, spec, d_rx_el, nr, d_tx_el, nt, fa_hz, d_paths, d_out, accumulate=0,
+                          stream=None):
+    """hrt_sparse_array_taps through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_sparse_array_taps failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_sparse_array_taps(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_rx_el),
+                                   C.c_uint32(int(nr)), C.c_void_p(d_tx_el), C.c_uint32(int(nt)),
+                                   C.c_double(float(fa_hz)), C.c_void_p(d_paths), C.c_void_p(d_out),
+                                   C.c_int(int(accumulate)), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_sparse_array_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_sparse_array_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces,
+                                  dominant, grid, rx_elements, tx_elements, array_frequency=None, return_paths=False,
+                                  stats=None):
+    """hrt_compute_sparse_array_taps through ctypes (dominant: a DominantSpec, grid: a TapsSpec whose parts are not
+    read) -> complex64 [nrx, ntx, Nr, Nt, 2, num_times, num_taps], or (h, dominant_views of the lists) with
+    return_paths.  Raises RuntimeError("hrt_compute_sparse_array_taps failed (<rc>): ...") on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    # (outputs too large for the host are refused by the library's limits first: allocate only what passes them)
+    T, L = (int(grid.num_times), int(grid.num_taps)) if grid is not None else (0, 0)
+    pts = nr * nt * T * L
+    nbytes = dominant_out_bytes(nrx, ntx, dominant) if dominant is not None else 0
+    fits = nbytes > 0 and 0 < pts <= (1 << 24) and T * L <= (1 << 20)
+    out = np.zeros((nrx, ntx, nr, nt, 2, T, L) if fits else (1,), np.complex64)
+    paths = np.zeros(nbytes if fits else 8, np.uint8) if return_paths else None
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_sparse_array_taps(
+            C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx), C.c_size_t(ntx),
+            C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+            C.byref(dominant) if dominant is not None else None, C.byref(grid) if grid is not None else None, *extra,
+            out.ctypes.data_as(c_float_p), paths.ctypes.data_as(C.c_void_p) if paths is not None else None,
+            C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_sparse_array_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    if not fits:
+        raise RuntimeError("hrt_compute_sparse_array_taps accepted a call beyond its limits")
+    return (out, dominant_views(paths, nrx, ntx, dominant.max_paths)) if return_paths else out
+
+
 # ---- test-only entries (include/hrt_device.h): a lane's own candidate lookup, what the tables were built with ----
 CAND_KINDS = dict(patch=1, image=2, txcell=4, cell_mask=8)
 

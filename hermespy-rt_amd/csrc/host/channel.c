@@ -1,10 +1,11 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel;
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
- * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps, hrt_compute_sparse_array_channel).
+ * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps, hrt_compute_sparse_array_channel,
+ * hrt_compute_sparse_array_taps).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -37,6 +38,7 @@
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
 #include "../hrt_sparse_channel.h"
+#include "../hrt_sparse_taps.h"
 #include "../hrt_svd.h"
 #include "../hrt_taps.h"
 
@@ -1813,6 +1815,146 @@ int hrt_compute_sparse_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec
     job.aux = &sj;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel");
+}
+
+/* ------------------------------------------------------------------ array taps of path lists (hrt_sparse_array_taps) */
+
+/* the taps spec of a sparse taps spec: the grid, and both parts (a list has no parts of its own) */
+static hrt_taps_spec sparse_taps_grid(const hrt_sparse_taps_spec *sp)
+{
+    const hrt_taps_spec t = {sp->fs_hz, sp->fc_hz, sp->t0_s, sp->dt_s, sp->l_min, sp->num_taps, sp->num_times,
+                             HRT_CHANNEL_LOS | HRT_CHANNEL_SCATTER};
+    return t;
+}
+
+/* the checks of a sparse taps spec (`who`) */
+static int sparse_taps_check(const hrt_sparse_taps_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    const uint64_t links = (uint64_t)sp->num_rx * sp->num_tx;
+    if (links == 0 || links > HRT_SP_MAX_LINKS)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx * num_tx = %llu (1 .. 65535)", who, (unsigned long long)links);
+    if (sp->max_paths == 0 || sp->max_paths > HRT_DM_MAX_PATHS)
+        return hrt_fail(HRT_E_INVALID, "%s: max_paths = %u (1 .. %u)", who, sp->max_paths, HRT_DM_MAX_PATHS);
+    if (links * sp->max_paths > HRT_DM_MAX_LINK_PATHS)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx * num_tx * max_paths = %llu > 2^22", who,
+                        (unsigned long long)(links * sp->max_paths));
+    const hrt_taps_spec grid = sparse_taps_grid(sp);
+    return taps_spec_check(&grid, who);
+}
+
+uint64_t hrt_sparse_taps_out_bytes(const hrt_sparse_taps_spec *spec, uint32_t nr, uint32_t nt)
+{
+    if (sparse_taps_check(spec, "hrt_sparse_taps_out_bytes")) return 0;
+    return (uint64_t)spec->num_rx * spec->num_tx * nr * nt * 2u * spec->num_times * spec->num_taps * 8u;
+}
+
+int hrt_sparse_array_taps(int device, const hrt_sparse_taps_spec *spec, const float *d_rx_el, uint32_t nr,
+                          const float *d_tx_el, uint32_t nt, double fa_hz, const void *d_paths, float *d_out,
+                          int accumulate, void *stream)
+{
+    const char *who = "hrt_sparse_array_taps";
+    int rc = sparse_taps_check(spec, who);
+    if (rc) return rc;
+    if (!d_paths || !d_out) return hrt_fail(HRT_E_INVALID, "%s: NULL device pointer", who);
+    const uint64_t grid = (uint64_t)spec->num_times * spec->num_taps;
+    const hrt_array_spec a = {nr, nt, d_rx_el, d_tx_el, fa_hz};
+    if ((rc = arrays_check(&a, grid, "num_times * num_taps", who))) return rc;
+    if ((uintptr_t)d_paths % 8u) return hrt_fail(HRT_E_INVALID, "%s: d_paths is not 8-byte aligned", who);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "%s: accumulate must be 0 or 1", who);
+    hrt_ksparse_taps K;
+    memset(&K, 0, sizeof K);
+    K.links = spec->num_rx * spec->num_tx;
+    K.max_paths = spec->max_paths;
+    if ((rc = ac_fields(&a, K.links, grid, who, &K.nr, &K.nt, &K.npairs, &K.fa_c))) return rc;
+    {   /* the grid of the array taps; a list has no records to chunk (nb = 0: nchunks stays 0) */
+        const hrt_taps_spec t = sparse_taps_grid(spec);
+        hrt_kview v;
+        uint64_t per_chunk;
+        memset(&v, 0, sizeof v);
+        v.nrx = spec->num_rx; v.ntx = spec->num_tx;
+        (void)taps_grid(&v, &t, K.npairs, 4u, &K.g, &per_chunk);
+    }
+    K.accumulate = (uint32_t)accumulate;
+    K.rx_el = d_rx_el; K.tx_el = d_tx_el;
+    K.paths = (const uint8_t *)d_paths;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_sparse_taps(&K, stream), "sparse taps kernel");
+    return HRT_OK;
+}
+
+/* what the deliver and finish hooks of hrt_compute_sparse_array_taps need */
+typedef struct {
+    hrt_sparse_taps_spec sp;
+    void *paths_out;     /* host, hrt_dominant_out_bytes; may be NULL */
+} spt_job;
+
+/* after the last batch, as sp_job_deliver: the taps are evaluated once, and only they (and the lists, if asked for)
+ * come down */
+static int spt_job_deliver(const ch_job *j, int device, const void *d_paths, void *out)
+{
+    const spt_job *sj = (const spt_job *)j->aux;
+    const hrt_array_spec a = ac_job_arrays(j);
+    const uint64_t bytes = hrt_sparse_taps_out_bytes(&sj->sp, j->nr, j->nt);
+    void *d_h = NULL;
+    int rc = hrt_device_malloc(device, &d_h, bytes);
+    if (!rc)
+        rc = hrt_sparse_array_taps(device, &sj->sp, a.rx_elements, j->nr, a.tx_elements, j->nt, j->fa, d_paths,
+                                   (float *)d_h, 0, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_h, bytes);
+    if (!rc && sj->paths_out) rc = hrt_device_download(device, sj->paths_out, d_paths, j->out_bytes);
+    if (d_h) hrt_device_free(device, d_h);
+    return rc;
+}
+
+static int spt_job_finish(const ch_job *j, const hrt_problem *p, void *out)
+{
+    (void)out;
+    const spt_job *sj = (const spt_job *)j->aux;
+    return sj->paths_out ? dm_job_finish(j, p, sj->paths_out) : HRT_OK;
+}
+
+int hrt_compute_sparse_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                  const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                  const hrt_dominant_spec *dspec, const hrt_taps_spec *grid, const Vec3 *rx_el,
+                                  size_t nr, const Vec3 *tx_el, size_t nt, double f_a, float *out, void *paths_out,
+                                  hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = dominant_check(dspec);
+    if (rc) return rc;
+    if ((rc = dominant_links_check(nrx, ntx, dspec))) return rc;
+    if (!grid) return hrt_fail(HRT_E_INVALID, "hrt_compute_sparse_array_taps: NULL grid");
+    if ((rc = ac_counts_check(nr, nt, "hrt_sparse_array_taps"))) return rc;
+    spt_job sj;
+    memset(&sj, 0, sizeof sj);
+    sj.sp.fs_hz = grid->fs_hz; sj.sp.fc_hz = grid->fc_hz; sj.sp.t0_s = grid->t0_s; sj.sp.dt_s = grid->dt_s;
+    sj.sp.l_min = grid->l_min; sj.sp.num_taps = grid->num_taps; sj.sp.num_times = grid->num_times;
+    sj.sp.num_rx = (uint32_t)nrx; sj.sp.num_tx = (uint32_t)ntx;
+    sj.sp.max_paths = dspec->max_paths;
+    sj.paths_out = paths_out;
+    {   /* the grid and the arrays (the element pointers stand in for the device ones: tested for NULL only) */
+        const hrt_taps_spec g = {grid->fs_hz, grid->fc_hz, grid->t0_s, grid->dt_s, grid->l_min, grid->num_taps,
+                                 grid->num_times, dspec->parts};
+        if ((rc = taps_spec_check(&g, "hrt_sparse_array_taps"))) return rc;
+        const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+        if ((rc = arrays_check(&a, (uint64_t)g.num_times * g.num_taps, "num_times * num_taps",
+                               "hrt_sparse_array_taps")))
+            return rc;
+    }
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = dspec;
+    job.out_bytes = (uint64_t)nrx * ntx * (16u + (uint64_t)dspec->max_paths * sizeof(hrt_dominant_path));
+    job.scratch_bytes = dm_job_scratch;
+    job.run = dm_job_run;
+    job.deliver = spt_job_deliver;
+    job.finish = spt_job_finish;
+    job.aux = &sj;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_sparse_array_taps", "hrt_compute_sparse_array_taps");
 }
 
 /* ------------------------------------------------------------------ beamformed channel responses (hrt_beam_channel) */

@@ -992,6 +992,64 @@ class Tracer:
         H = self.sparse_array_channel(paths, z, z, f0, df, num_freqs, t0, dt, num_times, 1.0, o7, accumulate)
         return H.view(tuple(H.shape[:2]) + tuple(H.shape[4:])) if out is None else out
 
+    def sparse_array_taps(self, paths, rx_elements, tx_elements, fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0,
+                          num_times=1, array_frequency=None, out=None, accumulate=False):
+        """The antenna-array impulse responses of dominant-path lists, formed on the device (hrt_sparse_array_taps;
+        include/hermespy_rt.h hrt_compute_sparse_array_taps): with n = min(kept, K) of the link,
+
+            h[rx, tx, i, j, pol, m, k] = sum_{p < n} a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p))
+                                                    * exp(j 2 pi f_a (r_i . u_rx_p + q_j . u_tx_p) / c)
+                                                    * sinc(l_min + k - f_s tau_p)
+
+        paths: what sparse_array_channel() accepts (a dominant_paths() result, a merged list, a cluster_list).  fs,
+        num_taps, l_min, fc, t0, dt and num_times are array_taps()'s (fc is a number here: no trace, no carrier to
+        default to); the elements and f_a are array_channel()'s.  No trace is needed: a traced link can be evaluated
+        again for another sampling rate, tap window, array or time axis.  Slots at or beyond n are never read.
+        Returns a complex64 tensor [nrx, ntx, Nr, Nt, 2, num_times, num_taps] on the device, enqueued on the current
+        stream, which apply_taps() and beams.apply take as it is; `out` is written in place, or added to with
+        accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        buf, nrx, ntx, K = self._path_lists(paths)
+        spec = abi.sparse_taps_spec(nrx, ntx, K, fs, num_taps, l_min, fc, t0, dt, num_times)
+        # (a call the library refuses may have no sensible size: a placeholder it does not write)
+        fits = (abi.sparse_taps_out_bytes(spec, nr, nt) > 0 and 0 < nr <= 1024 and 0 < nt <= 1024
+                and nr * nt * int(num_times) * int(num_taps) <= 1 << 24)
+        shape = (nrx, ntx, nr, nt, 2, int(num_times), int(num_taps)) if fits else (1,)
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        arrays, d_el = upload()
+        rc = self.L.hrt_sparse_array_taps(self.device.index, C.byref(spec), C.c_void_p(arrays.rx_elements), nr,
+                                          C.c_void_p(arrays.tx_elements), nt, float(arrays.array_frequency_hz),
+                                          C.c_void_p(buf.data_ptr()), C.c_void_p(out.data_ptr()),
+                                          1 if accumulate else 0, C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_sparse_array_taps: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_sparse_array_taps")
+        d_el.record_stream(stream)   # (the kernel reads the offsets and the lists after this call returns)
+        buf.record_stream(stream)
+        return out
+
+    def sparse_taps(self, paths, fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0, num_times=1, out=None,
+                    accumulate=False):
+        """The SISO impulse responses of dominant-path lists: sparse_array_taps() at one zero-offset element per side,
+        bit for bit, as a complex64 tensor [nrx, ntx, 2, num_times, num_taps] (taps()'s layout)."""
+        z = np.zeros((1, 3), np.float32)
+        o7 = None
+        if out is not None:
+            if out.dim() != 5 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous complex64 tensor [nrx, ntx, 2, num_times, num_taps]")
+            o7 = out.view(tuple(out.shape[:2]) + (1, 1) + tuple(out.shape[2:]))
+        h = self.sparse_array_taps(paths, z, z, fs, num_taps, l_min, fc, t0, dt, num_times, 1.0, o7, accumulate)
+        return h.view(tuple(h.shape[:2]) + tuple(h.shape[4:])) if out is None else out
+
     # ------------------------------------------------------------------ dense (host) view
     def to_dense(self, sentinel_u32=abi.SENTINEL_U32):
         """Assemble the reference's dense [rx][tx][b][p] scatter arrays on the host from the

@@ -521,6 +521,25 @@ int hrt_sparse_array_channel(int device, const hrt_sparse_spec *spec, const floa
                              const float *d_tx_el, uint32_t nt, double fa_hz, const void *d_paths, float *d_out,
                              int accumulate, void *stream);
 
+/* ---- the array taps of dominant-path lists (csrc/host/channel.c, csrc/hrt_sparse_taps.hip) ----
+ * h as hermespy_rt.h defines it (hrt_sparse_taps_spec, hrt_compute_sparse_array_taps), hrt_sparse_taps_out_bytes bytes
+ * at d_out, from the lists at d_paths (num_rx * num_tx * (16 + 72 max_paths) bytes in hrt_dominant_paths' layout: its
+ * output, a merged or a synthetic list; 8-byte aligned), the element offsets d_rx_el [nr][3] and d_tx_el [nt][3] -- all
+ * DEVICE pointers -- asynchronous on `stream` of `device`.  As hrt_sparse_array_channel: no problem handle, reads only
+ * the buffer and does not write it; accumulate = 0 overwrites d_out, 1 adds to it; one workgroup sums all live slots of
+ * a link in index order, so every byte of d_out is written exactly once (added to once), without atomics or scratch,
+ * and two calls with the same input give the same bytes; a link's bytes depend only on its own slots; slots at or
+ * beyond min(kept, max_paths) are never read.  The finiteness of the offsets is the caller's to ensure.  The size
+ * function returns 0 for a NULL or refused spec.  HRT_E_INVALID, before the device is touched: a NULL pointer; num_rx *
+ * num_tx of 0 or above 65 535; max_paths of 0 or above 1 024; num_rx * num_tx * max_paths above 2^22; num_taps or
+ * num_times 0; num_taps * num_times above 2^20; f_s not finite or <= 0; f_c, t0 or dt not finite; |l_min| or |l_min +
+ * num_taps| above 2^24; nr or nt outside 1..1024; nr * nt * num_times * num_taps above 2^24; f_a not finite or <= 0;
+ * d_paths not 8-byte aligned; accumulate not 0 or 1. */
+uint64_t hrt_sparse_taps_out_bytes(const hrt_sparse_taps_spec *spec, uint32_t nr, uint32_t nt);
+int hrt_sparse_array_taps(int device, const hrt_sparse_taps_spec *spec, const float *d_rx_el, uint32_t nr,
+                          const float *d_tx_el, uint32_t nt, double fa_hz, const void *d_paths, float *d_out,
+                          int accumulate, void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
