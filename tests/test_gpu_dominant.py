@@ -22,6 +22,11 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (name, rays, tx kept): the eligible scatter terms per link the CPU oracle gives are in the comments
+# The chunk count of a case falls out of its ray count (dm_plan: rays // 512, at most 256): C1's 10 000 rays give 19
+# chunks, which is the only reason the merge kernel runs in this file, in two groups of 16 and 3 lists; no case here
+# is sized for a merge shape, and none fills the pending slots exactly to 2 048 - K (that takes 1 024 live records
+# of a chunk in ascending order).  Those edges, asserted from the chunk plan and a model of the slot rules, are
+# tests/test_gpu_dominant_order.py.
 CASES = [
     ("C1", None, None),                # 10 000
     ("C3", 20000, None),               # 28 928 .. 29 018
