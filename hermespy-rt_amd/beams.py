@@ -4,6 +4,8 @@ plain numpy.
 
     dft_codebook   the unitary DFT codebook of an n-element uniform linear array (one beam per row)
     steering       the plane-wave response of an array towards given directions
+    gains          the gains g[beam, direction] of a codebook towards given directions: what ranks the beams of a
+                   dominant-path list's directions on the host
     apply          B = conj(W_rx) H W_tx^T on an array_channel or array_taps result: what beam_channel and beam_taps
                    compute without forming H
 
@@ -36,6 +38,19 @@ def steering(elements, directions, frequency):
     ph = (float(frequency) / C0) * (u.reshape(-1, 3) @ r.T)
     s = np.exp(2j * np.pi * (ph - np.rint(ph)))
     return s[0] if one else s
+
+
+def gains(elements, weights, directions, frequency, conj=False):
+    """complex128 [b, d]: g[beam, direction] = sum_i w[beam, i] exp(j 2 pi f r_i . u / c) of a codebook w [b, n] (or [n]:
+    one beam) over the elements r_i [n, 3] towards the unit vectors u [d, 3] (or [3]: one column); conj=True applies the
+    codebook conjugated, as the RX side does.  With the u_rx (conj=True) or u_tx of a dominant-path list these are the
+    g_rx[a](u_rx_p) and g_tx[b](u_tx_p) of beam_channel() and sparse_beam_channel()."""
+    w = np.asarray(weights, np.complex128)
+    w = w.reshape(1, -1) if w.ndim == 1 else w
+    s = steering(elements, np.asarray(directions, np.float64).reshape(-1, 3), frequency)   # [d, n]
+    if w.ndim != 2 or w.shape[1] != s.shape[1]:
+        raise ValueError("gains: weights %s do not match %d elements" % (w.shape, s.shape[1]))
+    return (np.conj(w) if conj else w) @ s.T
 
 
 def apply(H, rx_weights, tx_weights):

@@ -1,11 +1,11 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps;
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps, hrt_compute_sparse_array_channel,
- * hrt_compute_sparse_array_taps).
+ * hrt_compute_sparse_array_taps, hrt_compute_sparse_beam_channel).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -37,6 +37,7 @@
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
+#include "../hrt_sparse_beam.h"
 #include "../hrt_sparse_channel.h"
 #include "../hrt_sparse_taps.h"
 #include "../hrt_svd.h"
@@ -2273,6 +2274,140 @@ int hrt_compute_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, 
     job.out_bytes = (uint64_t)nrx * ntx * n_rx_beams * n_tx_beams * 2u * spec->num_times * spec->num_taps * 8u;
     job.scratch_bytes = bt_job_scratch;
     job.run = bt_job_run;
+    return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                        rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ beam channels of path lists (hrt_sparse_beam_channel) */
+
+/* the checks of a sparse beam call (`who`) behind sparse_check that need no device: the counts, the points, f_a.  There
+ * is no limit on Nr * Nt: the element-domain matrix is never formed */
+static int sparse_beam_check(const hrt_sparse_spec *sp, uint32_t nr, uint32_t nt, uint32_t br, uint32_t bt, double fa_hz,
+                             const char *who)
+{
+    if (nr < 1 || nr > HRT_BM_MAX_ELEMENTS || nt < 1 || nt > HRT_BM_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX elements (1 .. %u each)", who, nr, nt, HRT_BM_MAX_ELEMENTS);
+    if (br < 1 || br > HRT_BM_MAX_BEAMS || bt < 1 || bt > HRT_BM_MAX_BEAMS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX beams (1 .. %u each)", who, br, bt, HRT_BM_MAX_BEAMS);
+    const uint64_t pts = (uint64_t)br * bt * sp->num_times * sp->num_freqs;
+    if (pts > HRT_BM_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: Br * Bt * num_times * num_freqs = %llu > 2^24", who,
+                        (unsigned long long)pts);
+    if (!isfinite(fa_hz) || !(fa_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "%s: the array frequency must be finite and > 0", who);
+    return HRT_OK;
+}
+
+uint64_t hrt_sparse_beam_out_bytes(const hrt_sparse_spec *spec, uint32_t br, uint32_t bt)
+{
+    if (sparse_check(spec, "hrt_sparse_beam_out_bytes")) return 0;
+    return (uint64_t)spec->num_rx * spec->num_tx * br * bt * 2u * spec->num_times * spec->num_freqs * 8u;
+}
+
+int hrt_sparse_beam_channel(int device, const hrt_sparse_spec *spec, const float *d_rx_el, uint32_t nr,
+                            const float *d_tx_el, uint32_t nt, double fa_hz, const float *d_rx_w, uint32_t br,
+                            const float *d_tx_w, uint32_t bt, const void *d_paths, float *d_out, int accumulate,
+                            void *stream)
+{
+    const char *who = "hrt_sparse_beam_channel";
+    int rc = sparse_check(spec, who);
+    if (rc) return rc;
+    if (!d_rx_el || !d_tx_el || !d_rx_w || !d_tx_w || !d_paths || !d_out)
+        return hrt_fail(HRT_E_INVALID, "%s: NULL device pointer", who);
+    if ((rc = sparse_beam_check(spec, nr, nt, br, bt, fa_hz, who))) return rc;
+    if ((uintptr_t)d_paths % 8u) return hrt_fail(HRT_E_INVALID, "%s: d_paths is not 8-byte aligned", who);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "%s: accumulate must be 0 or 1", who);
+    hrt_ksparse_beam K;
+    memset(&K, 0, sizeof K);
+    K.links = spec->num_rx * spec->num_tx;
+    K.max_paths = spec->max_paths;
+    K.nr = nr; K.nt = nt; K.br = br; K.bt = bt; K.npairs = br * bt;
+    if ((uint64_t)K.links * 2u * K.npairs * spec->num_times * spec->num_freqs >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "%s: more than 2^39 outputs", who);
+    K.g.K = spec->num_freqs; K.g.T = spec->num_times;
+    K.g.K1 = (spec->num_freqs + HRT_CH_K2 - 1) / HRT_CH_K2;
+    K.g.rows = K.g.K1 * K.g.T;
+    K.g.pblocks = (K.npairs + HRT_AC_PAIRS - 1) / HRT_AC_PAIRS;
+    K.g.cblocks = (K.g.rows + HRT_AC_GROWS - 1) / HRT_AC_GROWS;
+    K.g.f0 = spec->f0_hz; K.g.df = spec->df_hz; K.g.t0 = spec->t0_s; K.g.dt = spec->dt_s;
+    K.g.fa_c = fa_hz / HRT_SPEED_OF_LIGHT;
+    K.accumulate = (uint32_t)accumulate;
+    K.rx_el = d_rx_el; K.tx_el = d_tx_el;
+    K.rx_w = d_rx_w; K.tx_w = d_tx_w;
+    K.paths = (const uint8_t *)d_paths;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_sparse_beam(&K, stream), "sparse beam kernel");
+    return HRT_OK;
+}
+
+/* after the last batch: the merged lists stay at d_paths; the beam channel is evaluated once, and only it (and the
+ * lists, if asked for) comes down.  The offsets and the weights are ch_compute's upload (ac_job_arrays,
+ * beam_job_beams); the aux is hrt_compute_sparse_array_channel's sp_job. */
+static int sb_job_deliver(const ch_job *j, int device, const void *d_paths, void *out)
+{
+    const sp_job *sj = (const sp_job *)j->aux;
+    const hrt_array_spec a = ac_job_arrays(j);
+    const hrt_beam_spec b = beam_job_beams(j);
+    const uint64_t bytes = hrt_sparse_beam_out_bytes(&sj->sp, j->nbr, j->nbt);
+    void *d_B = NULL;
+    int rc = hrt_device_malloc(device, &d_B, bytes);
+    if (!rc)
+        rc = hrt_sparse_beam_channel(device, &sj->sp, a.rx_elements, j->nr, a.tx_elements, j->nt, j->fa, b.rx_weights,
+                                     j->nbr, b.tx_weights, j->nbt, d_paths, (float *)d_B, 0, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_B, bytes);
+    if (!rc && sj->paths_out) rc = hrt_device_download(device, sj->paths_out, d_paths, j->out_bytes);
+    if (d_B) hrt_device_free(device, d_B);
+    return rc;
+}
+
+int hrt_compute_sparse_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                    const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                    const hrt_dominant_spec *dspec, const hrt_channel_spec *grid, const Vec3 *rx_el,
+                                    size_t nr, const Vec3 *tx_el, size_t nt, double f_a, const float *rx_weights,
+                                    size_t n_rx_beams, const float *tx_weights, size_t n_tx_beams, float *out,
+                                    void *paths_out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    const char *dev = "hrt_sparse_beam_channel";
+    int rc = dominant_check(dspec);
+    if (rc) return rc;
+    if ((rc = dominant_links_check(nrx, ntx, dspec))) return rc;
+    if (!grid) return hrt_fail(HRT_E_INVALID, "hrt_compute_sparse_beam_channel: NULL grid");
+    if ((rc = beam_counts_check(nr, nt, n_rx_beams, n_tx_beams, dev))) return rc;
+    sp_job sj;
+    memset(&sj, 0, sizeof sj);
+    sj.sp.f0_hz = grid->f0_hz; sj.sp.df_hz = grid->df_hz; sj.sp.num_freqs = grid->num_freqs;
+    sj.sp.t0_s = grid->t0_s; sj.sp.dt_s = grid->dt_s; sj.sp.num_times = grid->num_times;
+    sj.sp.num_rx = (uint32_t)nrx; sj.sp.num_tx = (uint32_t)ntx;
+    sj.sp.max_paths = dspec->max_paths;
+    sj.paths_out = paths_out;
+    {   /* the grid (the parts are the dominant spec's), the counts, the points and f_a */
+        const hrt_channel_spec g = {grid->f0_hz, grid->df_hz, grid->num_freqs, grid->t0_s, grid->dt_s,
+                                    grid->num_times, dspec->parts};
+        if ((rc = spec_check(&g))) return rc;
+        if ((rc = sparse_beam_check(&sj.sp, (uint32_t)nr, (uint32_t)nt, (uint32_t)n_rx_beams, (uint32_t)n_tx_beams, f_a,
+                                    dev)))
+            return rc;
+    }
+    if (!rx_el || !tx_el) return hrt_fail(HRT_E_INVALID, "%s: NULL element offsets", dev);
+    if (!rx_weights || !tx_weights) return hrt_fail(HRT_E_INVALID, "%s: NULL beam weights", dev);
+    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, dev))) return rc;
+    if ((rc = beam_weights_check(rx_weights, n_rx_beams, nr, "RX", dev))) return rc;
+    if ((rc = beam_weights_check(tx_weights, n_tx_beams, nt, "TX", dev))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_sparse_beam_channel")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = dspec;
+    job.out_bytes = (uint64_t)nrx * ntx * (16u + (uint64_t)dspec->max_paths * sizeof(hrt_dominant_path));
+    job.scratch_bytes = dm_job_scratch;
+    job.run = dm_job_run;
+    job.deliver = sb_job_deliver;
+    job.finish = sp_job_finish;
+    job.aux = &sj;
     return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                         rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);
 }

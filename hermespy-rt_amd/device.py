@@ -992,6 +992,57 @@ class Tracer:
         H = self.sparse_array_channel(paths, z, z, f0, df, num_freqs, t0, dt, num_times, 1.0, o7, accumulate)
         return H.view(tuple(H.shape[:2]) + tuple(H.shape[4:])) if out is None else out
 
+    def sparse_beam_channel(self, paths, rx_elements, tx_elements, rx_weights, tx_weights, f0, df, num_freqs, t0=0.0,
+                            dt=0.0, num_times=1, array_frequency=None, out=None, accumulate=False):
+        """The beamformed (codebook) channel of dominant-path lists, formed on the device (hrt_sparse_beam_channel;
+        include/hermespy_rt.h hrt_compute_sparse_beam_channel): with n = min(kept, K) of the link,
+
+            B[rx, tx, a, b, pol, m, k] = sum_{p < n} a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) g_rx[a](u_rx_p) g_tx[b](u_tx_p)
+            g_rx[a](u) = sum_i conj(W_rx[a, i]) exp(j 2 pi f_a r_i . u / c)
+            g_tx[b](u) = sum_j      W_tx[b, j]  exp(j 2 pi f_a q_j . u / c)
+
+        = beams.apply(sparse_array_channel(...), W_rx, W_tx) without the element-domain matrix being formed: the cost
+        follows Br * Bt, not Nr * Nt, and Nr * Nt is not limited.  paths: what sparse_array_channel() accepts; the
+        grid, the elements and f_a are array_channel()'s, the codebooks beam_channel()'s (rx_weights (Br, Nr) applied
+        conjugated, tx_weights (Bt, Nt) as they are, not normalised).  No trace is needed: a beam sweep or a codebook
+        search over a list costs what the list costs.  Returns a complex64 tensor [nrx, ntx, Br, Bt, 2, num_times,
+        num_freqs] on the device, enqueued on the current stream; `out` is written in place, or added to with
+        accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        wr = abi.weights(rx_weights.cpu().numpy() if hasattr(rx_weights, "cpu") else rx_weights, nr, "rx_weights")
+        wt = abi.weights(tx_weights.cpu().numpy() if hasattr(tx_weights, "cpu") else tx_weights, nt, "tx_weights")
+        if not (np.isfinite(wr.view(np.float32)).all() and np.isfinite(wt.view(np.float32)).all()):
+            raise ValueError("beam weights must be finite")
+        br, bt = wr.shape[0], wt.shape[0]
+        buf, nrx, ntx, K = self._path_lists(paths)
+        spec = abi.sparse_spec(nrx, ntx, K, f0, df, num_freqs, t0, dt, num_times)
+        # (a call the library refuses may have no sensible size: a placeholder it does not write)
+        fits = (abi.sparse_beam_out_bytes(spec, br, bt) > 0 and 0 < nr <= 256 and 0 < nt <= 256 and 0 < br <= 256
+                and 0 < bt <= 256 and br * bt * int(num_times) * int(num_freqs) <= 1 << 24)
+        shape = (nrx, ntx, br, bt, 2, int(num_times), int(num_freqs)) if fits else (1,)
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        arrays, beams_, d_el = upload((wr, wt))
+        rc = self.L.hrt_sparse_beam_channel(self.device.index, C.byref(spec), C.c_void_p(arrays.rx_elements), nr,
+                                            C.c_void_p(arrays.tx_elements), nt, float(arrays.array_frequency_hz),
+                                            C.c_void_p(beams_.rx_weights), br, C.c_void_p(beams_.tx_weights), bt,
+                                            C.c_void_p(buf.data_ptr()), C.c_void_p(out.data_ptr()),
+                                            1 if accumulate else 0, C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_sparse_beam_channel: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_sparse_beam_channel")
+        d_el.record_stream(stream)   # (the kernel reads the offsets, the weights and the lists after this call returns)
+        buf.record_stream(stream)
+        return out
+
     def sparse_array_taps(self, paths, rx_elements, tx_elements, fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0,
                           num_times=1, array_frequency=None, out=None, accumulate=False):
         """The antenna-array impulse responses of dominant-path lists, formed on the device (hrt_sparse_array_taps;

@@ -43,6 +43,7 @@ EXPORTED = (
     "hrt_equalizer_out_bytes", "hrt_channel_equalizer", "hrt_compute_channel_equalizer",
     "hrt_sparse_paths_bytes", "hrt_sparse_out_bytes", "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel",
     "hrt_sparse_taps_out_bytes", "hrt_sparse_array_taps", "hrt_compute_sparse_array_taps",
+    "hrt_sparse_beam_out_bytes", "hrt_sparse_beam_channel", "hrt_compute_sparse_beam_channel",
     "hrt_apply_patterns", "hrt_compute_set_patterns",
 )
 
@@ -363,6 +364,17 @@ def load():
                                                 C.c_size_t, C.c_size_t, C.c_size_t, dmp, tpp, V3, C.c_size_t, V3,
                                                 C.c_size_t, C.c_double, f32p, vp, C.POINTER(Stats)]
     L.hrt_compute_sparse_array_taps.restype = C.c_int
+    # the beam channel of dominant-path lists (hrt_sparse_spec: abi.SparseSpec)
+    L.hrt_sparse_beam_out_bytes.argtypes = [ssp, u32, u32]
+    L.hrt_sparse_beam_out_bytes.restype = u64
+    L.hrt_sparse_beam_channel.argtypes = [C.c_int, ssp, vp, u32, vp, u32, C.c_double, vp, u32, vp, u32, vp, vp,
+                                          C.c_int, vp]
+    L.hrt_sparse_beam_channel.restype = C.c_int
+    L.hrt_compute_sparse_beam_channel.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                                  C.c_size_t, C.c_size_t, C.c_size_t, dmp, spp, V3, C.c_size_t, V3,
+                                                  C.c_size_t, C.c_double, f32p, C.c_size_t, f32p, C.c_size_t, f32p, vp,
+                                                  C.POINTER(Stats)]
+    L.hrt_compute_sparse_beam_channel.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

@@ -621,6 +621,41 @@ int hrt_compute_sparse_array_channel(Scene *scene, const Vec3 *rx_pos, const Vec
                                      float *out /* complex interleaved, layout above */,
                                      void *paths_out /* hrt_dominant_out_bytes, or NULL */, hrt_stats *stats);
 
+/* The beamformed channel of dominant-path lists, formed on the device (include/hrt_device.h:
+ * hrt_sparse_beam_channel): what hrt_compute_beam_channel gives from the workspace, here from a buffer in exactly the
+ * layout hrt_dominant_paths writes (header uint64_t [L][2] = {kept, eligible}, then hrt_dominant_path [L][K]), so that
+ * a beam sweep, a codebook search or a re-evaluation on another grid or time axis costs what the list costs.  For every
+ * link, RX beam a, TX beam b, polarisation, time sample m and frequency k:
+ *     n = min(kept[link], K)
+ *     B[rx][tx][a][b][pol][m][k] = sum over slots p < n of
+ *           a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p)) g_rx[a](u_rx_p) g_tx[b](u_tx_p)
+ *     g_rx[a](u) = sum_i conj(W_rx[a][i]) exp(j 2 pi f_a r_i . u / c),   g_tx[b](u) = sum_j W_tx[b][j] exp(j 2 pi f_a q_j . u / c)
+ * The grid, the element offsets and f_a are hrt_compute_array_channel's; the weight layout and conventions are
+ * hrt_compute_beam_channel's: rx_weights complex [Br][Nr], tx_weights complex [Bt][Nt], re/im interleaved, the RX
+ * codebook applied conjugated, nothing normalised, one codebook for all RX and one for all TX.
+ * out: complex [num_rx][num_tx][Br][Bt][2][num_times][num_freqs], re/im interleaved (numpy complex64).
+ * The slot rules are hrt_compute_sparse_array_channel's: the LoS entry is an ordinary slot; power, path, bounce and tri
+ * are not read; slots at or beyond n are never read; a link with n = 0 writes zeros (or leaves `out` unchanged when
+ * accumulating).  Where kept = eligible for a link the result is hrt_compute_beam_channel's for the same parts, up to
+ * the order of the float32 sums; it equals hrt_compute_sparse_array_channel's H contracted with the two codebooks
+ * wherever H can be formed, and H is never formed: there is no limit on Nr * Nt.  Every byte of `out` is written
+ * exactly once (added to once when accumulating); no atomics and no scratch buffer; two calls with the same input give
+ * the same bytes; a link's bytes depend only on its own slots below n, the grid, the elements and the weights.
+ * hrt_compute_sparse_beam_channel runs hrt_compute_dominant_paths' batch loop (the lists merged on the device) and
+ * evaluates the merged lists once after the last batch; only `out`, and the lists if paths_out is not NULL, is copied
+ * back.  HRT_E_INVALID, before the device is touched: every hrt_compute_dominant_paths check; every grid check of
+ * hrt_channel_spec (the grid's parts are not read: the parts are the dominant spec's); Nr or Nt outside 1..256; Br or
+ * Bt outside 1..256; Br * Bt * num_times * num_freqs > 2^24; an offset, a weight or f_a not finite; f_a <= 0. */
+int hrt_compute_sparse_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                    const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                    size_t num_rays, size_t num_bounces, const hrt_dominant_spec *dominant_spec,
+                                    const hrt_channel_spec *grid, const Vec3 *rx_elements, size_t num_rx_elements,
+                                    const Vec3 *tx_elements, size_t num_tx_elements, double array_frequency_hz,
+                                    const float *rx_weights /* complex [Br][Nr] */, size_t num_rx_beams,
+                                    const float *tx_weights /* complex [Bt][Nt] */, size_t num_tx_beams,
+                                    float *out /* complex interleaved, layout above */,
+                                    void *paths_out /* hrt_dominant_out_bytes, or NULL */, hrt_stats *stats);
+
 /* The antenna-array impulse responses of dominant-path lists, formed on the device (include/hrt_device.h:
  * hrt_sparse_array_taps): the time-domain half of the above, what hrt_compute_array_taps gives from the workspace, here
  * from a buffer in exactly the layout hrt_dominant_paths writes (header uint64_t [L][2] = {kept, eligible}, then
