@@ -1167,6 +1167,69 @@ def run_compute_sparse_array_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_ve
     return (out, dominant_views(paths, nrx, ntx, dominant.max_paths)) if return_paths else out
 
 
+# ---- the beam taps of dominant-path lists (include/hermespy_rt.h: hrt_compute_sparse_beam_taps) ----
+def sparse_beam_taps_out_bytes(spec, br, bt):
+    """the bytes of the beam taps of a list (hrt_sparse_beam_taps_out_bytes; 0 for a spec the library refuses)"""
+    if not sparse_taps_out_bytes(spec, 1, 1):
+        return 0
+    return int(spec.num_rx) * int(spec.num_tx) * int(br) * int(bt) * 2 * int(spec.num_times) * int(spec.num_taps) * 8
+
+
+def run_sparse_beam_taps(lib, device, spec, d_rx_el, nr, d_tx_el, nt, fa_hz, d_rx_w, br, d_tx_w, bt, d_paths, d_out,
+                         accumulate=0, stream=None):
+    """hrt_sparse_beam_taps through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_sparse_beam_taps failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_sparse_beam_taps(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_rx_el),
+                                  C.c_uint32(int(nr)), C.c_void_p(d_tx_el), C.c_uint32(int(nt)),
+                                  C.c_double(float(fa_hz)), C.c_void_p(d_rx_w), C.c_uint32(int(br)),
+                                  C.c_void_p(d_tx_w), C.c_uint32(int(bt)), C.c_void_p(d_paths), C.c_void_p(d_out),
+                                  C.c_int(int(accumulate)), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_sparse_beam_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_sparse_beam_taps(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces,
+                                 dominant, grid, rx_elements, tx_elements, rx_weights, tx_weights,
+                                 array_frequency=None, return_paths=False, stats=None):
+    """hrt_compute_sparse_beam_taps through ctypes (dominant: a DominantSpec, grid: a TapsSpec whose parts are not read)
+    -> complex64 [nrx, ntx, Br, Bt, 2, num_times, num_taps], or (h, dominant_views of the lists) with return_paths.
+    rx_weights (Br, Nr) is applied conjugated, tx_weights (Bt, Nt) as it is.  Raises
+    RuntimeError("hrt_compute_sparse_beam_taps failed (<rc>): ...") on an error code."""
+    rx_pos = np.asarray(rx_pos, np.float32).reshape(-1, 3)
+    tx_pos = np.asarray(tx_pos, np.float32).reshape(-1, 3)
+    nrx, ntx = rx_pos.shape[0], tx_pos.shape[0]
+    _, rxp = _vec3_arg(rx_pos, nrx)
+    _, txp = _vec3_arg(tx_pos, ntx)
+    rxv_a, rxv = _vec3_arg(rx_vel, nrx)
+    txv_a, txv = _vec3_arg(tx_vel, ntx)
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    wr, wt = weights(rx_weights, nr, "rx_weights"), weights(tx_weights, nt, "tx_weights")
+    br, bt = wr.shape[0], wt.shape[0]
+    extra += (wr.ctypes.data_as(c_float_p), C.c_size_t(br), wt.ctypes.data_as(c_float_p), C.c_size_t(bt))
+    # (outputs too large for the host are refused by the library's limits first: allocate only what passes them)
+    T, L = (int(grid.num_times), int(grid.num_taps)) if grid is not None else (0, 0)
+    pts = br * bt * T * L
+    nbytes = dominant_out_bytes(nrx, ntx, dominant) if dominant is not None else 0
+    fits = nbytes > 0 and 0 < pts <= (1 << 24) and T * L <= (1 << 20)
+    out = np.zeros((nrx, ntx, br, bt, 2, T, L) if fits else (1,), np.complex64)
+    paths = np.zeros(nbytes if fits else 8, np.uint8) if return_paths else None
+    scene = lib.scene_load(str(scene_path).encode())
+    try:
+        rc = lib.hrt_compute_sparse_beam_taps(
+            C.byref(scene), rxp, txp, rxv, txv, C.c_float(f_ghz), C.c_size_t(nrx), C.c_size_t(ntx),
+            C.c_size_t(int(num_paths)), C.c_size_t(int(num_bounces)),
+            C.byref(dominant) if dominant is not None else None, C.byref(grid) if grid is not None else None, *extra,
+            out.ctypes.data_as(c_float_p), paths.ctypes.data_as(C.c_void_p) if paths is not None else None,
+            C.byref(stats) if stats is not None else None)
+    finally:
+        free_scene(scene)
+    if rc != 0:
+        raise RuntimeError("hrt_compute_sparse_beam_taps failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+    if not fits:
+        raise RuntimeError("hrt_compute_sparse_beam_taps accepted a call beyond its limits")
+    return (out, dominant_views(paths, nrx, ntx, dominant.max_paths)) if return_paths else out
+
+
 # ---- test-only entries (include/hrt_device.h): a lane's own candidate lookup, what the tables were built with ----
 CAND_KINDS = dict(patch=1, image=2, txcell=4, cell_mask=8)
 

@@ -1,11 +1,12 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel;
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
+ * hrt_sparse_beam_taps;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
  * hrt_compute_dominant_paths, hrt_compute_beam_channel, hrt_compute_beam_taps, hrt_compute_sparse_array_channel,
- * hrt_compute_sparse_array_taps, hrt_compute_sparse_beam_channel).
+ * hrt_compute_sparse_array_taps, hrt_compute_sparse_beam_channel, hrt_compute_sparse_beam_taps).
  *
  *     H[rx, tx, pol, m, k] = sum_p a_p^pol exp(j 2 pi (nu_p t_m - f_k tau_p))
  *
@@ -38,6 +39,7 @@
 #include "../hrt_power.h"
 #include "../hrt_propagate.h"
 #include "../hrt_sparse_beam.h"
+#include "../hrt_sparse_beam_taps.h"
 #include "../hrt_sparse_channel.h"
 #include "../hrt_sparse_taps.h"
 #include "../hrt_svd.h"
@@ -2407,6 +2409,141 @@ int hrt_compute_sparse_beam_channel(Scene *scene, const Vec3 *rx_pos, const Vec3
     job.run = dm_job_run;
     job.deliver = sb_job_deliver;
     job.finish = sp_job_finish;
+    job.aux = &sj;
+    return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                        rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);
+}
+
+/* ------------------------------------------------------------------ beam taps of path lists (hrt_sparse_beam_taps) */
+
+/* the checks of a sparse beam taps call (`who`) behind sparse_taps_check that need no device: the counts, the points,
+ * f_a.  There is no limit on Nr * Nt: the element-domain taps are never formed */
+static int sparse_beam_taps_check(const hrt_sparse_taps_spec *sp, uint32_t nr, uint32_t nt, uint32_t br, uint32_t bt,
+                                  double fa_hz, const char *who)
+{
+    if (nr < 1 || nr > HRT_BM_MAX_ELEMENTS || nt < 1 || nt > HRT_BM_MAX_ELEMENTS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX elements (1 .. %u each)", who, nr, nt, HRT_BM_MAX_ELEMENTS);
+    if (br < 1 || br > HRT_BM_MAX_BEAMS || bt < 1 || bt > HRT_BM_MAX_BEAMS)
+        return hrt_fail(HRT_E_INVALID, "%s: %u RX and %u TX beams (1 .. %u each)", who, br, bt, HRT_BM_MAX_BEAMS);
+    const uint64_t pts = (uint64_t)br * bt * sp->num_times * sp->num_taps;
+    if (pts > HRT_BM_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: Br * Bt * num_times * num_taps = %llu > 2^24", who, (unsigned long long)pts);
+    if (!isfinite(fa_hz) || !(fa_hz > 0.0))
+        return hrt_fail(HRT_E_INVALID, "%s: the array frequency must be finite and > 0", who);
+    return HRT_OK;
+}
+
+uint64_t hrt_sparse_beam_taps_out_bytes(const hrt_sparse_taps_spec *spec, uint32_t br, uint32_t bt)
+{
+    if (sparse_taps_check(spec, "hrt_sparse_beam_taps_out_bytes")) return 0;
+    return (uint64_t)spec->num_rx * spec->num_tx * br * bt * 2u * spec->num_times * spec->num_taps * 8u;
+}
+
+int hrt_sparse_beam_taps(int device, const hrt_sparse_taps_spec *spec, const float *d_rx_el, uint32_t nr,
+                         const float *d_tx_el, uint32_t nt, double fa_hz, const float *d_rx_w, uint32_t br,
+                         const float *d_tx_w, uint32_t bt, const void *d_paths, float *d_out, int accumulate,
+                         void *stream)
+{
+    const char *who = "hrt_sparse_beam_taps";
+    int rc = sparse_taps_check(spec, who);
+    if (rc) return rc;
+    if (!d_rx_el || !d_tx_el || !d_rx_w || !d_tx_w || !d_paths || !d_out)
+        return hrt_fail(HRT_E_INVALID, "%s: NULL device pointer", who);
+    if ((rc = sparse_beam_taps_check(spec, nr, nt, br, bt, fa_hz, who))) return rc;
+    if ((uintptr_t)d_paths % 8u) return hrt_fail(HRT_E_INVALID, "%s: d_paths is not 8-byte aligned", who);
+    if (accumulate != 0 && accumulate != 1) return hrt_fail(HRT_E_INVALID, "%s: accumulate must be 0 or 1", who);
+    hrt_ksparse_beam_taps K;
+    memset(&K, 0, sizeof K);
+    K.links = spec->num_rx * spec->num_tx;
+    K.max_paths = spec->max_paths;
+    K.nr = nr; K.nt = nt; K.br = br; K.bt = bt; K.npairs = br * bt;
+    if ((uint64_t)K.links * 2u * K.npairs * spec->num_times * spec->num_taps >= (1ull << 39))
+        return hrt_fail(HRT_E_INVALID, "%s: more than 2^39 outputs", who);
+    K.fa_c = fa_hz / HRT_SPEED_OF_LIGHT;
+    {   /* the grid of the beam taps (Br Bt pairs); a list has no records to chunk (nb = 0: nchunks stays 0) */
+        const hrt_taps_spec t = sparse_taps_grid(spec);
+        hrt_kview v;
+        uint64_t per_chunk;
+        memset(&v, 0, sizeof v);
+        v.nrx = spec->num_rx; v.ntx = spec->num_tx;
+        (void)taps_grid(&v, &t, K.npairs, 4u, &K.g, &per_chunk);
+    }
+    K.accumulate = (uint32_t)accumulate;
+    K.rx_el = d_rx_el; K.tx_el = d_tx_el;
+    K.rx_w = d_rx_w; K.tx_w = d_tx_w;
+    K.paths = (const uint8_t *)d_paths;
+    K.out = d_out;
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_sparse_beam_taps(&K, stream), "sparse beam taps kernel");
+    return HRT_OK;
+}
+
+/* after the last batch: the merged lists stay at d_paths; the beam taps are evaluated once, and only they (and the
+ * lists, if asked for) come down.  The offsets and the weights are beam_compute's upload (ac_job_arrays,
+ * beam_job_beams); the aux is hrt_compute_sparse_array_taps' spt_job. */
+static int sbt_job_deliver(const ch_job *j, int device, const void *d_paths, void *out)
+{
+    const spt_job *sj = (const spt_job *)j->aux;
+    const hrt_array_spec a = ac_job_arrays(j);
+    const hrt_beam_spec b = beam_job_beams(j);
+    const uint64_t bytes = hrt_sparse_beam_taps_out_bytes(&sj->sp, j->nbr, j->nbt);
+    void *d_h = NULL;
+    int rc = hrt_device_malloc(device, &d_h, bytes);
+    if (!rc)
+        rc = hrt_sparse_beam_taps(device, &sj->sp, a.rx_elements, j->nr, a.tx_elements, j->nt, j->fa, b.rx_weights,
+                                  j->nbr, b.tx_weights, j->nbt, d_paths, (float *)d_h, 0, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_h, bytes);
+    if (!rc && sj->paths_out) rc = hrt_device_download(device, sj->paths_out, d_paths, j->out_bytes);
+    if (d_h) hrt_device_free(device, d_h);
+    return rc;
+}
+
+int hrt_compute_sparse_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                 const hrt_dominant_spec *dspec, const hrt_taps_spec *grid, const Vec3 *rx_el,
+                                 size_t nr, const Vec3 *tx_el, size_t nt, double f_a, const float *rx_weights,
+                                 size_t n_rx_beams, const float *tx_weights, size_t n_tx_beams, float *out,
+                                 void *paths_out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    const char *dev = "hrt_sparse_beam_taps";
+    int rc = dominant_check(dspec);
+    if (rc) return rc;
+    if ((rc = dominant_links_check(nrx, ntx, dspec))) return rc;
+    if (!grid) return hrt_fail(HRT_E_INVALID, "hrt_compute_sparse_beam_taps: NULL grid");
+    if ((rc = beam_counts_check(nr, nt, n_rx_beams, n_tx_beams, dev))) return rc;
+    spt_job sj;
+    memset(&sj, 0, sizeof sj);
+    sj.sp.fs_hz = grid->fs_hz; sj.sp.fc_hz = grid->fc_hz; sj.sp.t0_s = grid->t0_s; sj.sp.dt_s = grid->dt_s;
+    sj.sp.l_min = grid->l_min; sj.sp.num_taps = grid->num_taps; sj.sp.num_times = grid->num_times;
+    sj.sp.num_rx = (uint32_t)nrx; sj.sp.num_tx = (uint32_t)ntx;
+    sj.sp.max_paths = dspec->max_paths;
+    sj.paths_out = paths_out;
+    {   /* the grid (the parts are the dominant spec's), the counts, the points and f_a */
+        const hrt_taps_spec g = {grid->fs_hz, grid->fc_hz, grid->t0_s, grid->dt_s, grid->l_min, grid->num_taps,
+                                 grid->num_times, dspec->parts};
+        if ((rc = taps_spec_check(&g, dev))) return rc;
+        if ((rc = sparse_beam_taps_check(&sj.sp, (uint32_t)nr, (uint32_t)nt, (uint32_t)n_rx_beams,
+                                         (uint32_t)n_tx_beams, f_a, dev)))
+            return rc;
+    }
+    if (!rx_el || !tx_el) return hrt_fail(HRT_E_INVALID, "%s: NULL element offsets", dev);
+    if (!rx_weights || !tx_weights) return hrt_fail(HRT_E_INVALID, "%s: NULL beam weights", dev);
+    if ((rc = ac_offsets_check(rx_el, nr, tx_el, nt, dev))) return rc;
+    if ((rc = beam_weights_check(rx_weights, n_rx_beams, nr, "RX", dev))) return rc;
+    if ((rc = beam_weights_check(tx_weights, n_tx_beams, nt, "TX", dev))) return rc;
+    if ((rc = ch_drop_in_check(scene, rx_pos, tx_pos, rx_vel, tx_vel, nrx, ntx, np, nb, out,
+                               "hrt_compute_sparse_beam_taps")))
+        return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = dspec;
+    job.out_bytes = (uint64_t)nrx * ntx * (16u + (uint64_t)dspec->max_paths * sizeof(hrt_dominant_path));
+    job.scratch_bytes = dm_job_scratch;
+    job.run = dm_job_run;
+    job.deliver = sbt_job_deliver;
+    job.finish = spt_job_finish;
     job.aux = &sj;
     return beam_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                         rx_weights, n_rx_beams, tx_weights, n_tx_beams, out, stats, t_begin);

@@ -1132,6 +1132,61 @@ py::object compute_sparse_array_taps_py(
     return py::make_tuple(out, dominant_dict(buf, lists, n, num_rx, num_tx, max_paths));
 }
 
+// compute_sparse_beam_taps: the beamformed (codebook) impulse responses of the max_paths strongest paths of every link,
+// selected and evaluated on the device (extension; see hrt_compute_sparse_beam_taps in hermespy_rt.h): complex64
+// (num_rx, num_tx, Br, Bt, 2, num_times, num_taps), or with return_paths the tuple (h, compute_dominant_paths' dict of
+// the lists).  rx_weights (Br, Nr) is applied conjugated, tx_weights (Bt, Nt) as it is.
+py::object compute_sparse_beam_taps_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double sampling_rate, unsigned long num_taps, farr rx_elements, farr tx_elements,
+    py::array rx_weights, py::array tx_weights, unsigned long max_paths, long l_min, py::object center_frequency,
+    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency,
+    py::object patterns, bool return_paths)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_taps > 0xffffffffUL || num_times > 0xffffffffUL)
+        throw std::invalid_argument("num_taps and num_times must fit 32 bits");
+    if (l_min < -(1L << 30) || l_min > (1L << 30))
+        throw py::value_error("hermespy_rt.compute_sparse_beam_taps: tap indices l_min outside +-2^24");
+    if (max_paths > 0xffffffffUL)
+        throw py::value_error("hermespy_rt.compute_sparse_beam_taps: max_paths must fit 32 bits");
+    const array_elements a(rx_elements, tx_elements);
+    const carr wr = as_weights(rx_weights, a.nr, "rx_weights"), wt = as_weights(tx_weights, a.nt, "tx_weights");
+    const size_t br = (size_t)wr.shape(0), bt = (size_t)wt.shape(0);
+    const double fc = center_frequency.is_none() ? (double)carrier_frequency * 1e9 : center_frequency.cast<double>();
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_dominant_spec dm{};
+    dm.max_paths = (uint32_t)max_paths;
+    dm.parts = parts_word(los, scatter);
+    hrt_taps_spec grid{};
+    grid.fs_hz = sampling_rate; grid.fc_hz = fc; grid.t0_s = t0; grid.dt_s = dt;
+    grid.l_min = (int32_t)l_min; grid.num_taps = (uint32_t)num_taps; grid.num_times = (uint32_t)num_times;
+    grid.parts = dm.parts;
+    // (the library validates everything before it traces anything: a refused call raises ValueError.  Outputs beyond
+    // the limits would be refused, so only ones within them are allocated.)
+    const uint64_t n = hrt_dominant_out_bytes(num_rx, num_tx, &dm);
+    const unsigned long long pts = (unsigned long long)br * bt * num_times * num_taps;
+    const bool fits = n && pts > 0 && pts <= (1ull << 24) && br <= 256 && bt <= 256 &&
+                      (uint64_t)num_taps * num_times <= (1ull << 20);
+    py::array_t<std::complex<float>> out(fits ? std::vector<size_t>{(size_t)num_rx, (size_t)num_tx, br, bt, (size_t)2,
+                                                                    (size_t)num_times, (size_t)num_taps}
+                                              : std::vector<size_t>{1});
+    float *dst = reinterpret_cast<float *>(out.mutable_data());
+    const float *pwr = reinterpret_cast<const float *>(wr.data()), *pwt = reinterpret_cast<const float *>(wt.data());
+    py::array_t<uint64_t> buf((size_t)(return_paths && n ? n / 8u : 1u));
+    uint8_t *lists = reinterpret_cast<uint8_t *>(buf.mutable_data());
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_sparse_beam_taps", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_sparse_beam_taps(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                            num_paths, num_bounces, &dm, &grid, a.rxe, a.nr, a.txe, a.nt, fa, pwr, br,
+                                            pwt, bt, dst, return_paths ? (void *)lists : nullptr, nullptr);
+    });
+    if (!return_paths) return out;
+    return py::make_tuple(out, dominant_dict(buf, lists, n, num_rx, num_tx, max_paths));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(hermespy_rt, m)
@@ -1307,6 +1362,19 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("max_paths"), py::arg("l_min") = 0, py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0,
           py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
           py::arg("array_frequency") = py::none(), py::arg("patterns") = py::none(), py::arg("return_paths") = false);
+    m.def("compute_sparse_beam_taps", &compute_sparse_beam_taps_py,
+          "Beamformed (codebook) impulse responses of the max_paths strongest paths of every link, selected and evaluated "
+          "on the device: complex64 (num_rx, num_tx, Br, Bt, 2, num_times, num_taps); rx_weights (Br, Nr) is applied "
+          "conjugated, tx_weights (Bt, Nt) as it is; with return_paths=True the tuple (h, the lists as "
+          "compute_dominant_paths returns them)",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("sampling_rate"), py::arg("num_taps"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("rx_weights"), py::arg("tx_weights"), py::arg("max_paths"), py::arg("l_min") = 0,
+          py::arg("center_frequency") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1,
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(),
+          py::arg("patterns") = py::none(), py::arg("return_paths") = false);
     m.def("version", []() { return std::string(hrt_version()); });
     // Between calls the library keeps the device workspace and the page-locked staging of the last
     // call (C3: 3.3 GB of HBM, 0.4 GB of pinned host memory; up to HRT_POOL_MAX_BYTES, default 24 GiB)

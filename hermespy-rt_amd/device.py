@@ -1088,6 +1088,59 @@ class Tracer:
         buf.record_stream(stream)
         return out
 
+    def sparse_beam_taps(self, paths, rx_elements, tx_elements, rx_weights, tx_weights, fs, num_taps, l_min=0, fc=0.0,
+                         t0=0.0, dt=0.0, num_times=1, array_frequency=None, out=None, accumulate=False):
+        """The beamformed (codebook) impulse responses of dominant-path lists, formed on the device
+        (hrt_sparse_beam_taps; include/hermespy_rt.h hrt_compute_sparse_beam_taps): with n = min(kept, K) of the link,
+
+            h[rx, tx, a, b, pol, m, k] = sum_{p < n} a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) g_rx[a](u_rx_p) g_tx[b](u_tx_p)
+                                                    * sinc(l_min + k - f_s tau_p)
+            g_rx[a](u) = sum_i conj(W_rx[a, i]) exp(j 2 pi f_a r_i . u / c)
+            g_tx[b](u) = sum_j      W_tx[b, j]  exp(j 2 pi f_a q_j . u / c)
+
+        = beams.apply(sparse_array_taps(...), W_rx, W_tx) without the element-domain taps being formed: the cost
+        follows Br * Bt, not Nr * Nt, and Nr * Nt is not limited.  paths: what sparse_beam_channel() accepts; fs,
+        num_taps, l_min, fc, t0, dt and num_times are sparse_array_taps()'s (fc is a number: no trace, no carrier to
+        default to); the elements and f_a are array_channel()'s, the codebooks beam_channel()'s (rx_weights (Br, Nr)
+        applied conjugated, tx_weights (Bt, Nt) as they are, not normalised).  No trace is needed: a beam sweep in the
+        time domain costs what the list costs.  Returns a complex64 tensor [nrx, ntx, Br, Bt, 2, num_times, num_taps]
+        on the device, enqueued on the current stream, which apply_taps() takes as it is; `out` is written in place,
+        or added to with accumulate=True.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        nr, nt, upload = self._elements(rx_elements, tx_elements, array_frequency)
+        wr = abi.weights(rx_weights.cpu().numpy() if hasattr(rx_weights, "cpu") else rx_weights, nr, "rx_weights")
+        wt = abi.weights(tx_weights.cpu().numpy() if hasattr(tx_weights, "cpu") else tx_weights, nt, "tx_weights")
+        if not (np.isfinite(wr.view(np.float32)).all() and np.isfinite(wt.view(np.float32)).all()):
+            raise ValueError("beam weights must be finite")
+        br, bt = wr.shape[0], wt.shape[0]
+        buf, nrx, ntx, K = self._path_lists(paths)
+        spec = abi.sparse_taps_spec(nrx, ntx, K, fs, num_taps, l_min, fc, t0, dt, num_times)
+        # (a call the library refuses may have no sensible size: a placeholder it does not write)
+        fits = (abi.sparse_beam_taps_out_bytes(spec, br, bt) > 0 and 0 < nr <= 256 and 0 < nt <= 256 and 0 < br <= 256
+                and 0 < bt <= 256 and br * bt * int(num_times) * int(num_taps) <= 1 << 24)
+        shape = (nrx, ntx, br, bt, 2, int(num_times), int(num_taps)) if fits else (1,)
+        with torch.cuda.device(self.device):
+            if out is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs `out`")
+                out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            elif (tuple(out.shape) != shape or out.dtype != torch.complex64 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous complex64 tensor of shape %s on %s" % (shape, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        arrays, beams_, d_el = upload((wr, wt))
+        rc = self.L.hrt_sparse_beam_taps(self.device.index, C.byref(spec), C.c_void_p(arrays.rx_elements), nr,
+                                         C.c_void_p(arrays.tx_elements), nt, float(arrays.array_frequency_hz),
+                                         C.c_void_p(beams_.rx_weights), br, C.c_void_p(beams_.tx_weights), bt,
+                                         C.c_void_p(buf.data_ptr()), C.c_void_p(out.data_ptr()),
+                                         1 if accumulate else 0, C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_sparse_beam_taps: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_sparse_beam_taps")
+        d_el.record_stream(stream)   # (the kernel reads the offsets, the weights and the lists after this call returns)
+        buf.record_stream(stream)
+        return out
+
     def sparse_taps(self, paths, fs, num_taps, l_min=0, fc=0.0, t0=0.0, dt=0.0, num_times=1, out=None,
                     accumulate=False):
         """The SISO impulse responses of dominant-path lists: sparse_array_taps() at one zero-offset element per side,

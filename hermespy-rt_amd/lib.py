@@ -44,6 +44,7 @@ EXPORTED = (
     "hrt_sparse_paths_bytes", "hrt_sparse_out_bytes", "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel",
     "hrt_sparse_taps_out_bytes", "hrt_sparse_array_taps", "hrt_compute_sparse_array_taps",
     "hrt_sparse_beam_out_bytes", "hrt_sparse_beam_channel", "hrt_compute_sparse_beam_channel",
+    "hrt_sparse_beam_taps_out_bytes", "hrt_sparse_beam_taps", "hrt_compute_sparse_beam_taps",
     "hrt_apply_patterns", "hrt_compute_set_patterns",
 )
 
@@ -375,6 +376,17 @@ def load():
                                                   C.c_size_t, C.c_double, f32p, C.c_size_t, f32p, C.c_size_t, f32p, vp,
                                                   C.POINTER(Stats)]
     L.hrt_compute_sparse_beam_channel.restype = C.c_int
+    # the beam taps of dominant-path lists (hrt_sparse_taps_spec: abi.SparseTapsSpec)
+    L.hrt_sparse_beam_taps_out_bytes.argtypes = [stp, u32, u32]
+    L.hrt_sparse_beam_taps_out_bytes.restype = u64
+    L.hrt_sparse_beam_taps.argtypes = [C.c_int, stp, vp, u32, vp, u32, C.c_double, vp, u32, vp, u32, vp, vp, C.c_int,
+                                       vp]
+    L.hrt_sparse_beam_taps.restype = C.c_int
+    L.hrt_compute_sparse_beam_taps.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                               C.c_size_t, C.c_size_t, C.c_size_t, dmp, tpp, V3, C.c_size_t, V3,
+                                               C.c_size_t, C.c_double, f32p, C.c_size_t, f32p, C.c_size_t, f32p, vp,
+                                               C.POINTER(Stats)]
+    L.hrt_compute_sparse_beam_taps.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

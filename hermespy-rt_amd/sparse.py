@@ -8,6 +8,8 @@ hermespy_rt.compute_sparse_array_channel), numpy only:
                     Tracer.sparse_taps, hermespy_rt.compute_sparse_array_taps) in float64, likewise, with S
     beam_reference  B of include/hermespy_rt.h (hrt_compute_sparse_beam_channel: Tracer.sparse_beam_channel,
                     hermespy_rt.compute_sparse_beam_channel) in float64, likewise, with S
+    beam_taps_reference  h of include/hermespy_rt.h (hrt_compute_sparse_beam_taps: Tracer.sparse_beam_taps,
+                    hermespy_rt.compute_sparse_beam_taps) in float64, likewise, with S
     dropped_power   the link's power from power_profiles minus the power the kept paths carry
     cluster_list    a synthetic list (clusters of rays per link) as a result dict, through dominant.from_terms
 
@@ -121,6 +123,42 @@ def beam_reference(views, rx_elements, tx_elements, rx_weights, tx_weights, fa, 
             B[rx, tx] = np.einsum("pa,pb,pq,pmk->abqmk", gr, gt, a, W, optimize=True)
             S[rx, tx] = np.abs(a).sum(axis=0)
     return B, S
+
+
+def beam_taps_reference(views, rx_elements, tx_elements, rx_weights, tx_weights, fa, fs, fc, l, t):
+    """(h, S): h complex128 [nrx, ntx, Br, Bt, 2, T, L] of include/hermespy_rt.h (hrt_compute_sparse_beam_taps) over the
+    first min(kept, K) slots of every link at the taps l [L] (integers), times t [T] (s), sampling rate fs and baseband
+    centre fc (Hz), elements [Nr, 3] / [Nt, 3] (m), array frequency fa (Hz) and codebooks rx_weights [Br, Nr] (applied
+    conjugated) / tx_weights [Bt, Nt]; S float64 [nrx, ntx, 2] = sum_p |a_p^pol| over the same slots.  The slots'
+    floats and the weights are widened to float64, nothing else is rounded; the sinc is numpy's sin(pi x) / (pi x);
+    slots at or beyond min(kept, K) are not read.  The element-domain taps are not formed: the gains g_rx[a](u_rx_p)
+    and g_tx[b](u_tx_p) are, per slot."""
+    re = abi.elements(rx_elements, "rx_elements").astype(np.float64)
+    te = abi.elements(tx_elements, "tx_elements").astype(np.float64)
+    wr = abi.weights(rx_weights, re.shape[0], "rx_weights").astype(np.complex128)
+    wt = abi.weights(tx_weights, te.shape[0], "tx_weights").astype(np.complex128)
+    l = np.atleast_1d(np.asarray(l, np.float64))
+    t = np.atleast_1d(np.asarray(t, np.float64))
+    kept = _numpy(views["kept"]).astype(np.int64).view(np.uint64)
+    nrx, ntx, K = _numpy(views["tau"]).shape
+    amp = np.stack([_numpy(views["a_te"]), _numpy(views["a_tm"])], axis=-1).astype(np.complex128)   # [.., K, 2]
+    tau, nu = _numpy(views["tau"]).astype(np.float64), _numpy(views["freq_shift"]).astype(np.float64)
+    urx, utx = _numpy(views["u_rx"]).astype(np.float64), _numpy(views["u_tx"]).astype(np.float64)
+    h = np.zeros((nrx, ntx, wr.shape[0], wt.shape[0], 2, t.size, l.size), np.complex128)
+    S = np.zeros((nrx, ntx, 2), np.float64)
+    for rx in range(nrx):
+        for tx in range(ntx):
+            n = int(min(int(kept[rx, tx]), K))
+            if n == 0:
+                continue
+            a = amp[rx, tx, :n]                                                               # [n, 2]
+            W = np.exp(2j * np.pi * (nu[rx, tx, :n, None] * t[None, :] - fc * tau[rx, tx, :n, None]))   # [n, T]
+            V = np.sinc(l[None, :] - fs * tau[rx, tx, :n, None])                              # [n, L]
+            gr = np.exp(2j * np.pi * (fa / SPEED_OF_LIGHT) * (urx[rx, tx, :n] @ re.T)) @ np.conj(wr).T   # [n, Br]
+            gt = np.exp(2j * np.pi * (fa / SPEED_OF_LIGHT) * (utx[rx, tx, :n] @ te.T)) @ wt.T            # [n, Bt]
+            h[rx, tx] = np.einsum("pa,pb,pq,pm,pl->abqml", gr, gt, a, W, V, optimize=True)
+            S[rx, tx] = np.abs(a).sum(axis=0)
+    return h, S
 
 
 def dropped_power(views, moments):

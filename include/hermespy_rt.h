@@ -694,6 +694,42 @@ int hrt_compute_sparse_array_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *
                                   float *out /* complex interleaved, layout above */,
                                   void *paths_out /* hrt_dominant_out_bytes, or NULL */, hrt_stats *stats);
 
+/* The beamformed impulse responses of dominant-path lists, formed on the device (include/hrt_device.h:
+ * hrt_sparse_beam_taps): what hrt_compute_beam_taps gives from the workspace, here from a buffer in exactly the layout
+ * hrt_dominant_paths writes (header uint64_t [L][2] = {kept, eligible}, then hrt_dominant_path [L][K]), so that a beam
+ * sweep in the time domain, or a re-evaluation at another rate, tap window, codebook or time axis, costs what the list
+ * costs.  An inverse FFT of hrt_compute_sparse_beam_channel is no substitute: it aliases every delay beyond 1 / df.
+ * For every link, RX beam a, TX beam b, polarisation, time sample m and tap l_i = l_min + i:
+ *     n = min(kept[link], K)
+ *     h[rx][tx][a][b][pol][m][l] = sum over slots p < n of
+ *           a_p^pol exp(j 2 pi (nu_p t_m - f_c tau_p)) g_rx[a](u_rx_p) g_tx[b](u_tx_p) sinc(l_min + l - f_s tau_p)
+ *     g_rx[a](u) = sum_i conj(W_rx[a][i]) exp(j 2 pi f_a r_i . u / c),   g_tx[b](u) = sum_j W_tx[b][j] exp(j 2 pi f_a q_j . u / c)
+ * with hrt_taps_spec's t_m, l_i, f_s, f_c and sinc rule, hrt_compute_array_taps' element offsets and f_a, and
+ * hrt_compute_beam_taps' weight layout and conventions: rx_weights complex [Br][Nr], tx_weights complex [Bt][Nt],
+ * re/im interleaved, the RX codebook applied conjugated, nothing normalised, one codebook for all RX and one for all TX.
+ * out: complex [num_rx][num_tx][Br][Bt][2][num_times][num_taps], re/im interleaved (numpy complex64).
+ * The slot rules are hrt_compute_sparse_array_channel's: the LoS entry is an ordinary slot; power, path, bounce and tri
+ * are not read; slots at or beyond n are never read; a link with n = 0 writes zeros (or leaves `out` unchanged when
+ * accumulating).  Where kept = eligible for a link the result is hrt_compute_beam_taps' for the same parts, up to the
+ * order of the float32 sums; it equals hrt_compute_sparse_array_taps' h contracted with the two codebooks wherever h
+ * can be formed, and h is never formed: there is no limit on Nr * Nt.  Every byte of `out` is written exactly once
+ * (added to once when accumulating); no atomics and no scratch buffer; two calls with the same input give the same
+ * bytes; a link's bytes depend only on its own slots below n, the grid, the elements and the weights.
+ * hrt_compute_sparse_beam_taps runs hrt_compute_dominant_paths' batch loop (the lists merged on the device) and
+ * evaluates the merged lists once after the last batch; only `out`, and the lists if paths_out is not NULL, is copied
+ * back.  HRT_E_INVALID, before the device is touched: every hrt_compute_dominant_paths check; every grid check of
+ * hrt_taps_spec (the grid's parts are not read: the parts are the dominant spec's); Nr or Nt outside 1..256; Br or Bt
+ * outside 1..256; Br * Bt * num_times * num_taps > 2^24; an offset, a weight or f_a not finite; f_a <= 0. */
+int hrt_compute_sparse_beam_taps(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                 size_t num_rays, size_t num_bounces, const hrt_dominant_spec *dominant_spec,
+                                 const hrt_taps_spec *grid, const Vec3 *rx_elements, size_t num_rx_elements,
+                                 const Vec3 *tx_elements, size_t num_tx_elements, double array_frequency_hz,
+                                 const float *rx_weights /* complex [Br][Nr] */, size_t num_rx_beams,
+                                 const float *tx_weights /* complex [Bt][Nt] */, size_t num_tx_beams,
+                                 float *out /* complex interleaved, layout above */,
+                                 void *paths_out /* hrt_dominant_out_bytes, or NULL */, hrt_stats *stats);
+
 /* Antenna radiation patterns and orientations (include/hrt_device.h: hrt_apply_patterns; csrc/hrt_patterns.hip).  A
  * pattern is a real factor per (path, RX, TX): for every unblocked scatter record p of link (rx, tx), and for every
  * clear LoS entry,

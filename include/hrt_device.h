@@ -561,6 +561,28 @@ int hrt_sparse_beam_channel(int device, const hrt_sparse_spec *spec, const float
                             const float *d_tx_w, uint32_t bt, const void *d_paths, float *d_out, int accumulate,
                             void *stream);
 
+/* ---- the beam taps of dominant-path lists (csrc/host/channel.c, csrc/hrt_sparse_beam_taps.hip) ----
+ * h as hermespy_rt.h defines it (hrt_compute_sparse_beam_taps), hrt_sparse_beam_taps_out_bytes bytes at d_out, from the
+ * lists at d_paths (num_rx * num_tx * (16 + 72 max_paths) bytes in hrt_dominant_paths' layout: its output, a merged or
+ * a synthetic list; 8-byte aligned), the element offsets d_rx_el [nr][3] and d_tx_el [nt][3] and the codebooks d_rx_w
+ * [br][nr][2] and d_tx_w [bt][nt][2] (hrt_beam_spec's layout and conventions) -- all DEVICE pointers -- asynchronous
+ * on `stream` of `device`.  The spec is hrt_sparse_array_taps'.  As hrt_sparse_array_taps: no problem handle, reads
+ * only the buffer and does not write it; accumulate = 0 overwrites d_out, 1 adds to it; one workgroup sums all live
+ * slots of a link in index order, so every byte of d_out is written exactly once (added to once), without atomics or
+ * scratch, and two calls with the same input give the same bytes; a link's bytes depend only on its own header word,
+ * its slots below min(kept, max_paths), the grid, the elements and the weights; slots at or beyond that are never
+ * read.  The element-domain taps are never formed: there is no limit on nr * nt.  The finiteness of the offsets and of
+ * the weights is the caller's to ensure (the host entries check it).  The size function returns 0 for a NULL or
+ * refused spec.  HRT_E_INVALID, before the device is touched: every refusal hrt_sparse_array_taps makes on the spec
+ * (num_rx * num_tx, max_paths, their product, the taps grid); a NULL pointer; nr or nt outside 1..256; br or bt outside
+ * 1..256; br * bt * num_times * num_taps above 2^24; f_a not finite or <= 0; d_paths not 8-byte aligned; accumulate
+ * not 0 or 1. */
+uint64_t hrt_sparse_beam_taps_out_bytes(const hrt_sparse_taps_spec *spec, uint32_t br, uint32_t bt);
+int hrt_sparse_beam_taps(int device, const hrt_sparse_taps_spec *spec, const float *d_rx_el, uint32_t nr,
+                         const float *d_tx_el, uint32_t nt, double fa_hz, const float *d_rx_w, uint32_t br,
+                         const float *d_tx_w, uint32_t bt, const void *d_paths, float *d_out, int accumulate,
+                         void *stream);
+
 /* sizes of the structs this build writes in full (a binding compares them with its own mirror) */
 uint64_t hrt_stats_size(void);
 uint64_t hrt_layout_size(void);
