@@ -696,6 +696,127 @@ def run_compute_channel_equalizer(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_ve
     return equalizer_views(out, eq)
 
 
+PC_MRT, PC_ZF, PC_RZF = 0, 1, 2        # hrt_precoder_spec.kind
+PC_TOTAL, PC_STREAM = 0, 1             # hrt_precoder_spec.norm
+PC_P = 1                               # hrt_precoder_spec.flags
+PC_SINGULAR, PC_NONFINITE = 1, 2       # a point's `status`
+PC_MAX_NR, PC_MAX_NT = 16, 64
+PC_KINDS = {"mrt": PC_MRT, "zf": PC_ZF, "rzf": PC_RZF}
+PC_NORMS = {"total": PC_TOTAL, "stream": PC_STREAM}
+
+
+class PrecoderSpec(C.Structure):
+    """include/hermespy_rt.h hrt_precoder_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("kind", C.c_uint32), ("norm", C.c_uint32),
+                ("flags", C.c_uint32), ("noise", C.c_float), ("power", C.c_float), ("regularization", C.c_float)]
+
+
+def _pc_name(value, names, what):
+    if isinstance(value, str):
+        if value.lower() not in names:
+            raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(repr(n) for n in names), value))
+        return names[value.lower()]
+    return int(value)
+
+
+def precoder_kind(kind):
+    """"mrt" / "zf" / "rzf" (any case) or the constant itself -> hrt_precoder_spec.kind; an unknown name raises
+    ValueError, an unknown number is passed on for the library to refuse"""
+    return _pc_name(kind, PC_KINDS, "kind")
+
+
+def precoder_norm(norm):
+    """"total" / "stream" (any case) or the constant itself -> hrt_precoder_spec.norm, as precoder_kind"""
+    return _pc_name(norm, PC_NORMS, "normalize")
+
+
+def precoder_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, noise, kind=PC_RZF, power=1.0, regularization=None,
+                  normalize=PC_TOTAL, weights=True, flags=None):
+    """regularization None: Nr N0 / Ptot under RZF (precode.default_regularization), 0 (not read) otherwise"""
+    if flags is None:
+        flags = PC_P if weights else 0
+    kind = precoder_kind(kind)
+    if regularization is None:
+        ok = kind == PC_RZF and float(power) > 0.0
+        regularization = int(nr) * float(noise) / float(power) if ok else 0.0
+    return PrecoderSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs), kind,
+                        precoder_norm(normalize), int(flags), float(noise), float(power), float(regularization))
+
+
+def precoder_regions(spec):
+    """the byte offsets of P, sinr, status and the end of a precoder output (hrt_precoder_out_bytes is the last)"""
+    pts = int(spec.num_rx) * int(spec.num_tx) * 2 * int(spec.num_times) * int(spec.num_freqs)
+    nr, nt = int(spec.nr), int(spec.nt)
+    o1 = pts * nt * nr * 8 if int(spec.flags) & PC_P else 0
+    o2 = o1 + pts * nr * 4
+    return 0, o1, o2, o2 + pts * 4
+
+
+def precoder_views(buf, spec):
+    """the regions of a flat uint8 precoder buffer (numpy array or torch tensor) as views: P complex64 [nrx, ntx, Nt,
+    Nr, 2, T, K] (None where not asked for), sinr float32 [nrx, ntx, Nr, 2, T, K], status [nrx, ntx, 2, T, K] (uint32
+    in numpy, int32 in torch), buffer"""
+    o = precoder_regions(spec)
+    nrx, ntx, nr, nt = int(spec.num_rx), int(spec.num_tx), int(spec.nr), int(spec.nt)
+    T, K = int(spec.num_times), int(spec.num_freqs)
+    if isinstance(buf, np.ndarray):
+        f32, c64, u32 = np.float32, np.complex64, np.uint32
+    else:
+        import torch
+        f32, c64, u32 = torch.float32, torch.complex64, torch.int32
+    out = {"P": None, "sinr": buf[o[1]:o[2]].view(f32).reshape(nrx, ntx, nr, 2, T, K),
+           "status": buf[o[2]:o[3]].view(u32).reshape(nrx, ntx, 2, T, K), "buffer": buf}
+    if int(spec.flags) & PC_P:
+        out["P"] = buf[o[0]:o[1]].view(c64).reshape(nrx, ntx, nt, nr, 2, T, K)
+    return out
+
+
+def _pc_positive(v):
+    return 0.0 < float(v) < float("inf")
+
+
+def precoder_fits(spec):
+    """whether the library accepts the spec (its limits, mirrored: an output beyond them is not allocated)"""
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    nr, nt, kind = int(spec.nr), int(spec.nt), int(spec.kind)
+    return (0 < nr <= PC_MAX_NR and 0 < nt <= PC_MAX_NT and 0 < nr * nt * grid <= 1 << 24
+            and 0 < int(spec.num_rx) * int(spec.num_tx) * 2 * grid < 1 << 31 and not int(spec.flags) & ~PC_P
+            and kind in (PC_MRT, PC_ZF, PC_RZF) and int(spec.norm) in (PC_TOTAL, PC_STREAM)
+            and (kind != PC_ZF or nr <= nt) and _pc_positive(spec.noise) and _pc_positive(spec.power)
+            and (kind != PC_RZF or _pc_positive(spec.regularization)))
+
+
+def run_channel_precoder(lib, device, spec, d_H, d_out, stream=None):
+    """hrt_channel_precoder through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_channel_precoder failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_channel_precoder(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                                  C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_channel_precoder failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_channel_precoder(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                                 rx_elements, tx_elements, noise, kind=PC_RZF, power=1.0, regularization=None,
+                                 normalize=PC_TOTAL, weights=True, flags=None, array_frequency=None, stats=None):
+    """hrt_compute_channel_precoder through ctypes -> precoder_views of a uint8 numpy buffer (spec: a ChannelSpec, as
+    for run_compute_array_channel; array_frequency defaults to the carrier).  The precoder is formed once, of the H
+    accumulated over all batches: it is not additive.  Raises RuntimeError("hrt_compute_channel_precoder failed
+    (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    pc = precoder_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), noise, kind, power, regularization,
+                       normalize, weights, flags)
+    extra += (C.c_uint32(int(pc.kind)), C.c_uint32(int(pc.norm)), C.c_uint32(int(pc.flags)), C.c_float(pc.noise),
+              C.c_float(pc.power), C.c_float(pc.regularization))
+    fits = precoder_fits(pc)
+    out = _run_pathsum(lib, "hrt_compute_channel_precoder", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (precoder_regions(pc)[3],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_channel_precoder accepted a call beyond its limits")
+    return precoder_views(out, pc)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

@@ -1,7 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_channel_precoder, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
  * hrt_sparse_beam_taps;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
@@ -37,6 +37,7 @@
 #include "../hrt_pathsum.h"
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
+#include "../hrt_precoder.h"
 #include "../hrt_propagate.h"
 #include "../hrt_sparse_beam.h"
 #include "../hrt_sparse_beam_taps.h"
@@ -1256,6 +1257,141 @@ int hrt_compute_channel_equalizer(Scene *scene, const Vec3 *rx_pos, const Vec3 *
     job.aux = &eq;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_equalizer");
+}
+
+/* ------------------------------------------------------------------ per-point precoders (hrt_channel_precoder) */
+
+static int pc_positive(float v)
+{
+    return v > 0.f && v <= 3.402823466e+38f;
+}
+
+/* the checks of a precoder call (`who`); device pointers are not read */
+static int pc_check(const hrt_precoder_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->num_times == 0 || sp->num_freqs == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, num_times and num_freqs must be > 0", who);
+    if (sp->nr < 1 || sp->nr > HRT_PC_MAX_NR || sp->nt < 1 || sp->nt > HRT_PC_MAX_NT)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u and nt = %u (nr 1 .. %u, nt 1 .. %u)", who, sp->nr, sp->nt,
+                        HRT_PC_MAX_NR, HRT_PC_MAX_NT);
+    if (sp->kind != HRT_PC_MRT && sp->kind != HRT_PC_ZF && sp->kind != HRT_PC_RZF)
+        return hrt_fail(HRT_E_INVALID, "%s: kind = %u is none of HRT_PC_MRT, HRT_PC_ZF, HRT_PC_RZF", who, sp->kind);
+    if (sp->norm != HRT_PC_TOTAL && sp->norm != HRT_PC_STREAM)
+        return hrt_fail(HRT_E_INVALID, "%s: norm = %u is neither HRT_PC_TOTAL nor HRT_PC_STREAM", who, sp->norm);
+    if (sp->kind == HRT_PC_ZF && sp->nr > sp->nt)
+        return hrt_fail(HRT_E_INVALID, "%s: zero-forcing needs nr <= nt (nr = %u, nt = %u)", who, sp->nr, sp->nt);
+    if (sp->flags & ~HRT_PC_P)
+        return hrt_fail(HRT_E_INVALID, "%s: flags = 0x%x has unknown bits", who, sp->flags);
+    if (!pc_positive(sp->noise))
+        return hrt_fail(HRT_E_INVALID, "%s: noise = %g must be finite and > 0", who, (double)sp->noise);
+    if (!pc_positive(sp->power))
+        return hrt_fail(HRT_E_INVALID, "%s: power = %g must be finite and > 0", who, (double)sp->power);
+    if (sp->kind == HRT_PC_RZF && !pc_positive(sp->regularization))
+        return hrt_fail(HRT_E_INVALID, "%s: regularization = %g must be finite and > 0", who,
+                        (double)sp->regularization);
+    const uint64_t grid = (uint64_t)sp->num_times * sp->num_freqs;   /* < 2^64 */
+    if (grid > HRT_PC_MAX_POINTS || (uint64_t)sp->nr * sp->nt * grid > HRT_PC_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr * nt * num_times * num_freqs > 2^24", who);
+    if ((uint64_t)sp->num_rx * sp->num_tx >= (1ull << 31) / (2u * grid))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 points or more", who);
+    return HRT_OK;
+}
+
+/* the regions of the output: byte offsets of P, sinr, status and the end (hermespy_rt.h) */
+static void pc_regions(const hrt_precoder_spec *sp, uint64_t off[4])
+{
+    const uint64_t points = (uint64_t)sp->num_rx * sp->num_tx * 2u * sp->num_times * sp->num_freqs;
+    off[0] = 0;
+    off[1] = off[0] + ((sp->flags & HRT_PC_P) ? points * sp->nt * sp->nr * 8u : 0u);
+    off[2] = off[1] + points * sp->nr * 4u;
+    off[3] = off[2] + points * 4u;
+}
+
+uint64_t hrt_precoder_out_bytes(const hrt_precoder_spec *spec)
+{
+    if (!spec) return 0;
+    uint64_t off[4];
+    pc_regions(spec, off);
+    return off[3];
+}
+
+int hrt_channel_precoder(int device, const hrt_precoder_spec *spec, const void *d_H, void *d_out, void *stream)
+{
+    int rc = pc_check(spec, "hrt_channel_precoder");
+    if (rc) return rc;
+    if (!d_H || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_channel_precoder: NULL device pointer");
+    uint64_t off[4];
+    pc_regions(spec, off);
+    hrt_kprecoder K;
+    memset(&K, 0, sizeof K);
+    K.nr = spec->nr; K.nt = spec->nt;
+    const uint32_t g = hrt_precoder_form(K.nr, K.nt);
+    K.mk = (K.nt + g - 1u) / g; K.nk = (K.nr + g - 1u) / g;
+    K.kind = spec->kind;
+    K.stream = spec->norm == HRT_PC_STREAM;
+    K.alpha = spec->kind == HRT_PC_RZF ? spec->regularization : 0.f;
+    K.n0 = spec->noise;
+    K.power = K.stream ? spec->power / (float)spec->nr : spec->power;
+    K.pts = 2ull * spec->num_times * spec->num_freqs;
+    K.points = (uint64_t)spec->num_rx * spec->num_tx * K.pts;
+    K.H = (const float *)d_H;
+    K.P = (spec->flags & HRT_PC_P) ? (float *)((char *)d_out + off[0]) : NULL;
+    K.sinr = (float *)((char *)d_out + off[1]);
+    K.status = (uint32_t *)((char *)d_out + off[2]);
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_precoder(&K, g, stream), "precoder kernel");
+    return HRT_OK;
+}
+
+/* after the last batch: H stays at d_H; the precoder is formed once, only its result comes down */
+static int pc_job_deliver(const ch_job *j, int device, const void *d_H, void *out)
+{
+    const hrt_precoder_spec *sp = (const hrt_precoder_spec *)j->aux;
+    const uint64_t bytes = hrt_precoder_out_bytes(sp);
+    void *d_pc = NULL;
+    int rc = hrt_device_malloc(device, &d_pc, bytes);
+    if (!rc) rc = hrt_channel_precoder(device, sp, d_H, d_pc, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_pc, bytes);
+    if (d_pc) hrt_device_free(device, d_pc);
+    return rc;
+}
+
+int hrt_compute_channel_precoder(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                 const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                                 size_t nt, double f_a, uint32_t kind, uint32_t norm, uint32_t flags, float noise,
+                                 float power, float regularization, void *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = array_check(spec, &a))) return rc;
+    if (!out) return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_precoder: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_precoder: num_rx or num_tx > 2^32");
+    hrt_precoder_spec pc;
+    memset(&pc, 0, sizeof pc);
+    pc.num_rx = (uint32_t)nrx; pc.num_tx = (uint32_t)ntx;
+    pc.nr = (uint32_t)nr; pc.nt = (uint32_t)nt;
+    pc.num_times = spec->num_times; pc.num_freqs = spec->num_freqs;
+    pc.kind = kind; pc.norm = norm; pc.flags = flags;
+    pc.noise = noise; pc.power = power; pc.regularization = regularization;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_channel) */
+    if (nrx && ntx && (rc = pc_check(&pc, "hrt_compute_channel_precoder"))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.deliver = pc_job_deliver;
+    job.aux = &pc;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_precoder");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

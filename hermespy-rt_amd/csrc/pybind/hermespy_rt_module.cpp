@@ -581,6 +581,80 @@ py::dict compute_channel_equalizer_py(
     return d;
 }
 
+// compute_channel_precoder: the per-point linear MIMO precoder (kind "mrt", "zf" or "rzf"; normalize "total" or "stream")
+// of compute_array_channel's H and the downlink SINR of every stream behind it, formed on the device (extension; see
+// hrt_compute_channel_precoder in hermespy_rt.h): a dict of views of one buffer -- P complex64 (num_rx, num_tx, Nt, Nr,
+// 2, num_times, num_freqs), None with weights=False; sinr float32 (num_rx, num_tx, Nr, 2, num_times, num_freqs); status
+// uint32 (num_rx, num_tx, 2, num_times, num_freqs) -- and the buffer itself (uint8).  regularization None: Nr noise /
+// power under "rzf".  The precoder is formed once, of the H of all batches.
+py::dict compute_channel_precoder_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    float noise, const std::string &kind, float power, py::object regularization, const std::string &normalize,
+    double t0, double dt, unsigned long num_times, bool los, bool scatter, py::object array_frequency, bool weights,
+    py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL || num_rx > 0xffffffffUL || num_tx > 0xffffffffUL)
+        throw std::invalid_argument("num_rx, num_tx, num_freqs and num_times must fit 32 bits");
+    if (kind != "mrt" && kind != "zf" && kind != "rzf") throw std::invalid_argument("kind must be 'mrt', 'zf' or 'rzf'");
+    if (normalize != "total" && normalize != "stream")
+        throw std::invalid_argument("normalize must be 'total' or 'stream'");
+    const array_elements a(rx_elements, tx_elements);
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    const uint32_t k = kind == "mrt" ? HRT_PC_MRT : kind == "zf" ? HRT_PC_ZF : HRT_PC_RZF;
+    const uint32_t norm = normalize == "total" ? HRT_PC_TOTAL : HRT_PC_STREAM, flags = weights ? HRT_PC_P : 0u;
+    const size_t nr = a.nr, nt = a.nt;
+    float alpha = 0.f;
+    if (!regularization.is_none()) alpha = regularization.cast<float>();
+    else if (k == HRT_PC_RZF && power > 0.f) alpha = (float)((double)nr * (double)noise / (double)power);
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t pts = (size_t)num_rx * num_tx * 2u * num_times * num_freqs;
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs) && nr <= 16u && nt <= 64u && pts < (1ull << 31);
+    hrt_precoder_spec pc{};
+    pc.num_rx = (uint32_t)num_rx; pc.num_tx = (uint32_t)num_tx; pc.nr = (uint32_t)nr; pc.nt = (uint32_t)nt;
+    pc.num_times = (uint32_t)num_times; pc.num_freqs = (uint32_t)num_freqs; pc.kind = k; pc.norm = norm;
+    pc.flags = flags; pc.noise = noise; pc.power = power; pc.regularization = alpha;
+    py::array_t<uint8_t> buf(fits ? (size_t)hrt_precoder_out_bytes(&pc) : (size_t)1);
+    uint8_t *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_channel_precoder", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_channel_precoder(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                            num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa, k, norm, flags,
+                                            noise, power, alpha, dst, nullptr);
+    });
+    size_t off = 0;
+    auto view = [&](auto zero, std::vector<size_t> shape) {
+        using T = decltype(zero);
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(T);
+        size_t count = 1;
+        for (size_t i = shape.size(); i-- > 0;) {
+            strides[i] = st;
+            st *= (py::ssize_t)shape[i];
+            count *= shape[i];
+        }
+        py::array_t<T> v(shape, strides, reinterpret_cast<T *>(dst + off), buf);
+        off += count * sizeof(T);
+        return v;
+    };
+    const size_t R = num_rx, X = num_tx, T_ = num_times, K_ = num_freqs;
+    py::dict d;
+    if (weights) d["P"] = view(std::complex<float>(), {R, X, nt, nr, 2, T_, K_});
+    else d["P"] = py::none();
+    d["sinr"] = view(0.0f, {R, X, nr, 2, T_, K_});
+    d["status"] = view((uint32_t)0, {R, X, 2, T_, K_});
+    d["buffer"] = buf;
+    return d;
+}
+
 // a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
 using carr = py::array_t<std::complex<float>, py::array::c_style>;
 carr as_weights(const py::array &w, size_t n_elements, const char *name)
@@ -1249,6 +1323,18 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("noise"), py::arg("kind") = "lmmse", py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
           py::arg("array_frequency") = py::none(), py::arg("weights") = true, py::arg("patterns") = py::none());
+    m.def("compute_channel_precoder", &compute_channel_precoder_py,
+          "Per-point linear MIMO precoder (kind 'mrt', 'zf' or 'rzf'; normalize 'total' or 'stream') of the "
+          "antenna-array channel and the downlink SINR behind it, formed on the device: a dict of views of one buffer "
+          "-- P (num_rx, num_tx, Nt, Nr, 2, num_times, num_freqs), sinr (.., Nr, 2, ..), status, buffer",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("noise"), py::arg("kind") = "rzf", py::arg("power") = 1.0f, py::arg("regularization") = py::none(),
+          py::arg("normalize") = "total", py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1,
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(),
+          py::arg("weights") = true, py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "

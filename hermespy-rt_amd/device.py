@@ -842,6 +842,66 @@ class Tracer:
                                array_frequency)
         return self.equalizer(H, noise, kind, weights)
 
+    def precoder(self, H, noise, kind="rzf", power=1.0, regularization=None, normalize="total", weights=True,
+                 out=None):
+        """Per-point linear MIMO precoder of an array channel and the downlink SINR of every stream behind it, on the
+        device (hrt_channel_precoder; include/hermespy_rt.h hrt_compute_channel_precoder).  For every link,
+        polarisation, time sample and frequency the model is y = H P s + n, E[s s^H] = I, E[n n^H] = noise I,
+        H = H[rx, tx, :, :, pol, m, k]: row i is the channel to stream (user port) i, Nt the transmit elements.
+        P0 = H^H for kind "mrt", H^H (H H^H)^-1 for "zf", H^H (H H^H + regularization I)^-1 for "rzf"; normalize "total":
+        P = sqrt(power / |P0|_F^2) P0, "stream": column i of P is sqrt(power / Nr) P0[:, i] / |P0[:, i]|:
+
+            P       complex64 [nrx, ntx, Nt, Nr, 2, T, K]     x = P s                         (None with weights=False)
+            sinr    float32   [nrx, ntx, Nr, 2, T, K]         |E_ii|^2 / (sum_{j != i} |E_ij|^2 + noise), E = H P
+            status  int32     [nrx, ntx, 2, T, K]             0, abi.PC_SINGULAR, abi.PC_NONFINITE
+
+        H: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, T, K] (array_channel(), or any tensor of that layout, such
+        as equalize.stack_users(H, "rx") of several users for a multi-user downlink; no trace is needed); Nr <= 16,
+        Nt <= 64, "zf" needs Nr <= Nt.  `noise`, `power` and `regularization`: one finite float > 0 each;
+        regularization=None under "rzf" is precode.default_regularization(Nr, noise, power) = Nr noise / power.
+        Modified Gram-Schmidt in float32 on [H^H; sqrt(regularization) I], never through the Gram matrix; E is formed
+        from H and the stored P.  A singular or non-finite point (H = 0 is singular for every kind) writes exact zeros
+        and its status.  The precoder is not additive: a sharded caller sums H over the shards first and then calls
+        precoder().  Returns a dict of views of one flat uint8 device tensor, itself under "buffer", enqueued on the
+        current stream; `out` (such a flat tensor) is written in place.  hermespy_rt_amd.precode has the host-side
+        reference and sinr_of() for a P scored through another H.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        spec = abi.precoder_spec(nrx, ntx, nr, nt, T, K, noise, kind, power, regularization, normalize, weights)
+        H = H.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and 0 < nr <= abi.PC_MAX_NR and 0 < nt <= abi.PC_MAX_NT
+        need = abi.precoder_regions(spec)[3] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_channel_precoder(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_channel_precoder: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_channel_precoder")
+        H.record_stream(stream)     # (the kernel reads it after this call returns)
+        return abi.precoder_views(out, spec)
+
+    def channel_precoder(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                         scatter=True, array_frequency=None, noise=1.0, kind="rzf", power=1.0, regularization=None,
+                         normalize="total", weights=True):
+        """The per-point precoder of the last trace's array channel, without leaving the device: bit for bit
+        precoder(array_channel(...), noise, kind, power, regularization, normalize, weights) with array_channel()'s
+        arguments.  On a sharded trace this is the precoder of the shard's partial channel, which is not the
+        channel's: sum array_channel() over the shards and call precoder()."""
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.precoder(H, noise, kind, power, regularization, normalize, weights)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

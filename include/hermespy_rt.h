@@ -458,6 +458,72 @@ int hrt_compute_channel_equalizer(Scene *scene, const Vec3 *rx_pos, const Vec3 *
                                   float noise,
                                   void *out /* host, hrt_equalizer_out_bytes bytes, layout above */, hrt_stats *stats);
 
+/* Per-point linear MIMO precoders (maximum-ratio transmission, zero-forcing, regularised zero-forcing) of the array
+ * channel and the downlink SINR of every stream behind them, formed on the device (include/hrt_device.h:
+ * hrt_channel_precoder).  A point is one (rx, tx, pol, time, frequency) of a tensor of hrt_compute_array_channel's
+ * layout: H = H[rx][tx][:][:][pol][m][k], Nr x Nt.  Row i of H is the channel to stream i, that is to user port i; Nt
+ * is the number of transmit elements.  The model is y = H P s + n with E[s s^H] = I and E[n n^H] = N0 I.
+ * Kinds (`kind`):
+ *   HRT_PC_MRT   P0 = H^H
+ *   HRT_PC_ZF    P0 = H^H (H H^H)^-1; needs Nr <= Nt
+ *   HRT_PC_RZF   P0 = H^H (H H^H + alpha I)^-1 with `regularization` alpha, finite and > 0
+ * Normalisation (`norm`), with `power` Ptot finite and > 0:
+ *   HRT_PC_TOTAL   P = sqrt(Ptot / |P0|_F^2) P0
+ *   HRT_PC_STREAM  column i of P is sqrt(Ptot / Nr) P0[:, i] / |P0[:, i]|
+ * The outputs lie in one flat buffer of hrt_precoder_out_bytes bytes, the point axes innermost, the regions in this
+ * order (P is absent, size 0, without HRT_PC_P in `flags`):
+ *   P       complex [num_rx][num_tx][Nt][Nr][2][T][K]   the precoder: x = P s                              (HRT_PC_P)
+ *   sinr    float   [num_rx][num_tx][Nr][2][T][K]       with E = H P, sinr_i = |E_ii|^2 / (sum_{j != i} |E_ij|^2 + N0)
+ *   status  uint32  [num_rx][num_tx][2][T][K]           0, HRT_PC_SINGULAR or HRT_PC_NONFINITE
+ * `noise` (N0), `power` and, for HRT_PC_RZF, `regularization` are one float each per call, finite and > 0 (the
+ * regularization of the other kinds is not read).  1 <= Nr <= 16, 1 <= Nt <= 64, Nr * Nt * T * K <= 2^24, fewer than
+ * 2^31 points.
+ * Algorithm (a definition: the tests emulate it).  ZF and RZF: modified Gram-Schmidt in float, column by column, on the
+ * augmented matrix A = [H^H; sqrt(alpha) I] = Q R ((Nt + Nr) x Nr; just H^H for ZF), never through the Gram matrix
+ * H H^H: the equalizer's factorisation with the two sides swapped, the column operations carried on an Nr x Nr block T
+ * that ends as R^-1, and P0 = Q1 T^H with Q1 the top Nt rows of Q.  The squared column norms of P0 are summed, P0 is
+ * scaled by the rule of `norm`, and E = H P is formed from H itself and the scaled P that is stored, not from an identity
+ * of the factorisation; the SINR is one float division.  With u = (Nr + Nt) 2^-24, a point is HRT_PC_SINGULAR when a
+ * diagonal entry of R is at or below 2 u times the largest column norm of A at the start, or when a column of P0
+ * (STREAM) or the whole P0 (TOTAL) has norm zero, as for H = 0 under every kind.  A point whose squared column norms of
+ * A do not sum to a finite float (NaN, Inf, or squares beyond float) is HRT_PC_NONFINITE, which takes precedence; so
+ * is a regular point whose squared norm of P0 is beyond float.  A flagged point writes exact zeros to P and sinr, plus
+ * its status.  A point's bits depend on its own matrix only (not on its neighbours, the batch or the launch); two calls
+ * give the same bytes.
+ * Multi-user use: the users of a downlink stacked along Nr, in any tensor of this layout
+ * (hermespy_rt_amd.equalize.stack_users(H, "rx")), give the base station's multi-user precoder and the SINR each user
+ * sees.  hrt_compute_channel_precoder traces and batches exactly as hrt_compute_array_channel does, keeps the
+ * accumulated H on the device and precodes once after the last batch: the precoder is NOT additive over batches or
+ * shards (H is summed first), only the result is copied back.  HRT_E_INVALID, before the device is touched: every
+ * refusal of hrt_compute_array_channel; a NULL out; every refusal of hrt_channel_precoder (include/hrt_device.h). */
+#define HRT_PC_MRT 0u
+#define HRT_PC_ZF 1u
+#define HRT_PC_RZF 2u
+#define HRT_PC_TOTAL 0u
+#define HRT_PC_STREAM 1u
+#define HRT_PC_P 1u
+#define HRT_PC_SINGULAR 1u
+#define HRT_PC_NONFINITE 2u
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t kind;                              /* HRT_PC_MRT, HRT_PC_ZF or HRT_PC_RZF */
+    uint32_t norm;                              /* HRT_PC_TOTAL or HRT_PC_STREAM */
+    uint32_t flags;                             /* HRT_PC_P (0: sinr and status only) */
+    float noise;                                /* N0, finite and > 0 */
+    float power;                                /* Ptot, finite and > 0 */
+    float regularization;                       /* alpha, finite and > 0 (HRT_PC_RZF; not read otherwise) */
+} hrt_precoder_spec;
+uint64_t hrt_precoder_out_bytes(const hrt_precoder_spec *spec);   /* 0 for NULL */
+int hrt_compute_channel_precoder(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                 const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                 size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                                 const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                                 size_t num_tx_elements, double array_frequency_hz, uint32_t kind, uint32_t norm,
+                                 uint32_t flags, float noise, float power, float regularization,
+                                 void *out /* host, hrt_precoder_out_bytes bytes, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

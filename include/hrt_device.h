@@ -430,6 +430,19 @@ int hrt_channel_svd(int device, const hrt_svd_spec *spec, const void *d_H, void 
  * finite and > 0; nr * nt * num_times * num_freqs > 2^24; 2^31 points or more. */
 int hrt_channel_equalizer(int device, const hrt_equalizer_spec *spec, const void *d_H, void *d_out, void *stream);
 
+/* ---- per-point linear MIMO precoders of an array channel (csrc/host/channel.c, csrc/hrt_precoder.hip) ----
+ * P, sinr and status as hermespy_rt.h defines them (hrt_precoder_spec, hrt_compute_channel_precoder),
+ * hrt_precoder_out_bytes bytes at d_out, from d_H (complex [num_rx][num_tx][nr][nt][2][num_times][num_freqs]: the
+ * output of hrt_array_channel, or any tensor of that layout), both DEVICE pointers, asynchronous on `stream` of
+ * `device`.  It needs no problem: it reads only the tensor, and does not write it.  Every byte of d_out is written
+ * exactly once; no scratch and no atomics, so two calls with the same input give the same bytes.  The precoder of one
+ * shard's partial H is not the channel's: a sharded caller sums H first.  HRT_E_INVALID, before the device is touched:
+ * a NULL pointer; num_rx, num_tx, num_times or num_freqs equal to 0; nr outside 1..16; nt outside 1..64; a kind other
+ * than HRT_PC_MRT, HRT_PC_ZF and HRT_PC_RZF; a norm other than HRT_PC_TOTAL and HRT_PC_STREAM; HRT_PC_ZF with nr > nt;
+ * `flags` with bits other than HRT_PC_P; a noise, a power or (HRT_PC_RZF) a regularization that is not finite and > 0;
+ * nr * nt * num_times * num_freqs > 2^24; 2^31 points or more. */
+int hrt_channel_precoder(int device, const hrt_precoder_spec *spec, const void *d_H, void *d_out, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
