@@ -223,7 +223,7 @@
                 float d2rx;
                 F3 w = shadow_dir(o[k], apex, d2rx);
                 if (!valid[k]) w = {0.f, 0.f, 1.f};
-                const Hit sh = masked ? closest_hit_masked(tri, P.acc.orig, P.rxt, rx, T, o[k], w, valid[k], lane, 2)
+                const Hit sh = masked ? closest_hit_masked<true>(tri, P.acc.orig, P.rxt, rx, T, o[k], w, valid[k], lane, 2)
                                       : closest_hit<VARIANT>(tri, tg, leaf, P.acc, P.rxt, rx, P.acc.orig, T, o[k], w, valid[k],
                                                              lane, ball, true, apex, L.mask, L.wleaf, 2);
                 bool unblocked = false;

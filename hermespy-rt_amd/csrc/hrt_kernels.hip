@@ -163,6 +163,26 @@ constexpr float kK1 = 1.1920928955078125e-07f * (1.f + 0x1p-18f);
 constexpr float kK2 = 1.f + 0x1p-20f;
 constexpr float kK3 = 1.f + 0x1p-19f;
 constexpr float kK5 = 1.1920928955078125e-07f * (1.f - 0x1p-18f);
+// The CERTAIN-HIT certificate of the staged test's last stage (HRT_STAGED_TEST): no u, v division where the
+// reference's `miss` is provably false.  For a lane that R1..R6 did not reject (so a >= eps: R0 rejects a < eps, and
+// a NaN fails C4), with Nu', Nv' the sign-corrected numerators:
+//   C1  Nu' >= 0        C2  Nv' >= 0        C3  fl(Nu' + Nv') <= fl(a * (1 - 2^-20))        C4  a <= 2^126
+// (Nu' <= a is implied: fl() is monotone, so Nu' <= fl(Nu' + Nv') by C2, and fl(a (1 - 2^-20)) <= a.)
+// Range: C1..C4 give 0 <= Nu', Nv' <= a and eps <= a <= 2^126, so the sum is at most 2^127 and the product at least
+// eps / 2: neither overflows nor underflows, and each carries one rounding of 2^-24 relative.  Outside the range
+// (a beyond 2^126, infinities, NaNs: every comparison is written so that a NaN fails it) the lane is not certain.
+// Proof that miss is false, u = fl(Nu'/a), v = fl(Nv'/a) (sign symmetry as above), h = 2^-24:
+//   * a >= eps: the reference's |det| < eps test does not fire.
+//   * 0 <= Nu'/a <= 1 and fl() is monotone with fl(0) = 0, fl(1) = 1: 0 <= u <= 1, so neither u < -eps nor
+//     u > 1 + eps.  Likewise v >= 0, so not v < -eps.  No margin is needed: division is correctly rounded.
+//   * Nu' + Nv' <= fl(Nu' + Nv') / (1 - h) <= a (1 - 2^-20)(1 + h) / (1 - h).  A quotient that underflows is off by at
+//     most 2^-149 absolutely, any other by h relatively, so u + v <= (Nu' + Nv')/a (1 + h) + 2^-148 and
+//     w = fl(u + v) <= (1 - 2^-20)(1 + h)^3 / (1 - h) + 2^-147 < 1 - 2^-20 + 5h < 1: not w > 1 + eps.
+// When the certificate holds in every lane that is not rejected -- the common case: a ray that reaches the divisions
+// mostly hits well inside the triangle -- the wave skips both divisions and the five comparisons; otherwise it runs the
+// reference's sequence as before.  The distance and the take rule are the reference's in both cases.
+constexpr float kCertW = 1.f - 0x1p-20f;
+constexpr float kCertMaxDet = 0x1p126f;
 
 __device__ __forceinline__ uint32_t lane_prefix(unsigned long long mask)
 {
@@ -609,6 +629,11 @@ __device__ __forceinline__ bool packet_culls(const Packet &P, float4 q0, float4 
 // SGPR pair, the ORs and the "every lane rejected?" test are scalar instructions (a ballot of an
 // OR of comparisons costs two extra VALU instructions per stage).  All 64 lanes are active here;
 // `inval` has the bits of the lanes that carry no ray.  Ties: lexicographic (distance, orig[J]).
+// The last stage divides for u and v only when some lane still in play does NOT hold the certain-hit certificate C1..C4
+// (stated and proved above kCertW: 0 <= Nu', 0 <= Nv', fl(Nu' + Nv') <= fl(a (1 - 2^-20)), a <= 2^126 imply that none of the
+// reference's five miss tests fires): one ballot of "in play and not certain", wave-uniform like every other skip here.
+// On the street canyon 99.98 % of the passes that reach the last stage are certain in every lane (`make STATS=1`, column
+// 15 against column 5).  The distance is always the reference's division: its bits are the result.
 #define HRT_BALLOT(c) __builtin_amdgcn_ballot_w64(c)
 #define HRT_STAGED_BODY(J)                                                                      \
     {                                                                                           \
@@ -643,13 +668,22 @@ __device__ __forceinline__ bool packet_culls(const Packet &P, float4 q0, float4 
                 rm |= HRT_BALLOT(nt_s < kK5 * a) | HRT_BALLOT(nt_s > (best * a) * kK2);         \
                 if (rm != ~0ull) {                                                              \
                     HRT_STAT(kind, 5, 1);                                                       \
-                    const float u = nu / det;                                                   \
-                    const float v = nv / det;                                                   \
-                    const float w = u + v;                                                      \
+                    const unsigned long long unc =                                              \
+                        ~rm & (HRT_BALLOT(!(nu_s >= 0.f)) | HRT_BALLOT(!(nv_s >= 0.f)) |        \
+                               HRT_BALLOT(!((nu_s + nv_s) <= kCertW * a)) |                     \
+                               HRT_BALLOT(!(a <= kCertMaxDet)));                                \
+                    bool miss = false;                                                          \
+                    if (unc != 0ull) {   /* some lane's hit is not certain: the exact tests */  \
+                        const float u = nu / det;                                               \
+                        const float v = nv / det;                                               \
+                        const float w = u + v;                                                  \
+                        miss = (det > -kEps && det < kEps) | (u < -kEps) |                      \
+                               (u > kOnePlusEps) | (v < -kEps) | (w > kOnePlusEps);             \
+                    } else {                                                                    \
+                        HRT_STAT(kind, 15, 1);                                                  \
+                    }                                                                           \
                     const float dist = nt / det;                                                \
                     const bool rej = (rm >> lane) & 1ull;                                       \
-                    const bool miss = (det > -kEps && det < kEps) | (u < -kEps) |               \
-                                      (u > kOnePlusEps) | (v < -kEps) | (w > kOnePlusEps);      \
                     const uint32_t oj = orig[(J)];   /* J is wave-uniform: a scalar load */      \
                     const bool take = !rej & !miss & (dist > kEps) &                            \
                                       ((dist < best) | ((dist == best) & (oj < who_o)));        \
@@ -660,6 +694,101 @@ __device__ __forceinline__ bool packet_culls(const Packet &P, float4 q0, float4 
             }                                                                                   \
         }                                                                                       \
     }
+
+// The same test for SHADOW walks (kind 2: closest_hit_masked, closest_hit_words), which return only WHICH triangle is
+// closest and whether it lies within one metre (quirks Q6, Q7): no distance division either.  The best candidate is
+// carried as the pair (nt_b, a_b) = its (Nt', a), never as a quotient; fl(nt_b / a_b) has the bits `best` had (sign
+// symmetry, above).  No hit yet: (1e9, 1), whose quotient is the 1e9f `best` starts with.  With h = 2^-24,
+// pn = fl(Nt' a_b), po = fl(nt_b a):
+//   R6'  dist > best certainly   <=  pn > fl(po k2)           k2 = 1 + 2^-20    (stage 3's cull)
+//   T1   dist < best certainly   <=  pn < fl(po (1 - 2^-20))  and po <= 2^120
+//   T2   dist > eps certainly    <=  Nt' > fl(k5h a)          k5h = eps (1 + 2^-18)
+// Three roundings (two products, the constant's) move the ratio pn / po by less than 4h, and the two quotients' by 2h
+// more: beyond a margin of 2^-20 = 16h the order of fl(Nt'/a) and fl(nt_b/a_b) is the order of the products, strictly.
+// Ranges.  A lane in play has a >= eps = 2^-23 (R0) and Nt' >= fl(k5 a) > 2^-47 (R5), and a stored pair was such a lane
+// (or is (1e9, 1)): po >= 2^-70 always and pn >= 2^-70 in the last stage -- no product UNDERFLOWS where it decides (in
+// stage 3 a tiny or negative Nt' gives a pn below po, which rejects nothing).  OVERFLOW: pn = inf against a finite
+// fl(po k2) rejects rightly (then po k2 < 2^128 (1 - 2^-20 + 3h) <= the true Nt' a_b (1 - 2^-20 + 4h)); po = inf rejects
+// nothing in stage 3 and is sent to the exact path by T1's guard; fl(k5h a) = inf fails T2.  NaNs fail T1 or T2 (the
+// comparisons are written so).  A lane in play that fails T1 or T2 is IN THE BAND; one ballot: if the band is empty,
+// every lane in play that does not miss takes the candidate; otherwise the wave forms both exact quotients and applies
+// the reference's rule, ties by `orig` included.  The walk ends with shadow_result: within one metre certainly if
+// nt_b <= fl(a_b (1 - 2^-20)), certainly not if nt_b > fl(a_b k2) (an infinite product fails this), else by the quotient.
+constexpr float kK5H = 1.1920928955078125e-07f * (1.f + 0x1p-18f);
+constexpr float kPairMax = 0x1p120f;
+#define HRT_STAGED_BODY_S(J)                                                                    \
+    {                                                                                           \
+        const float4 q0 = tri[HRT_ROW * (J)], q1 = tri[HRT_ROW * (J) + 1], q2 = tri[HRT_ROW * (J) + 2];           \
+        const F3 v1 = {q0.x, q0.y, q0.z};                                                       \
+        const F3 e1 = {q0.w, q1.x, q1.y};                                                       \
+        const F3 e2 = {q1.z, q1.w, q2.x};                                                       \
+        const F3 pv = cross3(d, e2);                                                            \
+        const float det = dot3(e1, pv);                                                         \
+        const F3 s = sub3(o, v1);                                                               \
+        const float nu = dot3(s, pv);                                                           \
+        const float a = fabsf(det);                                                             \
+        const uint32_t sg = __float_as_uint(det) & 0x80000000u;                                 \
+        const float nu_s = xor_sign(nu, sg);                                                    \
+        const float k1a = kK1 * a, k2a = kK2 * a;                                               \
+        unsigned long long rm = inval | HRT_BALLOT(a < kEps) | HRT_BALLOT(nu_s < -k1a) |        \
+                                HRT_BALLOT(nu_s > k2a);                                         \
+        if (rm != ~0ull) {                                                                      \
+            HRT_STAT(kind, 3, 1);                                                               \
+            const F3 q = cross3(s, e1);                                                         \
+            const float nv = dot3(d, q);                                                        \
+            const float nv_s = xor_sign(nv, sg);                                                \
+            rm |= HRT_BALLOT(nv_s < -k1a) | HRT_BALLOT((nu_s + nv_s) > kK3 * a);                \
+            if (rm != ~0ull) {                                                                  \
+                HRT_STAT(kind, 4, 1);                                                           \
+                const float nt = dot3(e2, q);                                                   \
+                const float nt_s = xor_sign(nt, sg);                                            \
+                const float pn = nt_s * a_b, po = nt_b * a;                                     \
+                rm |= HRT_BALLOT(nt_s < kK5 * a) | HRT_BALLOT(pn > po * kK2);                   \
+                if (rm != ~0ull) {                                                              \
+                    HRT_STAT(kind, 5, 1);                                                       \
+                    const unsigned long long unc =                                              \
+                        ~rm & (HRT_BALLOT(!(nu_s >= 0.f)) | HRT_BALLOT(!(nv_s >= 0.f)) |        \
+                               HRT_BALLOT(!((nu_s + nv_s) <= kCertW * a)) |                     \
+                               HRT_BALLOT(!(a <= kCertMaxDet)));                                \
+                    bool miss = false;                                                          \
+                    if (unc != 0ull) {   /* some lane's hit is not certain: the exact tests */  \
+                        const float u = nu / det;                                               \
+                        const float v = nv / det;                                               \
+                        const float w = u + v;                                                  \
+                        miss = (det > -kEps && det < kEps) | (u < -kEps) |                      \
+                               (u > kOnePlusEps) | (v < -kEps) | (w > kOnePlusEps);             \
+                    } else {                                                                    \
+                        HRT_STAT(kind, 15, 1);                                                  \
+                    }                                                                           \
+                    const unsigned long long band =                                             \
+                        ~rm & (HRT_BALLOT(!(nt_s > kK5H * a)) | HRT_BALLOT(!(pn < po * kCertW)) | \
+                               HRT_BALLOT(!(po <= kPairMax)));                                  \
+                    const bool rej = (rm >> lane) & 1ull;                                       \
+                    const uint32_t oj = orig[(J)];   /* J is wave-uniform: a scalar load */      \
+                    bool take = !rej & !miss;                                                   \
+                    if (band != 0ull) {   /* some lane in the band: the reference's rule */     \
+                        const float dist = nt / det;                                            \
+                        const float bq = nt_b / a_b;                                            \
+                        take = take & (dist > kEps) &                                           \
+                               ((dist < bq) | ((dist == bq) & (oj < who_o)));                   \
+                    }                                                                           \
+                    nt_b = take ? nt_s : nt_b;                                                  \
+                    a_b = take ? a : a_b;                                                       \
+                    who = take ? (J) : who;                                                     \
+                    who_o = take ? oj : who_o;                                                  \
+                }                                                                               \
+            }                                                                                   \
+        }                                                                                       \
+    }
+// what a shadow walk returns: the triangle, and the one-metre decision carried as a distance of 0 (within) or 2 (not),
+// so that `t <= 1.f` reads the same on every walk's result
+__device__ __forceinline__ Hit shadow_result(uint32_t who, float nt_b, float a_b)
+{
+    const bool yes = nt_b <= a_b * kCertW, no = nt_b > a_b * kK2;
+    bool within = yes;
+    if (HRT_BALLOT(!yes & !no) != 0ull) within = yes | (!no & (nt_b / a_b <= 1.f));
+    return {who, within ? 0.f : 2.f};
+}
 
 // ALL lanes of the wave must call this (uniform control flow); invalid lanes carry dummies.
 // Two phases per block of up to 16 rounds (1024 triangles): first every round is culled and
@@ -717,7 +846,8 @@ __device__ __forceinline__ unsigned long long rxt_cell_load(const hrt_krxt &X, u
 {
     return X.cell_mask[(uint64_t)apex_k * HRT_RXT_BINS + rxt_cell(d)];
 }
-template <typename TriPtr>
+// PAIR: a shadow walk that returns shadow_result (HRT_STAGED_BODY_S), not a distance
+template <bool PAIR = false, typename TriPtr>
 __device__ __forceinline__ Hit closest_hit_masked(TriPtr tri, const uint32_t *__restrict__ orig, const hrt_krxt &X,
                                                   uint32_t apex_k, uint32_t num_tri, F3 o, F3 d, bool valid,
                                                   uint32_t lane, [[maybe_unused]] int kind)
@@ -735,6 +865,15 @@ __device__ __forceinline__ Hit closest_hit_masked(TriPtr tri, const uint32_t *__
     HRT_STAT(kind, 0, 1);
     HRT_STAT(kind, 1, 1);
     HRT_STAT(kind, 2, __popcll(m));
+    if constexpr (PAIR) {
+        float nt_b = 1e9f, a_b = 1.f;
+        while (m) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(m);
+            m &= m - 1ull;
+            HRT_STAGED_BODY_S(j)
+        }
+        return shadow_result(who, nt_b, a_b);
+    }
     while (m) {   // any order: ties go by (distance, original index)
         const uint32_t j = (uint32_t)__builtin_ctzll(m);
         m &= m - 1ull;
@@ -862,7 +1001,7 @@ __device__ __forceinline__ void patch_load(const hrt_kpatch &X, const PatchRef R
 __device__ __forceinline__ bool patch_whole(const PatchRef R, bool valid) { return HRT_BALLOT(valid && !R.served) != 0ull; }
 
 // the trace of a wave from its lanes' mask words: the union over the wave, walked through the staged test
-template <typename TriPtr, typename OrigPtr>
+template <bool PAIR = false, typename TriPtr, typename OrigPtr>
 __device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint32_t (&w)[8], const bool whole, uint32_t num_tri,
                                                  F3 o, F3 d, bool valid, uint32_t lane, [[maybe_unused]] int kind)
 {
@@ -878,6 +1017,7 @@ __device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint3
     }
     HRT_STAT(kind, 0, 1);
     HRT_STAT(kind, 1, 1);
+    [[maybe_unused]] float nt_b = 1e9f, a_b = 1.f;   // PAIR: the best candidate's (Nt', a)
 #pragma unroll
     for (uint32_t r = 0; r < HRT_PATCH_WORDS; ++r) {
         unsigned long long m = ((unsigned long long)w[2u * r + 1u] << 32) | (unsigned long long)w[2u * r];
@@ -885,14 +1025,15 @@ __device__ __forceinline__ Hit closest_hit_words(TriPtr tri, OrigPtr orig, uint3
         while (m) {   // any order: ties go by (distance, original index)
             const uint32_t j = r * 64u + (uint32_t)__builtin_ctzll(m);
             m &= m - 1ull;
-            HRT_STAGED_BODY(j)
+            if constexpr (PAIR) HRT_STAGED_BODY_S(j) else HRT_STAGED_BODY(j)
         }
     }
+    if constexpr (PAIR) return shadow_result(who, nt_b, a_b);
     return {who, best};
 }
 
 // the trace of a wave whose lanes have located their patches (R; lanes past the end of the list: !valid)
-template <typename TriPtr, typename OrigPtr>
+template <bool PAIR = false, typename TriPtr, typename OrigPtr>
 __device__ __forceinline__ Hit closest_hit_patch(TriPtr tri, OrigPtr orig, const hrt_kpatch &X,
                                                  const PatchRef R, uint32_t apex_k, uint32_t num_tri, F3 o, F3 d,
                                                  bool valid, uint32_t lane, [[maybe_unused]] int kind)
@@ -900,7 +1041,7 @@ __device__ __forceinline__ Hit closest_hit_patch(TriPtr tri, OrigPtr orig, const
     uint32_t w[8];
     patch_load(X, R, apex_k, valid, w);
     HRT_STAT(kind, 6, (valid && R.served) ? 1 : 0);
-    return closest_hit_words(tri, orig, w, patch_whole(R, valid), num_tri, o, d, valid, lane, kind);
+    return closest_hit_words<PAIR>(tri, orig, w, patch_whole(R, valid), num_tri, o, d, valid, lane, kind);
 }
 
 // the mask words of the cube-map cell of direction d in TX tx's table (hrt_kpatch.txcell) -- the hot kernels through
@@ -3058,7 +3199,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
 #pragma unroll
             for (int q = 0; q < 8; ++q) wcur[q] = wnext[q];
             if (rx + 1u < P.num_rx) patch_load(P.patch, ref, rx + 1u, valid, wnext);
-            const Hit h = closest_hit_words(tri, l_orig, wcur, whole, T, o, w, valid, lane, 2);
+            const Hit h = closest_hit_words<true>(tri, l_orig, wcur, whole, T, o, w, valid, lane, 2);
             // The masks of the next RX are consumed HERE, behind the walk they were requested in front of and in front
             // of this RX's record stores: the wait for them then stands where only loads are outstanding.  Left to the
             // loop's back edge (their first use, the copy into wcur) it is an s_waitcnt vmcnt(0) behind the five to
@@ -3067,7 +3208,7 @@ __global__ __launch_bounds__(HRT_BLOCK, HRT_RECORDS_WAVES) void hrt_records_kern
 #pragma unroll
             for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(wnext[q]));
 #else
-            const Hit h = closest_hit_patch(tri, l_orig, P.patch, ref, rx, T, o, w, valid, lane, 2);
+            const Hit h = closest_hit_patch<true>(tri, l_orig, P.patch, ref, rx, T, o, w, valid, lane, 2);
 #endif
             bool unblocked = false;
             if (valid) {
@@ -4349,6 +4490,48 @@ __global__ void hrt_selftest_math_kernel(int fn, const float *in, float *out, ui
     out[i] = y;
 }
 
+// fn 11 of the selftest (a kernel of its own, so that the test entry costs hrt_selftest_math_kernel nothing): the
+// walk of the hot kernels, closest_hit_words, over triangles given INLINE.  Lane i works on item i of n / 168, floats
+// [168 i, 168 i + 168) of `in`: o, d, kind (u32 bits: 0 primary, 2 shadow; anything else: a lane without a ray), the
+// number of rows T <= 8 (u32 bits), then eight table rows of HRT_TRI_FLOATS floats -- v1 e1 e2 in the first nine
+// words as in the product's table, the row's ORIGINAL index as the bits of its last word.  Rows past T must be zero:
+// the wave walks the union of its lanes' rows, and a zero row is rejected at the first stage.  out [168 i]: the bits
+// of the winning row (HRT_NO_HIT: none); out [168 i + 1]: the bits of its distance (kind 0) or, for kind 2, 1 when the
+// distance is at most one and 0 otherwise -- all a shadow walk has to tell.
+struct InlineOrig {   // the tie-rule index of row j: the last word of the lane's own row j
+    const float *rows;
+    __device__ __forceinline__ uint32_t operator[](uint32_t j) const { return __float_as_uint(rows[HRT_TRI_FLOATS * j + HRT_TRI_FLOATS - 1u]); }
+};
+constexpr uint64_t kWalkItem = 8u + 8u * HRT_TRI_FLOATS;
+static_assert(kWalkItem == 168u && HRT_TRI_FLOATS % 4u == 0u, "selftest walk item: 16-byte aligned rows");
+__global__ __launch_bounds__(256) void hrt_selftest_walk_kernel(const float *in, float *out, uint64_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t items = n / kWalkItem;
+    if ((i & ~(uint64_t)63) >= items) return;   // (a whole wave)
+    const bool live = i < items;
+    const uint32_t lane = threadIdx.x & 63u;
+    const float *it = in + kWalkItem * (live ? i : 0u);   // (a lane past the last item reads item 0 and has no ray)
+    const F3 o = {it[0], it[1], it[2]}, d = {it[3], it[4], it[5]};
+    const uint32_t kind = __float_as_uint(it[6]);
+    const uint32_t T = min(__float_as_uint(it[7]), 8u);
+    const float4 *tri = reinterpret_cast<const float4 *>(it + 8);
+    const InlineOrig orig = {it + 8};
+    Hit h = {HRT_NO_HIT, 1e9f};
+#pragma unroll
+    for (int k = 0; k < 3; k += 2) {   // the primary lanes of the wave, then its shadow lanes
+        const bool mine = live && kind == (uint32_t)k;
+        uint32_t w[8] = {mine ? (1u << T) - 1u : 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        const Hit g = k == 2 ? closest_hit_words<true>(tri, orig, w, false, 8u, o, d, mine, lane, 2)
+                             : closest_hit_words(tri, orig, w, false, 8u, o, d, mine, lane, 0);
+        if (mine) h = g;
+    }
+    if (live) {
+        out[kWalkItem * i] = __uint_as_float(h.tri);
+        out[kWalkItem * i + 1u] = kind == 2u ? __uint_as_float(h.t <= 1.f ? 1u : 0u) : h.t;
+    }
+}
+
 // TEST ENTRY (hrt_debug_candidates, include/hrt_device.h): one query per lane, the lane's OWN lookup through the device
 // functions the hot kernels call -- no wave union, no walk.  in [n][8]: o, d, row, apex (u32 bits); out [n][10]:
 // served, patch index, eight mask words (zero when not served).  mode 0 / 1: the patch table for RX `apex` / for the
@@ -4931,6 +5114,13 @@ int hrt_hip_launch_order(const uint32_t *d_seg_start, const uint32_t *d_seg_band
 int hrt_hip_selftest_math(int fn, const float *d_in, float *d_out, uint64_t n, void *stream)
 {
     if (n == 0) return 0;
+    if (fn == 11) {
+        const uint64_t items = n / kWalkItem;
+        if (items == 0) return 0;
+        hipLaunchKernelGGL(hrt_selftest_walk_kernel, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, d_in, d_out, n);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(hrt_selftest_math_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, fn, d_in, d_out, n);
     return (int)hipGetLastError();

@@ -627,7 +627,12 @@ int hrt_scene_import_sionna(const char *xml_path, Scene *out);
  * floats [K i, K i + K) of `in` and of `out` belonging to item i (64 consecutive items share a wave):
  * fn 8, K = 8: the bitwise OR over the wave of the item's eight 32-bit words (carried as float bits);
  * fn 9, K = 1: in / c, c the float speed of light; fn 10, K = 4: (s, alpha, theta_s, theta_i) -> the
- * four scattering pattern terms of src/compute_paths.c:359-415. */
+ * four scattering pattern terms of src/compute_paths.c:359-415.
+ * fn 11, K = 168: the triangle walk of the trace and record kernels over rows given inline.  Item = o[3], d[3],
+ * kind (u32 bits: 0 primary, 2 shadow, other: a lane without a ray), T <= 8 (u32 bits), eight rows of 20 floats
+ * (v1, e1, e2 in the first nine words, the row's original index as the bits of the last; rows past T all zero).
+ * out[K i] = bits of the closest row (0xffffffff: none), out[K i + 1] = the bits of its distance (kind 0) or
+ * 1 / 0 for "distance <= 1" (kind 2); the rest of the item's output is zero. */
 int hrt_selftest_math(int device, int fn, const float *in, float *out, uint64_t n);
 
 /* Diagnostic counters of the trace kernel; all zero unless the library was built with
@@ -636,7 +641,9 @@ int hrt_selftest_math(int device, int fn, const float *in, float *out, uint64_t 
  * 2 candidate triangles after packet culling, 3 / 4 / 5 staged bodies reaching stage 2, stage 3,
  * the exact divisions, 6 (sub-)packets walked [flat: heavy packets], 7 packet-culling rounds of near
  * leaves [flat: candidates of heavy packets], 8 sphere-node rounds, 9 plane-node rounds, 10 plane
- * leaves judged, 11 of them with flagged triangles, 12 flagged triangles, 13-15 unused. */
+ * leaves judged, 11 of them with flagged triangles, 12 flagged triangles, 13 / 14 the longest and the total
+ * duration of a wave-trace of hrt_trace_kernel in shader clocks, 15 of the staged bodies of column 5 those in
+ * which every lane still in play held the certain-hit certificate (no u, v division). */
 int hrt_debug_kernel_stats(int device, uint64_t *out48, int reset);
 
 /* TEST ONLY -- a lane's own candidate lookup, for tests/test_gpu_candidates.py.  Every kernel that traces a ray on

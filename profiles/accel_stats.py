@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Diagnostic counters of the trace kernel on one generated room (library built with `make STATS=1`):
-    python profiles/accel_stats.py BOXES [RAYS]"""
+    python profiles/accel_stats.py BOXES [RAYS]        (or a bench workload: c1 .. c5)
+The counters' atomics slow the kernels down, and a fused launch or the chain kernel of a STATS build can give up
+waiting (a void step: error word & 0x300; the library then switches that kernel off for the process).  The script
+resets the counters and traces again, up to three times -- so after a void step a STATS build counts on the
+per-launch kernels, not on the fused ones."""
 import ctypes
 import json
 import os
@@ -32,12 +36,19 @@ else:
     tr = Tracer(p, [[5, 3, 1.5], [-8, -4, 2.0], [12, 9, 8.0]], [[-10, 5, 6.0]], [[0, 0, 0]] * 3, [[0, 0, 0]], 3.5, rays, 2)
 arr = (ctypes.c_uint64 * 48)()
 lib.load().hrt_debug_kernel_stats(0, arr, 1)
-tr.trace()
-torch.cuda.synchronize()
+for attempt in range(3):
+    tr.trace()
+    torch.cuda.synchronize()
+    if not (tr.error_word() & 0x300):
+        break
+    # a void step: a fused launch or the chain kernel gave up waiting (the counters' atomics slow them down); the library
+    # has switched that kernel off, so count again on the per-launch kernels
+    print("void step (error word %#x): counting again" % tr.error_word(), file=sys.stderr)
+    lib.load().hrt_debug_kernel_stats(0, arr, 1)
 lib.load().hrt_debug_kernel_stats(0, arr, 0)
 cols = ["wave_traces", "usable_full", "candidates", "stage2", "stage3", "exact", "subpackets", "cull_rounds",
         "sphere_rounds", "plane_rounds", "plane_leaves", "plane_leaves_flagged", "flagged", "max_clk", "sum_clk"]
-cols = cols[:13] + ["max_clk", "sum_clk", "clk15"]
+cols = cols[:13] + ["max_clk", "sum_clk", "exact_certain"]   # 15: the stage-4 passes that skip the u, v divisions
 for k, name in enumerate(("primary0", "primary", "shadow")):
     row = {c: int(arr[k * 16 + j]) for j, c in enumerate(cols)}
     wt = max(1, row["wave_traces"])
