@@ -2,7 +2,7 @@
 // hrt_chain_kernel inside its loops (hrt_kernels.hip).  Textual, not a function: compiled inside the kernel the
 // launch-0 instance keeps its 32 bytes of scratch at 72 registers; as an inlined __device__ function the same
 // text came out with 112 (measured: launch 0 +7 %).
-// In scope: P, b, lds; constexpr TRI_IN_LDS, VARIANT, FIRST, K, CHAIN; CHAIN: chunk_c, n_in_c, Ke_c, n_chunks_c
+// In scope: P, b, lds; constexpr TRI_IN_LDS, VARIANT, FIRST, K, CHAIN, TXCELL; CHAIN: chunk_c, n_in_c, Ke_c, n_chunks_c
 // (the macro-chunk the loop hands out), sc1_in (the live list was written inside this kernel).  `return` leaves the KERNEL: in the chain only a void step does that.
     constexpr int AUX = CHAIN ? 16 : 0;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -31,7 +31,10 @@
     const float2 *g_tg = reinterpret_cast<const float2 *>(P.acc.tg);
     const float4 *g_leaf = reinterpret_cast<const float4 *>(P.acc.leaf);
     const uint32_t n_leaf = P.acc.num_leaf;
-    const FusedLds L = fused_lds<TRI_IN_LDS, (VARIANT == 9), FIRST>(lds, T, n_leaf, P.num_rx, wave);
+    const FusedLds L = [&]() {
+        if constexpr (TXCELL) return fused0_lds(lds, T, P.num_tx);
+        else return fused_lds<TRI_IN_LDS, (VARIANT == 9), FIRST>(lds, T, n_leaf, P.num_rx, wave);
+    }();
 #ifdef HRT_PHASE_STATS
     // (make EXTRA=-DHRT_PHASE_STATS) time stamps of a workgroup's life (thread 0, 100 MHz wall clock):
     // g_phase[chunk] = {start, loads + staging done, traces + publish done, records done, prefix
@@ -119,10 +122,12 @@
         return {P.tx_pos[3 * tx], P.tx_pos[3 * tx + 1], P.tx_pos[3 * tx + 2]};
     };
 
+    [[maybe_unused]] uint32_t matw_row = 0u;   // TXCELL: the material word of row tid, in flight until the traces' barrier
     if constexpr (CHAIN) __syncthreads();   // (the previous chunk's readers of L.wcnt are done)
     if constexpr (!CHAIN) {
         // (the tables behind the state in one flight: a load -> store -> load chain costs a round trip per 4 KB)
-        fused_stage<TRI_IN_LDS, (VARIANT >= 4), FIRST>(P, L, T, n_leaf, tid);
+        if constexpr (TXCELL) fused0_stage(P, L, T, tid, matw_row);
+        else fused_stage<TRI_IN_LDS, (VARIANT >= 4), FIRST>(P, L, T, n_leaf, tid);
         __syncthreads();
     }
     auto tri = [&]() {
@@ -169,9 +174,14 @@
                 continue;
             }
             const F3 ok = FIRST ? tx_origin(k) : o[k];
-            if (FIRST && masked) {
+            if constexpr (TXCELL) {
+                const OrigWords ow = {lds_addr(L.orig), P.acc.orig, P.fused0_words != 0u};
+                h[k] = closest_hit_txcell((const float4 *)L.tri, ow, P.patch, htri[k], T, ok, d[k], valid[k], lane);
+            } else if (FIRST && masked) {
                 h[k] = closest_hit_masked(tri, P.acc.orig, P.rxt, P.num_rx + htri[k], T, ok, d[k], valid[k], lane, 0);
             } else if (FIRST && VARIANT == 2 && P.patch.txcell != nullptr) {
+                // (never taken since the plan sends these problems to the TXCELL instantiation: kept so that the
+                // shared instantiation, C4's launch 0, compiles to what it did)
                 if constexpr (FIRST && VARIANT == 2) h[k] = closest_hit_txcell(tri, P.acc.orig, P.patch, htri[k], T, ok, d[k], valid[k], lane);
             } else {
                 Ball ball = {{0.f, 0.f, 0.f}, 0.f, false};
@@ -182,6 +192,7 @@
             hm[k] = HRT_BALLOT(valid[k] && h[k].tri != HRT_NO_HIT);
             if (lane == 0) L.wcnt[16 + k * 4 + (int)wave] = (uint32_t)__popcll(hm[k]);
         }
+        if constexpr (TXCELL) if (P.fused0_words && tid < T) L.matw[tid] = matw_row;   // (requested at staging)
         __syncthreads();
         // (L.wcnt[16 ..]: K x 4 counts, sub-chunk-major = entry order)
 #pragma unroll
@@ -331,7 +342,8 @@
                     o[k] = tx_origin(k);
                     const F3 tv = {P.tx_vel[3 * tx], P.tx_vel[3 * tx + 1], P.tx_vel[3 * tx + 2]};
                     fs0[k] = dot3(tv, d[k]) * P.dop_mult;
-                    bounce_fetch(tri, mesh_r, h[k].tri, nk[k], matk[k]);
+                    if constexpr (TXCELL) bounce_fetch0(L.tri, L.matw, P.fused0_words != 0u, mesh_r, h[k].tri, nk[k], matk[k]);
+                    else bounce_fetch(tri, mesh_r, h[k].tri, nk[k], matk[k]);
                 }
                 bounce_apply<(FIRST && HRT_FUSED_INLINE0)>(L.mat, P.fsl_mult, nk[k], matk[k], h[k].t, o[k], d[k], a0[k], a1[k], a2[k], a3[k], tau[k], nth);
                 const uint32_t k4 = (pos + before + lane_prefix(hm[k])) * 4u;

@@ -3385,6 +3385,7 @@ struct FusedLds {
     float2 *tg;
     unsigned long long *mask;
     uint32_t *wcnt;
+    uint32_t *orig, *matw;   // (fused0_lds only)
 };
 template <bool TRI_IN_LDS, bool CAND_BUF, bool FIRST>
 __device__ __forceinline__ FusedLds fused_lds(float4 *lds, uint32_t T, uint32_t n_leaf, uint32_t num_rx, uint32_t wave)
@@ -3444,6 +3445,68 @@ __device__ __forceinline__ void fused_stage(const hrt_kparams &P, const FusedLds
     stage_rest<1, 2>(l_pos, n_pos, tid, ld_pos);
 }
 
+// Launch 0 on a patch-table problem (hrt_fused_kernel<..., TXCELL>; hrt_launch_plan.h sizes it: lds_fused0) reads the
+// rows, its counts, the materials and the TX positions, so its image is those alone -- seven workgroups per CU where
+// the shared image lets six in (C3: 25 840 B against 20 080 B):
+// [T x 5 float4 rows][64 u32][17 x 4 float4 materials][min(num_tx, 64) float4 TX pos]
+// [T u32 reference-order indices, padded to 16 B][T u32 material indices]      (the words: only while a seventh holds them)
+// With the words in, the walk's last stage and the shading read LDS only (the records kernel's l_orig, and the mesh's
+// material per ROW, so that a hit's material is one LDS read instead of a dependent global load behind the
+// previous packet's stores).
+__device__ __forceinline__ FusedLds fused0_lds(float4 *lds, uint32_t T, uint32_t num_tx)
+{
+    FusedLds L;
+    L.tri = lds;
+    L.tg = nullptr;
+    L.leaf = L.rx = L.wleaf = nullptr;
+    L.mask = nullptr;
+    L.wcnt = reinterpret_cast<uint32_t *>(lds + HRT_ROW * T);
+    L.mat = reinterpret_cast<float4 *>(L.wcnt + 64);
+    L.tx = L.mat + kMatItems;
+    L.orig = reinterpret_cast<uint32_t *>(L.tx + min(num_tx, kLdsTx));
+    L.matw = L.orig + (T + 3u) / 4u * 4u;
+    return L;
+}
+// That image in one flight.  The material of a row is behind two loads (the row's mesh, the mesh's material): the
+// first rides in the flight, the second is requested here and handed back in `matw` (row tid), for the caller to
+// store in front of its next barrier -- nothing waits for it in between.  No barrier.
+__device__ __forceinline__ void fused0_stage(const hrt_kparams &P, const FusedLds &L, const uint32_t T, const uint32_t tid,
+                                             uint32_t &matw)
+{
+    const float4 *g_tri = reinterpret_cast<const float4 *>(P.tri);
+    const float4 *g_mat = reinterpret_cast<const float4 *>(P.mat);
+    const uint32_t n_tri4 = HRT_ROW * T, n_pos = min(P.num_tx, kLdsTx), n_w = P.fused0_words ? T : 0u;
+    const auto ld_pos = [&](uint32_t k) { return stage_pos(P.tx_pos, k); };
+    const auto ld_orig = [&](uint32_t k) { return P.acc.orig[k]; };
+    const auto ld_mesh = [&](uint32_t k) { return __float_as_uint(P.tri[4u * (HRT_ROW * k + 4u) + 3u]); };
+    float4 s_tri[kStageTri], s_pos[1], s_mat[1];
+    uint32_t s_orig[1], s_mesh[1];
+    copy16_request(s_tri, g_tri, n_tri4, tid);
+    stage_load(s_pos, n_pos, tid, ld_pos);
+    copy16_request(s_mat, g_mat, kMatItems, tid);
+    stage_load(s_orig, n_w, tid, ld_orig);
+    stage_load(s_mesh, n_w, tid, ld_mesh);
+    copy16_commit(s_tri, L.tri, g_tri, n_tri4, tid);
+    stage_store(L.tx, s_pos, n_pos, tid);
+    copy16_commit(s_mat, L.mat, g_mat, kMatItems, tid);
+    stage_store(L.orig, s_orig, n_w, tid);
+    matw = 0u;
+    if (tid < n_w) matw = ldu(make_rsrc(reinterpret_cast<const uint8_t *>(P.mesh)), 0u, s_mesh[0] * (HRT_MESH_FLOATS * 4u) + 12u);
+    // (n_pos <= 64 and, with the words in, T <= 250: one item per thread, nothing behind the first batch)
+}
+// the reference-order index of a row for the walks of that kernel: from its image where the words are in
+// (the LDS side through its address, lds_addr: as two pointers of one type the two loads are merged into one flat load)
+struct OrigWords {
+    uint32_t l;   // lds_addr of the words
+    const uint32_t *g;
+    bool in_lds;
+    __device__ __forceinline__ uint32_t operator[](const uint32_t j) const
+    {
+        if (in_lds) return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(l + 4u * j);
+        return g[j];
+    }
+};
+
 // The bounce itself for a ray that hit triangle `ptri` at distance `pt` (src/compute_paths.c:
 // 611-659): incidence angle, Fresnel, free-space loss, delay, reflection.  Same sequence as the
 // shade kernel's, in two steps: bounce_fetch requests what comes from memory (the triangle's normal,
@@ -3457,6 +3520,18 @@ __device__ __forceinline__ void bounce_fetch(TriPtr tri, Rsrc mesh_r, uint32_t p
     n = {q2.y, q2.z, q2.w};
     const uint32_t mesh = __float_as_uint(tri[HRT_ROW * ptri + 4].w);
     mat = ldu(mesh_r, 0u, mesh * (HRT_MESH_FLOATS * 4u) + 12u);
+}
+// ... of launch 0 on patch tables: the material from the image's words where they are in (fused0_lds)
+__device__ __forceinline__ void bounce_fetch0(const float4 *tri, const uint32_t *l_matw, const bool words, Rsrc mesh_r,
+                                              uint32_t ptri, F3 &n, uint32_t &mat)
+{
+    if (words) {
+        const float4 q2 = tri[HRT_ROW * ptri + 2];
+        n = {q2.y, q2.z, q2.w};
+        mat = l_matw[ptri];
+    } else {
+        bounce_fetch(tri, mesh_r, ptri, n, mat);
+    }
 }
 template <bool INL>
 __device__ __forceinline__ void bounce_apply(const float4 *l_mat, float fsl_mult, F3 n, uint32_t mat, float pt, F3 &o,
@@ -3511,6 +3586,9 @@ constexpr uint32_t kShortList = 256u * 1024u;   // entries: one packet per wave 
 #ifndef HRT_FUSED_WAVES0
 #define HRT_FUSED_WAVES0 7   /* launch 0: at most 72 VGPRs (8 waves spill and are slower) */
 #endif
+#ifndef HRT_FUSED_WAVES0X
+#define HRT_FUSED_WAVES0X 7   /* launch 0 on patch tables (TXCELL): seven workgroups per CU fit its image */
+#endif
 #ifndef HRT_FUSED_WAVESB
 #define HRT_FUSED_WAVESB 4
 #endif
@@ -3532,9 +3610,13 @@ constexpr uint32_t kShortList = 256u * 1024u;   // entries: one packet per wave 
 // One macro-chunk of launch b = csrc/hrt_fused_body.inc: the body of hrt_fused_kernel, and -- CHAIN -- of
 // hrt_chain_kernel's loops: there the tables are staged once per workgroup by the kernel, and the live list
 // travels between the bounces with sc1 accesses.
-template <bool TRI_IN_LDS, int VARIANT, bool FIRST, int K>
-__global__ __launch_bounds__(HRT_BLOCK, (FIRST ? HRT_FUSED_WAVES0 : HRT_FUSED_WAVESB)) void hrt_fused_kernel(const hrt_kparams P, const uint32_t b)
+// TXCELL: launch 0 of a patch-table problem (FIRST, the staged flat walk, a TX cell table and no per-cell masks: the
+// plan's fused0_txcell) as an instantiation of its own -- its image is fused0_lds, its walk closest_hit_txcell alone,
+// and its registers are its own to spend (the instantiation without the flag is also C4's launch 0, on per-cell masks).
+template <bool TRI_IN_LDS, int VARIANT, bool FIRST, int K, bool TXCELL = false>
+__global__ __launch_bounds__(HRT_BLOCK, (TXCELL ? HRT_FUSED_WAVES0X : FIRST ? HRT_FUSED_WAVES0 : HRT_FUSED_WAVESB)) void hrt_fused_kernel(const hrt_kparams P, const uint32_t b)
 {
+    static_assert(!TXCELL || (TRI_IN_LDS && VARIANT == 2 && FIRST), "TXCELL: launch 0, staged flat walk");
     extern __shared__ float4 lds[];
     constexpr bool CHAIN = false;
     const uint32_t chunk_c = 0u, n_in_c = 0u, Ke_c = 0u, n_chunks_c = 0u;
@@ -3613,7 +3695,7 @@ template <bool TRI_IN_LDS, int VARIANT, int K>
 __global__ __launch_bounds__(HRT_BLOCK, HRT_FUSED_WAVESB) void hrt_chain_kernel(const hrt_kparams P, const uint32_t b0)
 {
     extern __shared__ float4 lds[];
-    constexpr bool FIRST = false, CHAIN = true;
+    constexpr bool FIRST = false, CHAIN = true, TXCELL = false;
     const uint32_t tid = threadIdx.x;
     uint32_t *counts = reinterpret_cast<uint32_t *>(P.ws + P.off_counts);
     uint32_t *err_word = &counts[P.num_bounces + 1];
@@ -4605,8 +4687,20 @@ static void launch_trace_t(const hrt_kparams *P, uint32_t bounce, uint32_t block
 #ifndef HRT_FUSED_KB
 #define HRT_FUSED_KB 2   /* ... at later launches (15 words of state per entry stay in registers) */
 #endif
+// (make EXTRA=-DHRT_PHASE_STATS, with HRT_PHASE_FILE set: how many workgroups of launch 0 a CU holds at its real image)
+template <typename F>
+static void phase_occupancy([[maybe_unused]] F fn, [[maybe_unused]] const char *which, [[maybe_unused]] size_t lds)
+{
+#ifdef HRT_PHASE_STATS
+    if (getenv("HRT_PHASE_FILE")) {
+        int per_cu = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, HRT_BLOCK, lds);
+        fprintf(stderr, "launch 0, %s instantiation: %zu B of LDS, %d workgroups per CU\n", which, lds, per_cu);
+    }
+#endif
+}
 template <bool LDS, int V>
-static void launch_fused_t(const hrt_kparams *P, uint32_t bounce, size_t lds, hipStream_t st, hipError_t *err)
+static void launch_fused_t(const hrt_kparams *P, uint32_t bounce, size_t lds, bool txcell, hipStream_t st, hipError_t *err)
 {
     const uint64_t n_max = (bounce == 0) ? P->n0 : P->cap;
     if (bounce == 0) {
@@ -4614,6 +4708,19 @@ static void launch_fused_t(const hrt_kparams *P, uint32_t bounce, size_t lds, hi
         // (a short launch set: one packet per wave, see the kernel) + the workgroups of the LoS pass
         const uint32_t blocks = (uint32_t)((n_max + (n_max <= kShortList ? 1 : K) * HRT_BLOCK - 1) /
                                            ((n_max <= kShortList ? 1 : K) * HRT_BLOCK)) + P->los_blocks;
+        if constexpr (LDS && V == 2) {
+            if (txcell) {   // patch tables: the instantiation and the image of its own
+                if (lds > 64u * 1024u) {   // (staged rows are at most 40 KiB by default; HRT_TUNE can stage more)
+                    *err = hipFuncSetAttribute(reinterpret_cast<const void *>(&hrt_fused_kernel<true, 2, true, K, true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    if (*err != hipSuccess) return;
+                }
+                phase_occupancy(hrt_fused_kernel<true, 2, true, K, true>, "patch tables", lds);
+                hipLaunchKernelGGL((hrt_fused_kernel<true, 2, true, K, true>), dim3(blocks), dim3(HRT_BLOCK), lds, st, *P, bounce);
+                return;
+            }
+        }
+        phase_occupancy(hrt_fused_kernel<LDS, V, true, K>, "shared", lds);
         if (lds > 64u * 1024u) {
             *err = hipFuncSetAttribute(reinterpret_cast<const void *>(&hrt_fused_kernel<LDS, V, true, K>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -4934,11 +5041,14 @@ int hrt_hip_launch_fused(const hrt_kparams *P_in, uint32_t bounce, void *stream)
     const hrt_kparams *P = &Pc;
     if (P->cap / HRT_BLOCK + 1u > P->lb_chunks) return (int)hipErrorInvalidValue;   // (one word per chunk)
     if (!hrt_plan_fuses(&pl, bounce)) return -1;   // not a HIP failure: this launch runs as two kernels
-    const size_t lds = (size_t)pl.lds_fused;
+    // (launch 0 on patch tables: the plan's instantiation and image; the words are one item per thread at staging)
+    const bool txcell = bounce == 0 && pl.fused0_txcell;
+    Pc.fused0_words = (txcell && pl.fused0_words && P->num_tri <= HRT_BLOCK) ? 1u : 0u;
+    const size_t lds = (size_t)(txcell ? pl.lds_fused0 : pl.lds_fused);
     hipStream_t st = (hipStream_t)stream;
     hipError_t err = hipSuccess;
     switch (HRT_WALK(pl.in_lds, pl.fused_v)) {
-#define HRT_CASE(LDS, V) case HRT_WALK(LDS, V): launch_fused_t<LDS, V>(P, bounce, lds, st, &err); break;
+#define HRT_CASE(LDS, V) case HRT_WALK(LDS, V): launch_fused_t<LDS, V>(P, bounce, lds, txcell, st, &err); break;
         HRT_CASE(true, 0) HRT_CASE(true, 1) HRT_CASE(true, 2) HRT_CASE(true, 3) HRT_CASE(true, 6) HRT_CASE(true, 4)
         HRT_CASE(true, 5) HRT_CASE(false, 0) HRT_CASE(false, 1) HRT_CASE(false, 3) HRT_CASE(false, 6) HRT_CASE(false, 5)
 #undef HRT_CASE

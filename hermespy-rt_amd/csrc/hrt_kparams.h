@@ -219,6 +219,8 @@ typedef struct {
     const uint32_t *wide_inv;   /* [T] index in the reference's loop order -> table row (the inverse of acc.orig) */
     uint32_t cnt_per_wave;   /* survivor counts at off_chunk_cnt: 1 = one word per WAVE of a chunk (the fine walk, whose
                               * waves do not wait for each other), 0 = one per chunk; set by the launch shims */
+    uint32_t fused0_words;   /* launch 0 on patch tables: its LDS image holds the reference-order and the material words
+                              * (hrt_launch_plan.fused0_words); set by the launch shim */
 } hrt_kparams;
 
 /* the counter block at off_counts (zeroed at the start of every trace), four parts of cnt_stride bytes

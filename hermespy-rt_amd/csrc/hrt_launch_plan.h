@@ -23,6 +23,11 @@
 #define HRT_LDS_TAIL_FUSED 256u
 #define HRT_LDS_TAIL_SHADE 32u
 #define HRT_LDS_TAIL_IMAGE 16u
+/* launch 0 on patch tables (hrt_fused_kernel<..., TXCELL>): seven workgroups of it share a CU's 160 KiB, and the two
+ * word tables ride in its image only while it stays within a seventh */
+#define HRT_LDS_CU (160u * 1024u)
+#define HRT_FUSED0_PER_CU 7u
+#define HRT_LDS_FUSED0_MAX (HRT_LDS_CU / HRT_FUSED0_PER_CU)
 
 typedef struct {
     /* table facts */
@@ -52,6 +57,14 @@ typedef struct {
     uint64_t t_normals;   /* the shade kernel's triangle normals + mesh rows, 0 if it reads them from global memory */
     /* the LDS images */
     uint64_t lds_trace, lds_fused, lds_chain, lds_records, lds_image, lds_shade;
+    /* launch 0 of a patch-table problem (flat one-block walk on a staged table, a TX cell table, no per-cell masks):
+     * its own instantiation of hrt_fused_kernel with an image of what that path reads, lds_fused0; else all 0 */
+    uint8_t fused0_txcell;
+    uint8_t fused0_words;   /* the image holds the two word tables: reference-order indices and material indices */
+    uint64_t t_mat0;        /* the materials without expf's table */
+    uint64_t t_tx0;         /* min(num_tx, HRT_LDS_TX) TX positions */
+    uint64_t t_words0;      /* one of the two word tables: a word per row, padded to 16 B; 0 if they are out */
+    uint64_t lds_fused0;    /* rows + tail + t_mat0 + t_tx0 + 2 t_words0 */
 } hrt_launch_plan;
 
 static inline hrt_launch_plan hrt_plan(const hrt_kparams *P)
@@ -93,6 +106,18 @@ static inline hrt_launch_plan hrt_plan(const hrt_kparams *P)
     pl.lds_records = pl.t_rows + pl.t_rx + pl.t_mat_exp + pl.t_orig;
     pl.lds_image = pl.t_rows + HRT_LDS_TAIL_IMAGE;
     pl.lds_shade = pl.t_mat_exp + pl.t_rx + HRT_LDS_TAIL_SHADE + pl.t_normals;
+
+    pl.fused0_txcell = !pl.fine && pl.in_lds && pl.fused_v == 2 && P->patch.txcell != NULL && P->rxt.cell_mask == NULL;
+    if (pl.fused0_txcell) {
+        const uint64_t words = (pl.t_orig + 15u) / 16u * 16u;
+        pl.t_mat0 = HRT_NUM_MATERIALS * HRT_MAT_FLOATS * 4u;
+        pl.t_tx0 = (uint64_t)(P->num_tx < HRT_LDS_TX ? P->num_tx : HRT_LDS_TX) * 16u;
+        pl.lds_fused0 = pl.t_rows + HRT_LDS_TAIL_FUSED + pl.t_mat0 + pl.t_tx0;
+        /* (with the words in, 88 T < HRT_LDS_FUSED0_MAX: such a table has at most 250 rows, a word per thread) */
+        pl.fused0_words = pl.lds_fused0 + 2u * words <= HRT_LDS_FUSED0_MAX;
+        pl.t_words0 = pl.fused0_words ? words : 0u;
+        pl.lds_fused0 += 2u * pl.t_words0;
+    }
     return pl;
 }
 

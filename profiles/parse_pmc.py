@@ -44,7 +44,7 @@ def kind(name):
 
 
 def is_launch0(name):
-    m = re.search(r"hrt_fused_kernel<(\w+), (\d+), (\w+), (\d+)>", name)
+    m = re.search(r"hrt_fused_kernel<(\w+), (\d+), (\w+), (\d+)(?:, \w+)?>", name)
     return bool(m) and m.group(3) == "true"
 
 

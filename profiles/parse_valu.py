@@ -29,7 +29,7 @@ with open(os.path.join(HERE, "%s_pmc_valu_%s.csv" % (tag, workload)), "w", newli
 
 
 def launch0(name):
-    m = re.search(r"hrt_fused_kernel<(\w+), (\d+), (\w+), (\d+)>", name)
+    m = re.search(r"hrt_fused_kernel<(\w+), (\d+), (\w+), (\d+)(?:, \w+)?>", name)
     return bool(m) and m.group(3) == "true"
 
 
