@@ -817,6 +817,143 @@ def run_compute_channel_precoder(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel
     return precoder_views(out, pc)
 
 
+CS_POWER, CS_CAPACITY = 0, 1           # hrt_codebook_spec.metric
+CS_TABLE, CS_EFFECTIVE = 1, 2          # hrt_codebook_spec.flags
+CS_NONFINITE = 1                       # a subband's `status`
+CS_NO_INDEX = 0xFFFFFFFF               # a flagged subband's `index`
+CS_MAX_NR, CS_MAX_NT, CS_MAX_L, CS_MAX_C = 16, 64, 4, 4096
+CS_METRICS = {"power": CS_POWER, "capacity": CS_CAPACITY}
+
+
+class CodebookSpec(C.Structure):
+    """include/hermespy_rt.h hrt_codebook_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("layers", C.c_uint32), ("entries", C.c_uint32),
+                ("subband", C.c_uint32), ("metric", C.c_uint32), ("flags", C.c_uint32), ("noise", C.c_float)]
+
+
+def codebook_metric(metric):
+    """"power" / "capacity" (any case) or the constant itself -> hrt_codebook_spec.metric; an unknown name raises
+    ValueError, an unknown number is passed on for the library to refuse"""
+    return _pc_name(metric, CS_METRICS, "metric")
+
+
+def codebook_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, layers, entries, metric=CS_CAPACITY, noise=None,
+                  subband=None, table=False, effective=False, flags=None):
+    """subband None: wideband (S = K); noise None: 1.0 under POWER (not read), refused under CAPACITY (0)"""
+    if flags is None:
+        flags = (CS_TABLE if table else 0) | (CS_EFFECTIVE if effective else 0)
+    metric = codebook_metric(metric)
+    if noise is None:
+        noise = 1.0 if metric == CS_POWER else 0.0
+    return CodebookSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs), int(layers),
+                        int(entries), int(num_freqs) if subband is None else int(subband), metric, int(flags),
+                        float(noise))
+
+
+def codebook_subbands(spec):
+    """B = ceil(K / S) (0 where S is 0)"""
+    S = int(spec.subband)
+    return (int(spec.num_freqs) + S - 1) // S if S > 0 else 0
+
+
+def codebook_regions(spec):
+    """the byte offsets of index, metric, status, table, effective and the end of a codebook selection output
+    (hrt_codebook_out_bytes is the last)"""
+    links = int(spec.num_rx) * int(spec.num_tx)
+    sub = links * 2 * int(spec.num_times) * codebook_subbands(spec)
+    pts = links * 2 * int(spec.num_times) * int(spec.num_freqs)
+    o3 = 3 * sub * 4
+    o4 = o3 + (sub * int(spec.entries) * 4 if int(spec.flags) & CS_TABLE else 0)
+    o5 = o4 + (pts * int(spec.nr) * int(spec.layers) * 8 if int(spec.flags) & CS_EFFECTIVE else 0)
+    return 0, sub * 4, 2 * sub * 4, o3, o4, o5
+
+
+def codebook_views(buf, spec):
+    """the regions of a flat uint8 codebook selection buffer (numpy array or torch tensor) as views: index [nrx, ntx, 2,
+    T, B] (uint32 in numpy, int32 in torch: a flagged subband reads -1 there), metric float32 and status of that shape,
+    table float32 [nrx, ntx, C, 2, T, B] and effective complex64 [nrx, ntx, Nr, L, 2, T, K] (None where not asked
+    for), buffer"""
+    o = codebook_regions(spec)
+    nrx, ntx, nr = int(spec.num_rx), int(spec.num_tx), int(spec.nr)
+    T, K, B = int(spec.num_times), int(spec.num_freqs), codebook_subbands(spec)
+    if isinstance(buf, np.ndarray):
+        f32, c64, u32 = np.float32, np.complex64, np.uint32
+    else:
+        import torch
+        f32, c64, u32 = torch.float32, torch.complex64, torch.int32
+    out = {"index": buf[o[0]:o[1]].view(u32).reshape(nrx, ntx, 2, T, B),
+           "metric": buf[o[1]:o[2]].view(f32).reshape(nrx, ntx, 2, T, B),
+           "status": buf[o[2]:o[3]].view(u32).reshape(nrx, ntx, 2, T, B), "table": None, "effective": None,
+           "buffer": buf}
+    if int(spec.flags) & CS_TABLE:
+        out["table"] = buf[o[3]:o[4]].view(f32).reshape(nrx, ntx, int(spec.entries), 2, T, B)
+    if int(spec.flags) & CS_EFFECTIVE:
+        out["effective"] = buf[o[4]:o[5]].view(c64).reshape(nrx, ntx, nr, int(spec.layers), 2, T, K)
+    return out
+
+
+def codebook_fits(spec):
+    """whether the library accepts the spec (its limits, mirrored: an output beyond them is not allocated)"""
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    nr, nt, L, Cn, S = int(spec.nr), int(spec.nt), int(spec.layers), int(spec.entries), int(spec.subband)
+    links = int(spec.num_rx) * int(spec.num_tx)
+    return (0 < nr <= CS_MAX_NR and 0 < nt <= CS_MAX_NT and 0 < L <= min(CS_MAX_L, nt) and 0 < Cn <= CS_MAX_C
+            and 0 < S <= int(spec.num_freqs) and 0 < links * 2 * grid < 1 << 31
+            and links * 2 * int(spec.num_times) * codebook_subbands(spec) * Cn < 1 << 31
+            and int(spec.metric) in (CS_POWER, CS_CAPACITY) and not int(spec.flags) & ~(CS_TABLE | CS_EFFECTIVE)
+            and (int(spec.metric) == CS_POWER or _pc_positive(spec.noise)))
+
+
+def codebook_array(codebook, nt=None):
+    """a codebook as a contiguous complex64 [C, Nt, L] numpy array ([C, Nt] is taken as L = 1)"""
+    a = np.asarray(codebook)
+    if a.dtype.kind not in "fc":
+        raise ValueError("codebook must be a real or complex floating-point array, got %s" % (a.dtype,))
+    a = np.ascontiguousarray(a, np.complex64)
+    if a.ndim == 2:
+        a = a.reshape(a.shape[0], a.shape[1], 1)
+    if a.ndim != 3 or (nt is not None and a.shape[1] != nt):
+        raise ValueError("codebook must have shape (C, %s, L), got %s" % ("Nt" if nt is None else nt, a.shape))
+    return a
+
+
+def run_codebook_select(lib, device, spec, d_H, d_codebook, d_out, stream=None):
+    """hrt_codebook_select through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_codebook_select failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_codebook_select(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                                 C.c_void_p(d_codebook), C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_codebook_select failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_codebook_select(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                                rx_elements, tx_elements, codebook, metric=CS_CAPACITY, noise=None, subband=None,
+                                table=False, effective=False, flags=None, array_frequency=None, stats=None):
+    """hrt_compute_codebook_select through ctypes -> codebook_views of a uint8 numpy buffer (spec: a ChannelSpec, as
+    for run_compute_array_channel; codebook: complex [C, Nt, L], None passes NULL; array_frequency defaults to the
+    carrier).  The selection runs once, on the H accumulated over all batches: it is not additive.  Raises
+    RuntimeError("hrt_compute_codebook_select failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    if codebook is None:
+        cb, entries, layers = None, 1, 1
+    else:
+        cb = codebook_array(codebook)
+        entries, layers = cb.shape[0], cb.shape[2]
+    cs = codebook_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), layers, entries, metric, noise,
+                       subband, table, effective, flags)
+    extra += (cb.ctypes.data_as(C.POINTER(C.c_float)) if cb is not None else None, C.c_uint32(layers),
+              C.c_uint32(entries), C.c_uint32(int(cs.subband)), C.c_uint32(int(cs.metric)), C.c_uint32(int(cs.flags)),
+              C.c_float(cs.noise))
+    fits = codebook_fits(cs) and cb is not None and cb.shape[1] == nt
+    out = _run_pathsum(lib, "hrt_compute_codebook_select", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (codebook_regions(cs)[5],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_codebook_select accepted a call beyond its limits")
+    return codebook_views(out, cs)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

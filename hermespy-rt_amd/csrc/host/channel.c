@@ -1,7 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_channel_precoder, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_channel_precoder, hrt_codebook_select, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
  * hrt_sparse_beam_taps;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
@@ -31,6 +31,7 @@
 #include "../hrt_beam_channel.h"
 #include "../hrt_beam_taps.h"
 #include "../hrt_channel.h"
+#include "../hrt_codebook.h"
 #include "../hrt_covariance.h"
 #include "../hrt_dominant.h"
 #include "../hrt_equalizer.h"
@@ -1392,6 +1393,146 @@ int hrt_compute_channel_precoder(Scene *scene, const Vec3 *rx_pos, const Vec3 *t
     job.aux = &pc;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_precoder");
+}
+
+/* ------------------------------------------------------------------ codebook selection (hrt_codebook_select) */
+
+/* the checks of a codebook selection call (`who`); device pointers are not read */
+static int cs_check(const hrt_codebook_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->num_times == 0 || sp->num_freqs == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, num_times and num_freqs must be > 0", who);
+    if (sp->nr < 1 || sp->nr > HRT_CS_MAX_NR || sp->nt < 1 || sp->nt > HRT_CS_MAX_NT)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u and nt = %u (nr 1 .. %u, nt 1 .. %u)", who, sp->nr, sp->nt,
+                        HRT_CS_MAX_NR, HRT_CS_MAX_NT);
+    if (sp->layers < 1 || sp->layers > HRT_CS_MAX_L || sp->layers > sp->nt)
+        return hrt_fail(HRT_E_INVALID, "%s: layers = %u (1 .. min(%u, nt = %u))", who, sp->layers, HRT_CS_MAX_L,
+                        sp->nt);
+    if (sp->entries < 1 || sp->entries > HRT_CS_MAX_C)
+        return hrt_fail(HRT_E_INVALID, "%s: entries = %u (1 .. %u)", who, sp->entries, HRT_CS_MAX_C);
+    if (sp->subband < 1 || sp->subband > sp->num_freqs)
+        return hrt_fail(HRT_E_INVALID, "%s: subband = %u (1 .. num_freqs = %u)", who, sp->subband, sp->num_freqs);
+    if (sp->metric != HRT_CS_POWER && sp->metric != HRT_CS_CAPACITY)
+        return hrt_fail(HRT_E_INVALID, "%s: metric = %u is neither HRT_CS_POWER nor HRT_CS_CAPACITY", who, sp->metric);
+    if (sp->flags & ~(HRT_CS_TABLE | HRT_CS_EFFECTIVE))
+        return hrt_fail(HRT_E_INVALID, "%s: flags = 0x%x has unknown bits", who, sp->flags);
+    if (sp->metric == HRT_CS_CAPACITY && !pc_positive(sp->noise))
+        return hrt_fail(HRT_E_INVALID, "%s: noise = %g must be finite and > 0", who, (double)sp->noise);
+    const uint64_t grid = (uint64_t)sp->num_times * sp->num_freqs;   /* < 2^64 */
+    if (grid >= (1ull << 31) || (uint64_t)sp->num_rx * sp->num_tx >= (1ull << 31) / (2u * grid))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 points or more", who);
+    const uint64_t B = ((uint64_t)sp->num_freqs + sp->subband - 1u) / sp->subband;
+    /* (B <= K, so the points check above bounds num_rx num_tx 2 T B by 2^31 and the product by 2^43) */
+    if ((uint64_t)sp->num_rx * sp->num_tx * 2u * sp->num_times * B * sp->entries >= (1ull << 31))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 table entries or more", who);
+    return HRT_OK;
+}
+
+/* the regions of the output: byte offsets of index, metric, status, table, effective and the end (hermespy_rt.h) */
+static void cs_regions(const hrt_codebook_spec *sp, uint64_t off[6])
+{
+    const uint64_t links = (uint64_t)sp->num_rx * sp->num_tx;
+    const uint64_t B = sp->subband ? ((uint64_t)sp->num_freqs + sp->subband - 1u) / sp->subband : 0u;
+    const uint64_t sub = links * 2u * sp->num_times * B, points = links * 2u * sp->num_times * sp->num_freqs;
+    off[0] = 0;
+    off[1] = off[0] + sub * 4u;
+    off[2] = off[1] + sub * 4u;
+    off[3] = off[2] + sub * 4u;
+    off[4] = off[3] + ((sp->flags & HRT_CS_TABLE) ? sub * sp->entries * 4u : 0u);
+    off[5] = off[4] + ((sp->flags & HRT_CS_EFFECTIVE) ? points * sp->nr * sp->layers * 8u : 0u);
+}
+
+uint64_t hrt_codebook_out_bytes(const hrt_codebook_spec *spec)
+{
+    if (!spec) return 0;
+    uint64_t off[6];
+    cs_regions(spec, off);
+    return off[5];
+}
+
+int hrt_codebook_select(int device, const hrt_codebook_spec *spec, const void *d_H, const void *d_codebook, void *d_out,
+                        void *stream)
+{
+    int rc = cs_check(spec, "hrt_codebook_select");
+    if (rc) return rc;
+    if (!d_H || !d_codebook || !d_out) return hrt_fail(HRT_E_INVALID, "hrt_codebook_select: NULL device pointer");
+    hrt_kcodebook K;
+    memset(&K, 0, sizeof K);
+    K.nr = spec->nr; K.nt = spec->nt; K.l = spec->layers; K.c = spec->entries;
+    K.ct = hrt_codebook_tile(K.nt, K.l);
+    K.capacity = spec->metric == HRT_CS_CAPACITY;
+    K.T = spec->num_times; K.K = spec->num_freqs; K.S = spec->subband;
+    K.B = (K.K + K.S - 1u) / K.S;
+    K.n0 = K.capacity ? spec->noise : 1.f;
+    K.pts = 2ull * K.T * K.K;
+    K.subbands = (uint64_t)spec->num_rx * spec->num_tx * 2u * K.T * K.B;
+    K.flags = spec->flags;
+    K.out = d_out;                  /* (the kernel places the regions by cs_regions' rule) */
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_codebook(&K, d_H, d_codebook, stream), "codebook selection kernel");
+    return HRT_OK;
+}
+
+typedef struct {
+    hrt_codebook_spec spec;
+    const float *codebook;          /* host, complex [entries][nt][layers] */
+} cs_job_aux;
+
+/* after the last batch: H stays at d_H; the codebook goes up, selection runs once, only its result comes down */
+static int cs_job_deliver(const ch_job *j, int device, const void *d_H, void *out)
+{
+    const cs_job_aux *a = (const cs_job_aux *)j->aux;
+    const uint64_t bytes = hrt_codebook_out_bytes(&a->spec);
+    const uint64_t cb_bytes = (uint64_t)a->spec.entries * a->spec.nt * a->spec.layers * 8u;
+    void *d_cs = NULL, *d_cb = NULL;
+    int rc = hrt_device_malloc(device, &d_cs, bytes);
+    if (!rc) rc = hrt_device_malloc(device, &d_cb, cb_bytes);
+    if (!rc) rc = hrt_device_upload(device, d_cb, a->codebook, cb_bytes);
+    if (!rc) rc = hrt_codebook_select(device, &a->spec, d_H, d_cb, d_cs, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_cs, bytes);
+    if (d_cb) hrt_device_free(device, d_cb);
+    if (d_cs) hrt_device_free(device, d_cs);
+    return rc;
+}
+
+int hrt_compute_codebook_select(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                                const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                                size_t nt, double f_a, const float *codebook, uint32_t layers, uint32_t entries,
+                                uint32_t subband, uint32_t metric, uint32_t flags, float noise, void *out,
+                                hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = array_check(spec, &a))) return rc;
+    if (!out || !codebook) return hrt_fail(HRT_E_INVALID, "hrt_compute_codebook_select: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_codebook_select: num_rx or num_tx > 2^32");
+    cs_job_aux aux;
+    memset(&aux, 0, sizeof aux);
+    aux.codebook = codebook;
+    aux.spec.num_rx = (uint32_t)nrx; aux.spec.num_tx = (uint32_t)ntx;
+    aux.spec.nr = (uint32_t)nr; aux.spec.nt = (uint32_t)nt;
+    aux.spec.num_times = spec->num_times; aux.spec.num_freqs = spec->num_freqs;
+    aux.spec.layers = layers; aux.spec.entries = entries; aux.spec.subband = subband;
+    aux.spec.metric = metric; aux.spec.flags = flags; aux.spec.noise = noise;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_channel) */
+    if (nrx && ntx && (rc = cs_check(&aux.spec, "hrt_compute_codebook_select"))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.deliver = cs_job_deliver;
+    job.aux = &aux;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_codebook_select");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

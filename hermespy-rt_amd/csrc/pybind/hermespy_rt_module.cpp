@@ -655,6 +655,96 @@ py::dict compute_channel_precoder_py(
     return d;
 }
 
+// compute_codebook_select: per-subband precoder codebook selection (metric "power" or "capacity") on
+// compute_array_channel's H, formed on the device (extension; see hrt_compute_codebook_select in hermespy_rt.h): a dict of
+// views of one buffer -- index uint32, metric float32 and status uint32 (num_rx, num_tx, 2, num_times, B); table float32
+// (num_rx, num_tx, C, 2, num_times, B), None without table=True; effective complex64 (num_rx, num_tx, Nr, L, 2, num_times,
+// num_freqs), None without effective=True -- and the buffer itself (uint8).  codebook: complex64 (C, Nt, L) or (C, Nt);
+// subband None: wideband.  The selection runs once, on the H of all batches.
+py::dict compute_codebook_select_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    py::array codebook, const std::string &metric, py::object noise, py::object subband, double t0, double dt,
+    unsigned long num_times, bool los, bool scatter, py::object array_frequency, bool table, bool effective,
+    py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL || num_rx > 0xffffffffUL || num_tx > 0xffffffffUL)
+        throw std::invalid_argument("num_rx, num_tx, num_freqs and num_times must fit 32 bits");
+    if (metric != "power" && metric != "capacity") throw std::invalid_argument("metric must be 'power' or 'capacity'");
+    const array_elements a(rx_elements, tx_elements);
+    const size_t nr = a.nr, nt = a.nt;
+    if (codebook.ndim() != 2 && codebook.ndim() != 3)
+        throw std::invalid_argument("codebook must have shape (C, Nt, L) or (C, Nt)");
+    const auto cb = py::array_t<std::complex<float>, py::array::c_style | py::array::forcecast>::ensure(codebook);
+    if (!cb) throw std::invalid_argument("codebook must be a complex array");
+    const size_t C_ = (size_t)cb.shape(0), L_ = cb.ndim() == 3 ? (size_t)cb.shape(2) : 1u;
+    if ((size_t)cb.shape(1) != nt) throw std::invalid_argument("codebook must have shape (C, Nt, L) with Nt tx_elements");
+    if (C_ > 0xffffffffUL || L_ > 0xffffffffUL) throw std::invalid_argument("codebook too large");
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    const uint32_t mt = metric == "power" ? HRT_CS_POWER : HRT_CS_CAPACITY;
+    const uint32_t flags = (table ? HRT_CS_TABLE : 0u) | (effective ? HRT_CS_EFFECTIVE : 0u);
+    const float n0 = noise.is_none() ? (mt == HRT_CS_POWER ? 1.f : 0.f) : noise.cast<float>();
+    unsigned long S = num_freqs;
+    if (!subband.is_none()) {
+        const long long sv = subband.cast<long long>();
+        if (sv < 0 || sv > 0xffffffffLL) throw std::invalid_argument("subband must fit 32 bits");
+        S = (unsigned long)sv;
+    }
+    hrt_codebook_spec cs{};
+    cs.num_rx = (uint32_t)num_rx; cs.num_tx = (uint32_t)num_tx; cs.nr = (uint32_t)nr; cs.nt = (uint32_t)nt;
+    cs.num_times = (uint32_t)num_times; cs.num_freqs = (uint32_t)num_freqs; cs.layers = (uint32_t)L_;
+    cs.entries = (uint32_t)C_; cs.subband = (uint32_t)S; cs.metric = mt; cs.flags = flags; cs.noise = n0;
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t pts = (size_t)num_rx * num_tx * 2u * num_times * num_freqs;
+    const size_t B_ = S ? (num_freqs + S - 1u) / S : 0u;
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs) && nr <= 16u && nt <= 64u && L_ >= 1u && L_ <= 4u
+                      && C_ >= 1u && C_ <= 4096u && S >= 1u && S <= num_freqs && pts < (1ull << 31)
+                      && (unsigned long long)num_rx * num_tx * 2u * num_times * B_ * C_ < (1ull << 31);
+    py::array_t<uint8_t> buf(fits ? (size_t)hrt_codebook_out_bytes(&cs) : (size_t)1);
+    uint8_t *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_codebook_select", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_codebook_select(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                           num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa,
+                                           reinterpret_cast<const float *>(cb.data()), cs.layers, cs.entries, cs.subband,
+                                           mt, flags, n0, dst, nullptr);
+    });
+    size_t off = 0;
+    auto view = [&](auto zero, std::vector<size_t> shape) {
+        using T = decltype(zero);
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(T);
+        size_t count = 1;
+        for (size_t i = shape.size(); i-- > 0;) {
+            strides[i] = st;
+            st *= (py::ssize_t)shape[i];
+            count *= shape[i];
+        }
+        py::array_t<T> v(shape, strides, reinterpret_cast<T *>(dst + off), buf);
+        off += count * sizeof(T);
+        return v;
+    };
+    const size_t R = num_rx, X = num_tx, T_ = num_times, K_ = num_freqs;
+    py::dict d;
+    d["index"] = view((uint32_t)0, {R, X, 2, T_, B_});
+    d["metric"] = view(0.0f, {R, X, 2, T_, B_});
+    d["status"] = view((uint32_t)0, {R, X, 2, T_, B_});
+    if (table) d["table"] = view(0.0f, {R, X, C_, 2, T_, B_});
+    else d["table"] = py::none();
+    if (effective) d["effective"] = view(std::complex<float>(), {R, X, nr, L_, 2, T_, K_});
+    else d["effective"] = py::none();
+    d["buffer"] = buf;
+    return d;
+}
+
 // a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
 using carr = py::array_t<std::complex<float>, py::array::c_style>;
 carr as_weights(const py::array &w, size_t n_elements, const char *name)
@@ -1335,6 +1425,18 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("normalize") = "total", py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1,
           py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(),
           py::arg("weights") = true, py::arg("patterns") = py::none());
+    m.def("compute_codebook_select", &compute_codebook_select_py,
+          "Per-subband precoder codebook selection (metric 'power' or 'capacity') on the antenna-array channel, formed "
+          "on the device: a dict of views of one buffer -- index, metric, status (num_rx, num_tx, 2, num_times, B), "
+          "table (num_rx, num_tx, C, 2, num_times, B), effective (num_rx, num_tx, Nr, L, 2, num_times, num_freqs), buffer",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("codebook"), py::arg("metric") = "capacity", py::arg("noise") = py::none(),
+          py::arg("subband") = py::none(), py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1,
+          py::arg("los") = true, py::arg("scatter") = true, py::arg("array_frequency") = py::none(),
+          py::arg("table") = false, py::arg("effective") = false, py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "

@@ -902,6 +902,81 @@ class Tracer:
                                array_frequency)
         return self.precoder(H, noise, kind, power, regularization, normalize, weights)
 
+    def codebook_select(self, H, codebook, metric="capacity", noise=None, subband=None, table=False, effective=False,
+                        out=None):
+        """Per-subband precoder codebook selection (the PMI search of limited feedback) on an array channel, on the
+        device (hrt_codebook_select; include/hermespy_rt.h hrt_compute_codebook_select).  Every entry W_c of
+        `codebook` (complex64 [C, Nt, L], used as given) is scored against the matrices H[rx, tx, :, :, pol, m, k] of a
+        subband of `subband` = S consecutive frequencies (None: wideband, S = K; the last subband holds the
+        remainder): with E = H_k W_c, metric "power" is the mean of |E|_F^2 over the subband, "capacity" the mean of
+        log2 det(I + E^H E / noise).  With B = ceil(K / S):
+
+            index      int32     [nrx, ntx, 2, T, B]          argmax_c, the lowest on a tie (-1: flagged)
+            metric     float32   [nrx, ntx, 2, T, B]          its score
+            status     int32     [nrx, ntx, 2, T, B]          0, abi.CS_NONFINITE
+            table      float32   [nrx, ntx, C, 2, T, B]       every score                      (None without table=True)
+            effective  complex64 [nrx, ntx, Nr, L, 2, T, K]   H_k W_c* as it was scored        (None without effective=True)
+
+        `effective` has array_channel()'s layout with Nt = L: equalizer(), svd() and precoder() take it as it is.
+        H: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, T, K] (array_channel(), or any tensor of that layout; no
+        trace is needed); Nr <= 16, Nt <= 64, L <= min(4, Nt), C <= 4096.  `codebook`: a device tensor or anything
+        numpy converts (copied to the device then); hermespy_rt_amd.codebook builds DFT and dual-polarised ones.
+        `noise`: one finite float > 0, needed under "capacity".  A subband with a non-finite entry of H or a
+        non-finite score writes index -1, metric 0 and zeros.  Selection is not additive: a sharded caller sums H over
+        the shards first.  Returns a dict of views of one flat uint8 device tensor, itself under "buffer", enqueued
+        on the current stream; `out` (such a flat tensor) is written in place.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        if hasattr(codebook, "is_cuda"):
+            W = codebook
+            if W.dim() == 2:
+                W = W.unsqueeze(2)
+            if not (W.is_cuda and W.device == self.device and W.dtype == torch.complex64 and W.dim() == 3):
+                raise ValueError("codebook must be a complex64 tensor [C, Nt, L] on %s" % (self.device,))
+        else:
+            W = torch.from_numpy(abi.codebook_array(codebook)).to(self.device)
+        if int(W.shape[1]) != nt:
+            raise ValueError("codebook [C, %d, L] expected, got %s" % (nt, tuple(W.shape)))
+        entries, layers = int(W.shape[0]), int(W.shape[2])
+        spec = abi.codebook_spec(nrx, ntx, nr, nt, T, K, layers, entries, metric, noise, subband, table, effective)
+        H, W = H.contiguous(), W.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and abi.codebook_fits(spec)
+        need = abi.codebook_regions(spec)[5] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_codebook_select(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                        C.c_void_p(W.data_ptr() if W.numel() else None), C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_codebook_select: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_codebook_select")
+        H.record_stream(stream)     # (the kernel reads them after this call returns)
+        W.record_stream(stream)
+        return abi.codebook_views(out, spec)
+
+    def channel_codebook_select(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1,
+                                los=True, scatter=True, array_frequency=None, codebook=None, metric="capacity",
+                                noise=None, subband=None, table=False, effective=False):
+        """The codebook selection on the last trace's array channel, without leaving the device: bit for bit
+        codebook_select(array_channel(...), codebook, metric, noise, subband, table, effective) with
+        array_channel()'s arguments.  On a sharded trace this is the selection on the shard's partial channel, which
+        is not the channel's: sum array_channel() over the shards and call codebook_select()."""
+        if codebook is None:
+            raise ValueError("channel_codebook_select needs a codebook")
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.codebook_select(H, codebook, metric, noise, subband, table, effective)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

@@ -42,6 +42,7 @@ EXPORTED = (
     "hrt_svd_out_bytes", "hrt_channel_svd", "hrt_compute_channel_svd",
     "hrt_equalizer_out_bytes", "hrt_channel_equalizer", "hrt_compute_channel_equalizer",
     "hrt_precoder_out_bytes", "hrt_channel_precoder", "hrt_compute_channel_precoder",
+    "hrt_codebook_out_bytes", "hrt_codebook_select", "hrt_compute_codebook_select",
     "hrt_sparse_paths_bytes", "hrt_sparse_out_bytes", "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel",
     "hrt_sparse_taps_out_bytes", "hrt_sparse_array_taps", "hrt_compute_sparse_array_taps",
     "hrt_sparse_beam_out_bytes", "hrt_sparse_beam_channel", "hrt_compute_sparse_beam_channel",
@@ -399,6 +400,17 @@ def load():
                                                C.c_size_t, C.c_double, u32, u32, u32, C.c_float, C.c_float,
                                                C.c_float, vp, C.POINTER(Stats)]
     L.hrt_compute_channel_precoder.restype = C.c_int
+    # per-subband codebook selection on an array channel (hrt_codebook_spec: abi.CodebookSpec)
+    csp = C.POINTER(abi.CodebookSpec)
+    L.hrt_codebook_out_bytes.argtypes = [csp]
+    L.hrt_codebook_out_bytes.restype = u64
+    L.hrt_codebook_select.argtypes = [C.c_int, csp, vp, vp, vp, vp]
+    L.hrt_codebook_select.restype = C.c_int
+    L.hrt_compute_codebook_select.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                              C.c_size_t, C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3,
+                                              C.c_size_t, C.c_double, f32p, u32, u32, u32, u32, u32, C.c_float, vp,
+                                              C.POINTER(Stats)]
+    L.hrt_compute_codebook_select.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

@@ -524,6 +524,72 @@ int hrt_compute_channel_precoder(Scene *scene, const Vec3 *rx_pos, const Vec3 *t
                                  uint32_t flags, float noise, float power, float regularization,
                                  void *out /* host, hrt_precoder_out_bytes bytes, layout above */, hrt_stats *stats);
 
+/* Per-subband precoder codebook selection (limited feedback: the PMI search) on the array channel, formed on the device
+ * (include/hrt_device.h: hrt_codebook_select).  A point is one (rx, tx, pol, time m, frequency k) of a tensor of
+ * hrt_compute_array_channel's layout, H = H[rx][tx][:][:][pol][m][k], Nr x Nt.  A subband is `subband` = S consecutive
+ * frequencies of one (rx, tx, pol, m); there are B = ceil(K / S) of them, the last holds the remainder, S = K is
+ * wideband selection.  The codebook is complex [C][Nt][L], used as given (its power normalisation is the caller's).
+ * For entry c at frequency k, E_c,k = H_k W_c is Nr x L, and with n the number of frequencies of the subband
+ *   HRT_CS_POWER     mu_c = (1/n) sum_k |E_c,k|_F^2
+ *   HRT_CS_CAPACITY  mu_c = (1/n) sum_k log2 det(I_L + E_c,k^H E_c,k / N0), `noise` N0 finite and > 0 (not read
+ *                    under HRT_CS_POWER)
+ * the sums over k ascending, and c* = argmax_c mu_c, the lowest index on a tie.
+ * The outputs lie in one flat buffer of hrt_codebook_out_bytes bytes, the point axes innermost, in this order:
+ *   index      uint32  [num_rx][num_tx][2][T][B]          c*
+ *   metric     float   [num_rx][num_tx][2][T][B]          mu_c*
+ *   status     uint32  [num_rx][num_tx][2][T][B]          0 or HRT_CS_NONFINITE
+ *   table      float   [num_rx][num_tx][C][2][T][B]       every mu_c                                  (HRT_CS_TABLE)
+ *   effective  complex [num_rx][num_tx][Nr][L][2][T][K]   E_c*,k: array_channel's layout with nt = L  (HRT_CS_EFFECTIVE)
+ * `effective` holds the bits of the E that was scored, not a second evaluation in another order, and is taken as it is
+ * by hrt_channel_equalizer, hrt_channel_svd and hrt_channel_precoder.
+ * 1 <= Nr <= 16, 1 <= Nt <= 64, 1 <= L <= min(4, Nt), 1 <= C <= 4096, 1 <= S <= K, fewer than 2^31 points and fewer
+ * than 2^31 table entries (num_rx num_tx C 2 T B).
+ * Algorithm (a definition: the tests emulate it).  All float, no contraction.  Row i, layer l of E over t ascending
+ * from zero, h = H[i][t], w = W[t][l]:  er = er + (hr wr - hi wi), ei = ei + (hr wi + hi wr).  Over the rows i
+ * ascending, from zero: gd[a] = gd[a] + (er_a er_a + ei_a ei_a) and, for b < a (G = E^H E, lower triangle),
+ * gr[a][b] = gr[a][b] + (er_a er_b + ei_a ei_b), gi[a][b] = gi[a][b] + (er_a ei_b - ei_a er_b).  POWER: the value of
+ * a frequency is ((gd[0] + gd[1]) + gd[2]) + gd[3].  CAPACITY: A[a][a] = 1 + gd[a] / N0, A[a][b] = (gr / N0, gi / N0),
+ * then the unpivoted LDL^H for j ascending: for m < j, v = A[j][m] less, for p < m ascending,
+ * ((l_jp.r l_mp.r + l_jp.i l_mp.i) d_p, (l_jp.i l_mp.r - l_jp.r l_mp.i) d_p), and l_jm = (v.r / d_m, v.i / d_m);
+ * d_j = A[j][j] less (l_jm.r l_jm.r + l_jm.i l_jm.i) d_m for m < j ascending; the determinant is ((d_0 d_1) d_2) d_3,
+ * for L = 1 it is 1 + |E|^2 / N0, and the value is its log2 as csrc/hrt_codebook.h restates it in float operations
+ * (exponent by the bits, a fixed polynomial on the mantissa; not the hardware's approximate instruction).  mu_c is the
+ * sum of the values over k ascending, divided by (float)n.
+ * A subband that holds a non-finite entry of H, or whose mu_c is not finite for some c (a square beyond float), is
+ * HRT_CS_NONFINITE: index 0xFFFFFFFF, metric 0, zeros in its table row and in `effective` at all its frequencies.
+ * H = 0 is regular: every mu_c ties and index 0 wins.  A subband's bytes depend on its own matrices and the codebook
+ * only (not on neighbours, the tiling of the codebook or the launch); two calls give the same bytes; every output byte
+ * is written exactly once.
+ * hrt_compute_codebook_select traces and batches exactly as hrt_compute_array_channel does, keeps the accumulated H on
+ * the device and selects once after the last batch: selection is NOT additive over batches or shards.  The codebook
+ * is copied in, only the result is copied back.  HRT_E_INVALID, before the device is touched: every refusal of
+ * hrt_compute_array_channel; a NULL codebook or out; every refusal of hrt_codebook_select (include/hrt_device.h). */
+#define HRT_CS_POWER 0u
+#define HRT_CS_CAPACITY 1u
+#define HRT_CS_TABLE 1u
+#define HRT_CS_EFFECTIVE 2u
+#define HRT_CS_NONFINITE 1u
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t layers;                            /* L: columns of an entry, 1 .. min(4, Nt) */
+    uint32_t entries;                           /* C: 1 .. 4096 */
+    uint32_t subband;                           /* S: 1 .. K */
+    uint32_t metric;                            /* HRT_CS_POWER or HRT_CS_CAPACITY */
+    uint32_t flags;                             /* HRT_CS_TABLE | HRT_CS_EFFECTIVE */
+    float noise;                                /* N0, finite and > 0 (HRT_CS_CAPACITY; not read otherwise) */
+} hrt_codebook_spec;
+uint64_t hrt_codebook_out_bytes(const hrt_codebook_spec *spec);   /* 0 for NULL */
+int hrt_compute_codebook_select(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                                const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                                size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                                const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                                size_t num_tx_elements, double array_frequency_hz,
+                                const float *codebook /* host, complex [entries][Nt][layers] */, uint32_t layers,
+                                uint32_t entries, uint32_t subband, uint32_t metric, uint32_t flags, float noise,
+                                void *out /* host, hrt_codebook_out_bytes bytes, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

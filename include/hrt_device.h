@@ -443,6 +443,21 @@ int hrt_channel_equalizer(int device, const hrt_equalizer_spec *spec, const void
  * nr * nt * num_times * num_freqs > 2^24; 2^31 points or more. */
 int hrt_channel_precoder(int device, const hrt_precoder_spec *spec, const void *d_H, void *d_out, void *stream);
 
+/* ---- per-subband precoder codebook selection on an array channel (csrc/host/channel.c, csrc/hrt_codebook.hip) ----
+ * index, metric, status, table and effective as hermespy_rt.h defines them (hrt_codebook_spec,
+ * hrt_compute_codebook_select), hrt_codebook_out_bytes bytes at d_out, from d_H (complex
+ * [num_rx][num_tx][nr][nt][2][num_times][num_freqs]: the output of hrt_array_channel, or any tensor of that layout) and
+ * d_codebook (complex [entries][nt][layers]), all DEVICE pointers, asynchronous on `stream` of `device`.  It needs no
+ * problem: it reads only the two tensors, and writes neither.  Every byte of d_out is written exactly once; no scratch
+ * and no atomics, so two calls with the same input give the same bytes.  The selection of one shard's partial H is not
+ * the channel's: a sharded caller sums H first.  HRT_E_INVALID, before the device is touched: a NULL pointer; num_rx,
+ * num_tx, num_times or num_freqs equal to 0; nr outside 1..16; nt outside 1..64; layers outside 1..min(4, nt); entries
+ * outside 1..4096; subband outside 1..num_freqs; a metric other than HRT_CS_POWER and HRT_CS_CAPACITY; `flags` with
+ * bits other than HRT_CS_TABLE and HRT_CS_EFFECTIVE; under HRT_CS_CAPACITY a noise that is not finite and > 0; 2^31
+ * points or more; 2^31 table entries (num_rx num_tx entries 2 num_times B) or more. */
+int hrt_codebook_select(int device, const hrt_codebook_spec *spec, const void *d_H, const void *d_codebook, void *d_out,
+                        void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
