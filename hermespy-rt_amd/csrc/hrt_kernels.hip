@@ -2131,20 +2131,28 @@ __device__ __forceinline__ F3 shadow_dir(F3 o, F3 rx, float &d2rx)
 #define HRT_TRACE_WAVES_FINE 8   /* the fine walk is bound by dependent loads: 8 waves per SIMD (64 registers, some scratch) beat
                                   * the 5 it takes unconstrained (95 registers): city 100 k 19.4 -> 18.4 ms, room 24 k 10.0 -> 9.4 */
 #endif
-template <bool TRI_IN_LDS, int VARIANT>
-__global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VARIANT == 9 ? HRT_TRACE_WAVES_FINE : HRT_TRACE_WAVES_PER_SIMD))) void hrt_trace_kernel(
+#ifndef HRT_TRACE_WAVES_PATCH
+#define HRT_TRACE_WAVES_PATCH 7   /* PATCH: 62 VGPRs, nothing spilled, so 8 waves a SIMD run; asked for 8 the allocator keeps 63 and spills 3 SGPRs */
+#endif
+// PATCH (with <true, 2> only): the primary rays of a later launch of a patch-table problem and nothing else (the plan's
+// trace_patch) -- never launch 0, no shadow units (hrt_records_kernel's), no per-cell masks -- on an image of what that
+// path reads: [T x 5 float4 rows][4 waves x 16 u64 masks][4 u32] (lds_trace_patch), an eighth of a CU up to 249 rows.
+// (The reference-order words in that image too, so that the walk's last stage reads LDS: measured, nothing; HISTORY.)
+template <bool TRI_IN_LDS, int VARIANT, bool PATCH = false>
+__global__ __launch_bounds__(HRT_BLOCK, (PATCH ? HRT_TRACE_WAVES_PATCH : (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VARIANT == 9 ? HRT_TRACE_WAVES_FINE : HRT_TRACE_WAVES_PER_SIMD)))) void hrt_trace_kernel(
     const hrt_kparams P, const uint32_t b)
 {
+    static_assert(!PATCH || (TRI_IN_LDS && VARIANT == 2), "PATCH: the staged flat one-block walk");
     extern __shared__ float4 lds[];
     const uint32_t tid = threadIdx.x;
-    const bool first = (b == 0);
+    const bool first = PATCH ? false : (b == 0);
     const uint32_t *counts = reinterpret_cast<const uint32_t *>(P.ws + P.off_counts);
     if (counts[P.num_bounces + 1] & kErrVoid) return;   // a fused launch of this trace timed out: the host redoes the step
     const uint32_t n_in = first ? P.n0 : counts[b];
     const uint32_t n_chunks = (n_in + HRT_BLOCK - 1) / HRT_BLOCK;
     // unit types of this launch: the shadow rays (b >= 1), one type per RX (k = rx) -- with patch tables
     // they are hrt_records_kernel's, not this kernel's -- and the primary rays (b < num_bounces; k = num_rx)
-    const bool psa = VARIANT == 2 && P.patch.mask != nullptr && !first;   // (shadow rays: hrt_records_kernel's)
+    const bool psa = PATCH || (VARIANT == 2 && P.patch.mask != nullptr && !first);   // (shadow rays: hrt_records_kernel's)
     const uint32_t sh_units = (first || psa) ? 0u : P.num_rx;
     const uint32_t kinds = sh_units + ((b < P.num_bounces) ? 1u : 0u);
     // (static deal: chunks padded to a multiple of 8, see the XCD-aware numbering below)
@@ -2162,19 +2170,26 @@ __global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VA
     // LDS image (hrt_launch_plan.h sizes it: lds_trace): [T x 5 float4 rows | T float2 guard pairs, padded to
     // 16 B | 2 float4 per leaf] (only if staged) [num_rx RX pos][4 waves x 16 u64 masks]
     // [4 waves x 16 float4 leaf constants][4 u32]
+    // (PATCH: no guard pairs, leaf records, RX positions or per-wave scratch -- null, nothing of its path reads them)
     float4 *l_tri = lds;
-    float2 *l_tg = reinterpret_cast<float2 *>(lds + HRT_ROW * T);
-    float4 *l_leaf = lds + HRT_ROW * T + (T + 1u) / 2u;
-    float4 *l_rx = TRI_IN_LDS ? l_leaf + 2u * n_leaf : lds;
-    unsigned long long *l_mask = reinterpret_cast<unsigned long long *>(l_rx + P.num_rx) +
+    float2 *l_tg = PATCH ? nullptr : reinterpret_cast<float2 *>(lds + HRT_ROW * T);
+    float4 *l_leaf = PATCH ? nullptr : lds + HRT_ROW * T + (T + 1u) / 2u;
+    float4 *l_rx = PATCH ? nullptr : (TRI_IN_LDS ? l_leaf + 2u * n_leaf : lds);
+    // (PATCH: the mask words follow the rows, the counters the mask words)
+    unsigned long long *l_mask = reinterpret_cast<unsigned long long *>(PATCH ? lds + HRT_ROW * T : l_rx + P.num_rx) +
                                  (tid >> 6) * kMaskRounds;
     // (per wave 2 * kMaskRounds float4 = 128 words of scratch: leaf constants / the tree walks' stacks and queues)
-    float4 *l_wleaf = reinterpret_cast<float4 *>(reinterpret_cast<unsigned long long *>(l_rx + P.num_rx) +
+    float4 *l_wleaf = PATCH ? nullptr : reinterpret_cast<float4 *>(reinterpret_cast<unsigned long long *>(l_rx + P.num_rx) +
                                                  (HRT_BLOCK / 64u) * kMaskRounds) + (tid >> 6) * wave_scratch4(VARIANT == 9);
-    uint32_t *l_wcnt = reinterpret_cast<uint32_t *>(
+    uint32_t *l_wcnt = PATCH ? reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned long long *>(lds + HRT_ROW * T) +
+                                                            (HRT_BLOCK / 64u) * kMaskRounds) : reinterpret_cast<uint32_t *>(
         reinterpret_cast<float4 *>(reinterpret_cast<unsigned long long *>(l_rx + P.num_rx) +
                                    (HRT_BLOCK / 64u) * kMaskRounds) + (HRT_BLOCK / 64u) * wave_scratch4(VARIANT == 9));
-    {   // the tables: one flight (stage_load), guard pairs and leaf records only for the tree variants, which read them
+    if constexpr (PATCH) {   // the rows alone
+        float4 s_tri[kStageTri];
+        copy16_request(s_tri, g_tri, HRT_ROW * T, tid);
+        copy16_commit(s_tri, l_tri, g_tri, HRT_ROW * T, tid);
+    } else {   // the tables: one flight (stage_load), guard pairs and leaf records only for the tree variants, which read them
         constexpr bool kTree = TRI_IN_LDS && VARIANT >= 4;
         const uint32_t n_tri4 = TRI_IN_LDS ? HRT_ROW * T : 0u;
         const uint32_t n_tg = kTree ? T : 0u, n_leaf4 = kTree ? 2u * n_leaf : 0u;
@@ -2274,7 +2289,7 @@ __global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VA
             apex_k = P.num_rx + tx;
         }
         // (tables of <= 64 triangles: apex-bound traces go through the per-cell candidate masks)
-        const bool masked = VARIANT == 2 && P.rxt.cell_mask != nullptr && (shadow || first);
+        const bool masked = !PATCH && VARIANT == 2 && P.rxt.cell_mask != nullptr && (shadow || first);
         Ball ball = {{0.f, 0.f, 0.f}, 0.f, false};
         if constexpr (VARIANT >= 2 && VARIANT != 6)
             if (!masked && (VARIANT != 2 || shadow || first)) ball = origin_ball(o, valid);
@@ -2334,7 +2349,7 @@ __global__ __launch_bounds__(HRT_BLOCK, (VARIANT == 2 ? HRT_TRACE_WAVES_V2 : (VA
                              : closest_hit<VARIANT>(tri, tg, leaf, P.acc, P.rxt, apex_k, P.acc.orig, T, o, d, valid, lane,
                                                     ball, shadow, apex, l_mask, l_wleaf, shadow ? 2 : (first ? 0 : 1), wq);
 #ifdef HRT_UNIT_CLOCKS
-        if (lane == 0) {
+        if (!PATCH && lane == 0) {   // (the walk's statistics live in the per-wave scratch, which PATCH does not have)
             const unsigned long long dt = wall_clock64() - t_w0;
             // (no counter: half a million same-address atomics per step would be the measurement)
             const unsigned int slot = (b * 600011u + unit * 4u + (tid >> 6)) & ((1u << 21) - 1u);
@@ -4667,16 +4682,32 @@ __global__ __launch_bounds__(256) void hrt_debug_candidates_kernel(const float *
     for (int k = 0; k < 8; ++k) y[2 + k] = w[k];
 }
 
-template <bool LDS, int V>
+// (make EXTRA=-DHRT_PHASE_STATS, with HRT_PHASE_FILE set: how many workgroups of a kernel a CU holds at its real image)
+template <typename F>
+static void phase_occupancy([[maybe_unused]] F fn, [[maybe_unused]] const char *what, [[maybe_unused]] const char *which,
+                            [[maybe_unused]] size_t lds)
+{
+#ifdef HRT_PHASE_STATS
+    if (getenv("HRT_PHASE_FILE")) {
+        int per_cu = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, HRT_BLOCK, lds);
+        fprintf(stderr, "%s, %s instantiation: %zu B of LDS, %d workgroups per CU\n", what, which, lds, per_cu);
+    }
+#endif
+}
+
+template <bool LDS, int V, bool PATCH = false>
 static void launch_trace_t(const hrt_kparams *P, uint32_t bounce, uint32_t blocks, size_t lds,
                            hipStream_t st, hipError_t *err)
 {
     if (lds > 64u * 1024u) {
-        *err = hipFuncSetAttribute(reinterpret_cast<const void *>(&hrt_trace_kernel<LDS, V>),
+        *err = hipFuncSetAttribute(reinterpret_cast<const void *>(&hrt_trace_kernel<LDS, V, PATCH>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (*err != hipSuccess) return;
     }
-    hipLaunchKernelGGL((hrt_trace_kernel<LDS, V>), dim3(blocks), dim3(HRT_BLOCK), lds, st, *P,
+    if (LDS && V == 2 && bounce >= 2u)
+        phase_occupancy(hrt_trace_kernel<LDS, V, PATCH>, "primary rays of a later launch", PATCH ? "patch tables" : "shared", lds);
+    hipLaunchKernelGGL((hrt_trace_kernel<LDS, V, PATCH>), dim3(blocks), dim3(HRT_BLOCK), lds, st, *P,
                        bounce);
 }
 
@@ -4687,18 +4718,6 @@ static void launch_trace_t(const hrt_kparams *P, uint32_t bounce, uint32_t block
 #ifndef HRT_FUSED_KB
 #define HRT_FUSED_KB 2   /* ... at later launches (15 words of state per entry stay in registers) */
 #endif
-// (make EXTRA=-DHRT_PHASE_STATS, with HRT_PHASE_FILE set: how many workgroups of launch 0 a CU holds at its real image)
-template <typename F>
-static void phase_occupancy([[maybe_unused]] F fn, [[maybe_unused]] const char *which, [[maybe_unused]] size_t lds)
-{
-#ifdef HRT_PHASE_STATS
-    if (getenv("HRT_PHASE_FILE")) {
-        int per_cu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, HRT_BLOCK, lds);
-        fprintf(stderr, "launch 0, %s instantiation: %zu B of LDS, %d workgroups per CU\n", which, lds, per_cu);
-    }
-#endif
-}
 template <bool LDS, int V>
 static void launch_fused_t(const hrt_kparams *P, uint32_t bounce, size_t lds, bool txcell, hipStream_t st, hipError_t *err)
 {
@@ -4715,12 +4734,12 @@ static void launch_fused_t(const hrt_kparams *P, uint32_t bounce, size_t lds, bo
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                     if (*err != hipSuccess) return;
                 }
-                phase_occupancy(hrt_fused_kernel<true, 2, true, K, true>, "patch tables", lds);
+                phase_occupancy(hrt_fused_kernel<true, 2, true, K, true>, "launch 0", "patch tables", lds);
                 hipLaunchKernelGGL((hrt_fused_kernel<true, 2, true, K, true>), dim3(blocks), dim3(HRT_BLOCK), lds, st, *P, bounce);
                 return;
             }
         }
-        phase_occupancy(hrt_fused_kernel<LDS, V, true, K>, "shared", lds);
+        phase_occupancy(hrt_fused_kernel<LDS, V, true, K>, "launch 0", "shared", lds);
         if (lds > 64u * 1024u) {
             *err = hipFuncSetAttribute(reinterpret_cast<const void *>(&hrt_fused_kernel<LDS, V, true, K>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -4964,6 +4983,11 @@ int hrt_hip_launch_trace(const hrt_kparams *P_in, uint32_t bounce, void *stream)
         if (blocks > max_grid) blocks = max_grid;
         if (hrt_plan_image(&pl, bounce)) {
             hipLaunchKernelGGL(hrt_image_kernel, dim3((uint32_t)blocks), dim3(HRT_BLOCK), (size_t)pl.lds_image, st, *P, bounce);
+            return (int)hipGetLastError();
+        }
+        if (hrt_plan_trace_patch(&pl, bounce)) {   // its own instantiation on an image of what the primary rays read
+            launch_trace_t<true, 2, true>(P, bounce, (uint32_t)blocks, (size_t)pl.lds_trace_patch, st, &err);
+            if (err != hipSuccess) return (int)err;
             return (int)hipGetLastError();
         }
     }

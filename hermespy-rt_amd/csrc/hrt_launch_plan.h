@@ -28,6 +28,9 @@
 #define HRT_LDS_CU (160u * 1024u)
 #define HRT_FUSED0_PER_CU 7u
 #define HRT_LDS_FUSED0_MAX (HRT_LDS_CU / HRT_FUSED0_PER_CU)
+/* the primary rays of launches >= 2 on patch tables (hrt_trace_kernel<true, 2, PATCH>): eight workgroups per CU */
+#define HRT_TRACE_PATCH_PER_CU 8u
+#define HRT_LDS_TRACE_PATCH_MAX (HRT_LDS_CU / HRT_TRACE_PATCH_PER_CU)
 
 typedef struct {
     /* table facts */
@@ -65,6 +68,10 @@ typedef struct {
     uint64_t t_tx0;         /* min(num_tx, HRT_LDS_TX) TX positions */
     uint64_t t_words0;      /* one of the two word tables: a word per row, padded to 16 B; 0 if they are out */
     uint64_t lds_fused0;    /* rows + tail + t_mat0 + t_tx0 + 2 t_words0 */
+    /* the primary rays of launches >= 2 of a records-kernel problem (hrt_plan_trace_patch): hrt_trace_kernel's own
+     * instantiation with an image of what that path reads, lds_trace_patch; else both 0 */
+    uint8_t trace_patch;
+    uint64_t lds_trace_patch;   /* rows + t_masks + tail: an eighth of a CU holds it up to 249 rows */
 } hrt_launch_plan;
 
 static inline hrt_launch_plan hrt_plan(const hrt_kparams *P)
@@ -118,6 +125,8 @@ static inline hrt_launch_plan hrt_plan(const hrt_kparams *P)
         pl.t_words0 = pl.fused0_words ? words : 0u;
         pl.lds_fused0 += 2u * pl.t_words0;
     }
+    pl.trace_patch = pl.own_records && pl.trace_v == 2;   /* (own_records: a staged table, the flat one-block walk) */
+    if (pl.trace_patch) pl.lds_trace_patch = pl.t_rows + pl.t_masks + HRT_LDS_TAIL_TRACE;
     return pl;
 }
 
@@ -125,6 +134,9 @@ static inline hrt_launch_plan hrt_plan(const hrt_kparams *P)
 static inline int hrt_plan_own_records(const hrt_launch_plan *pl, uint32_t b) { return b != 0u && pl->own_records; }
 /* launch b: the primary rays are hrt_image_kernel's (launch 1 of a records-kernel problem with image tables) */
 static inline int hrt_plan_image(const hrt_launch_plan *pl, uint32_t b) { return b == 1u && pl->image; }
+/* launch b: the primary rays are hrt_trace_kernel<true, 2, PATCH>'s (launches >= 2 of a records-kernel problem; launch 1
+ * is the image kernel's, or without image tables the shared instantiation's, as launch 0 is when it does not fuse) */
+static inline int hrt_plan_trace_patch(const hrt_launch_plan *pl, uint32_t b) { return b >= 2u && pl->trace_patch; }
 /* launch b can run as one fused kernel: launch 0 unless the fine leaves are walked, later launches on a staged
  * table with a one-block walk */
 static inline int hrt_plan_fuses(const hrt_launch_plan *pl, uint32_t b)

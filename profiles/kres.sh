@@ -16,7 +16,7 @@ for l in sys.stdin:
         n=t.split(':',1)[1].strip()
         n=re.sub(r'_ZN12_GLOBAL__N_1\d+','',n)
         cur=n[:40].ljust(42)
-    elif any(t.startswith(k) for k in ('VGPRs:','SGPRs:','TotalSGPRs','ScratchSize','Occupancy','LDS Size')):
+    elif any(t.startswith(k) for k in ('VGPRs:','SGPRs:','TotalSGPRs','ScratchSize','Occupancy','SGPRs Spill','VGPRs Spill','LDS Size')):
         cur+=' '+t.replace(' [bytes/lane]','').replace(' [waves/SIMD]','').replace(' [bytes/block]','')
 if cur: print(cur)
 "
