@@ -954,6 +954,115 @@ def run_compute_codebook_select(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel,
     return codebook_views(out, cs)
 
 
+DT_LLR = 1                             # hrt_detect_spec.flags
+DT_NONFINITE = 1                       # a point's `status`
+DT_NO_INDEX = 0xFFFFFFFF               # a flagged point's `index`
+DT_MAX_NR, DT_MAX_B, DT_MAX_BITS = 64, 8, 12
+
+
+class DetectSpec(C.Structure):
+    """include/hermespy_rt.h hrt_detect_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("bits", C.c_uint32), ("flags", C.c_uint32),
+                ("noise", C.c_float)]
+
+
+def detect_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, bits, noise, llr=True, flags=None):
+    if flags is None:
+        flags = DT_LLR if llr else 0
+    return DetectSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs), int(bits),
+                      int(flags), float(noise))
+
+
+def detect_regions(spec):
+    """the byte offsets of index, metric, status, llr and the end of a detection output (hrt_detect_out_bytes is the
+    last)"""
+    pts = int(spec.num_rx) * int(spec.num_tx) * 2 * int(spec.num_times) * int(spec.num_freqs)
+    o3 = 3 * pts * 4
+    return 0, pts * 4, 2 * pts * 4, o3, o3 + (pts * int(spec.nt) * int(spec.bits) * 4 if int(spec.flags) & DT_LLR else 0)
+
+
+def detect_views(buf, spec):
+    """the regions of a flat uint8 detection buffer (numpy array or torch tensor) as views: index [nrx, ntx, 2, T, K]
+    (uint32 in numpy, int32 in torch: a flagged point reads -1 there), metric float32 and status of that shape, llr
+    float32 [nrx, ntx, Nt, B, 2, T, K] (None where not asked for), buffer"""
+    o = detect_regions(spec)
+    nrx, ntx, T, K = int(spec.num_rx), int(spec.num_tx), int(spec.num_times), int(spec.num_freqs)
+    if isinstance(buf, np.ndarray):
+        f32, u32 = np.float32, np.uint32
+    else:
+        import torch
+        f32, u32 = torch.float32, torch.int32
+    out = {"index": buf[o[0]:o[1]].view(u32).reshape(nrx, ntx, 2, T, K),
+           "metric": buf[o[1]:o[2]].view(f32).reshape(nrx, ntx, 2, T, K),
+           "status": buf[o[2]:o[3]].view(u32).reshape(nrx, ntx, 2, T, K), "llr": None, "buffer": buf}
+    if int(spec.flags) & DT_LLR:
+        out["llr"] = buf[o[3]:o[4]].view(f32).reshape(nrx, ntx, int(spec.nt), int(spec.bits), 2, T, K)
+    return out
+
+
+def detect_fits(spec):
+    """whether the library accepts the spec (its limits, mirrored: an output beyond them is not allocated)"""
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    nr, nt, b = int(spec.nr), int(spec.nt), int(spec.bits)
+    return (0 < nr <= DT_MAX_NR and 0 < b <= DT_MAX_B and 0 < nt and nt * b <= DT_MAX_BITS
+            and 0 < nr * nt * grid <= 1 << 24 and 0 < int(spec.num_rx) * int(spec.num_tx) * 2 * grid < 1 << 31
+            and not int(spec.flags) & ~DT_LLR and _pc_positive(spec.noise))
+
+
+def constellation_array(constellation):
+    """a constellation as a contiguous complex64 [M] numpy array and its B (M = 2^B; -1 where M is no power of two)"""
+    a = np.asarray(constellation)
+    if a.dtype.kind not in "fc":
+        raise ValueError("constellation must be a real or complex floating-point array, got %s" % (a.dtype,))
+    a = np.ascontiguousarray(a, np.complex64)
+    if a.ndim != 1:
+        raise ValueError("constellation must have shape (M,), got %s" % (a.shape,))
+    m = a.shape[0]
+    return a, (m.bit_length() - 1 if m >= 2 and not m & (m - 1) else -1)
+
+
+def run_channel_detect(lib, device, spec, d_H, d_Y, d_constellation, d_out, stream=None):
+    """hrt_channel_detect through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_channel_detect failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_channel_detect(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                                C.c_void_p(d_Y), C.c_void_p(d_constellation), C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_channel_detect failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_channel_detect(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                               rx_elements, tx_elements, Y, constellation, noise, llr=True, flags=None,
+                               array_frequency=None, stats=None):
+    """hrt_compute_channel_detect through ctypes -> detect_views of a uint8 numpy buffer (spec: a ChannelSpec, as for
+    run_compute_array_channel; Y: complex [nrx, ntx, Nr, 2, T, K] and constellation: complex [2^B], None passes NULL;
+    array_frequency defaults to the carrier).  Detection runs once, on the H accumulated over all batches: it is not
+    additive.  A Y of another shape or a constellation whose size is no power of two raises ValueError (the library
+    cannot see either).  Raises RuntimeError("hrt_compute_channel_detect failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    fp = C.POINTER(C.c_float)
+    if constellation is None:
+        s, b = None, 1
+    else:
+        s, b = constellation_array(constellation)
+        if b < 0:
+            raise ValueError("constellation must hold 2^B symbols, got %d" % s.shape[0])
+    ds = detect_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), b, noise, llr, flags)
+    y = None if Y is None else np.ascontiguousarray(Y, np.complex64)
+    if y is not None and y.shape != (nrx, ntx, nr, 2, int(spec.num_times), int(spec.num_freqs)):
+        raise ValueError("Y [%d, %d, %d, 2, %d, %d] expected, got %s"
+                         % (nrx, ntx, nr, int(spec.num_times), int(spec.num_freqs), y.shape))
+    extra += (y.ctypes.data_as(fp) if y is not None else None, s.ctypes.data_as(fp) if s is not None else None,
+              C.c_uint32(int(ds.bits)), C.c_uint32(int(ds.flags)), C.c_float(ds.noise))
+    fits = detect_fits(ds) and s is not None and y is not None
+    out = _run_pathsum(lib, "hrt_compute_channel_detect", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (detect_regions(ds)[4],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_channel_detect accepted a call beyond its limits")
+    return detect_views(out, ds)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

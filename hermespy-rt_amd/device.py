@@ -977,6 +977,80 @@ class Tracer:
                                array_frequency)
         return self.codebook_select(H, codebook, metric, noise, subband, table, effective)
 
+    def detect(self, H, Y, constellation, noise, llr=True, out=None):
+        """Per-point maximum-likelihood MIMO detection with max-log bit LLRs on an array channel, on the device
+        (hrt_channel_detect; include/hermespy_rt.h hrt_compute_channel_detect).  For the point (rx, tx, pol, m, k),
+        with H = H[rx, tx, :, :, pol, m, k] (Nr x Nt, Nt streams) and y = Y[rx, tx, :, pol, m, k], every hypothesis
+        q < Q = M^Nt -- stream j sends constellation[(q >> (j B)) & (M - 1)], M = 2^B -- is scored by
+        d_q = |y - H s(q)|^2:
+
+            index   int32    [nrx, ntx, 2, T, K]          argmin_q d_q, the lowest on a tie (-1: flagged)
+            metric  float32  [nrx, ntx, 2, T, K]          its distance
+            status  int32    [nrx, ntx, 2, T, K]          0, abi.DT_NONFINITE
+            llr     float32  [nrx, ntx, Nt, B, 2, T, K]   (min_{bit 0} d_q - min_{bit 1} d_q) / noise  (None without llr)
+
+        Bit b = 0 of a stream is the most significant bit of its symbol's index; a positive LLR favours bit 1.
+        H: a complex64 device tensor [nrx, ntx, Nr, Nt, 2, T, K] (array_channel(), or any tensor of that layout; no
+        trace is needed); Y: complex64 [nrx, ntx, Nr, 2, T, K]; Nr <= 64, B <= 8, Nt B <= 12.  `constellation`: a
+        device tensor or anything numpy converts (copied to the device then), used as given;
+        hermespy_rt_amd.detect builds QAM and PSK ones.  `noise`: one finite float > 0.  A point with a non-finite
+        distance or LLR writes index -1, metric 0 and zeros.  Detection is not additive: a sharded caller sums H over
+        the shards first.  Returns a dict of views of one flat uint8 device tensor, itself under "buffer", enqueued
+        on the current stream; `out` (such a flat tensor) is written in place.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        if not (hasattr(Y, "is_cuda") and Y.is_cuda and Y.device == self.device and Y.dtype == torch.complex64):
+            raise ValueError("Y must be a complex64 tensor on %s" % (self.device,))
+        if tuple(Y.shape) != (nrx, ntx, nr, 2, T, K):
+            raise ValueError("Y %s expected, got %s" % ((nrx, ntx, nr, 2, T, K), tuple(Y.shape)))
+        if hasattr(constellation, "is_cuda"):
+            S = constellation
+            if not (S.is_cuda and S.device == self.device and S.dtype == torch.complex64 and S.dim() == 1):
+                raise ValueError("constellation must be a complex64 tensor [M] on %s" % (self.device,))
+        else:
+            S = torch.from_numpy(abi.constellation_array(constellation)[0]).to(self.device)
+        M = int(S.shape[0])
+        if M < 2 or M & (M - 1):
+            raise ValueError("constellation must hold 2^B symbols, got %d" % M)
+        spec = abi.detect_spec(nrx, ntx, nr, nt, T, K, M.bit_length() - 1, noise, llr)
+        H, Y, S = H.contiguous(), Y.contiguous(), S.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and abi.detect_fits(spec)
+        need = abi.detect_regions(spec)[4] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_channel_detect(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                       C.c_void_p(Y.data_ptr() if Y.numel() else None), C.c_void_p(S.data_ptr()),
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_channel_detect: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_channel_detect")
+        H.record_stream(stream)     # (the kernel reads them after this call returns)
+        Y.record_stream(stream)
+        S.record_stream(stream)
+        return abi.detect_views(out, spec)
+
+    def channel_detect(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                       scatter=True, array_frequency=None, Y=None, constellation=None, noise=None, llr=True):
+        """The detection on the last trace's array channel, without leaving the device: bit for bit
+        detect(array_channel(...), Y, constellation, noise, llr) with array_channel()'s arguments.  On a sharded
+        trace this is the detection on the shard's partial channel, which is not the channel's: sum array_channel()
+        over the shards and call detect()."""
+        if Y is None or constellation is None or noise is None:
+            raise ValueError("channel_detect needs Y, a constellation and the noise power")
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.detect(H, Y, constellation, noise, llr)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

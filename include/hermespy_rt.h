@@ -590,6 +590,59 @@ int hrt_compute_codebook_select(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx
                                 uint32_t entries, uint32_t subband, uint32_t metric, uint32_t flags, float noise,
                                 void *out /* host, hrt_codebook_out_bytes bytes, layout above */, hrt_stats *stats);
 
+/* Per-point maximum-likelihood MIMO detection with max-log bit LLRs on the array channel, formed on the device
+ * (include/hrt_device.h: hrt_channel_detect).  A point is one (rx, tx, pol, time m, frequency k).  H is
+ * H[rx][tx][:][:][pol][m][k], Nr x Nt, from a tensor of hrt_compute_array_channel's layout; y is Y[rx][tx][:][pol][m][k]
+ * from a tensor complex [num_rx][num_tx][Nr][2][T][K].  Nt is the number of streams.  The constellation is complex [M]
+ * with M = 2^B, used as given (normalisation is the caller's); the index of a symbol is its bit label.  A hypothesis
+ * q < Q = M^Nt assigns the symbol x_j = (q >> (j B)) & (M - 1) to stream j; bit b of stream j is
+ * (x_j >> (B - 1 - b)) & 1, so b = 0 is the label's most significant bit, the first bit in the TS 38.211 order.
+ * 1 <= Nr <= 64, 1 <= B <= 8, Nt B <= 12 (Q <= 4096, Nt <= 12), fewer than 2^31 points, the other size refusals are
+ * hrt_channel_equalizer's; `noise` N0 finite and > 0.
+ * Algorithm (a definition: the tests emulate it).  All float, no contraction.
+ *   products   p_ij = H_ij s with s = S[x_j], as (hr sr - hi si, hr si + hi sr)
+ *   row sums   e_i = (..((p_i0 + p_i1) + p_i2)..), over j ascending
+ *   residuals  r_i = y_i - e_i
+ *   distance   d_q = sum_i (r.re r.re + r.im r.im), over i ascending from zero
+ *   decision   q* = argmin_q d_q, the lowest q on a tie
+ *   minima     for every (j, b): m0 the minimum of d_q over the q whose bit is 0, m1 over those whose bit is 1
+ *   LLR        llr[j][b] = (m0 - m1) / N0, one IEEE subtraction and one IEEE division: positive where bit 1 is the
+ *              likelier
+ * The outputs lie in one flat buffer of hrt_detect_out_bytes bytes, the point axes innermost, in this order:
+ *   index   uint32  [num_rx][num_tx][2][T][K]           q*
+ *   metric  float   [num_rx][num_tx][2][T][K]           d_q*
+ *   status  uint32  [num_rx][num_tx][2][T][K]           0 or HRT_DT_NONFINITE
+ *   llr     float   [num_rx][num_tx][Nt][B][2][T][K]    present only with HRT_DT_LLR in `flags`
+ * A point is HRT_DT_NONFINITE when some d_q is not finite or, with HRT_DT_LLR, some LLR is not finite (a quotient
+ * beyond float; without HRT_DT_LLR no LLR is formed and none is tested).  A non-finite entry of H or y reaches every
+ * d_q; the flag is tracked explicitly, not left to a minimum that drops NaNs.  A flagged point writes index
+ * 0xFFFFFFFF, metric 0 and zeros in its LLRs.  H = 0 is regular.  A point's bytes depend on its own H, y, the
+ * constellation and N0 only; two calls give the same bytes; every output byte is written exactly once.
+ * hrt_compute_channel_detect traces and batches exactly as hrt_compute_array_channel does, keeps the accumulated H on
+ * the device, copies Y and the constellation up and detects once after the last batch: detection is NOT additive over
+ * batches or shards.  Only the result is copied back.  HRT_E_INVALID, before the device is touched: every refusal of
+ * hrt_compute_array_channel; a NULL Y, constellation or out; every refusal of hrt_channel_detect (include/hrt_device.h). */
+#define HRT_DT_LLR 1u
+#define HRT_DT_NONFINITE 1u
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt, Nt streams */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t bits;                              /* B: bits per symbol, 1 .. 8, Nt B <= 12 */
+    uint32_t flags;                             /* HRT_DT_LLR */
+    float noise;                                /* N0, finite and > 0 */
+} hrt_detect_spec;
+uint64_t hrt_detect_out_bytes(const hrt_detect_spec *spec);   /* 0 for NULL */
+int hrt_compute_channel_detect(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                               const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                               size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                               const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                               size_t num_tx_elements, double array_frequency_hz,
+                               const float *Y /* host, complex [num_rx][num_tx][Nr][2][T][K] */,
+                               const float *constellation /* host, complex [2^bits] */, uint32_t bits, uint32_t flags,
+                               float noise, void *out /* host, hrt_detect_out_bytes bytes, layout above */,
+                               hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

@@ -458,6 +458,20 @@ int hrt_channel_precoder(int device, const hrt_precoder_spec *spec, const void *
 int hrt_codebook_select(int device, const hrt_codebook_spec *spec, const void *d_H, const void *d_codebook, void *d_out,
                         void *stream);
 
+/* ---- per-point maximum-likelihood detection on an array channel (csrc/host/channel.c, csrc/hrt_detect.hip) ----
+ * index, metric, status and llr as hermespy_rt.h defines them (hrt_detect_spec, hrt_compute_channel_detect),
+ * hrt_detect_out_bytes bytes at d_out, from d_H (complex [num_rx][num_tx][nr][nt][2][num_times][num_freqs]: the output
+ * of hrt_array_channel, or any tensor of that layout), d_Y (complex [num_rx][num_tx][nr][2][num_times][num_freqs]) and
+ * d_constellation (complex [2^bits]), all DEVICE pointers, asynchronous on `stream` of `device`.  It needs no
+ * problem: it reads only the three tensors, and writes none of them.  Every byte of d_out is written exactly once; no
+ * scratch and no atomics, so two calls with the same input give the same bytes.  Detection on one shard's partial H
+ * is not the channel's: a sharded caller sums H first.  HRT_E_INVALID, before the device is touched: a NULL pointer;
+ * num_rx, num_tx, num_times or num_freqs equal to 0; nr outside 1..64; bits outside 1..8; nt < 1 or nt * bits > 12;
+ * `flags` with bits other than HRT_DT_LLR; a noise that is not finite and > 0; nr * nt * num_times * num_freqs > 2^24;
+ * 2^31 points or more. */
+int hrt_channel_detect(int device, const hrt_detect_spec *spec, const void *d_H, const void *d_Y,
+                       const void *d_constellation, void *d_out, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
