@@ -1624,3 +1624,12 @@ def debug_table_info(lib, problem):
     if rc != 0:
         raise RuntimeError("hrt_debug_table_info failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
     return dict(nuv=nuv[:T], hmax=f3[0], ro_rx=f3[1], ro_img=f3[2], num_patch=int(npatch.value), kinds=int(kinds.value))
+
+
+def debug_last_launch(lib, problem, shard, workspace_ptr, workspace_bytes):
+    """hrt_debug_last_launch: launch nb = shard.num_bounces alone (shadow traces + scatter records of bounce nb - 1) on
+    the live list the caller planted in the workspace (hit block nb - 1, counts[nb]).  Blocks until done.  Raises
+    RuntimeError on an error code (a refusal launches nothing)."""
+    rc = lib.hrt_debug_last_launch(problem, C.byref(shard), C.c_void_p(int(workspace_ptr)), C.c_uint64(int(workspace_bytes)))
+    if rc != 0:
+        raise RuntimeError("hrt_debug_last_launch failed (%d): %s" % (rc, lib.hrt_last_error().decode()))

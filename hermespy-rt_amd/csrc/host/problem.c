@@ -1177,58 +1177,48 @@ static uint32_t fuse_mode(const hrt_problem *p)
     return HRT_FUSE_LAUNCH0 | (p->num_tri <= HRT_FUSE_MAX_TRI ? HRT_FUSE_BOUNCES : 0u);
 }
 
-static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_dirs,
-                      const uint32_t *d_order, void *d_ws, uint64_t ws_bytes, void *stream,
-                      hrt_timer *timer, uint32_t flags)
+/* The kernel parameters of a trace of shard `s` on workspace `d_ws` with layout *L: everything the launch shims read.
+ * One place for hrt_trace and the test entry hrt_debug_last_launch, so that the two cannot drift apart. */
+static int fill_kparams(const hrt_problem *p, const hrt_shard *s, const float *d_dirs, const uint32_t *d_order,
+                        void *d_ws, uint32_t flags, const hrt_layout *L, hrt_kparams *K)
 {
-    if (!p || !d_dirs || !d_ws) return hrt_fail(HRT_E_INVALID, "hrt_trace: NULL argument");
-    hrt_layout L;
-    int rc = hrt_layout_query(p, s, &L);
-    if (rc) return rc;
-    if (ws_bytes < L.total_bytes)
-        return hrt_fail(HRT_E_INVALID, "workspace too small: %llu < %llu bytes",
-                        (unsigned long long)ws_bytes, (unsigned long long)L.total_bytes);
-    if (((uintptr_t)d_ws & 255u) || ((uintptr_t)d_dirs & 3u))
-        return hrt_fail(HRT_E_INVALID, "workspace must be 256-byte aligned");
-
-    hrt_kparams K;
-    memset(&K, 0, sizeof K);
-    K.tri = p->d_tri; K.mesh = p->d_mesh; K.mat = p->d_mat;
-    K.num_tri = p->num_tri; K.num_mesh = p->num_mesh;
-    K.acc = p->kaccel;
-    K.rxt = p->krxt;
-    K.patch = p->kpatch;
-    K.rx_pos = p->d_rx_pos; K.tx_pos = p->d_tx_pos; K.rx_vel = p->d_rx_vel; K.tx_vel = p->d_tx_vel;
-    K.num_rx = p->num_rx; K.num_tx = p->num_tx;
-    K.fsl_mult = p->fsl_mult; K.dop_mult = p->dop_mult;
-    K.dirs = d_dirs;
-    K.order = d_order;
-    K.dirs_in_launch_order = (flags & HRT_DIRS_IN_LAUNCH_ORDER) ? 1u : 0u;
-    K.num_local = (uint32_t)hrt_shard_num_local(s);
-    K.num_bounces = s->num_bounces;
-    K.n0 = p->num_tx * K.num_local;
-    K.ws = (uint8_t *)d_ws;
-    K.cap = L.cap;
-    K.off_counts = L.off_counts; K.off_los = L.off_los; K.off_hits = L.off_hits;
-    K.hit_block_bytes = L.hit_block_bytes; K.off_recs = L.off_recs;
-    K.rec_block_bytes = L.rec_block_bytes; K.off_masks = L.off_masks;
-    K.off_chunk_cnt = L.off_chunk_cnt; K.off_super_cnt = L.off_super_cnt;
-    K.num_super = (uint32_t)L.num_super;
-    K.off_res = L.off_res;
-    K.off_lb = L.off_lb;
-    K.cnt_stride = (uint32_t)HRT_CNT_STRIDE(s->num_bounces);
-    K.host_flag = p->d_fuse_flag;
-    K.lb_stride = (uint32_t)L.lb_stride;
-    K.off_wide_q = L.off_wide_q; K.off_wide_key = L.off_wide_key; K.wide_cap = (uint32_t)L.wide_cap;
-    K.wide_inv = p->d_inv;
-    K.wide_cos = p->tune.wide_cos != 0.0 ? (float)p->tune.wide_cos : (p->num_tri >= HRT_WIDE_COS_BIG_TRI ? HRT_WIDE_COS_BIG : HRT_WIDE_COS);
-    K.tune = p->tune.k;
-    K.lb_chunks = (uint32_t)round_up(L.cap / HRT_BLOCK + 1, 64);
-    K.fuse = fuse_mode(p);
+    memset(K, 0, sizeof *K);
+    K->tri = p->d_tri; K->mesh = p->d_mesh; K->mat = p->d_mat;
+    K->num_tri = p->num_tri; K->num_mesh = p->num_mesh;
+    K->acc = p->kaccel;
+    K->rxt = p->krxt;
+    K->patch = p->kpatch;
+    K->rx_pos = p->d_rx_pos; K->tx_pos = p->d_tx_pos; K->rx_vel = p->d_rx_vel; K->tx_vel = p->d_tx_vel;
+    K->num_rx = p->num_rx; K->num_tx = p->num_tx;
+    K->fsl_mult = p->fsl_mult; K->dop_mult = p->dop_mult;
+    K->dirs = d_dirs;
+    K->order = d_order;
+    K->dirs_in_launch_order = (flags & HRT_DIRS_IN_LAUNCH_ORDER) ? 1u : 0u;
+    K->num_local = (uint32_t)hrt_shard_num_local(s);
+    K->num_bounces = s->num_bounces;
+    K->n0 = p->num_tx * K->num_local;
+    K->ws = (uint8_t *)d_ws;
+    K->cap = L->cap;
+    K->off_counts = L->off_counts; K->off_los = L->off_los; K->off_hits = L->off_hits;
+    K->hit_block_bytes = L->hit_block_bytes; K->off_recs = L->off_recs;
+    K->rec_block_bytes = L->rec_block_bytes; K->off_masks = L->off_masks;
+    K->off_chunk_cnt = L->off_chunk_cnt; K->off_super_cnt = L->off_super_cnt;
+    K->num_super = (uint32_t)L->num_super;
+    K->off_res = L->off_res;
+    K->off_lb = L->off_lb;
+    K->cnt_stride = (uint32_t)HRT_CNT_STRIDE(s->num_bounces);
+    K->host_flag = p->d_fuse_flag;
+    K->lb_stride = (uint32_t)L->lb_stride;
+    K->off_wide_q = L->off_wide_q; K->off_wide_key = L->off_wide_key; K->wide_cap = (uint32_t)L->wide_cap;
+    K->wide_inv = p->d_inv;
+    K->wide_cos = p->tune.wide_cos != 0.0 ? (float)p->tune.wide_cos : (p->num_tri >= HRT_WIDE_COS_BIG_TRI ? HRT_WIDE_COS_BIG : HRT_WIDE_COS);
+    K->tune = p->tune.k;
+    K->lb_chunks = (uint32_t)round_up(L->cap / HRT_BLOCK + 1, 64);
+    K->fuse = fuse_mode(p);
     if (p->sort_rays) {
         uint32_t txb = 0;
         while ((1u << txb) < p->num_tx) ++txb;
-        K.sort.enabled = 1u;
+        K->sort.enabled = 1u;
         {   /* 15 bits of cell, dealt to the axes so that the cells come out about cubic (a bit at a
              * time to the axis whose cells are longest); HRT_SORT_DIR_RES: cells per cube-face edge
              * of the direction bins (default 2: 24 bins); sort_fine: how many of the 15 cell bits
@@ -1247,30 +1237,50 @@ static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_d
             for (int k = 0; k < 3; ++k) {
                 ext[k] = p->scene_hi[k] - p->scene_lo[k];
                 if (!(ext[k] > 0.f)) ext[k] = 1e-30f;
-                K.sort.bits[k] = 0;
+                K->sort.bits[k] = 0;
             }
             for (int n = 0; n < 15; ++n) {
                 int best = 0;
                 for (int k = 1; k < 3; ++k)
-                    if (ext[k] / (float)(1u << K.sort.bits[k]) > ext[best] / (float)(1u << K.sort.bits[best])) best = k;
-                K.sort.bits[best]++;
+                    if (ext[k] / (float)(1u << K->sort.bits[k]) > ext[best] / (float)(1u << K->sort.bits[best])) best = k;
+                K->sort.bits[best]++;
             }
-            K.sort.nfine = nfine;
+            K->sort.nfine = nfine;
             for (int k = 0; k < 3; ++k) {
-                K.sort.lo[k] = p->scene_lo[k];
-                K.sort.inv_cell[k] = (float)(1u << K.sort.bits[k]) / ext[k];
+                K->sort.lo[k] = p->scene_lo[k];
+                K->sort.inv_cell[k] = (float)(1u << K->sort.bits[k]) / ext[k];
             }
-            K.sort.dir_res = res;
-            K.sort.dir_bits = bits;
-            K.sort.tx_shift = 15u + bits;
-            K.sort.key_bits = 15u + bits + txb;
-            if (K.sort.key_bits > 32u) return hrt_fail(HRT_E_INVALID, "re-sort keys do not fit 32 bits");
+            K->sort.dir_res = res;
+            K->sort.dir_bits = bits;
+            K->sort.tx_shift = 15u + bits;
+            K->sort.key_bits = 15u + bits + txb;
+            if (K->sort.key_bits > 32u) return hrt_fail(HRT_E_INVALID, "re-sort keys do not fit 32 bits");
         }
-        K.sort.off_scratch = L.off_sort_scratch;
-        K.sort.off_keys = L.off_sort_keys;
-        K.sort.off_tmp = L.off_sort_tmp;
-        K.sort.tmp_bytes = L.sort_tmp_bytes;
+        K->sort.off_scratch = L->off_sort_scratch;
+        K->sort.off_keys = L->off_sort_keys;
+        K->sort.off_tmp = L->off_sort_tmp;
+        K->sort.tmp_bytes = L->sort_tmp_bytes;
     }
+    return HRT_OK;
+}
+
+static int trace_impl(const hrt_problem *p, const hrt_shard *s, const float *d_dirs,
+                      const uint32_t *d_order, void *d_ws, uint64_t ws_bytes, void *stream,
+                      hrt_timer *timer, uint32_t flags)
+{
+    if (!p || !d_dirs || !d_ws) return hrt_fail(HRT_E_INVALID, "hrt_trace: NULL argument");
+    hrt_layout L;
+    int rc = hrt_layout_query(p, s, &L);
+    if (rc) return rc;
+    if (ws_bytes < L.total_bytes)
+        return hrt_fail(HRT_E_INVALID, "workspace too small: %llu < %llu bytes",
+                        (unsigned long long)ws_bytes, (unsigned long long)L.total_bytes);
+    if (((uintptr_t)d_ws & 255u) || ((uintptr_t)d_dirs & 3u))
+        return hrt_fail(HRT_E_INVALID, "workspace must be 256-byte aligned");
+
+    hrt_kparams K;
+    rc = fill_kparams(p, s, d_dirs, d_order, d_ws, flags, &L, &K);
+    if (rc) return rc;
 
     HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
     const uint32_t nb = s->num_bounces;
@@ -1550,6 +1560,54 @@ int hrt_debug_table_info(const hrt_problem *p, uint32_t *nuv, float *hmax_ro_rx_
         free(pdef);
         if (rc) return rc;
     }
+    return HRT_OK;
+}
+
+/* ------------------------------------------------------------------ the last launch alone (test entry) */
+
+/* TEST ONLY (include/hrt_device.h): launch nb = s->num_bounces of a trace -- shadow traces and scatter records of bounce
+ * nb - 1, nothing else -- on a live list the caller planted: hit block nb - 1 and counts[nb] of the workspace.  The
+ * kernel parameters are trace_impl's (fill_kparams) and so are the shims; the kernels are those trace_impl runs for
+ * launch nb when it runs it unfused: hrt_records_kernel where the plan gives it the records, else the trace kernel
+ * (shadow units only) and hrt_shade_kernel<.., true>.  Default stream; blocks until done. */
+int hrt_debug_last_launch(const hrt_problem *p, const hrt_shard *s, void *d_ws, uint64_t ws_bytes)
+{
+    if (!p || !s || !d_ws) return hrt_fail(HRT_E_INVALID, "hrt_debug_last_launch: NULL argument");
+    hrt_layout L;
+    int rc = hrt_layout_query(p, s, &L);   /* (num_bounces = 0 is refused here, as by hrt_trace) */
+    if (rc) return rc;
+    if (ws_bytes < L.total_bytes)
+        return hrt_fail(HRT_E_INVALID, "workspace too small: %llu < %llu bytes",
+                        (unsigned long long)ws_bytes, (unsigned long long)L.total_bytes);
+    if ((uintptr_t)d_ws & 255u) return hrt_fail(HRT_E_INVALID, "workspace must be 256-byte aligned");
+    hrt_kparams K;
+    rc = fill_kparams(p, s, NULL, NULL, d_ws, 0u, &L, &K);   /* (no launch after the first reads the directions) */
+    if (rc) return rc;
+    const uint32_t nb = s->num_bounces;
+    uint8_t *ws = (uint8_t *)d_ws;
+    uint32_t n_in = 0;
+    int e;
+    HRT_HIP(hrt_hip_set_device(p->device), "hipSetDevice");
+    HRT_HIP(hrt_hip_stream_sync(NULL), "hipStreamSynchronize");
+    HRT_HIP(hrt_hip_d2h(&n_in, ws + L.off_counts + 4ull * nb, 4), "hipMemcpy D2H");
+    if (n_in > L.cap)
+        return hrt_fail(HRT_E_INVALID, "hrt_debug_last_launch: counts[%u] = %u exceeds the capacity %llu", nb, n_in,
+                        (unsigned long long)L.cap);
+    /* what a trace has zeroed or produced by the time launch nb runs, and launch nb reads: the error word, the unit
+     * counters, the survivor counts and the status words -- everything between counts[nb] and the LoS entries.
+     * counts[0 .. nb] and the blocks stay as the caller left them. */
+    const uint64_t clr = L.off_counts + 4ull * (nb + 1u);
+    HRT_HIP(hrt_hip_memset_async(ws + clr, 0, L.off_los - clr, NULL), "hipMemsetAsync");
+    const hrt_launch_plan plan = hrt_plan(&K);
+    if (hrt_plan_own_records(&plan, nb)) {
+        e = hrt_hip_launch_records(&K, nb, NULL);
+        if (e < 0) return hrt_fail(HRT_E_INVALID, "hrt_debug_last_launch: the records kernel refused the launch its plan gives it");
+        if (e) return hrt_fail_hip(e, "hrt_records_kernel");
+    } else {
+        if ((e = hrt_hip_launch_trace(&K, nb, NULL))) return hrt_fail_hip(e, "hrt_trace_kernel");
+        if ((e = hrt_hip_launch_shade(&K, nb, NULL))) return hrt_fail_hip(e, "hrt_shade_kernel");
+    }
+    HRT_HIP(hrt_hip_stream_sync(NULL), "hipStreamSynchronize");
     return HRT_OK;
 }
 

@@ -246,6 +246,12 @@ class Tracer:
         if self._patterns is not None:
             self._apply_patterns()
 
+    def debug_last_launch(self):
+        """TEST ONLY (hrt_debug_last_launch): run launch nb alone -- the shadow traces and scatter records of bounce
+        nb - 1 -- on the live list the caller wrote into hit_block(nb - 1) and counts_tensor()[nb].  Blocks."""
+        self.torch.cuda.synchronize(self.device)
+        abi.debug_last_launch(self.L, self.problem, self.shard, self.ws.data_ptr(), self.ws.numel())
+
     def _dirs_ptr(self):
         return (self.dirs_launch if self.flags & _lib.DIRS_IN_LAUNCH_ORDER else self.dirs).data_ptr()
 

@@ -23,7 +23,7 @@ EXPORTED = (
     "hrt_timer_read", "hrt_device_count", "hrt_device_malloc", "hrt_device_free",
     "hrt_device_upload", "hrt_device_download", "hrt_device_sync", "hrt_device_mem_info",
     "hrt_selftest_math", "hrt_debug_kernel_stats", "hrt_scene_import_sionna",
-    "hrt_debug_candidates", "hrt_debug_table_info",
+    "hrt_debug_candidates", "hrt_debug_table_info", "hrt_debug_last_launch",
     "hrt_export_meta_words", "hrt_export_words", "hrt_export_locate", "hrt_gather_create", "hrt_gather_destroy",
     "hrt_gather_meta_words", "hrt_gather_meta_device", "hrt_gather_prepare", "hrt_gather_set_meta", "hrt_gather_meta",
     "hrt_gather_pack", "hrt_gather_recv_buffer", "hrt_gather_export", "hrt_gather_received", "hrt_rccl_unique_id",
@@ -195,6 +195,9 @@ def load():
     L.hrt_debug_candidates.restype = C.c_int
     L.hrt_debug_table_info.argtypes = [vp, C.POINTER(u32), f32p, C.POINTER(u64), C.POINTER(u32)]
     L.hrt_debug_table_info.restype = C.c_int
+    # test-only: the last launch of a trace alone, on a planted live list
+    L.hrt_debug_last_launch.argtypes = [vp, C.POINTER(Shard), vp, u64]
+    L.hrt_debug_last_launch.restype = C.c_int
     L.hrt_scene_import_sionna.argtypes = [C.c_char_p, C.POINTER(abi.Scene)]
     L.hrt_scene_import_sionna.restype = C.c_int
     # packed export and gather (include/hrt_device.h)

@@ -698,6 +698,20 @@ int hrt_debug_candidates(const hrt_problem *p, int mode, uint64_t n, const float
 int hrt_debug_table_info(const hrt_problem *p, uint32_t *nuv, float *hmax_ro_rx_ro_img, uint64_t *num_patch,
                          uint32_t *kinds);
 
+/* TEST ONLY -- the last launch of a trace alone, for tests/test_gpu_records_planted.py.  With nb = s->num_bounces,
+ * launch nb traces the shadow rays of the entries of hit block nb - 1 and writes their scatter records (record block
+ * and mask block nb - 1); it has no primary rays.  The caller plants hit block nb - 1 and counts[nb] (the number of its
+ * entries) in the workspace; this entry runs launch nb on them with hrt_trace's own kernel parameters and launch shims:
+ * hrt_records_kernel where the launch plan gives it the records (patch tables), else hrt_trace_kernel (shadow units)
+ * followed by hrt_shade_kernel<.., true>.  It never runs the fused kernel or the chain kernel: where hrt_trace would
+ * fuse launch nb, the trace + shade pair runs instead.  Before the launch it zeroes what hrt_trace has zeroed or
+ * produced by then and launch nb reads -- the error word counts[nb + 1] and every control word between it and the LoS
+ * entries (unit counters, survivor counts, status words); counts[0 .. nb], the LoS entries and the hit, record and mask
+ * blocks are left alone (the trace + shade pair also writes the shadow result scratch behind the mask blocks).
+ * HRT_E_INVALID, nothing launched: NULL arguments, a bad shard (num_bounces = 0 included), a workspace that is too
+ * small or not 256-byte aligned, counts[nb] > cap.  Default stream; blocks until done. */
+int hrt_debug_last_launch(const hrt_problem *p, const hrt_shard *s, void *d_workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,10 @@ typedef struct {
      * array's value for one TX, without the reference's replication quirks Q9/Q10); RaysInfo
      * snapshots are not taken (scat_rays may be NULL). */
     int compact;
+    /* optional, like the extras above: [nb][ntx*np][5] a_te_re, a_te_im, a_tm_re, a_tm_im, tau of a ray AFTER its hit at
+     * that bounce -- with the snapshot's (o, d), hit_tri and hit_theta the whole state the scatter loop reads
+     * (tests/test_oracle_scatter_records.py); slots of rays that did not hit are left alone */
+    float *hit_state;
 } hrt_oracle_opts;
 
 /* src/compute_paths.c:125-132 field order */
@@ -301,6 +305,52 @@ int hrt_oracle_max_threads(void)
 #else
     return 1;
 #endif
+}
+
+/* The per-receiver scatter loop of one entry: src/compute_paths.c:671-723.  The entry left triangle `tr` (material `mat`,
+ * mesh velocity `mvel`) at `o` (already advanced) in direction `d` with incidence angle theta, amplitudes a[4] and
+ * delay `tau`.  Every RX IN ORDER, carrying theta (Q7): a shadow hit at any distance overwrites theta for this RX and
+ * every later one; a shadow hit within one metre (Q6: t <= 1) blocks -- amplitudes and tau are zeroed, nothing else
+ * is written; else the scatter pattern (Q8), arrival direction, delay, free-space loss (f2 > 1) are written to slot
+ * off0 + rx * rx_stride of `scat`, the record's Doppler term to dfs[rx] and 1 to unblocked[rx].  The whole-path
+ * oracle below and hrt_oracle_scatter_records both call it. */
+static void scatter_to_receivers(const tri_t *tris, uint32_t T, const float *rx_pos, size_t nrx, v3 o, v3 d,
+                                 const tri_t *tr, uint32_t mat, v3 mvel, float theta, const float a[4], float tau,
+                                 float fsl_mult, float dop_mult, const hrt_oracle_chan *scat, size_t off0,
+                                 size_t rx_stride, float *dfs, uint8_t *unblocked)
+{
+    const float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    for (size_t rx = 0; rx < nrx; ++rx) {
+        const size_t off = off0 + rx * rx_stride;                     /* :674 */
+        v3 w = sub3(ld3(rx_pos + 3 * rx), o);
+        float d2rx = sqrtf(dot3(w, w));
+        w = unit3(w);
+        hit_t sh = closest_hit(tris, T, o, w);
+        if (sh.tri != HRT_NO_HIT) theta = sh.theta;               /* Q7 */
+        if (sh.tri != HRT_NO_HIT && sh.t <= 1.f) {                /* Q6 */
+            scat->a_te_re[off] = scat->a_te_im[off] = scat->a_tm_re[off] =
+                scat->a_tm_im[off] = scat->tau[off] = 0.f;
+            unblocked[rx] = 0;
+            continue;
+        }
+        float th_s = acosf(dot3(w, tr->n));                       /* :694 */
+        float S[4];
+        scatter_pattern(th_s, theta, mat, S);
+        float o0 = a0 * S[0] - a1 * S[1];                         /* :698-705, Q8 */
+        float o1 = a0 * S[1] + a1 * S[0];
+        float o2 = a2 * S[2] - a3 * S[3];
+        float o3 = a2 * S[3] + a3 * S[2];
+        v3 mw = {-w.x, -w.y, -w.z};
+        st3(scat->directions_rx + 3 * off, mw);                   /* :707 */
+        scat->tau[off] = tau + d2rx / HRT_C_F;                    /* :709 */
+        float f2 = fsl_mult * d2rx;                               /* :711-718 */
+        f2 *= f2;
+        if (f2 > 1.f) { o0 /= f2; o1 /= f2; o2 /= f2; o3 /= f2; }
+        scat->a_te_re[off] = o0; scat->a_te_im[off] = o1;
+        scat->a_tm_re[off] = o2; scat->a_tm_im[off] = o3;
+        dfs[rx] = dot3(sub3(w, d), mvel) * dop_mult;              /* :720-721 */
+        unblocked[rx] = 1;
+    }
 }
 
 /* Whole path: src/compute_paths.c:419-757.  Returns 0, or -1 on allocation failure /
@@ -512,38 +562,17 @@ int hrt_oracle_compute_paths(const hrt_oracle_scene *sc,
                 v3 zz = sub3(d, d);
                 dfs[i * (nrx + 1) + nrx] = dot3(zz, mvel) * dop_mult;
 
+                if (opt && opt->hit_state) {
+                    float *hs = opt->hit_state + 5 * (compact ? (b * ntx + tx) * npo + PO(p) : b * nq + q);
+                    hs[0] = a0; hs[1] = a1; hs[2] = a2; hs[3] = a3; hs[4] = s[10];
+                }
+
                 /* scatter to every rx IN ORDER, carrying theta (Q7)           :671-723 */
-                float theta = h.theta;
-                for (size_t rx = 0; rx < nrx; ++rx) {
-                    const size_t off = ((rx * ntx + tx) * nb + b) * npo + PO(p);   /* :674 */
-                    v3 w = sub3(ld3(rx_pos + 3 * rx), o);
-                    float d2rx = sqrtf(dot3(w, w));
-                    w = unit3(w);
-                    hit_t sh = closest_hit(tris, T, o, w);
-                    if (sh.tri != HRT_NO_HIT) theta = sh.theta;               /* Q7 */
-                    if (sh.tri != HRT_NO_HIT && sh.t <= 1.f) {                /* Q6 */
-                        scat->a_te_re[off] = scat->a_te_im[off] = scat->a_tm_re[off] =
-                            scat->a_tm_im[off] = scat->tau[off] = 0.f;
-                        unblocked[i * nrx + rx] = 0;
-                        continue;
-                    }
-                    float th_s = acosf(dot3(w, tr->n));                       /* :694 */
-                    float S[4];
-                    scatter_pattern(th_s, theta, mat, S);
-                    float o0 = a0 * S[0] - a1 * S[1];                         /* :698-705, Q8 */
-                    float o1 = a0 * S[1] + a1 * S[0];
-                    float o2 = a2 * S[2] - a3 * S[3];
-                    float o3 = a2 * S[3] + a3 * S[2];
-                    v3 mw = {-w.x, -w.y, -w.z};
-                    st3(scat->directions_rx + 3 * off, mw);                   /* :707 */
-                    scat->tau[off] = s[10] + d2rx / HRT_C_F;                  /* :709 */
-                    float f2 = fsl_mult * d2rx;                               /* :711-718 */
-                    f2 *= f2;
-                    if (f2 > 1.f) { o0 /= f2; o1 /= f2; o2 /= f2; o3 /= f2; }
-                    scat->a_te_re[off] = o0; scat->a_te_im[off] = o1;
-                    scat->a_tm_re[off] = o2; scat->a_tm_im[off] = o3;
-                    dfs[i * (nrx + 1) + rx] = dot3(sub3(w, d), mvel) * dop_mult; /* :720-721 */
-                    unblocked[i * nrx + rx] = 1;
+                {
+                    const float a[4] = {a0, a1, a2, a3};
+                    scatter_to_receivers(tris, T, rx_pos, nrx, o, d, tr, mat, mvel, h.theta, a, s[10], fsl_mult, dop_mult,
+                                         scat, (tx * nb + b) * npo + PO(p), ntx * nb * npo, dfs + i * (nrx + 1),
+                                         unblocked + i * nrx);
                 }
             }
 
@@ -700,6 +729,58 @@ int hrt_oracle_mirror(const hrt_oracle_scene *sc, const uint32_t *tri, const flo
         dd = sub3(dd, mul3(nn, 2.f * dn));
         st3(d_out + 3 * i, dd);
         st3(o_out + 3 * i, add3(ld3(o_in + 3 * i), mul3(dd, 1e-4f)));
+    }
+    free(tris);
+    return bad;
+}
+
+/* The scatter records of n entries of the caller's own: scatter_to_receivers (:671-723) for entry i with state
+ * o, d [n][3], tri [n] (flat index of the triangle the entry left: its normal, material and mesh velocity), theta [n],
+ * amp [n][4] (a_te_re, a_te_im, a_tm_re, a_tm_im), tau [n].  Outputs, all [nrx][n], written exactly where the
+ * reference writes (the caller pre-fills them; a blocked record gets its five zeros and nothing else): the four
+ * amplitudes, tau, dirs [nrx][n][3], dfs, unblocked (0 / 1, always written).  -1: allocation failure; -2: a triangle
+ * index past the table or a material index out of range (those entries are skipped). */
+int hrt_oracle_scatter_records(const hrt_oracle_scene *sc, float f_ghz, const float *rx_pos, size_t nrx, size_t n,
+                               const float *o, const float *d, const uint32_t *tri, const float *theta,
+                               const float *amp, const float *tau, float *a_te_re, float *a_te_im, float *a_tm_re,
+                               float *a_tm_im, float *tau_out, float *dirs, float *dfs, uint8_t *unblocked)
+{
+    const uint32_t T = sc->num_tri;
+    tri_t *tris = prepare_tris(sc);
+    if (!tris) return -1;
+    /* multipliers (:483-488) */
+    const float f_hz = (float)((double)f_ghz * 1e9);
+    const float fsl_mult = 4.f * HRT_PI_F * f_hz / HRT_C_F;
+    const float dop_mult = f_hz / HRT_C_F;
+    hrt_oracle_chan out = {dirs, NULL, a_te_re, a_te_im, a_tm_re, a_tm_im, tau_out, NULL};
+    int bad = 0;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (size_t i = 0; i < n; ++i) {
+        if (tri[i] >= T || sc->mesh_material[sc->tri_mesh[tri[i]]] >= HRT_NUM_MATERIALS) {
+#pragma omp atomic write
+            bad = -2;
+            continue;
+        }
+        const uint32_t mesh = sc->tri_mesh[tri[i]];
+        float l_dfs[64];
+        uint8_t l_ub[64];
+        /* (receivers in blocks of 64 would break the theta carry: the loop runs over all of them, into heap rows) */
+        float *rdfs = nrx <= 64 ? l_dfs : (float *)malloc(nrx * sizeof(float));
+        uint8_t *rub = nrx <= 64 ? l_ub : (uint8_t *)malloc(nrx);
+        if (!rdfs || !rub) {
+#pragma omp atomic write
+            bad = -1;
+        } else {
+            for (size_t rx = 0; rx < nrx; ++rx) rdfs[rx] = dfs[rx * n + i];   /* a blocked record keeps the pre-fill */
+            scatter_to_receivers(tris, T, rx_pos, nrx, ld3(o + 3 * i), ld3(d + 3 * i), &tris[tri[i]],
+                                 sc->mesh_material[mesh], ld3(sc->mesh_velocity + 3 * mesh), theta[i], amp + 4 * i,
+                                 tau[i], fsl_mult, dop_mult, &out, i, n, rdfs, rub);
+            for (size_t rx = 0; rx < nrx; ++rx) {
+                dfs[rx * n + i] = rdfs[rx];
+                unblocked[rx * n + i] = rub[rx];
+            }
+        }
+        if (nrx > 64) { free(rdfs); free(rub); }
     }
     free(tris);
     return bad;

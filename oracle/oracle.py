@@ -40,7 +40,7 @@ class _Opts(C.Structure):
     _fields_ = [("p_begin", C.c_uint64), ("p_end", C.c_uint64), ("p_stride", C.c_uint64),
                 ("num_threads", C.c_int), ("hit_tri", _u32p), ("hit_theta", _f32p),
                 ("live", _u64p), ("tests", _u64p), ("eta_table", _f32p), ("normals", _f32p),
-                ("launch_dirs", _f32p), ("compact", C.c_int)]
+                ("launch_dirs", _f32p), ("compact", C.c_int), ("hit_state", _f32p)]
 
 
 def build(force=False):
@@ -85,6 +85,9 @@ def lib():
         _lib.hrt_oracle_shadow_dirs.argtypes = [_f32p, _f32p, C.c_size_t, _f32p]
         _lib.hrt_oracle_mirror.restype = C.c_int
         _lib.hrt_oracle_mirror.argtypes = [C.POINTER(_Scene), _u32p, _f32p, _f32p, _f32p, C.c_size_t, _f32p, _f32p]
+        _lib.hrt_oracle_scatter_records.restype = C.c_int
+        _lib.hrt_oracle_scatter_records.argtypes = [C.POINTER(_Scene), C.c_float, _f32p, C.c_size_t, C.c_size_t, _f32p, _f32p,
+                                                    _u32p, _f32p, _f32p, _f32p] + [_f32p] * 7 + [_u8p]
     return _lib
 
 
@@ -141,8 +144,8 @@ def _p(a, t=_f32p):
 def compute_paths(scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces,
                   zero_freq_shift=None, subset=None, num_threads=0, extras=True):
     """Run the oracle; returns the same dict layout as hermespy_rt_amd.abi.run_compute_paths
-    plus 'extras' (hit_tri [nb, ntx, np], hit_theta, live [nb+1], tests, eta_table, normals,
-    launch_dirs).  `subset` = (p_begin, p_end, p_stride) restricts the processed paths."""
+    plus 'extras' (hit_tri [nb, ntx, np], hit_theta, hit_state [nb, ntx, np, 5] (the four amplitudes and tau after
+    the hit; sentinels where the ray did not hit), live [nb+1], tests, eta_table, normals, launch_dirs).  `subset` = (p_begin, p_end, p_stride) restricts the processed paths."""
     L = lib()
     flat = flatten(read_hrt(scene_path))
     T = flat["tri_vtx"].shape[0]
@@ -185,12 +188,13 @@ def compute_paths(scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, 
     ex = {}
     if extras:
         ex = dict(hit_tri=np.empty(nb * ntx * npth, np.uint32),
-                  hit_theta=_sentinel(nb * ntx * npth),
+                  hit_theta=_sentinel(nb * ntx * npth), hit_state=_sentinel(5 * nb * ntx * npth),
                   live=np.zeros(nb + 1, np.uint64), tests=np.zeros(1, np.uint64),
                   eta_table=np.zeros(17 * 12, np.float32), normals=np.zeros(3 * T, np.float32),
                   launch_dirs=np.zeros(3 * npth, np.float32))
         opts.hit_tri = _p(ex["hit_tri"], _u32p)
         opts.hit_theta = _p(ex["hit_theta"])
+        opts.hit_state = _p(ex["hit_state"])
         opts.live = _p(ex["live"], _u64p)
         opts.tests = _p(ex["tests"], _u64p)
         opts.eta_table = _p(ex["eta_table"])
@@ -215,6 +219,7 @@ def compute_paths(scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, 
     if extras:
         ex["hit_tri"] = ex["hit_tri"].reshape(nb, ntx, npth)
         ex["hit_theta"] = ex["hit_theta"].reshape(nb, ntx, npth)
+        ex["hit_state"] = ex["hit_state"].reshape(nb, ntx, npth, 5)
         ex["eta_table"] = ex["eta_table"].reshape(17, 12)
         ex["normals"] = ex["normals"].reshape(T, 3)
         ex["launch_dirs"] = ex["launch_dirs"].reshape(npth, 3)
@@ -349,3 +354,39 @@ def mirror(scene, tri, src, through, o):
     if rc != 0:
         raise RuntimeError("hrt_oracle_mirror failed: %d" % rc)
     return d, o2
+
+
+REC_FIELDS = ("a_te_re", "a_te_im", "a_tm_re", "a_tm_im", "tau", "dirx", "diry", "dirz", "dfs")
+
+
+def scatter_records(scene, f_ghz, rx_pos, states):
+    """The oracle's own per-receiver scatter loop (hrt_oracle.c scatter_to_receivers: Q6, Q7, Q8, the f2 rule, tau,
+    directions_rx, the Doppler term, the unblocked flag) for n entries of the caller's own.  states: dict(o [n][3],
+    d [n][3], tri [n] flat (reference-order) index of the triangle the entry left, theta [n], amp [n][4] (a_te_re,
+    a_te_im, a_tm_re, a_tm_im), tau [n]).  -> dict of REC_FIELDS, each float32 [nrx][n], + unblocked bool [nrx][n].
+    Fields the reference does not write (a blocked record's direction and Doppler term) hold SENTINEL_U32 bits."""
+    flat, sc = _scene_arg(scene)
+    rx = _rows3(rx_pos)
+    o, d = _rows3(states["o"]), _rows3(states["d"])
+    n, nrx = o.shape[0], rx.shape[0]
+    tri = np.ascontiguousarray(np.asarray(states["tri"], np.uint32).reshape(-1))
+    theta = np.ascontiguousarray(np.asarray(states["theta"], np.float32).reshape(-1))
+    amp = np.ascontiguousarray(np.asarray(states["amp"], np.float32).reshape(-1, 4))
+    tau = np.ascontiguousarray(np.asarray(states["tau"], np.float32).reshape(-1))
+    assert d.shape[0] == tri.size == theta.size == amp.shape[0] == tau.size == n
+    out = {k: _sentinel(nrx * n) for k in ("a_te_re", "a_te_im", "a_tm_re", "a_tm_im", "tau", "dfs")}
+    dirs = _sentinel(nrx * n * 3)
+    ub = np.full(nrx * n, 0xAD, np.uint8)
+    rc = lib().hrt_oracle_scatter_records(C.byref(sc), C.c_float(f_ghz), _p(rx), nrx, n, _p(o), _p(d), _p(tri, _u32p),
+                                          _p(theta), _p(amp), _p(tau), _p(out["a_te_re"]), _p(out["a_te_im"]),
+                                          _p(out["a_tm_re"]), _p(out["a_tm_im"]), _p(out["tau"]), _p(dirs), _p(out["dfs"]),
+                                          _p(ub, _u8p))
+    if rc != 0:
+        raise RuntimeError("hrt_oracle_scatter_records failed: %d" % rc)
+    dirs = dirs.reshape(nrx, n, 3)
+    res = {k: out[k].reshape(nrx, n) for k in out}
+    res.update(dirx=np.ascontiguousarray(dirs[..., 0]), diry=np.ascontiguousarray(dirs[..., 1]),
+               dirz=np.ascontiguousarray(dirs[..., 2]))
+    assert np.isin(ub, (0, 1)).all()
+    res["unblocked"] = ub.reshape(nrx, n).astype(bool)
+    return res

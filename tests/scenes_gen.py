@@ -124,6 +124,59 @@ def nasty(path):
     write_hrt(path, meshes)
 
 
+def _grid_quad(p0, eu, ev, nu, nv):
+    """the parallelogram p0 + s eu + t ev as nu x nv cells of two triangles: (vs, idx)"""
+    p0, eu, ev = (np.asarray(x, np.float64) for x in (p0, eu, ev))
+    vs = np.array([p0 + eu * (i / nu) + ev * (j / nv) for j in range(nv + 1) for i in range(nu + 1)], np.float32)
+    idx = []
+    for j in range(nv):
+        for i in range(nu):
+            a = j * (nu + 1) + i
+            idx += [[a, a + 1, a + nu + 2], [a, a + nu + 2, a + nu + 1]]
+    return vs, np.array(idx, np.uint32)
+
+
+#: endpoints of slab(): RX 0 behind wall A (every entry on wall A is blocked there within a millimetre), RX 1 behind
+#: wall B (from (0, 0.5, 2) on wall A the shadow ray meets wall B at exactly one metre), RX 2 sits 2^-8 m (3.9 mm) in
+#: front of wall A, RX 3 in the open
+SLAB_RX = [[-2.0, 1.0, 2.5], [3.0, 0.5, 2.0], [0.00390625, 0.25, 1.25], [4.0, -4.0, 3.0]]
+SLAB_TX = [[0.5, -3.0, 1.5]]
+
+
+def slab(path, moving=True):
+    """An axis-aligned scene on dyadic coordinates: a floor, wall A in the plane x = 0 and wall B parallel to it in
+    x = 1, EXACTLY one metre apart, a box of 6 x 3 x 3 x 2 triangles (so that the table has more than 64 rows: patch
+    tables), and one needle no patch grid can serve.  115 triangles in 5 meshes; moving=True gives every mesh but the
+    floor a velocity of its own (the walls' differ from the box's: a blocker's mesh is not the entry's).  Endpoints:
+    SLAB_RX, SLAB_TX.  Returns the triangle count."""
+    vel = (lambda v: v) if moving else (lambda v: [0, 0, 0])
+    quad = np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
+    meshes = [
+        dict(vs=np.array([[-4, -6, 0], [8, -6, 0], [8, 6, 0], [-4, 6, 0]], np.float32), idx=quad, material_index=1,
+             velocity=[0, 0, 0]),
+        dict(vs=np.array([[0, -2, 0], [0, 2, 0], [0, 2, 4], [0, -2, 4]], np.float32), idx=quad, material_index=2,
+             velocity=vel([0, 3, 0])),
+        dict(vs=np.array([[1, -2, 0], [1, 2, 0], [1, 2, 4], [1, -2, 4]], np.float32), idx=quad, material_index=5,
+             velocity=vel([-7, 0, 2])),
+    ]
+    c, h = np.array([4.0, 3.0, 1.0]), np.array([0.5, 0.5, 1.0])   # the box: 1 x 1 x 2 m, every face 3 x 3 cells
+    vs, idx = [], []
+    for ax in range(3):
+        u, v = (ax + 1) % 3, (ax + 2) % 3
+        for sgn in (-1.0, 1.0):
+            p0 = c.copy(); p0[ax] += sgn * h[ax]; p0[u] -= h[u]; p0[v] -= h[v]
+            eu, ev = np.zeros(3), np.zeros(3)
+            eu[u], ev[v] = 2 * h[u], 2 * h[v]
+            fv, fi = _grid_quad(p0, eu, ev, 3, 3)
+            idx.append(fi + sum(len(x) for x in vs)); vs.append(fv)
+    meshes.append(dict(vs=np.concatenate(vs), idx=np.concatenate(idx).astype(np.uint32), material_index=4,
+                       velocity=vel([12, -5, 1])))
+    meshes.append(dict(vs=np.array([[-3, -5, 0.5], [7, -5, 0.5], [2, -4.999, 0.5]], np.float32),
+                       idx=np.array([[0, 1, 2]], np.uint32), material_index=9, velocity=vel([0, 0, -4])))
+    write_hrt(path, meshes)
+    return sum(len(m["idx"]) for m in meshes)
+
+
 def cfg(scene_path, rx, tx, np_, nb, f=3.5, rx_vel=None, tx_vel=None):
     z = [0.0, 0.0, 0.0]
     return dict(scene_path=str(scene_path), rx_pos=rx, tx_pos=tx, rx_vel=rx_vel or [z] * len(rx),
