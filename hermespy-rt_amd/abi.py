@@ -1063,6 +1063,104 @@ def run_compute_channel_detect(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, 
     return detect_views(out, ds)
 
 
+KB_LLR, KB_SORTED = 1, 2               # hrt_kbest_spec.flags
+KB_NONFINITE, KB_DEFICIENT = 1, 2       # a point's `status`
+KB_NO_INDEX = 0xFFFFFFFF                # a non-finite point's `index` (status decides: with Nt B = 32 it is a hypothesis)
+KB_MAX_NR, KB_MAX_NT, KB_MAX_B, KB_MAX_BITS, KB_MAX_K = 64, 16, 8, 32, 64
+
+
+class KbestSpec(C.Structure):
+    """include/hermespy_rt.h hrt_kbest_spec"""
+    _fields_ = [("num_rx", C.c_uint32), ("num_tx", C.c_uint32), ("nr", C.c_uint32), ("nt", C.c_uint32),
+                ("num_times", C.c_uint32), ("num_freqs", C.c_uint32), ("bits", C.c_uint32), ("flags", C.c_uint32),
+                ("k", C.c_uint32), ("noise", C.c_float), ("clip", C.c_float)]
+
+
+def kbest_spec(num_rx, num_tx, nr, nt, num_times, num_freqs, bits, noise, k, clip, sorted=True, llr=True,
+               flags=None):
+    if flags is None:
+        flags = (KB_LLR if llr else 0) | (KB_SORTED if sorted else 0)
+    return KbestSpec(int(num_rx), int(num_tx), int(nr), int(nt), int(num_times), int(num_freqs), int(bits),
+                     int(flags), int(k), float(noise), float(clip))
+
+
+def kbest_regions(spec):
+    """the byte offsets of index, metric, status, llr and the end of a K-best detection output (hrt_kbest_out_bytes
+    is the last): detect_regions' layout"""
+    pts = int(spec.num_rx) * int(spec.num_tx) * 2 * int(spec.num_times) * int(spec.num_freqs)
+    o3 = 3 * pts * 4
+    return 0, pts * 4, 2 * pts * 4, o3, o3 + (pts * int(spec.nt) * int(spec.bits) * 4 if int(spec.flags) & KB_LLR else 0)
+
+
+def kbest_views(buf, spec):
+    """the regions of a flat uint8 K-best detection buffer as views, as detect_views gives them: index, metric, status
+    [nrx, ntx, 2, T, K], llr float32 [nrx, ntx, Nt, B, 2, T, K] (None where not asked for), buffer"""
+    o = kbest_regions(spec)
+    nrx, ntx, T, K = int(spec.num_rx), int(spec.num_tx), int(spec.num_times), int(spec.num_freqs)
+    if isinstance(buf, np.ndarray):
+        f32, u32 = np.float32, np.uint32
+    else:
+        import torch
+        f32, u32 = torch.float32, torch.int32
+    out = {"index": buf[o[0]:o[1]].view(u32).reshape(nrx, ntx, 2, T, K),
+           "metric": buf[o[1]:o[2]].view(f32).reshape(nrx, ntx, 2, T, K),
+           "status": buf[o[2]:o[3]].view(u32).reshape(nrx, ntx, 2, T, K), "llr": None, "buffer": buf}
+    if int(spec.flags) & KB_LLR:
+        out["llr"] = buf[o[3]:o[4]].view(f32).reshape(nrx, ntx, int(spec.nt), int(spec.bits), 2, T, K)
+    return out
+
+
+def kbest_fits(spec):
+    """whether the library accepts the spec (its limits, mirrored: an output beyond them is not allocated)"""
+    grid = int(spec.num_times) * int(spec.num_freqs)
+    nr, nt, b, k = int(spec.nr), int(spec.nt), int(spec.bits), int(spec.k)
+    return (0 < nr <= KB_MAX_NR and 0 < b <= KB_MAX_B and 0 < nt <= KB_MAX_NT and nt * b <= KB_MAX_BITS
+            and 0 < k <= KB_MAX_K and not k & (k - 1)
+            and 0 < nr * nt * grid <= 1 << 24 and 0 < int(spec.num_rx) * int(spec.num_tx) * 2 * grid < 1 << 31
+            and not int(spec.flags) & ~(KB_LLR | KB_SORTED) and _pc_positive(spec.noise) and _pc_positive(spec.clip))
+
+
+def run_kbest(lib, device, spec, d_H, d_Y, d_constellation, d_out, stream=None):
+    """hrt_channel_kbest through ctypes on device pointers (integers or None).  Raises
+    RuntimeError("hrt_channel_kbest failed (<rc>): ...") on an error code."""
+    rc = lib.hrt_channel_kbest(int(device), C.byref(spec) if spec is not None else None, C.c_void_p(d_H),
+                               C.c_void_p(d_Y), C.c_void_p(d_constellation), C.c_void_p(d_out), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("hrt_channel_kbest failed (%d): %s" % (rc, lib.hrt_last_error().decode()))
+
+
+def run_compute_channel_kbest(lib, scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, num_paths, num_bounces, spec,
+                              rx_elements, tx_elements, Y, constellation, noise, k, clip, sorted=True, llr=True,
+                              flags=None, array_frequency=None, stats=None):
+    """hrt_compute_channel_kbest through ctypes -> kbest_views of a uint8 numpy buffer; the arguments are
+    run_compute_channel_detect's, with the list size k, the LLR clip and the ordering switch.  Detection runs once,
+    on the H accumulated over all batches.  A Y of another shape or a constellation whose size is no power of two
+    raises ValueError.  Raises RuntimeError("hrt_compute_channel_kbest failed (<rc>): ...") on an error code."""
+    nr, nt, extra = _array_args(rx_elements, tx_elements, f_ghz, array_frequency)
+    nrx, ntx = np.asarray(rx_pos).size // 3, np.asarray(tx_pos).size // 3
+    fp = C.POINTER(C.c_float)
+    if constellation is None:
+        s, b = None, 1
+    else:
+        s, b = constellation_array(constellation)
+        if b < 0:
+            raise ValueError("constellation must hold 2^B symbols, got %d" % s.shape[0])
+    ks = kbest_spec(nrx, ntx, nr, nt, int(spec.num_times), int(spec.num_freqs), b, noise, k, clip, sorted, llr, flags)
+    y = None if Y is None else np.ascontiguousarray(Y, np.complex64)
+    if y is not None and y.shape != (nrx, ntx, nr, 2, int(spec.num_times), int(spec.num_freqs)):
+        raise ValueError("Y [%d, %d, %d, 2, %d, %d] expected, got %s"
+                         % (nrx, ntx, nr, int(spec.num_times), int(spec.num_freqs), y.shape))
+    extra += (y.ctypes.data_as(fp) if y is not None else None, s.ctypes.data_as(fp) if s is not None else None,
+              C.c_uint32(int(ks.bits)), C.c_uint32(int(ks.flags)), C.c_uint32(int(ks.k)), C.c_float(ks.noise),
+              C.c_float(ks.clip))
+    fits = kbest_fits(ks) and s is not None and y is not None
+    out = _run_pathsum(lib, "hrt_compute_channel_kbest", scene_path, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz,
+                       num_paths, num_bounces, spec, (kbest_regions(ks)[4],) if fits else None, extra, stats, np.uint8)
+    if not fits:
+        raise RuntimeError("hrt_compute_channel_kbest accepted a call beyond its limits")
+    return kbest_views(out, ks)
+
+
 # hrt_power_spec: the moments' field indices (include/hermespy_rt.h HRT_POWER_*)
 (POWER_COUNT, POWER_P, POWER_P_TAU, POWER_P_TAU2, POWER_P_NU, POWER_P_NU2, POWER_P_URX_X, POWER_P_URX_Y,
  POWER_P_URX_Z, POWER_P_UTX_X, POWER_P_UTX_Y, POWER_P_UTX_Z, POWER_P_LOS, POWER_FIELDS) = range(14)

@@ -1,7 +1,7 @@
 /* channel.c -- channel frequency responses, impulse responses, power statistics and the strongest paths from traced
  * paths, on the device (include/hrt_device.h: hrt_channel, hrt_array_channel, hrt_taps, hrt_array_taps,
  * hrt_power_profiles, hrt_dominant_paths, hrt_beam_channel, hrt_beam_taps, hrt_array_covariance, hrt_propagate,
- * hrt_channel_svd, hrt_channel_equalizer, hrt_channel_precoder, hrt_codebook_select, hrt_channel_detect, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
+ * hrt_channel_svd, hrt_channel_equalizer, hrt_channel_precoder, hrt_codebook_select, hrt_channel_detect, hrt_channel_kbest, hrt_sparse_array_channel, hrt_sparse_array_taps, hrt_sparse_beam_channel,
  * hrt_sparse_beam_taps;
  * include/hermespy_rt.h: hrt_compute_array_covariance, hrt_compute_received_signal, hrt_compute_channel,
  * hrt_compute_array_channel, hrt_compute_taps, hrt_compute_array_taps, hrt_compute_power_profiles,
@@ -36,6 +36,7 @@
 #include "../hrt_detect.h"
 #include "../hrt_dominant.h"
 #include "../hrt_equalizer.h"
+#include "../hrt_kbest.h"
 #include "../hrt_pathsum.h"
 #include "../hrt_patterns.h"
 #include "../hrt_power.h"
@@ -1657,6 +1658,138 @@ int hrt_compute_channel_detect(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
     job.aux = &aux;
     return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
                       out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_detect");
+}
+
+/* ------------------------------------------------------------------ K-best tree-search detection (hrt_channel_kbest) */
+
+/* the checks of a K-best detection call (`who`); device pointers are not read */
+static int kb_check(const hrt_kbest_spec *sp, const char *who)
+{
+    if (!sp) return hrt_fail(HRT_E_INVALID, "%s: NULL spec", who);
+    if (sp->num_rx == 0 || sp->num_tx == 0 || sp->num_times == 0 || sp->num_freqs == 0)
+        return hrt_fail(HRT_E_INVALID, "%s: num_rx, num_tx, num_times and num_freqs must be > 0", who);
+    if (sp->nr < 1 || sp->nr > HRT_KB_MAX_NR)
+        return hrt_fail(HRT_E_INVALID, "%s: nr = %u (1 .. %u)", who, sp->nr, HRT_KB_MAX_NR);
+    if (sp->bits < 1 || sp->bits > HRT_KB_MAX_B)
+        return hrt_fail(HRT_E_INVALID, "%s: bits = %u (1 .. %u)", who, sp->bits, HRT_KB_MAX_B);
+    if (sp->nt < 1 || sp->nt > HRT_KB_MAX_NT || sp->nt * sp->bits > HRT_KB_MAX_BITS)
+        return hrt_fail(HRT_E_INVALID, "%s: nt = %u streams of %u bits (1 <= nt <= %u, nt * bits <= %u)", who, sp->nt,
+                        sp->bits, HRT_KB_MAX_NT, HRT_KB_MAX_BITS);
+    if (!hrt_kbest_k_ok(sp->k))
+        return hrt_fail(HRT_E_INVALID, "%s: k = %u (1, 2, 4, .. %u)", who, sp->k, HRT_KB_MAX_K);
+    if (sp->flags & ~(HRT_KB_LLR | HRT_KB_SORTED))
+        return hrt_fail(HRT_E_INVALID, "%s: flags = 0x%x has unknown bits", who, sp->flags);
+    if (!pc_positive(sp->noise))
+        return hrt_fail(HRT_E_INVALID, "%s: noise = %g must be finite and > 0", who, (double)sp->noise);
+    if (!pc_positive(sp->clip))
+        return hrt_fail(HRT_E_INVALID, "%s: clip = %g must be finite and > 0", who, (double)sp->clip);
+    const uint64_t grid = (uint64_t)sp->num_times * sp->num_freqs;   /* < 2^64 */
+    if (grid > HRT_EQ_MAX_POINTS || (uint64_t)sp->nr * sp->nt * grid > HRT_EQ_MAX_POINTS)
+        return hrt_fail(HRT_E_INVALID, "%s: nr * nt * num_times * num_freqs > 2^24", who);
+    if ((uint64_t)sp->num_rx * sp->num_tx >= (1ull << 31) / (2u * grid))
+        return hrt_fail(HRT_E_INVALID, "%s: 2^31 points or more", who);
+    return HRT_OK;
+}
+
+uint64_t hrt_kbest_out_bytes(const hrt_kbest_spec *spec)
+{
+    if (!spec) return 0;
+    const uint64_t points = (uint64_t)spec->num_rx * spec->num_tx * 2u * spec->num_times * spec->num_freqs;
+    return points * 12u + ((spec->flags & HRT_KB_LLR) ? points * spec->nt * spec->bits * 4u : 0u);
+}
+
+int hrt_channel_kbest(int device, const hrt_kbest_spec *spec, const void *d_H, const void *d_Y,
+                      const void *d_constellation, void *d_out, void *stream)
+{
+    int rc = kb_check(spec, "hrt_channel_kbest");
+    if (rc) return rc;
+    if (!d_H || !d_Y || !d_constellation || !d_out)
+        return hrt_fail(HRT_E_INVALID, "hrt_channel_kbest: NULL device pointer");
+    hrt_kkbest K;
+    memset(&K, 0, sizeof K);
+    K.nr = spec->nr; K.nt = spec->nt; K.b = spec->bits; K.k = spec->k;
+    K.g = hrt_kbest_form(K.nr, K.nt, K.k);
+    K.mk = (K.nr + K.g - 1u) / K.g;
+    K.llr = (spec->flags & HRT_KB_LLR) != 0u;
+    K.sorted = (spec->flags & HRT_KB_SORTED) != 0u;
+    /* (HRT_KBEST_NO_SKIP=1 walks every batch: for measuring the skip, the bytes are the same) */
+    const char *ns = getenv("HRT_KBEST_NO_SKIP");
+    K.skip = !(ns && ns[0] == '1');
+    K.n0 = spec->noise;
+    K.clip = spec->clip;
+    K.pts = 2u * spec->num_times * spec->num_freqs;                 /* <= 2^25 */
+    K.points = spec->num_rx * spec->num_tx * K.pts;                 /* < 2^31 */
+    K.out = d_out;                  /* (the kernel places the regions by hrt_kbest_out_bytes' rule) */
+    HRT_HIP(hrt_hip_set_device(device), "hipSetDevice");
+    HRT_HIP(hrt_hip_launch_kbest(&K, d_H, d_Y, d_constellation, stream), "K-best detection kernel");
+    return HRT_OK;
+}
+
+typedef struct {
+    hrt_kbest_spec spec;
+    const float *Y;                 /* host, complex [num_rx][num_tx][nr][2][T][K] */
+    const float *constellation;     /* host, complex [2^bits] */
+} kb_job_aux;
+
+/* after the last batch: H stays at d_H; Y and the constellation go up, detection runs once, only its result comes
+ * down */
+static int kb_job_deliver(const ch_job *j, int device, const void *d_H, void *out)
+{
+    const kb_job_aux *a = (const kb_job_aux *)j->aux;
+    const uint64_t bytes = hrt_kbest_out_bytes(&a->spec);
+    const uint64_t y_bytes = (uint64_t)a->spec.num_rx * a->spec.num_tx * a->spec.nr * 2u * a->spec.num_times
+                             * a->spec.num_freqs * 8u;
+    const uint64_t s_bytes = 8ull << a->spec.bits;
+    void *d_kb = NULL, *d_y = NULL, *d_s = NULL;
+    int rc = hrt_device_malloc(device, &d_kb, bytes);
+    if (!rc) rc = hrt_device_malloc(device, &d_y, y_bytes);
+    if (!rc) rc = hrt_device_malloc(device, &d_s, s_bytes);
+    if (!rc) rc = hrt_device_upload(device, d_y, a->Y, y_bytes);
+    if (!rc) rc = hrt_device_upload(device, d_s, a->constellation, s_bytes);
+    if (!rc) rc = hrt_channel_kbest(device, &a->spec, d_H, d_y, d_s, d_kb, NULL);
+    if (!rc) rc = hrt_device_sync(device, NULL);
+    if (!rc) rc = hrt_device_download(device, out, d_kb, bytes);
+    if (d_s) hrt_device_free(device, d_s);
+    if (d_y) hrt_device_free(device, d_y);
+    if (d_kb) hrt_device_free(device, d_kb);
+    return rc;
+}
+
+int hrt_compute_channel_kbest(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                              const Vec3 *tx_vel, float f_ghz, size_t nrx, size_t ntx, size_t np, size_t nb,
+                              const hrt_channel_spec *spec, const Vec3 *rx_el, size_t nr, const Vec3 *tx_el,
+                              size_t nt, double f_a, const float *Y, const float *constellation, uint32_t bits,
+                              uint32_t flags, uint32_t k, float noise, float clip, void *out, hrt_stats *stats)
+{
+    const double t_begin = hrt_now_s();
+    int rc = ac_counts_check(nr, nt, "hrt_array_channel");
+    if (rc) return rc;
+    /* (the element pointers stand in for the device ones: array_check tests them for NULL only) */
+    const hrt_array_spec a = {(uint32_t)nr, (uint32_t)nt, (const float *)rx_el, (const float *)tx_el, f_a};
+    if ((rc = array_check(spec, &a))) return rc;
+    if (!out || !Y || !constellation) return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_kbest: NULL argument");
+    if (nrx > UINT32_MAX || ntx > UINT32_MAX)
+        return hrt_fail(HRT_E_INVALID, "hrt_compute_channel_kbest: num_rx or num_tx > 2^32");
+    kb_job_aux aux;
+    memset(&aux, 0, sizeof aux);
+    aux.Y = Y;
+    aux.constellation = constellation;
+    aux.spec.num_rx = (uint32_t)nrx; aux.spec.num_tx = (uint32_t)ntx;
+    aux.spec.nr = (uint32_t)nr; aux.spec.nt = (uint32_t)nt;
+    aux.spec.num_times = spec->num_times; aux.spec.num_freqs = spec->num_freqs;
+    aux.spec.bits = bits; aux.spec.flags = flags; aux.spec.k = k; aux.spec.noise = noise; aux.spec.clip = clip;
+    /* (num_rx and num_tx 0: ch_drop_in_check's refusal, below, as in hrt_compute_array_channel) */
+    if (nrx && ntx && (rc = kb_check(&aux.spec, "hrt_compute_channel_kbest"))) return rc;
+    ch_job job;
+    memset(&job, 0, sizeof job);
+    job.spec = spec;
+    job.out_bytes = (uint64_t)nrx * ntx * nr * nt * 2u * spec->num_times * spec->num_freqs * 8u;
+    job.scratch_bytes = ac_job_scratch;
+    job.run = ac_job_run;
+    job.deliver = kb_job_deliver;
+    job.aux = &aux;
+    return ac_compute(scene, rx_pos, tx_pos, rx_vel, tx_vel, f_ghz, nrx, ntx, np, nb, &job, rx_el, nr, tx_el, nt, f_a,
+                      out, stats, t_begin, "hrt_array_channel", "hrt_compute_channel_kbest");
 }
 
 /* ------------------------------------------------------------------ power statistics (hrt_power_profiles) */

@@ -826,6 +826,88 @@ py::dict compute_channel_detect_py(
     return d;
 }
 
+// compute_channel_kbest: per-point K-best tree-search detection with list max-log bit LLRs on compute_array_channel's
+// H, formed on the device (extension; see hrt_compute_channel_kbest in hermespy_rt.h): the dict of
+// compute_channel_detect -- index, metric, status, llr (None without llr=True), buffer.  k: the list size (1, 2, 4, ..
+// 64); clip: the LLR clip; sorted: sorted QR.  Detection runs once, on the H of all batches.
+py::dict compute_channel_kbest_py(
+    const std::string &mesh_filepath, farr rx_positions, farr tx_positions, farr rx_velocities, farr tx_velocities,
+    float carrier_frequency, unsigned long num_rx, unsigned long num_tx, unsigned long num_paths,
+    unsigned long num_bounces, double f0, double df, unsigned long num_freqs, farr rx_elements, farr tx_elements,
+    py::array Y, py::array constellation, float noise, unsigned long k, float clip, double t0, double dt,
+    unsigned long num_times, bool los, bool scatter, py::object array_frequency, bool sorted, bool llr,
+    py::object patterns)
+{
+    const endpoints e(rx_positions, tx_positions, rx_velocities, tx_velocities, num_rx, num_tx, num_paths, num_bounces);
+    if (num_freqs > 0xffffffffUL || num_times > 0xffffffffUL || num_rx > 0xffffffffUL || num_tx > 0xffffffffUL
+        || k > 0xffffffffUL)
+        throw std::invalid_argument("num_rx, num_tx, num_freqs, num_times and k must fit 32 bits");
+    const array_elements a(rx_elements, tx_elements);
+    const size_t nr = a.nr, nt = a.nt;
+    using cf = py::array_t<std::complex<float>, py::array::c_style | py::array::forcecast>;
+    const auto sy = cf::ensure(constellation);
+    if (!sy || sy.ndim() != 1) throw std::invalid_argument("constellation must be a complex array of shape (M,)");
+    const size_t M_ = (size_t)sy.shape(0);
+    uint32_t bits = 0;
+    while (bits < 31u && ((size_t)1 << bits) < M_) ++bits;
+    if (M_ < 2u || ((size_t)1 << bits) != M_) throw std::invalid_argument("constellation must hold 2^B symbols");
+    const auto yy = cf::ensure(Y);
+    if (!yy || yy.ndim() != 6 || (size_t)yy.shape(0) != num_rx || (size_t)yy.shape(1) != num_tx
+        || (size_t)yy.shape(2) != nr || yy.shape(3) != 2 || (size_t)yy.shape(4) != num_times
+        || (size_t)yy.shape(5) != num_freqs)
+        throw std::invalid_argument("Y must be a complex array of shape (num_rx, num_tx, Nr, 2, num_times, num_freqs)");
+    const double fa = array_frequency.is_none() ? (double)carrier_frequency * 1e9 : array_frequency.cast<double>();
+    check_scene_file(mesh_filepath);
+    hrt_channel_spec spec{};
+    spec.f0_hz = f0; spec.df_hz = df; spec.num_freqs = (uint32_t)num_freqs;
+    spec.t0_s = t0; spec.dt_s = dt; spec.num_times = (uint32_t)num_times;
+    spec.parts = parts_word(los, scatter);
+    const uint32_t flags = (llr ? HRT_KB_LLR : 0u) | (sorted ? HRT_KB_SORTED : 0u);
+    hrt_kbest_spec ks{};
+    ks.num_rx = (uint32_t)num_rx; ks.num_tx = (uint32_t)num_tx; ks.nr = (uint32_t)nr; ks.nt = (uint32_t)nt;
+    ks.num_times = (uint32_t)num_times; ks.num_freqs = (uint32_t)num_freqs; ks.bits = bits; ks.flags = flags;
+    ks.k = (uint32_t)k; ks.noise = noise; ks.clip = clip;
+    // (the library validates everything before it traces anything: a refused call raises ValueError; an output beyond
+    // its limits is not allocated)
+    const size_t pts = (size_t)num_rx * num_tx * 2u * num_times * num_freqs;
+    const bool fits = a.fits((unsigned long long)num_times * num_freqs) && nr <= 64u && nt <= 16u && bits >= 1u
+                      && bits <= 8u && nt * bits <= 32u && pts < (1ull << 31);
+    py::array_t<uint8_t> buf(fits ? (size_t)hrt_kbest_out_bytes(&ks) : (size_t)1);
+    uint8_t *dst = buf.mutable_data();
+    const pattern_scope pattern_guard(patterns, num_rx, num_tx);
+    run_pathsum("compute_channel_kbest", mesh_filepath, [&](Scene *scene) {
+        return hrt_compute_channel_kbest(scene, e.rxp, e.txp, e.rxv, e.txv, carrier_frequency, num_rx, num_tx,
+                                         num_paths, num_bounces, &spec, a.rxe, a.nr, a.txe, a.nt, fa,
+                                         reinterpret_cast<const float *>(yy.data()),
+                                         reinterpret_cast<const float *>(sy.data()), bits, flags, (uint32_t)k, noise,
+                                         clip, dst, nullptr);
+    });
+    size_t off = 0;
+    auto view = [&](auto zero, std::vector<size_t> shape) {
+        using T = decltype(zero);
+        std::vector<py::ssize_t> strides(shape.size());
+        py::ssize_t st = sizeof(T);
+        size_t count = 1;
+        for (size_t i = shape.size(); i-- > 0;) {
+            strides[i] = st;
+            st *= (py::ssize_t)shape[i];
+            count *= shape[i];
+        }
+        py::array_t<T> v(shape, strides, reinterpret_cast<T *>(dst + off), buf);
+        off += count * sizeof(T);
+        return v;
+    };
+    const size_t R = num_rx, X = num_tx, T_ = num_times, K_ = num_freqs;
+    py::dict d;
+    d["index"] = view((uint32_t)0, {R, X, 2, T_, K_});
+    d["metric"] = view(0.0f, {R, X, 2, T_, K_});
+    d["status"] = view((uint32_t)0, {R, X, 2, T_, K_});
+    if (llr) d["llr"] = view(0.0f, {R, X, nt, (size_t)bits, 2, T_, K_});
+    else d["llr"] = py::none();
+    d["buffer"] = buf;
+    return d;
+}
+
 // a codebook argument of compute_beam_channel: complex64 (beams, n_elements), C-contiguous (copied if it is not)
 using carr = py::array_t<std::complex<float>, py::array::c_style>;
 carr as_weights(const py::array &w, size_t n_elements, const char *name)
@@ -1529,6 +1611,18 @@ PYBIND11_MODULE(hermespy_rt, m)
           py::arg("Y"), py::arg("constellation"), py::arg("noise"), py::arg("t0") = 0.0, py::arg("dt") = 0.0,
           py::arg("num_times") = 1, py::arg("los") = true, py::arg("scatter") = true,
           py::arg("array_frequency") = py::none(), py::arg("llr") = true, py::arg("patterns") = py::none());
+    m.def("compute_channel_kbest", &compute_channel_kbest_py,
+          "Per-point K-best tree-search MIMO detection with list max-log bit LLRs on the antenna-array channel, formed "
+          "on the device: a dict of views of one buffer -- index, metric, status (num_rx, num_tx, 2, num_times, "
+          "num_freqs), llr (num_rx, num_tx, Nt, B, 2, num_times, num_freqs), buffer",
+          py::arg("mesh_filepath"), py::arg("rx_positions"), py::arg("tx_positions"),
+          py::arg("rx_velocities"), py::arg("tx_velocities"), py::arg("carrier_frequency"),
+          py::arg("num_rx"), py::arg("num_tx"), py::arg("num_paths"), py::arg("num_bounces"),
+          py::arg("f0"), py::arg("df"), py::arg("num_freqs"), py::arg("rx_elements"), py::arg("tx_elements"),
+          py::arg("Y"), py::arg("constellation"), py::arg("noise"), py::arg("k"), py::arg("clip"),
+          py::arg("t0") = 0.0, py::arg("dt") = 0.0, py::arg("num_times") = 1, py::arg("los") = true,
+          py::arg("scatter") = true, py::arg("array_frequency") = py::none(), py::arg("sorted") = true,
+          py::arg("llr") = true, py::arg("patterns") = py::none());
     m.def("compute_beam_channel", &compute_beam_channel_py,
           "Beamformed (codebook) channel of the traced paths, formed on the device: complex64 "
           "(num_rx, num_tx, Br, Bt, 2, num_times, num_freqs); rx_weights (Br, Nr) is applied conjugated, tx_weights "

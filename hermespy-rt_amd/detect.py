@@ -10,6 +10,8 @@ bit bookkeeping around the hard decision and the LLRs.
     hard_bits           the bits of every stream of a hypothesis q
     bit_errors          the number of differing bits
     linear_llrs         the max-log LLRs behind a linear equalizer (Tracer.equalizer's W and sinr), for comparison
+    kbest_reference     the K-best tree search (Tracer.kbest, hrt_kbest_spec) in float64, device layout, with the
+                        pruning gaps that tell which points a float32 search may decide differently
 
 The conventions are those of include/hermespy_rt.h (hrt_detect_spec): H [nrx, ntx, Nr, Nt, 2, T, K], Y
 [nrx, ntx, Nr, 2, T, K], a constellation [M = 2^B] used as given whose index is the bit label, hypothesis q < M^Nt with
@@ -22,6 +24,8 @@ import numpy as np
 NONFINITE = 1
 NO_INDEX = 0xFFFFFFFF
 MAX_BITS = 12
+DEFICIENT = 2                           # hrt_kbest_spec: a null column
+KB_MAX_NT, KB_MAX_BITS, KB_MAX_K = 16, 32, 64
 
 
 def _bits_of(constellation):
@@ -179,6 +183,127 @@ def ml_reference(H, Y, constellation, noise, llr=True, table=False):
     if table:
         out["distances"] = d
     return out
+
+
+def kbest_reference(H, Y, constellation, noise, k, clip, sorted=True, llr=True):
+    """The K-best tree search of include/hermespy_rt.h (hrt_kbest_spec) in float64 in the device layout: QR of
+    [H | y] by modified Gram-Schmidt (sorted: the smallest residual column next, the lowest stream on a tie; a column
+    at or below the threshold is null), the tree from the last position with PED = rho at the root, the K smallest
+    (PED', key) of a level survive, the decision and the clamped max-log LLRs over the final list.  -> dict:
+    index uint32, metric float64 and status uint32 [nrx, ntx, 2, T, K] (NONFINITE: index NO_INDEX, metric 0, zero
+    LLRs; DEFICIENT: a null column), llr float64 [nrx, ntx, Nt, B, 2, T, K] (None without llr), and per point
+        gap        the smallest PED difference between the K-th and the (K + 1)-th candidate of any level, relative to
+                   sigma = (|y|_2 + |H|_F max|S| sqrt(Nt))^2 (inf where no level had more than K candidates)
+        order_gap  sorted only: the smallest difference between the two smallest residual norms at a pick, relative
+                   to the largest squared column norm of H (inf unsorted)
+        lead       the PED difference of the two best leaves of the final list, relative to sigma (inf: one leaf)
+    A float32 search may keep another list where gap is of the order of float32's rounding, another order where
+    order_gap is, another index where lead is."""
+    S, B = _bits_of(constellation)
+    n0, cl, K = float(noise), float(clip), int(k)
+    if not 0.0 < n0 < np.inf:
+        raise ValueError("noise must be finite and > 0, got %r" % (noise,))
+    if not 0.0 < cl < np.inf:
+        raise ValueError("clip must be finite and > 0, got %r" % (clip,))
+    if K < 1 or K > KB_MAX_K or K & (K - 1):
+        raise ValueError("k must be 1, 2, 4, .. %d, got %r" % (KB_MAX_K, k))
+    H, Y = np.asarray(H, np.complex128), np.asarray(Y, np.complex128)
+    if H.ndim != 7 or H.shape[4] != 2 or Y.shape != H.shape[:3] + H.shape[4:]:
+        raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] and Y [nrx, ntx, Nr, 2, T, K] expected, got %s and %s"
+                         % (H.shape, Y.shape))
+    nr, nt = H.shape[2], H.shape[3]
+    if nt > KB_MAX_NT or nt * B > KB_MAX_BITS:
+        raise ValueError("Nt = %d, Nt * B = %d: beyond %d and %d" % (nt, nt * B, KB_MAX_NT, KB_MAX_BITS))
+    M = 1 << B
+    lead_shape = H.shape[:2] + H.shape[4:]
+    A = np.concatenate([_points(H), np.moveaxis(Y, 2, -1)[..., None]], -1).reshape(-1, nr, nt + 1)
+    P = A.shape[0]
+    ar = np.arange(P)
+    with np.errstate(all="ignore"):
+        n2 = (A.real ** 2 + A.imag ** 2).sum(1)                 # [P, Nt + 1]
+        bad = ~np.isfinite(n2.sum(-1))
+        A = np.where(bad[:, None, None], 0.0, A)
+        n2 = np.where(bad[:, None], 0.0, n2)
+        nmax = n2[:, :nt].max(-1)
+        sigma = (np.sqrt(n2[:, nt]) + np.sqrt(n2[:, :nt].sum(-1)) * np.abs(S).max() * np.sqrt(nt)) ** 2
+        thr = (nr + nt) * 2.0 ** -23 * np.sqrt(nmax)
+        R = np.zeros((P, nt, nt), np.complex128)                # [position, stream]
+        z = np.zeros((P, nt), np.complex128)
+        order = np.zeros((P, nt), np.int64)
+        chosen = np.zeros((P, nt + 1), bool)
+        deficient = np.zeros(P, bool)
+        order_gap = np.full(P, np.inf)
+        for t in range(nt):
+            cn = (A[:, :, :nt].real ** 2 + A[:, :, :nt].imag ** 2).sum(1)
+            if sorted:
+                cn = np.where(chosen[:, :nt], np.inf, cn)
+                c = np.argmin(cn, -1)                           # the first of the smallest
+                if t + 1 < nt:
+                    two = np.sort(cn, -1)[:, :2]
+                    order_gap = np.minimum(order_gap, (two[:, 1] - two[:, 0]) / np.where(nmax > 0, nmax, 1.0))
+            else:
+                c = np.full(P, t)
+            r = np.sqrt(cn[ar, c])
+            null = ~(r > thr)
+            deficient |= null
+            q = np.where(null[:, None], 0.0, A[ar, :, c] / np.where(null, 1.0, r)[:, None])
+            A[ar, :, c] = np.where(null[:, None], A[ar, :, c], q)
+            chosen[ar, c] = True
+            w = np.where(chosen, 0.0, np.einsum("pi,pij->pj", np.conj(q), A))
+            A = A - q[:, :, None] * w[:, None, :]
+            R[:, t, :] = w[:, :nt]
+            R[ar, t, c] = np.where(null, 0.0, r)
+            z[:, t] = w[:, nt]
+            order[:, t] = c
+        rho = (A[:, :, nt].real ** 2 + A[:, :, nt].imag ** 2).sum(1)
+        bad |= ~np.isfinite(rho)
+        ped, key = rho[:, None].copy(), np.zeros((P, 1), np.int64)
+        gap = np.full(P, np.inf)
+        x = np.arange(M)
+        for i in range(nt - 1, -1, -1):
+            c = order[:, i]
+            b = np.repeat(z[:, i, None], ped.shape[1], 1)
+            acc = None
+            for t in range(i + 1, nt):
+                u = order[:, t]
+                term = R[ar, i, u][:, None] * S[(key >> (u * B)[:, None]) & (M - 1)]
+                acc = term if acc is None else acc + term
+            if acc is not None:
+                b = b - acc
+            e = b[:, :, None] - R[ar, i, c].real[:, None, None] * S[None, None, :]
+            cp = (ped[:, :, None] + (e.real ** 2 + e.imag ** 2)).reshape(P, -1)
+            ck = (key[:, :, None] | (x[None, None, :] << (c * B)[:, None, None])).reshape(P, -1)
+            o1 = np.argsort(ck, -1, kind="stable")
+            cp, ck = np.take_along_axis(cp, o1, -1), np.take_along_axis(ck, o1, -1)
+            o2 = np.argsort(cp, -1, kind="stable")              # (NaN last; such a point is flagged)
+            cp, ck = np.take_along_axis(cp, o2, -1), np.take_along_axis(ck, o2, -1)
+            bad |= ~np.isfinite(cp).all(-1)
+            if cp.shape[1] > K:
+                gap = np.minimum(gap, (cp[:, K] - cp[:, K - 1]) / np.where(sigma > 0, sigma, 1.0))
+            ped, key = cp[:, :K], ck[:, :K]
+        index, best = key[:, 0], ped[:, 0]
+        lead = (ped[:, 1] - ped[:, 0]) / np.where(sigma > 0, sigma, 1.0) if ped.shape[1] > 1 else np.full(P, np.inf)
+        L = None
+        if llr:
+            L = np.empty((P, nt, B))
+            for j in range(nt):
+                for bb in range(B):
+                    one = ((key >> (j * B + (B - 1 - bb))) & 1).astype(bool)
+                    m0 = np.where(one, np.inf, ped).min(-1)
+                    m1 = np.where(one, ped, np.inf).min(-1)
+                    both = np.isfinite(m0) & np.isfinite(m1)
+                    v = np.where(both, m0, 0.0) - np.where(both, m1, 0.0)
+                    v = v / n0
+                    bad |= both & ~np.isfinite(v)
+                    v = np.clip(v, -cl, cl)
+                    L[:, j, bb] = np.where(both, v, np.where(np.isfinite(m0), -cl, cl))
+            L = np.where(bad[:, None, None], 0.0, L)
+            L = np.moveaxis(L.reshape(lead_shape + (nt, B)), (-2, -1), (2, 3))
+    status = np.where(bad, NONFINITE, np.where(deficient, DEFICIENT, 0))
+    sh = lambda v: v.reshape(lead_shape)
+    return {"index": sh(np.where(bad, NO_INDEX, index).astype(np.uint32)), "metric": sh(np.where(bad, 0.0, best)),
+            "status": sh(status.astype(np.uint32)), "llr": L, "gap": sh(gap), "order_gap": sh(order_gap),
+            "lead": sh(lead)}
 
 
 def linear_llrs(W, sinr, Y, constellation, kind="lmmse"):

@@ -1057,6 +1057,86 @@ class Tracer:
                                array_frequency)
         return self.detect(H, Y, constellation, noise, llr)
 
+    def kbest(self, H, Y, constellation, noise, k, clip, sorted=True, llr=True, out=None):
+        """Per-point K-best tree-search MIMO detection with list max-log bit LLRs on an array channel, on the device
+        (hrt_channel_kbest; include/hermespy_rt.h hrt_kbest_spec): near-ML detection at sizes detect() refuses
+        (4 x 4 with 16-, 64- or 256-QAM, 8 streams of QPSK or 16-QAM).  H, Y, the constellation, the hypothesis index
+        and the bit order are detect()'s.  [H | y] is factored by modified Gram-Schmidt -- sorted QR with
+        `sorted` (the weakest residual column first, so the strongest stream is detected first), stream order
+        without --, then the tree is walked from the last position, the `k` paths (1, 2, 4, .. 64) of smallest
+        partial distance surviving every level, ties to the lower partial hypothesis index:
+
+            index   int32    [nrx, ntx, 2, T, K]          the best leaf of the final list (-1: non-finite; with
+                                                          Nt B = 32 a hypothesis reads -1 too: status decides)
+            metric  float32  [nrx, ntx, 2, T, K]          its distance |y - H s|^2, comparable with detect()'s
+            status  int32    [nrx, ntx, 2, T, K]          0, abi.KB_NONFINITE, abi.KB_DEFICIENT (a null column of
+                                                          the QR: rank-deficient H or Nr < Nt; still detected)
+            llr     float32  [nrx, ntx, Nt, B, 2, T, K]   (min_{bit 0} - min_{bit 1}) / noise over the final list's
+                                                          leaves, clamped to +-clip; a bit whose other value no leaf
+                                                          of the list carries gets +-clip  (None without llr)
+
+        Nr <= 64, Nt <= 16, B <= 8, Nt B <= 32.  k = 1 with sorted=True is ordered successive interference
+        cancellation; where M^(Nt-1) <= k the decision is the exhaustive one, where M^Nt <= k the LLRs are too.
+        Returns a dict of views of one flat uint8 device tensor, itself under "buffer", enqueued on the current
+        stream; `out` (such a flat tensor) is written in place.  Invalid arguments raise ValueError."""
+        torch = self.torch
+        if not (hasattr(H, "is_cuda") and H.is_cuda and H.device == self.device and H.dtype == torch.complex64):
+            raise ValueError("H must be a complex64 tensor on %s" % (self.device,))
+        if H.dim() != 7 or H.shape[4] != 2:
+            raise ValueError("H [nrx, ntx, Nr, Nt, 2, T, K] expected, got %s" % (tuple(H.shape),))
+        nrx, ntx, nr, nt, _, T, K = (int(v) for v in H.shape)
+        if not (hasattr(Y, "is_cuda") and Y.is_cuda and Y.device == self.device and Y.dtype == torch.complex64):
+            raise ValueError("Y must be a complex64 tensor on %s" % (self.device,))
+        if tuple(Y.shape) != (nrx, ntx, nr, 2, T, K):
+            raise ValueError("Y %s expected, got %s" % ((nrx, ntx, nr, 2, T, K), tuple(Y.shape)))
+        if hasattr(constellation, "is_cuda"):
+            S = constellation
+            if not (S.is_cuda and S.device == self.device and S.dtype == torch.complex64 and S.dim() == 1):
+                raise ValueError("constellation must be a complex64 tensor [M] on %s" % (self.device,))
+        else:
+            S = torch.from_numpy(abi.constellation_array(constellation)[0]).to(self.device)
+        M = int(S.shape[0])
+        if M < 2 or M & (M - 1):
+            raise ValueError("constellation must hold 2^B symbols, got %d" % M)
+        if int(k) != k:
+            raise ValueError("k must be an integer, got %r" % (k,))
+        if not 0 <= int(k) < 1 << 32:
+            raise ValueError("k = %r is outside 1 .. 64" % (k,))
+        spec = abi.kbest_spec(nrx, ntx, nr, nt, T, K, M.bit_length() - 1, noise, k, clip, sorted, llr)
+        H, Y, S = H.contiguous(), Y.contiguous(), S.contiguous()
+        # (a spec the library refuses may have no sensible size: a placeholder it does not write)
+        fits = H.numel() > 0 and abi.kbest_fits(spec)
+        need = abi.kbest_regions(spec)[4] if fits else 1
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            elif (tuple(out.shape) != (need,) or out.dtype != torch.uint8 or out.device != self.device
+                  or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d,) on %s" % (need, self.device))
+            stream = torch.cuda.current_stream(self.device)
+        rc = self.L.hrt_channel_kbest(self.device.index, C.byref(spec), C.c_void_p(H.data_ptr()),
+                                      C.c_void_p(Y.data_ptr() if Y.numel() else None), C.c_void_p(S.data_ptr()),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc == -1:
+            raise ValueError("hrt_channel_kbest: " + self.L.hrt_last_error().decode())
+        _lib.check(rc, "hrt_channel_kbest")
+        H.record_stream(stream)     # (the kernel reads them after this call returns)
+        Y.record_stream(stream)
+        S.record_stream(stream)
+        return abi.kbest_views(out, spec)
+
+    def channel_kbest(self, rx_elements, tx_elements, f0, df, num_freqs, t0=0.0, dt=0.0, num_times=1, los=True,
+                      scatter=True, array_frequency=None, Y=None, constellation=None, noise=None, k=None, clip=None,
+                      sorted=True, llr=True):
+        """The K-best detection on the last trace's array channel, without leaving the device: bit for bit
+        kbest(array_channel(...), Y, constellation, noise, k, clip, sorted, llr) with array_channel()'s arguments.
+        On a sharded trace sum array_channel() over the shards and call kbest()."""
+        if Y is None or constellation is None or noise is None or k is None or clip is None:
+            raise ValueError("channel_kbest needs Y, a constellation, the noise power, k and the clip")
+        H = self.array_channel(rx_elements, tx_elements, f0, df, num_freqs, t0, dt, num_times, los, scatter,
+                               array_frequency)
+        return self.kbest(H, Y, constellation, noise, k, clip, sorted, llr)
+
     def power_profiles(self, tau0, dtau, num_delay_bins, num_zenith_bins=0, num_azimuth_bins=0, los=True,
                        scatter=True, out=None, accumulate=False):
         """Per-link power statistics of the last trace, formed on the device (hrt_power_profiles): incoherent sums

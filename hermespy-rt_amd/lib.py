@@ -44,6 +44,7 @@ EXPORTED = (
     "hrt_precoder_out_bytes", "hrt_channel_precoder", "hrt_compute_channel_precoder",
     "hrt_codebook_out_bytes", "hrt_codebook_select", "hrt_compute_codebook_select",
     "hrt_detect_out_bytes", "hrt_channel_detect", "hrt_compute_channel_detect",
+    "hrt_kbest_out_bytes", "hrt_channel_kbest", "hrt_compute_channel_kbest",
     "hrt_sparse_paths_bytes", "hrt_sparse_out_bytes", "hrt_sparse_array_channel", "hrt_compute_sparse_array_channel",
     "hrt_sparse_taps_out_bytes", "hrt_sparse_array_taps", "hrt_compute_sparse_array_taps",
     "hrt_sparse_beam_out_bytes", "hrt_sparse_beam_channel", "hrt_compute_sparse_beam_channel",
@@ -426,6 +427,17 @@ def load():
                                              C.c_size_t, C.c_double, f32p, f32p, u32, u32, C.c_float, vp,
                                              C.POINTER(Stats)]
     L.hrt_compute_channel_detect.restype = C.c_int
+    # per-point K-best tree-search detection on an array channel (hrt_kbest_spec: abi.KbestSpec)
+    ksp = C.POINTER(abi.KbestSpec)
+    L.hrt_kbest_out_bytes.argtypes = [ksp]
+    L.hrt_kbest_out_bytes.restype = u64
+    L.hrt_channel_kbest.argtypes = [C.c_int, ksp, vp, vp, vp, vp, vp]
+    L.hrt_channel_kbest.restype = C.c_int
+    L.hrt_compute_channel_kbest.argtypes = [C.POINTER(abi.Scene), V3, V3, V3, V3, C.c_float, C.c_size_t,
+                                            C.c_size_t, C.c_size_t, C.c_size_t, spp, V3, C.c_size_t, V3,
+                                            C.c_size_t, C.c_double, f32p, f32p, u32, u32, u32, C.c_float, C.c_float,
+                                            vp, C.POINTER(Stats)]
+    L.hrt_compute_channel_kbest.restype = C.c_int
     # antenna patterns and orientations (hrt_pattern_spec: abi.PatternSpec; hrt_patterns_host: abi.PatternsHost)
     L.hrt_apply_patterns.argtypes = [vp, C.POINTER(Shard), vp, u64, C.POINTER(abi.PatternSpec), vp]
     L.hrt_apply_patterns.restype = C.c_int

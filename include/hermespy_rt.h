@@ -643,6 +643,83 @@ int hrt_compute_channel_detect(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_
                                float noise, void *out /* host, hrt_detect_out_bytes bytes, layout above */,
                                hrt_stats *stats);
 
+/* Per-point K-best tree-search MIMO detection with list max-log bit LLRs on the array channel, formed on the device
+ * (include/hrt_device.h: hrt_channel_kbest): near-ML detection beyond hrt_detect_spec's Q <= 4096.  Points, H, y, the
+ * constellation, the digits x_j of a hypothesis q and the bits are hrt_detect_spec's.  1 <= Nr <= 64 (Nr < Nt is
+ * accepted), 1 <= Nt <= 16, 1 <= B <= 8, Nt B <= 32, the list size K in {1, 2, 4, 8, 16, 32, 64}, `noise` N0 and
+ * `clip` finite and > 0, the size refusals of hrt_channel_detect.
+ * Algorithm (a definition: the tests emulate it).  All float, no contraction.  An inner product <a, c> = a^H c or a
+ * squared norm of columns is summed in the order csrc/hrt_kbest.h fixes (per lane over its rows ascending, then a
+ * butterfly over the hrt_kbest_form(Nr, Nt, K) lanes of the point); its terms are (ar cr + ai ci), (ar ci - ai cr),
+ * (ar ar + ai ai).
+ *   start      A = [H | y], Nr x (Nt + 1).  n_c the squared norms of its columns; thr = ((float)(Nr + Nt) 2^-23)
+ *              sqrtf(largest n_c of H's columns); the sum of all n_c, over c ascending, not finite: NONFINITE.
+ *   position t = 0 .. Nt - 1:
+ *     pick       without HRT_KB_SORTED the stream c = t.  With it (sorted QR), of the streams not yet picked the one
+ *                with the smallest squared norm of its current residual column, recomputed from the column (not
+ *                downdated), the lowest stream on a tie (a strict < over the streams ascending).
+ *     diagonal   r = sqrtf(that squared norm).  !(r > thr): a NULL column -- row t of R is 0, z_t = 0, no column
+ *                changes, the point is HRT_KB_DEFICIENT.  Else R_tt = r (real) and a_c <- a_c / r, entry by entry.
+ *     project    for every stream u not yet picked, ascending, then for y: w = <a_c, a_u>, R_tu = w (z_t = w for y),
+ *                a_u <- a_u - w a_c as (ur - (wr cr - wi ci), ui - (wr ci + wi cr)).
+ *   rho        the squared norm of what is left of the column y.  Not finite: NONFINITE.
+ *   tree       the list starts as one empty path with PED = rho and key 0.  For position i = Nt - 1 down to 0, with c
+ *              the stream at position i, every path of the list forms
+ *                b = z_i - (..((R_i,i+1 s_i+1) + R_i,i+2 s_i+2) + ..), positions ascending, s_t the path's symbol
+ *                    of the stream at position t, products (rr sr - ri si, rr si + ri sr); b = z_i at i = Nt - 1
+ *              and M children, x = 0 .. M - 1 with s = S[x]:
+ *                e = (b.re - R_ii s.re, b.im - R_ii s.im),  PED' = PED + (e.re e.re + e.im e.im),
+ *                key' = key | x << (c B)
+ *              (a PED' that is not finite: NONFINITE).  Of all children of the level the K with the smallest PED'
+ *              make the next list, the lower key on equal PED'.  A key holds every decided stream's digit at its OWN
+ *              position j B (not the detection position's) and zeros elsewhere, so keys are distinct, the list is
+ *              defined independently of how it is found, and a leaf's key is its hypothesis q.
+ *   decision   index: the leaf of the final list with the smallest PED, the lowest q on a tie; metric: its PED.  The
+ *              PED of a leaf is |y - H s(q)|^2 up to rounding (rho included), comparable with hrt_detect_spec's d_q.
+ *   LLR        for every (j, b): m0 the minimum PED over the FINAL list's leaves whose bit is 0, m1 over those whose
+ *              bit is 1 (not over every leaf visited).  Both exist: v = (m0 - m1) / N0 (not finite: NONFINITE), then
+ *              v > clip: clip, v < -clip: -clip.  No leaf with bit 0 (the decision's bit is 1): +clip; none with
+ *              bit 1: -clip.
+ * With K = 1 and HRT_KB_SORTED this is ordered successive interference cancellation.  Where M^(Nt-1) <= K no path is
+ * ever pruned before the last level, so index and metric are the exhaustive minimum of the PED; where M^Nt <= K the
+ * LLRs are the exhaustive ones, clamped.
+ * The outputs lie in one flat buffer of hrt_kbest_out_bytes bytes, in hrt_detect_spec's order and shapes: index
+ * uint32, metric float, status uint32 [num_rx][num_tx][2][T][K], llr float [num_rx][num_tx][Nt][B][2][T][K] (present
+ * only with HRT_KB_LLR).  status is 0, HRT_KB_NONFINITE (1) or HRT_KB_DEFICIENT (2): a NONFINITE point writes status 1
+ * exactly, index 0xFFFFFFFF, metric 0 and zeros in its LLRs (with Nt B = 32 that index is also a valid hypothesis:
+ * status decides).  The LLR quotient is tested only with HRT_KB_LLR.  A non-finite entry of H or y reaches a column
+ * norm; the flag is tracked explicitly.  A DEFICIENT point is detected all the same: a null level ties all its children
+ * and the lower keys survive.  H = 0 follows the same rules: every column is null (status 2), index 0, metric |y|^2.
+ * A point's bytes depend on its own H, y, the constellation, N0, K, clip and flags only; two calls give the same
+ * bytes; every output byte is written exactly once.
+ * hrt_compute_channel_kbest traces and batches exactly as hrt_compute_channel_detect does and detects once after the
+ * last batch: detection is NOT additive over batches or shards.  HRT_E_INVALID, before the device is touched: every
+ * refusal of hrt_compute_array_channel; a NULL Y, constellation or out; every refusal of hrt_channel_kbest. */
+#define HRT_KB_LLR 1u
+#define HRT_KB_SORTED 2u
+#define HRT_KB_NONFINITE 1u
+#define HRT_KB_DEFICIENT 2u
+typedef struct {
+    uint32_t num_rx, num_tx;                    /* receivers, transmitters */
+    uint32_t nr, nt;                            /* the matrix of a point: Nr x Nt, Nt streams */
+    uint32_t num_times, num_freqs;              /* T, K */
+    uint32_t bits;                              /* B: bits per symbol, 1 .. 8, Nt B <= 32 */
+    uint32_t flags;                             /* HRT_KB_LLR | HRT_KB_SORTED */
+    uint32_t k;                                 /* the list size: 1, 2, 4, .. 64 */
+    float noise;                                /* N0, finite and > 0 */
+    float clip;                                 /* the LLR clip, finite and > 0 */
+} hrt_kbest_spec;
+uint64_t hrt_kbest_out_bytes(const hrt_kbest_spec *spec);   /* 0 for NULL */
+int hrt_compute_channel_kbest(Scene *scene, const Vec3 *rx_pos, const Vec3 *tx_pos, const Vec3 *rx_vel,
+                              const Vec3 *tx_vel, float carrier_frequency_GHz, size_t num_rx, size_t num_tx,
+                              size_t num_rays, size_t num_bounces, const hrt_channel_spec *spec,
+                              const Vec3 *rx_elements, size_t num_rx_elements, const Vec3 *tx_elements,
+                              size_t num_tx_elements, double array_frequency_hz,
+                              const float *Y /* host, complex [num_rx][num_tx][Nr][2][T][K] */,
+                              const float *constellation /* host, complex [2^bits] */, uint32_t bits, uint32_t flags,
+                              uint32_t k, float noise, float clip,
+                              void *out /* host, hrt_kbest_out_bytes bytes, layout above */, hrt_stats *stats);
+
 /* Per-link power statistics of the traced paths, formed on the device (include/hrt_device.h: hrt_power_profiles).
  * INCOHERENT sums over the terms hrt_channel sums (the same parts; blocked records add nothing and are not counted):
  *   LoS entry (shard rank 0, LoS not blocked): coincident a = 1, tau = nu = 0, u_rx = (1, 0, 0), u_tx = (-1, 0, 0);

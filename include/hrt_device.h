@@ -472,6 +472,18 @@ int hrt_codebook_select(int device, const hrt_codebook_spec *spec, const void *d
 int hrt_channel_detect(int device, const hrt_detect_spec *spec, const void *d_H, const void *d_Y,
                        const void *d_constellation, void *d_out, void *stream);
 
+/* ---- per-point K-best tree-search detection on an array channel (csrc/host/channel.c, csrc/hrt_kbest.hip) ----
+ * index, metric, status and llr as hermespy_rt.h defines them (hrt_kbest_spec, hrt_compute_channel_kbest),
+ * hrt_kbest_out_bytes bytes at d_out, from d_H, d_Y and d_constellation as hrt_channel_detect takes them, all DEVICE
+ * pointers, asynchronous on `stream` of `device`.  It needs no problem, reads only the three tensors and writes none
+ * of them.  Every byte of d_out is written exactly once; no scratch and no atomics, so two calls with the same input
+ * give the same bytes.  HRT_E_INVALID, before the device is touched: a NULL pointer; num_rx, num_tx, num_times or
+ * num_freqs equal to 0; nr outside 1..64; nt outside 1..16; bits outside 1..8; nt * bits > 32; k not one of 1, 2, 4,
+ * 8, 16, 32, 64; `flags` with bits other than HRT_KB_LLR | HRT_KB_SORTED; a noise or a clip that is not finite and
+ * > 0; nr * nt * num_times * num_freqs > 2^24; 2^31 points or more. */
+int hrt_channel_kbest(int device, const hrt_kbest_spec *spec, const void *d_H, const void *d_Y,
+                      const void *d_constellation, void *d_out, void *stream);
+
 /* ---- per-link power statistics from the traced paths (csrc/host/channel.c, csrc/hrt_power.hip) ----
  * moments, pdp, arrival and departure as hermespy_rt.h defines them (hrt_power_spec, hrt_compute_power_profiles),
  * hrt_power_out_doubles doubles at d_out, formed from the workspace of a finished hrt_trace (its counts read on the
